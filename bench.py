@@ -1,13 +1,22 @@
 #!/usr/bin/env python3
 """bench.py -- BASELINE.json's metric on MI355X: "SenseVoiceSmall steady-state RTF @16kHz, 1/2/4/8 MI355X; STFT+mel GB/s".
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
+
+A plain run times the headline leg (1. below) and nothing else: set-up, warm-up, EXACTLY K timed steps, the outputs of the last
+step if --dump-outputs is given, the line.  --full adds everything else the line can carry: the recogniser legs (2.), the Yolo
+leg (3.) and the CPU baselines; --no-model / --no-yolo / --no-cpu-baseline and the leg options below act inside --full.
+
+--dump-outputs DIR writes what the last timed step computed, as a caller of SenseVoiceFrontend.compute_batch receives it (rank 0's
+shard): DIR/lfr_features.npy = the LFR features of a fixed, seeded sample of the batch's utterances, float32
+[sample, lfr_rows, 560], and DIR/lfr_utterances.npy = their indices in the batch (float64).  The inputs depend only on the
+arguments, so two builds run with the same arguments can be compared output for output.
 
 One process per GPU.  With --gpus N > 1 and no WORLD_SIZE in the environment the script SPAWNS its N ranks itself (RANK /
 LOCAL_RANK / WORLD_SIZE / MASTER_ADDR=127.0.0.1 / MASTER_PORT set per child); under `python -m torch.distributed.run` it
 takes the launcher's environment.  It refuses to run when the world size differs from --gpus.  Rank 0 prints ONE JSON line.
 
-Three legs per run, all on synthetic inputs that are resident in HBM before anything is timed (1 and 2: 16 kHz audio; 3 -- `yolo` --
+Three legs per --full run, all on synthetic inputs that are resident in HBM before anything is timed (1 and 2: 16 kHz audio; 3 -- `yolo` --
 BASELINE configs[4]: a Yolo26n-seg-shaped network, batch 64 of 640 x 640 images per GPU as one hipGraph, 3 warm-up + 10 timed
 forwards as examples/yolo26n-seg/src/benchmark.rs:29-56, priced against the f32 MFMA peak, two images checked against the batch-1
 plan, the oracle's convolution route on one host core beside it):
@@ -15,9 +24,10 @@ plan, the oracle's convolution route on one host core beside it):
  1. STFT+mel (BASELINE configs[1], the line's `metric` / `value`): a "step" = one pass of SenseVoiceFrontend (PCM -> log-mel ->
     LFR) over `--batch` 30 s utterances per GPU (default 2048 = 17 hours of audio, 6.2 GB of PCM and features resident in
     HBM; 256 distinct synthetic utterances repeated on the device).  EXACTLY --steps steps are timed between barrier + device
-    sync fences, MAX over ranks; value = algorithmic GB/s of the whole job.  The recogniser legs run first and a step takes
-    ~3.7 ms, so a run with few steps is not a measurement of the device's ~25 ms clock ramp (at 256 utterances per step the first
-    40 steps read 0.72 -> 0.48 ms).  `roofline` prices the dominant kernel (fe_main_kernel), timed
+    sync fences, MAX over ranks; value = algorithmic GB/s of the whole job.  A step takes ~3.7 ms and the warm-up runs at least
+    --warmup steps and at least WARM_S seconds of them (with --full the recogniser legs run before it as well), so a run with few
+    steps is not a measurement of the device's ~25 ms clock ramp (at 256 utterances per step the first 40 steps read
+    0.72 -> 0.48 ms).  `roofline` prices the dominant kernel (fe_main_kernel), timed
     with HIP events on the stream it runs on.
  2. SenseVoice-shaped recogniser (BASELINE's headline: steady-state RTF; configs[2] and [3]) -- `sensevoice` object:
       * every N: one shard of configs[3] per GPU (32 x 10 s utterances): front-end -> CMVN -> 70-layer encoder (compiled
@@ -31,7 +41,7 @@ plan, the oracle's convolution route on one host core beside it):
     weights are synthetic (8d) -- labelled as such in the line.  The model's dominant kernel (the quantised linear) gets its
     own roofline fields, and the oracle runs the same layer stack on one host core as the CPU baseline.
 
-`cpu_baseline` (rank 0, N = 1 only): the CPU oracle -- a C++ restatement of lele's x86 AVX2 path, one thread = lele's
+`cpu_baseline` (--full, rank 0, N = 1 only): the CPU oracle -- a C++ restatement of lele's x86 AVX2 path, one thread = lele's
 execution model -- on a bounded sample of each leg.  A reported baseline, not the target.
 """
 import argparse
@@ -54,6 +64,9 @@ VALU_PEAK_TLANE = 78.6  # T lane-ops/s: 256 CUs x 128 lanes x 2.4 GHz
 HBM_PEAK_GBS = 8000.0   # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
 I8_PEAK_TOPS = 3944.0   # MI355X_MICROARCH.md: i8 MFMA >= 3944 TOPS measured (16x16x64)
 F32_PEAK_TFLOPS = 157.3  # MI355X_MICROARCH.md: f32 vector (= f32-input MFMA) peak
+WARM_S = 0.5            # front-end leg: least warm-up time, past the device's clock ramp
+DUMP_UTTERANCES = 32    # --dump-outputs: utterances sampled from the batch (1.1 MB of features each at 30 s)
+DUMP_SEED = 0
 
 
 def synth_batch(batch, n, seed0):
@@ -268,22 +281,42 @@ def frontend_leg(args, ctx, rank, world, fence, dist, device):
     else:
         pcm, pbuf = base, base.buf
     out = ctx.buf()
-    for _ in range(args.warmup):
+    # at least --warmup steps and at least WARM_S seconds of them: past the first --warmup steps each step is synchronised, so
+    # the host clock reads device time
+    done, t0 = 0, time.perf_counter()
+    while done < args.warmup or time.perf_counter() - t0 < WARM_S:
         fe.compute_batch(pcm, out)
+        done += 1
+        if done >= args.warmup:
+            ctx.sync()
     fence()
     fe.set_profiling(True)
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        fe.compute_batch(pcm, out)
+        res = fe.compute_batch(pcm, out)
     fence()
     wall = time.perf_counter() - t0
     sum_ms, main_ms, runs = fe.profile_read()
     fe.set_profiling(False)
     wall = max_over_ranks(wall, dist, device)
+    if args.dump_outputs and rank == 0 and args.steps > 0:
+        dump_frontend(args.dump_outputs, res, mine, ctx)
     pbuf.close()
     out.close()
     return {"wall": wall, "n": n, "t_lfr": t_lfr, "cols": cols, "nf": nf, "bytes_per_utt": bytes_per_utt, "main_ms": main_ms,
             "sum_ms": sum_ms, "runs": runs}
+
+
+def dump_frontend(path, res, mine, ctx):
+    """--dump-outputs: the LFR features of a fixed, seeded sample of this rank's utterances, as the last timed step left them"""
+    from lele_amd import kernels as K
+    idx = np.sort(np.random.default_rng(DUMP_SEED).choice(mine, min(mine, DUMP_UTTERANCES), replace=False)).astype(np.int64)
+    buf = ctx.buf()
+    feats = K.gather(res, idx, 0, out=buf, ctx=ctx).numpy()
+    buf.close()
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "lfr_features.npy"), feats.astype(np.float32, copy=False))
+    np.save(os.path.join(path, "lfr_utterances.npy"), idx.astype(np.float64))
 
 
 def open_comm(args, ctx, rank, world, dist, device):
@@ -1122,24 +1155,23 @@ def run_rank(args):
             dist.barrier()
             torch.cuda.synchronize()
 
-    # The recogniser legs run first: they are seconds of sustained device work, so the front-end's W warm-up + K timed steps --
-    # half a millisecond each -- then run at settled clocks even when the caller asks for few steps (a cold 20-step run reads
-    # 0.55-0.57 ms per step where the steady state is 0.48).
+    # --full: the recogniser and Yolo legs run first (seconds of sustained device work before the front-end's warm-up)
     sv = None
     yo = None
     c0 = None
-    if rank == 0 and world == 1 and not args.no_model:
-        try:
-            c0 = configs0_leg(ctx)
-        except Exception as e:  # noqa: BLE001
-            c0 = {"failed": str(e)}
-    comm, comm_note, ranks_seen = open_comm(args, ctx, rank, world, dist, device)
-    if not args.no_model:
-        sv = sensevoice_leg(args, ctx, rank, world, fence, dist, device, comm, comm_note, ranks_seen)
-    if not args.no_yolo:
-        yo = yolo_leg(args, ctx, rank, world, fence, dist, device, comm, comm_note, ranks_seen)
-    if comm is not None:
-        comm.close()
+    if args.full:
+        if rank == 0 and world == 1 and not args.no_model:
+            try:
+                c0 = configs0_leg(ctx)
+            except Exception as e:  # noqa: BLE001
+                c0 = {"failed": str(e)}
+        comm, comm_note, ranks_seen = open_comm(args, ctx, rank, world, dist, device)
+        if not args.no_model:
+            sv = sensevoice_leg(args, ctx, rank, world, fence, dist, device, comm, comm_note, ranks_seen)
+        if not args.no_yolo:
+            yo = yolo_leg(args, ctx, rank, world, fence, dist, device, comm, comm_note, ranks_seen)
+        if comm is not None:
+            comm.close()
     fe = frontend_leg(args, ctx, rank, world, fence, dist, device)
 
     if rank == 0:
@@ -1227,7 +1259,7 @@ def run_rank(args):
             line["configs0"] = c0
             if dev_probs is not None and not args.no_cpu_baseline:
                 line["configs0"]["cpu_baseline"] = cpu_baseline_configs0(dev_probs)
-        if world == 1 and not args.no_cpu_baseline:  # reported baseline: rank 0 at N=1 only
+        if args.full and world == 1 and not args.no_cpu_baseline:  # reported baseline: rank 0 at N=1 only
             lifted = os.path.join(ROOT, "_lifted", "yolo26seg_plan.json")
             if yo is not None and "lookalike" in yo and os.path.exists(lifted):
                 line["yolo"]["cpu_baseline"] = cpu_baseline_yolo_graph(lifted)
@@ -1328,6 +1360,10 @@ def main():
     ap.add_argument("--yolo-batch", type=int, default=64, help="configs[4]: 640 x 640 images per GPU per forward")
     ap.add_argument("--yolo-runs", type=int, default=10, help="configs[4]: timed forwards after 3 warm-up ones (examples/yolo26n-seg/src/benchmark.rs:29-56)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true", help="also run the recogniser legs (configs[0], [2], [3]), the configs[4] leg and the CPU "
+                    "baselines; a plain run times the front-end leg alone")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's outputs (a seeded sample of the LFR features) as "
+                    "DIR/<name>.npy")
     ap.add_argument("--allow-fallback", action="store_true", help="N > 1: if the C ABI's RCCL communicator cannot be set up on every rank, gather the "
                     "ids with torch.distributed instead of failing (the line then names that transport)")
     ap.add_argument("--dry-run", action="store_true", help=argparse.SUPPRESS)

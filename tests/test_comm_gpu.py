@@ -158,7 +158,7 @@ def test_bench_two_ranks_on_one_gpu_end_to_end():
     env = dict(os.environ, LELE_BENCH_SHARE_GPU="1", LELE_BENCH_BACKEND="gloo")
     env.pop("WORLD_SIZE", None)
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--batch", "64",
-                        "--layers", "2", "--per-gpu", "4", "--sv-steps", "2", "--allow-fallback", "--gather-logits"], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE,
+                        "--layers", "2", "--per-gpu", "4", "--sv-steps", "2", "--allow-fallback", "--gather-logits", "--full"], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE,
                        text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     last = r.stdout.strip().splitlines()[-1]

@@ -238,3 +238,30 @@ def test_stft_ops_bit_exact(ctx, orc):
     short = sig[:100]
     assert np.array_equal(K.stft_power_spectrum(short, 256, 64, 256, ctx=ctx).numpy(),
                           orc.stft_power(short, 256, 64, 256))
+
+
+def test_plain_bench_run_times_the_front_end_and_dumps_its_last_step(orc, tmp_path):
+    """`bench.py` without --full: the front-end leg alone, exactly --steps timed steps, and --dump-outputs writes a seeded sample of
+    the last step's LFR features (float32, indices beside them in float64, under 64 MB) that the oracle reproduces utterance by utterance"""
+    import json
+    import subprocess
+    import sys
+    import bench
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
+    batch = 40
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--batch", str(batch),
+                        "--dump-outputs", str(tmp_path)], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-2000:]
+    line = json.loads(r.stdout.strip().splitlines()[-1])
+    assert line["steps"] == 3 and line["warmup"] == 1 and line["ms_per_step"] > 0 and line["unit"] == "GB/s" and line["dtype"] == "f32"
+    assert not any(k in line for k in ("sensevoice", "yolo", "configs0", "cpu_baseline", "cpu_baseline_all_cores"))
+    feats, idx = np.load(tmp_path / "lfr_features.npy"), np.load(tmp_path / "lfr_utterances.npy")
+    assert feats.dtype == np.float32 and idx.dtype == np.float64
+    assert sum(os.path.getsize(tmp_path / f) for f in os.listdir(tmp_path)) <= 64 << 20
+    n = bench.SAMPLE_RATE * bench.SECONDS
+    assert feats.shape == (min(batch, bench.DUMP_UTTERANCES), line["config"]["lfr_rows"], 560)
+    assert np.array_equal(idx, np.unique(idx)) and idx.min() >= 0 and idx.max() < batch
+    for j in (0, len(idx) - 1):   # utterance i of the batch is synthesised from seed i
+        ref = orc.frontend_compute(bench.synth_batch(1, n, int(idx[j]))[0])
+        assert close(feats[j], ref), float(np.abs(feats[j] - ref).max())

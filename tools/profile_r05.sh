@@ -8,7 +8,7 @@ OUT=$R/gpurun_out/prof_r05
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
 # 1. the default bench invocation, plain; the front-end leg under rocprofv3 --kernel-trace --stats
-timeout 400 python $R/bench.py > "$OUT/bench_plain.json" 2> "$OUT/bench_plain.log"
+timeout 400 python $R/bench.py --full > "$OUT/bench_plain.json" 2> "$OUT/bench_plain.log"
 timeout 200 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/stats" -o bench -- python $R/bench.py --no-model --no-yolo --no-cpu-baseline > "$OUT/bench_under_rocprof.json" 2> "$OUT/stats.log"
 # 2. per-kernel tables of the compiled SenseVoice-shaped plan (configs[2] and one configs[3] shard)
 for C in c3 c4; do

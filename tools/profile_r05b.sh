@@ -7,7 +7,7 @@ R=${GRAFT_REPO_ROOT:-/root/repo}
 OUT=$R/gpurun_out/prof_r05b
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
-timeout 400 python $R/bench.py > "$OUT/bench_plain.json" 2> "$OUT/bench_plain.log"
+timeout 400 python $R/bench.py --full > "$OUT/bench_plain.json" 2> "$OUT/bench_plain.log"
 for C in c3 c4; do
   timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/sv" -o ${C}_compiled -- \
       python $R/tools/sensevoice_graph.py --compiled-only --configs $C --runs 8 > "$OUT/sv_${C}.json" 2> "$OUT/sv_${C}.log"

@@ -2,7 +2,7 @@
 """Condense gpurun_out/prof_<tag>/ (written by tools/profile_round.sh on the GPU box) into the tracked files under profiles/:
 
   <tag>_frontend_kernel_stats.csv     rocprofv3 --kernel-trace --stats of `python bench.py --no-model` (kernel_stats table, verbatim)
-  <tag>_bench_plain.json              the JSON line of an unprofiled default `python bench.py`
+  <tag>_bench_plain.json              the JSON line of an unprofiled `python bench.py --full`
   <tag>_bench_under_rocprof.json      the JSON line of the profiled run (its roofline.kernel_ms must agree with AverageNs above)
   <tag>_frontend_pmc.json             FETCH_SIZE / WRITE_SIZE / SQ counters of fe_main_kernel, averaged per launch
   <tag>_valu_rate.json                tools/valu_rate: measured VALU issue cost per wave-instruction (plain and packed f32)
