@@ -149,6 +149,17 @@ int lele_hip_frontend_compute(LeleFrontend* fe, const LeleTensor* pcm, LeleBuf* 
  * out [batch, T, n_mels*lfr_m].  (lele loops over utterances on the host; examples/sensevoice/src/main.rs:58-86) */
 int lele_hip_frontend_compute_batch(LeleFrontend* fe, const LeleTensor* pcm, LeleBuf* out, int64_t* out_shape,
                                     int32_t* out_rank);
+/* Segments of ONE pcm buffer (f32 [N]) in one launch: segment i = pcm[starts[i], starts[i] + lengths[i]) (host arrays of `count`;
+ * any order, overlaps and repeats allowed, any start).  out [R, n_mels*lfr_m] holds the segments' rows one after another (the packed
+ * layout): rows row_offsets[i] .. row_offsets[i+1] (host array of count + 1, written) are what lele_hip_frontend_compute gives for
+ * that segment alone, bit for bit.  A segment shorter than one frame has 0 rows (its offsets repeat); count == 0 or R == 0 gives rank
+ * 0.  Segments are checked before anything is launched (start < 0, length < 0 or start + length > N fail and leave `out` as it
+ * was).  The default FeatureConfig takes one launch over every segment's 64-frame blocks; the segment layout is shape metadata,
+ * uploaded once per distinct layout into a table the frontend owns until it is destroyed, so a graph may record the call (run the
+ * layout once before capturing it).  Other FeatureConfigs (the generic path) run the generic kernels once per segment: correct,
+ * not fast. */
+int lele_hip_frontend_compute_segments(LeleFrontend* fe, const LeleTensor* pcm, const int64_t* starts, const int64_t* lengths,
+                                       int64_t count, LeleBuf* out, int64_t* row_offsets, int64_t* out_shape, int32_t* out_rank);
 /* log-mel before LFR ([num_frames, n_mels]) of the last compute call's shape, for tests */
 int lele_hip_frontend_logmel(LeleFrontend* fe, const LeleTensor* pcm, LeleBuf* out, int64_t* out_shape,
                              int32_t* out_rank);
@@ -164,6 +175,15 @@ int lele_hip_lfr(LeleCtx* ctx, const LeleTensor* x, int64_t m, int64_t n, LeleBu
 /* Cmvn::compute, src/features/cmvn.rs:14-66: per-utterance mean/var over time.  [T,D] or [1,T,D] as upstream; extension:
  * [B,T,D] with B > 1 normalises each of the B utterances with its own statistics in one launch pair */
 int lele_hip_cmvn(LeleCtx* ctx, const LeleTensor* x, float eps, LeleBuf* out, int64_t* out_shape, int32_t* out_rank);
+/* Cmvn::compute of every segment of a packed x [R, D] (row_offsets: host, count + 1, from 0 to R, non-decreasing): each segment
+ * normalised with its own statistics, bit for bit what lele_hip_cmvn gives on that segment's rows alone; 0-row segments are
+ * skipped.  out [R, D]. */
+int lele_hip_cmvn_segments(LeleCtx* ctx, const LeleTensor* x, const int64_t* row_offsets, int64_t count, float eps, LeleBuf* out,
+                           int64_t* out_shape, int32_t* out_rank);
+/* Packed x [R, D] -> out [count, t_max, D]: segment b's rows, then `pad` up to t_max (0 = the longest segment's rows; a smaller
+ * non-zero t_max is an error).  An exact copy: the [B, T, D] + lengths form a padded encoder input takes. */
+int lele_hip_segments_to_padded(LeleCtx* ctx, const LeleTensor* x, const int64_t* row_offsets, int64_t count, int64_t t_max,
+                                float pad, LeleBuf* out, int64_t* out_shape, int32_t* out_rank);
 /* Cmvn::apply_with_stats, cmvn.rs:67-92 */
 int lele_hip_cmvn_apply_with_stats(LeleCtx* ctx, const LeleTensor* x, const LeleTensor* mean, const LeleTensor* std_,
                                    float eps, LeleBuf* out, int64_t* out_shape, int32_t* out_rank);

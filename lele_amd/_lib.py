@@ -59,6 +59,14 @@ def lib():
         _lib.lele_hip_buf_data.restype = C.c_void_p
         _lib.lele_hip_buf_bytes.restype = C.c_size_t
         _lib.lele_hip_ctx_stream.restype = C.c_void_p
+        _i64p, _i32p = C.POINTER(C.c_int64), C.POINTER(C.c_int32)
+        for name, at in (  # (a saved older build -- LELE_HIP_LIBRARY -- may lack them)
+                ("lele_hip_frontend_compute_segments", [C.c_void_p, C.c_void_p, _i64p, _i64p, C.c_int64, C.c_void_p, _i64p, _i64p, _i32p]),
+                ("lele_hip_cmvn_segments", [C.c_void_p, C.c_void_p, _i64p, C.c_int64, C.c_float, C.c_void_p, _i64p, _i32p]),
+                ("lele_hip_segments_to_padded", [C.c_void_p, C.c_void_p, _i64p, C.c_int64, C.c_int64, C.c_float, C.c_void_p, _i64p, _i32p])):
+            fn = getattr(_lib, name, None)
+            if fn is not None:
+                fn.argtypes = at
     return _lib
 
 
@@ -414,6 +422,11 @@ def as_tensor(x, keep, mem=None, views=False):
     t = LeleTensor(a.ctypes.data_as(C.c_void_p), shape, a.ndim, _NP2DT[a.dtype], MEM_HOST if mem is None else mem)
     keep.append(t)
     return C.byref(t)
+
+
+def i64_ptr(a):
+    """contiguous np.int64 array -> int64_t* (the caller keeps `a` alive)"""
+    return a.ctypes.data_as(C.POINTER(C.c_int64))
 
 
 def i64_array(vals, keep):

@@ -76,6 +76,26 @@ inline int64_t numel(const LeleTensor* t) {
 }  // namespace lele
 
 // Opaque types of the C ABI -------------------------------------------------------------------------------
+struct LeleCtx;
+
+// Device copies of small host tables that a launch reads as shape metadata (the segment layouts of compute_segments, cmvn_segments,
+// segments_to_padded), one per distinct key.  A table is uploaded once and never rewritten, so a graph that recorded a launch reading
+// it stays valid.  Outside a capture a miss uploads synchronously; inside one a miss is an error (run the sequence once before
+// capturing it) and a hit pins the table until its owner is destroyed.  Tables no capture has used are dropped together, after the
+// streams are drained, once more than kMaxLoose of them have accumulated (a server whose every batch has a new layout).
+struct DevTables {
+    struct Entry {
+        void* d = nullptr;
+        bool pinned = false;
+    };
+    std::map<std::string, Entry> m;
+    size_t loose = 0;
+    static constexpr size_t kMaxLoose = 64;
+    // device copy of the table that `build` writes for `key` (called on a miss only)
+    int get(LeleCtx* ctx, std::string key, void (*build)(const void* arg, std::vector<char>& blob), const void* arg, const void** out);
+    void release();  // frees every table (the owner's streams are idle)
+};
+
 struct LeleCtx {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -123,6 +143,9 @@ struct LeleCtx {
     // (add3 / fused_quantized_linear_residual with an operand that broadcasts OUTWARD: the in-place second pass is not possible)
     LeleBuf* tmp[3] = {nullptr, nullptr, nullptr};
     int tmp_buf(int i, LeleBuf** out);
+
+    // row-offset tables of cmvn_segments / segments_to_padded (features_ops.hip)
+    DevTables seg_tables;
 
     // ---- lanes: extra streams of this context, for plans whose independent branches should overlap (lele_hip_lane_*).
     // The fields above (stream, arena*, scratch*, tmp) are always those of the CURRENT lane -- every op of the library keeps using

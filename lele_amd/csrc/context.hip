@@ -130,6 +130,53 @@ int LeleCtx::get_scratch(size_t bytes, void** out) {
     return 0;
 }
 
+int DevTables::get(LeleCtx* ctx, std::string key, void (*build)(const void* arg, std::vector<char>& blob), const void* arg,
+                   const void** out) {
+    auto it = m.find(key);
+    if (it != m.end()) {
+        if (ctx->capturing && !it->second.pinned) {
+            it->second.pinned = true;
+            --loose;
+        }
+        *out = it->second.d;
+        return 0;
+    }
+    LELE_REQUIRE(!ctx->capturing, "graph capture: this segment layout has no device table yet; run the sequence once before capturing it");
+    if (loose >= kMaxLoose) {  // no capture refers to these: once every stream is idle, nothing does
+        LELE_TRY(ctx->sync_all());
+        for (auto i = m.begin(); i != m.end();) {
+            if (i->second.pinned) {
+                ++i;
+                continue;
+            }
+            (void)hipFree(i->second.d);
+            i = m.erase(i);
+        }
+        loose = 0;
+    }
+    std::vector<char> blob;
+    build(arg, blob);
+    void* d = nullptr;
+    LELE_HIP_CHECK(hipMalloc(&d, std::max<size_t>(blob.size(), 16)));
+    if (!blob.empty()) {
+        hipError_t e = hipMemcpy(d, blob.data(), blob.size(), hipMemcpyHostToDevice);
+        if (e != hipSuccess) {
+            (void)hipFree(d);
+            LELE_HIP_CHECK(e);
+        }
+    }
+    m[std::move(key)] = Entry{d, false};
+    ++loose;
+    *out = d;
+    return 0;
+}
+
+void DevTables::release() {
+    for (auto& kv : m) (void)hipFree(kv.second.d);
+    m.clear();
+    loose = 0;
+}
+
 int LeleCtx::dev_ptr(const LeleTensor* t, const void** out) {
     if (!t) {
         *out = nullptr;
@@ -261,6 +308,7 @@ int lele_hip_ctx_destroy(LeleCtx* c) {
     if (c->device >= 0 && c->device < 64) --g_live_ctx[c->device];
     for (void* p : c->arena_overflow) (void)hipFree(p);
     for (auto& kv : c->weights) (void)hipFree(kv.second);
+    c->seg_tables.release();
     if (c->arena) (void)hipFree(c->arena);
     if (c->scratch) (void)hipFree(c->scratch);
     if (c->mailbox) (void)hipHostFree(c->mailbox);

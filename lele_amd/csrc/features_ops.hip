@@ -75,6 +75,61 @@ __global__ void cmvn_apply_kernel(const float* __restrict__ x, int64_t t, int64_
     }
 }
 
+// Segmented forms (cmvn_segments): grid.y = segment, whose rows are off[y] .. off[y + 1] of x [R, d]; the same per-thread arithmetic
+// as the two kernels above on those rows, so each segment's result is lele_hip_cmvn's on that segment alone, bit for bit.
+__global__ void cmvn_seg_moments_kernel(const float* __restrict__ x, const int64_t* __restrict__ off, int64_t d, float eps,
+                                        float* __restrict__ mean_out, float* __restrict__ sd_out) {
+    const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t r0 = off[blockIdx.y], t = off[blockIdx.y + 1] - r0;
+    if (k >= d || t == 0) return;
+    const float* xu = x + r0 * d + k;
+    float sum = 0.0f, sq = 0.0f;
+    int64_t ti = 0;
+    for (; ti + 8 <= t; ti += 8) {
+        float v[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) v[u] = xu[(ti + u) * d];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+            sum = sum + v[u];
+            sq = sq + v[u] * v[u];
+        }
+    }
+    for (; ti < t; ++ti) {
+        const float v = xu[ti * d];
+        sum = sum + v;
+        sq = sq + v * v;
+    }
+    const float tf = (float)t;
+    const float mean = sum / tf;
+    float var = sq / tf - mean * mean;
+    var = (var > 0.0f) ? var : 0.0f;
+    mean_out[(int64_t)blockIdx.y * d + k] = mean;
+    sd_out[(int64_t)blockIdx.y * d + k] = sqrtf(var + eps);
+}
+__global__ void cmvn_seg_apply_kernel(const float* __restrict__ x, const int64_t* __restrict__ off, int64_t d,
+                                      const float* __restrict__ mean, const float* __restrict__ sd, float* __restrict__ out) {
+    const int64_t u = blockIdx.y, r0 = off[u], total = (off[u + 1] - r0) * d;
+    x += r0 * d;
+    out += r0 * d;
+    for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total;
+         idx += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t k = idx % d;
+        out[idx] = (x[idx] - mean[u * d + k]) / sd[u * d + k];  // cmvn.rs:58-62
+    }
+}
+
+// segments_to_padded: out [count, t_max, d], row t of segment b = x row off[b] + t for t < off[b + 1] - off[b], else `pad`.  grid.y =
+// segment, a pure copy.
+__global__ void seg_pad_kernel(const float* __restrict__ x, const int64_t* __restrict__ off, int64_t t_max, int64_t d, float pad,
+                               float* __restrict__ out) {
+    const int64_t b = blockIdx.y, r0 = off[b], rows = off[b + 1] - r0, have = rows * d, total = t_max * d;
+    x += r0 * d;
+    out += b * total;
+    for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (int64_t)gridDim.x * blockDim.x)
+        out[idx] = idx < have ? x[idx] : pad;
+}
+
 __global__ void cmvn_stats_kernel(const float* __restrict__ x, int64_t t, int64_t d, float eps,
                                   const float* __restrict__ mean, const float* __restrict__ sd,
                                   float* __restrict__ out) {
@@ -278,6 +333,31 @@ int feature_2d(const LeleTensor* x, int64_t* t, int64_t* d, const char* who) {
     return 2;
 }
 
+// the packed layout of cmvn_segments / segments_to_padded: x [R, D] f32, row_offsets[0] == 0, non-decreasing, row_offsets[count] == R
+int seg_offsets(const LeleTensor* x, const int64_t* off, int64_t count, int64_t* r, int64_t* d, int64_t* tmax, const char* who) {
+    LELE_REQUIRE(x->dtype == LELE_F32 && x->rank == 2, "%s: x must be f32 [R, D]", who);
+    LELE_REQUIRE(count >= 0 && off, "%s: bad row_offsets (count %lld)", who, (long long)count);
+    *r = x->shape[0];
+    *d = x->shape[1];
+    LELE_REQUIRE(off[0] == 0 && off[count] == *r, "%s: row_offsets must run from 0 to R = %lld (got %lld .. %lld)", who, (long long)*r,
+                 (long long)off[0], (long long)off[count]);
+    *tmax = 0;
+    for (int64_t i = 0; i < count; ++i) {
+        LELE_REQUIRE(off[i + 1] >= off[i], "%s: row_offsets decrease at segment %lld", who, (long long)i);
+        *tmax = std::max(*tmax, off[i + 1] - off[i]);
+    }
+    return 0;
+}
+void build_offsets(const void* arg, std::vector<char>& blob) {
+    const std::string& key = *(const std::string*)arg;
+    blob.assign(key.begin(), key.end());
+}
+// the row offsets on the device: shape metadata, one table per distinct layout (DevTables: safe under graph capture)
+int offsets_table(LeleCtx* ctx, const int64_t* off, int64_t count, const void** out) {
+    std::string key((const char*)off, (size_t)(count + 1) * 8);
+    return ctx->seg_tables.get(ctx, key, build_offsets, &key, out);
+}
+
 }  // namespace
 
 namespace lele {
@@ -347,6 +427,62 @@ int lele_hip_cmvn(LeleCtx* ctx, const LeleTensor* x, float eps, LeleBuf* out, in
     }
     std::vector<int64_t> shp(x->shape, x->shape + x->rank);
     return set_shape_v(out_shape, out_rank, shp);
+}
+
+int lele_hip_cmvn_segments(LeleCtx* ctx, const LeleTensor* x, const int64_t* row_offsets, int64_t count, float eps, LeleBuf* out,
+                           int64_t* out_shape, int32_t* out_rank) {
+    LELE_REQUIRE(ctx && x && out, "cmvn_segments: NULL argument");
+    int64_t r = 0, d = 0, tmax = 0;
+    LELE_TRY(seg_offsets(x, row_offsets, count, &r, &d, &tmax, "cmvn_segments"));
+    LELE_HIP_CHECK(hipSetDevice(ctx->device));
+    const void* doff = nullptr;
+    if (count > 0 && r > 0 && d > 0) LELE_TRY(offsets_table(ctx, row_offsets, count, &doff));
+    LELE_TRY(ctx->arena_reset());
+    const void* dx = nullptr;
+    LELE_TRY(ctx->dev_ptr(x, &dx));
+    LELE_TRY(out->reserve((size_t)r * d * 4));
+    if (count > 0 && r > 0 && d > 0) {
+        void *dm = nullptr, *ds = nullptr;
+        LELE_TRY(ctx->arena_alloc((size_t)count * d * 4, &dm));
+        LELE_TRY(ctx->arena_alloc((size_t)count * d * 4, &ds));
+        for (int64_t c0 = 0; c0 < count; c0 += 65535) {  // grid.y limit
+            const int64_t nc = std::min<int64_t>(65535, count - c0);
+            hipLaunchKernelGGL(cmvn_seg_moments_kernel, dim3((unsigned)((d + 63) / 64), (unsigned)nc), dim3(64), 0, ctx->stream,
+                               (const float*)dx, (const int64_t*)doff + c0, d, eps, (float*)dm + c0 * d, (float*)ds + c0 * d);
+            const int blocks = (int)std::max<int64_t>(1, std::min<int64_t>((tmax * d + 255) / 256, 1024));
+            hipLaunchKernelGGL(cmvn_seg_apply_kernel, dim3(blocks, (unsigned)nc), dim3(256), 0, ctx->stream, (const float*)dx,
+                               (const int64_t*)doff + c0, d, (const float*)dm + c0 * d, (const float*)ds + c0 * d, (float*)out->data);
+        }
+        LELE_HIP_CHECK(hipGetLastError());
+    }
+    return set_shape(out_shape, out_rank, {r, d});
+}
+
+int lele_hip_segments_to_padded(LeleCtx* ctx, const LeleTensor* x, const int64_t* row_offsets, int64_t count, int64_t t_max, float pad,
+                                LeleBuf* out, int64_t* out_shape, int32_t* out_rank) {
+    LELE_REQUIRE(ctx && x && out, "segments_to_padded: NULL argument");
+    int64_t r = 0, d = 0, tmax = 0;
+    LELE_TRY(seg_offsets(x, row_offsets, count, &r, &d, &tmax, "segments_to_padded"));
+    LELE_REQUIRE(t_max == 0 || t_max >= tmax, "segments_to_padded: t_max %lld is shorter than the longest segment (%lld rows)",
+                 (long long)t_max, (long long)tmax);
+    if (t_max == 0) t_max = tmax;
+    LELE_HIP_CHECK(hipSetDevice(ctx->device));
+    const void* doff = nullptr;
+    if (count > 0 && t_max > 0 && d > 0) LELE_TRY(offsets_table(ctx, row_offsets, count, &doff));
+    LELE_TRY(ctx->arena_reset());
+    const void* dx = nullptr;
+    LELE_TRY(ctx->dev_ptr(x, &dx));
+    LELE_TRY(out->reserve((size_t)count * t_max * d * 4));
+    if (count > 0 && t_max > 0 && d > 0) {
+        const int blocks = (int)std::max<int64_t>(1, std::min<int64_t>((t_max * d + 255) / 256, 1024));
+        for (int64_t c0 = 0; c0 < count; c0 += 65535) {
+            const int64_t nc = std::min<int64_t>(65535, count - c0);
+            hipLaunchKernelGGL(seg_pad_kernel, dim3(blocks, (unsigned)nc), dim3(256), 0, ctx->stream, (const float*)dx,
+                               (const int64_t*)doff + c0, t_max, d, pad, (float*)out->data + c0 * t_max * d);
+        }
+        LELE_HIP_CHECK(hipGetLastError());
+    }
+    return set_shape(out_shape, out_rank, {count, t_max, d});
 }
 
 int lele_hip_cmvn_apply_with_stats(LeleCtx* ctx, const LeleTensor* x, const LeleTensor* mean, const LeleTensor* sd,

@@ -43,6 +43,27 @@ struct FeDev {                 // device tables (all owned by LeleFrontend)
     int lfr_m, lfr_n;
 };
 
+// Which 64-frame block of which utterance a workgroup takes.  compute / compute_batch: block x of utterance y of the grid (equal-length
+// utterances utt_stride samples apart).  compute_segments: the kernel has located the block's segment in its table and offset every
+// pointer to it; the body then sees ONE utterance (y = 0) and the block's index inside the segment.
+struct GridBlock {
+    __device__ __forceinline__ unsigned x() const { return blockIdx.x; }
+    __device__ __forceinline__ unsigned y() const { return blockIdx.y; }
+};
+struct SegBlock {
+    unsigned bx;
+    __device__ __forceinline__ unsigned x() const { return bx; }
+    __device__ __forceinline__ unsigned y() const { return 0u; }
+};
+
+// One segment of compute_segments (a (start, length) range of the PCM buffer with at least one frame), built on the host.
+struct FeSeg {
+    int64_t start, len;         // samples
+    int64_t num_frames, t_lfr;  // as compute() gives them for pcm[start, start + len)
+    int64_t row0;               // first output row of the packed result
+    int64_t block0;             // first 64-frame block of the 1-D grid
+};
+
 // ------------------------------------------------------------------------------------------------------
 // Kernel 1: exact sequential frame sums.  grid (ceil(F/64), batch), block 64.
 // ------------------------------------------------------------------------------------------------------
@@ -156,12 +177,12 @@ constexpr int kStdMelOff[6] = {0, 3, 7, 13, 23, 40};
 // that four workgroups' LDS fits a CU) were measured twice in round 4: <3, true> with 48 spilled registers 7.41 ms per 2048 x 30 s, and
 // -- after the pass body lost its copies -- <3, false> at 128 registers without a spill in the loop 3.59 ms against 3.47 ms for
 // <4, false> at three waves (148 registers) in the same call: the product instantiates <4, false> only; docs/experiments.md.
-template <int MODE, bool STDMEL, bool FUSED, int PASSES, bool LOWREG>
+template <int MODE, bool STDMEL, bool FUSED, int PASSES, bool LOWREG, class Blk>
 __device__ __forceinline__ void fe_main_body(const float* __restrict__ pcm, int64_t utt_stride,
                                              int64_t num_frames, int64_t t_lfr,
                                              const float* __restrict__ means, const FeDev& tb,
                                              float* __restrict__ out, float* __restrict__ logmel_out,
-                                             int aligned16, float* s_melw) {
+                                             int aligned16, float* s_melw, Blk bl) {
     constexpr int FR = 16 * PASSES;           // frames per workgroup
     constexpr int kRows = FR + 2;             // hop rows of the run (400 = 2.5 hops)
     constexpr int kXFloats = FUSED ? (kRows * kSumPitch > 4 * kWaveLdsFloats ? kRows * kSumPitch : 4 * kWaveLdsFloats)
@@ -183,8 +204,8 @@ __device__ __forceinline__ void fe_main_body(const float* __restrict__ pcm, int6
     if (FUSED) {
         // stage the run [64*blockIdx.x*hop, +66 hops) as [hop row][offset] (x32768, exact) -- same layout and bank
         // argument as fe_frame_sum_kernel, 256 threads, all loads of a thread issued before the first use
-        const float* ubase = pcm + (int64_t)blockIdx.y * utt_stride;
-        const int64_t s0 = (int64_t)blockIdx.x * FR * fe::kHop;
+        const float* ubase = pcm + (int64_t)bl.y() * utt_stride;
+        const int64_t s0 = (int64_t)bl.x() * FR * fe::kHop;
         constexpr int kVecPerRow = fe::kHop / 4;
         constexpr int kVecs = kRows * kVecPerRow;
         constexpr int kIters = (kVecs + 255) / 256;
@@ -221,11 +242,11 @@ __device__ __forceinline__ void fe_main_body(const float* __restrict__ pcm, int6
     const int h = fe::rev4(p);
     float* xw = s_x + wave * kWaveLdsFloats;           // this wave's exchange / power region
     float* xf = xw + g * kFrameXchgFloats;             // this frame's 2 KB round buffer
-    const float* base = pcm + (int64_t)blockIdx.y * utt_stride;
-    const float* mean_u = means + (int64_t)blockIdx.y * num_frames;
+    const float* base = pcm + (int64_t)bl.y() * utt_stride;
+    const float* mean_u = means + (int64_t)bl.y() * num_frames;
     const int d_out = tb.n_mels * tb.lfr_m;
-    float* out_u = out ? out + (int64_t)blockIdx.y * t_lfr * d_out : nullptr;
-    float* lm_u = logmel_out ? logmel_out + (int64_t)blockIdx.y * num_frames * tb.n_mels : nullptr;
+    float* out_u = out ? out + (int64_t)bl.y() * t_lfr * d_out : nullptr;
+    float* lm_u = logmel_out ? logmel_out + (int64_t)bl.y() * num_frames * tb.n_mels : nullptr;
 
     // Hann window coefficients of this lane's samples n = p + 16 q (features/window.rs), kept in registers (LOWREG: re-read per pass)
     float win[fe::kQ];
@@ -239,7 +260,7 @@ __device__ __forceinline__ void fe_main_body(const float* __restrict__ pcm, int6
     float xr[fe::kQ];
     float mean_next = 0.0f;
     auto issue_loads = [&](int pass) {
-        const int64_t f = (int64_t)blockIdx.x * FR + wave * (4 * PASSES) + pass * 4 + g;
+        const int64_t f = (int64_t)bl.x() * FR + wave * (4 * PASSES) + pass * 4 + g;
         const int64_t fc = f < num_frames ? f : 0;
         const float* src = base + fc * fe::kHop + p;
         if (!FUSED) mean_next = mean_u[fc];
@@ -274,7 +295,7 @@ __device__ __forceinline__ void fe_main_body(const float* __restrict__ pcm, int6
     // in different blocks (no DPP operand: 25 v_mov_dpp + 25 v_mov a pass) and the 25 samples were copied twice per pass.
     auto run_pass = [&](int pass, auto load_next_c) {
         constexpr bool load_next = decltype(load_next_c)::value;
-        const int64_t f = (int64_t)blockIdx.x * FR + wave * (4 * PASSES) + pass * 4 + g;
+        const int64_t f = (int64_t)bl.x() * FR + wave * (4 * PASSES) + pass * 4 + g;
         const bool valid = f < num_frames;
         const float mean = FUSED ? s_mean[wave * (4 * PASSES) + pass * 4 + g] : mean_next;
         if (LOWREG) {  // the compiler must not hoist these loads out of the pass loop (that is the register form again)
@@ -441,7 +462,27 @@ __global__ __launch_bounds__(256) void fe_main_kernel(const float* __restrict__ 
                                                       const float* __restrict__ means, FeDev tb, float* __restrict__ out,
                                                       float* __restrict__ logmel_out, int aligned16) {
     extern __shared__ float s_melw[];  // [mel_steps][16] (the table-driven mel loop only)
-    fe_main_body<MODE, STDMEL, FUSED, 4, false>(pcm, utt_stride, num_frames, t_lfr, means, tb, out, logmel_out, aligned16, s_melw);
+    fe_main_body<MODE, STDMEL, FUSED, 4, false>(pcm, utt_stride, num_frames, t_lfr, means, tb, out, logmel_out, aligned16, s_melw,
+                                                GridBlock{});
+}
+
+// ------------------------------------------------------------------------------------------------------
+// compute_segments: fe_main_body over a 1-D grid of every segment's 64-frame blocks (a segment's last block is partial, so no block
+// spans two segments).  Always the fused form (the frame sums inside the block): the two-kernel form is a lab switch of compute().  A block finds its segment through a per-block index (blk_seg[block] = segment) rather than a binary
+// search over the segments' first blocks: the search would be log2(count) DEPENDENT loads at the head of every block (11 for 2048
+// segments, each an L2 round trip before the first PCM request can go out), the index is one, plus the segment's record, for 4 bytes a
+// block of table.  Everything after the lookup is fe_main_body on that segment alone, with the segment's own length
+// for the float4 / scalar clamp and its own alignment, so each segment's rows are those compute() gives for it, bit for bit.
+// ------------------------------------------------------------------------------------------------------
+template <int MODE, bool STDMEL>
+__global__ __launch_bounds__(256) void fe_seg_main_kernel(const float* __restrict__ pcm, const FeSeg* __restrict__ segs,
+                                                          const int* __restrict__ blk_seg, FeDev tb, float* __restrict__ out) {
+    extern __shared__ float s_melw[];
+    const FeSeg s = segs[blk_seg[blockIdx.x]];
+    const float* base = pcm + s.start;
+    const int aligned16 = (((uintptr_t)base & 15) == 0) && (s.len % 4 == 0);  // per block: the segment's own alignment and length
+    fe_main_body<MODE, STDMEL, true, 4, false>(base, s.len, s.num_frames, s.t_lfr, nullptr, tb, out + s.row0 * (tb.n_mels * tb.lfr_m),
+                                               nullptr, aligned16, s_melw, SegBlock{(unsigned)(blockIdx.x - s.block0)});
 }
 // ------------------------------------------------------------------------------------------------------
 // Generic path: any FeatureConfig the reference accepts (other sample rates / frame lengths / n_fft = 1024).
@@ -661,6 +702,7 @@ struct LeleFrontend {
     const float* g_mw = nullptr;
     FeDev dev{};
     std::vector<void*> allocs;
+    DevTables seg_tables;  // compute_segments: [FeSeg x segments][int blk_seg x blocks] per distinct layout
     // optional per-kernel stopwatch (bench.py roofline block): 3 events per run, read back lazily
     bool profiling = false;
     std::vector<hipEvent_t> events;  // triples (before sum, between, after main)
@@ -887,6 +929,7 @@ int lele_hip_frontend_destroy(LeleFrontend* fe) {
     if (!fe) return 0;
     (void)hipStreamSynchronize(fe->ctx->stream);
     for (void* p : fe->allocs) (void)hipFree(p);
+    fe->seg_tables.release();
     for (hipEvent_t e : fe->events) (void)hipEventDestroy(e);
     delete fe;
     return 0;
@@ -911,6 +954,82 @@ static int ilog2_i(int n) {
     while ((1 << (l + 1)) <= n) ++l;
     return l;
 }
+// generic path (FeatureConfigs other than 400 / 160 / 512): `batch` utterances pcm_len samples apart at dpcm -> outp ([batch, t_lfr,
+// cols] or, want_logmel, [batch, nf, n_mels]); dmean: batch * nf floats of scratch
+static int fe_generic(LeleFrontend* fe, const float* dpcm, int64_t batch, int64_t pcm_len, int64_t nf, int64_t t_lfr, int64_t cols,
+                      float* outp, bool want_logmel, void* dmean) {
+    LeleCtx* ctx = fe->ctx;
+    // generic path: as many utterances per pass as fit 256 MiB of scratch (means, frames [rows, n_fft], power [rows, bins], logmel
+    // [rows, mels]; rows = utterances x frames) -- five launches a pass (looping over utterances on the host made the launches
+    // the cost: 256 x 30 s at 16 kHz / 20 ms frames 16.1 ms)
+    const int64_t bins = fe->n_fft / 2 + 1, nm = fe->cfg.n_mels;
+    // the fused form (fe_generic_fused_kernel): frames per workgroup so that their LDS image stays under 64 KB; anything larger
+    // (n_fft > 4096) keeps the four kernels
+    if (fe->fused && fe->n_fft <= 4096 && fe->frame_len <= fe->n_fft && batch <= 65535) {   // (lab: LELE_HIP_FE_FUSED=0 keeps the four kernels)
+        const int n = (int)fe->n_fft;
+        // (the kernel is bound by latency under its barriers, so by occupancy against work per workgroup: 4 frames of 1024 points with
+        // the twiddles in LDS = 55 KB = two workgroups a CU ran 15 ms where the four kernels took 12)
+        int fpb = n <= 512 ? 4 : n <= 1024 ? 2 : 1;   // measured (tools/fe_fpb.sh): n = 512: 3.9 / 2.6 / 2.4 / 3.1 ms for 1 / 2 / 4 / 8; n = 1024: 6.1 / 5.2 / 7.1 / 17.2
+        if (const char* e = lab_env("LELE_HIP_FE_FPB")) fpb = std::max(1, atoi(e));   // (lab) frames per workgroup
+        const size_t padded = (size_t)fpb * n + (((size_t)fpb * n) >> 5) + 1;
+        const size_t lds = (2 * padded + (size_t)fpb * bins + (size_t)(fpb - 1) * fe->hop_len + fe->frame_len + fpb) * 4;
+        if (lds <= 96 * 1024) {
+            const float *twr = nullptr, *twi = nullptr;
+            LELE_TRY(fft_twiddles(ctx, n, &twr, &twi));
+            LELE_HIP_CHECK(ensure_dyn_lds(reinterpret_cast<const void*>(fe_generic_fused_kernel), (int)lds));
+            const int64_t per_utt_lm = nf * nm * 4;
+            const int64_t ubf = want_logmel ? batch : std::max<int64_t>(1, std::min<int64_t>(batch, (int64_t(1) << 28) / std::max<int64_t>(per_utt_lm, 1)));
+            void* glm = nullptr;
+            if (!want_logmel) LELE_TRY(ctx->arena_alloc((size_t)ubf * nf * nm * 4, &glm));
+            for (int64_t u = 0; u < batch; u += ubf) {
+                const int64_t nu = std::min<int64_t>(ubf, batch - u);
+                const float* up = (const float*)dpcm + u * pcm_len;
+                float* lm = want_logmel ? outp + u * nf * nm : (float*)glm;
+                hipLaunchKernelGGL(fe_generic_mean_kernel, dim3((unsigned)((nu * nf + 63) / 64)), dim3(64), 0, ctx->stream, up, nu * nf, nf, pcm_len,
+                                   (int)fe->frame_len, (int)fe->hop_len, (float*)dmean);
+                hipLaunchKernelGGL(fe_generic_fused_kernel, dim3((unsigned)((nf + fpb - 1) / fpb), (unsigned)nu), dim3(256), lds, ctx->stream, up,
+                                   pcm_len, nf, (int)fe->frame_len, (int)fe->hop_len, n, ilog2_i(n), fpb, fe->g_window, twr, twi, (int)nm,
+                                   fe->g_mstart, fe->g_moff, fe->g_mw, (const float*)dmean, lm);
+                if (!want_logmel) {
+                    dim3 lg((unsigned)std::max<int64_t>(1, std::min<int64_t>((t_lfr * cols + 255) / 256, 8192)), (unsigned)nu);
+                    hipLaunchKernelGGL(fe_generic_lfr_kernel, lg, dim3(256), 0, ctx->stream, (const float*)lm, nf, nm, fe->cfg.lfr_m,
+                                       fe->cfg.lfr_n, t_lfr, outp + u * t_lfr * cols);
+                }
+            }
+            LELE_HIP_CHECK(hipGetLastError());
+            return 0;
+        }
+    }
+    const int64_t per_utt = nf * (4 + fe->n_fft * 4 + bins * 4 + nm * 4);
+    const int64_t ub = std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(batch, 65535), (int64_t(1) << 28) / std::max<int64_t>(per_utt, 1)));
+    void *gm = nullptr, *gf = nullptr, *gp = nullptr, *gl = nullptr;
+    LELE_TRY(ctx->arena_alloc((size_t)ub * nf * 4, &gm));
+    LELE_TRY(ctx->arena_alloc((size_t)ub * nf * fe->n_fft * 4, &gf));
+    LELE_TRY(ctx->arena_alloc((size_t)ub * nf * bins * 4, &gp));
+    if (!want_logmel) LELE_TRY(ctx->arena_alloc((size_t)ub * nf * nm * 4, &gl));
+    auto blocks = [](int64_t n) { return dim3((unsigned)std::max<int64_t>(1, std::min<int64_t>((n + 255) / 256, 8192))); };
+    for (int64_t u = 0; u < batch; u += ub) {
+        const int64_t nu = std::min<int64_t>(ub, batch - u), rows = nu * nf;
+        const float* up = (const float*)dpcm + u * pcm_len;
+        float* lm = want_logmel ? outp + u * nf * nm : (float*)gl;
+        hipLaunchKernelGGL(fe_generic_mean_kernel, dim3((unsigned)((rows + 63) / 64)), dim3(64), 0, ctx->stream, up, rows, nf, pcm_len,
+                           (int)fe->frame_len, (int)fe->hop_len, (float*)gm);
+        hipLaunchKernelGGL(fe_generic_frame_kernel, blocks(rows * fe->n_fft), dim3(256), 0, ctx->stream, up, (const float*)gm,
+                           fe->g_window, rows, nf, pcm_len, (int)fe->frame_len, (int)fe->hop_len, (int)fe->n_fft, (float*)gf);
+        LELE_TRY(fft_rows_power(ctx, (const float*)gf, rows, fe->n_fft, (float*)gp));
+        hipLaunchKernelGGL(fe_generic_mel_kernel, blocks(rows * nm), dim3(256), 0, ctx->stream, (const float*)gp, rows, (int)bins,
+                           (int)nm, fe->g_mstart, fe->g_moff, fe->g_mw, lm);
+        if (!want_logmel) {
+            dim3 lg = blocks(t_lfr * cols);
+            lg.y = (unsigned)nu;
+            hipLaunchKernelGGL(fe_generic_lfr_kernel, lg, dim3(256), 0, ctx->stream, (const float*)lm, nf, nm,
+                               fe->cfg.lfr_m, fe->cfg.lfr_n, t_lfr, outp + u * t_lfr * cols);
+        }
+    }
+    LELE_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
 static int fe_run(LeleFrontend* fe, const LeleTensor* pcm, int64_t batch, int64_t pcm_len, LeleBuf* out,
                   bool want_logmel, int64_t* out_shape, int32_t* out_rank) {
     LeleCtx* ctx = fe->ctx;
@@ -931,81 +1050,10 @@ static int fe_run(LeleFrontend* fe, const LeleTensor* pcm, int64_t batch, int64_
     const size_t out_elems = want_logmel ? (size_t)batch * nf * fe->cfg.n_mels : (size_t)batch * t_lfr * cols;
     LELE_TRY(out->reserve(out_elems * sizeof(float)));
     if (!fe->fast) {
-        // generic path: as many utterances per pass as fit 256 MiB of scratch (means, frames [rows, n_fft], power [rows, bins], logmel
-        // [rows, mels]; rows = utterances x frames) -- five launches a pass (looping over utterances on the host made the launches
-        // the cost: 256 x 30 s at 16 kHz / 20 ms frames 16.1 ms)
-        const int64_t bins = fe->n_fft / 2 + 1, nm = fe->cfg.n_mels;
-        // the fused form (fe_generic_fused_kernel): frames per workgroup so that their LDS image stays under 64 KB; anything larger
-        // (n_fft > 4096) keeps the four kernels
-        if (fe->fused && fe->n_fft <= 4096 && fe->frame_len <= fe->n_fft && batch <= 65535) {   // (lab: LELE_HIP_FE_FUSED=0 keeps the four kernels)
-            const int n = (int)fe->n_fft;
-            // (the kernel is bound by latency under its barriers, so by occupancy against work per workgroup: 4 frames of 1024 points with
-            // the twiddles in LDS = 55 KB = two workgroups a CU ran 15 ms where the four kernels took 12)
-            int fpb = n <= 512 ? 4 : n <= 1024 ? 2 : 1;   // measured (tools/fe_fpb.sh): n = 512: 3.9 / 2.6 / 2.4 / 3.1 ms for 1 / 2 / 4 / 8; n = 1024: 6.1 / 5.2 / 7.1 / 17.2
-            if (const char* e = lab_env("LELE_HIP_FE_FPB")) fpb = std::max(1, atoi(e));   // (lab) frames per workgroup
-            const size_t padded = (size_t)fpb * n + (((size_t)fpb * n) >> 5) + 1;
-            const size_t lds = (2 * padded + (size_t)fpb * bins + (size_t)(fpb - 1) * fe->hop_len + fe->frame_len + fpb) * 4;
-            if (lds <= 96 * 1024) {
-                const float *twr = nullptr, *twi = nullptr;
-                LELE_TRY(fft_twiddles(ctx, n, &twr, &twi));
-                LELE_HIP_CHECK(ensure_dyn_lds(reinterpret_cast<const void*>(fe_generic_fused_kernel), (int)lds));
-                const int64_t per_utt_lm = nf * nm * 4;
-                const int64_t ubf = want_logmel ? batch : std::max<int64_t>(1, std::min<int64_t>(batch, (int64_t(1) << 28) / std::max<int64_t>(per_utt_lm, 1)));
-                void* glm = nullptr;
-                if (!want_logmel) LELE_TRY(ctx->arena_alloc((size_t)ubf * nf * nm * 4, &glm));
-                for (int64_t u = 0; u < batch; u += ubf) {
-                    const int64_t nu = std::min<int64_t>(ubf, batch - u);
-                    const float* up = (const float*)dpcm + u * pcm_len;
-                    float* lm = want_logmel ? (float*)out->data + u * nf * nm : (float*)glm;
-                    hipLaunchKernelGGL(fe_generic_mean_kernel, dim3((unsigned)((nu * nf + 63) / 64)), dim3(64), 0, ctx->stream, up, nu * nf, nf, pcm_len,
-                                       (int)fe->frame_len, (int)fe->hop_len, (float*)dmean);
-                    hipLaunchKernelGGL(fe_generic_fused_kernel, dim3((unsigned)((nf + fpb - 1) / fpb), (unsigned)nu), dim3(256), lds, ctx->stream, up,
-                                       pcm_len, nf, (int)fe->frame_len, (int)fe->hop_len, n, ilog2_i(n), fpb, fe->g_window, twr, twi, (int)nm,
-                                       fe->g_mstart, fe->g_moff, fe->g_mw, (const float*)dmean, lm);
-                    if (!want_logmel) {
-                        dim3 lg((unsigned)std::max<int64_t>(1, std::min<int64_t>((t_lfr * cols + 255) / 256, 8192)), (unsigned)nu);
-                        hipLaunchKernelGGL(fe_generic_lfr_kernel, lg, dim3(256), 0, ctx->stream, (const float*)lm, nf, nm, fe->cfg.lfr_m,
-                                           fe->cfg.lfr_n, t_lfr, (float*)out->data + u * t_lfr * cols);
-                    }
-                }
-                LELE_HIP_CHECK(hipGetLastError());
-                if (want_logmel) {
-                    if (batch == 1) return set_shape(out_shape, out_rank, {nf, nm});
-                    return set_shape(out_shape, out_rank, {batch, nf, nm});
-                }
-                return 0;
-            }
-        }
-        const int64_t per_utt = nf * (4 + fe->n_fft * 4 + bins * 4 + nm * 4);
-        const int64_t ub = std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(batch, 65535), (int64_t(1) << 28) / std::max<int64_t>(per_utt, 1)));
-        void *gm = nullptr, *gf = nullptr, *gp = nullptr, *gl = nullptr;
-        LELE_TRY(ctx->arena_alloc((size_t)ub * nf * 4, &gm));
-        LELE_TRY(ctx->arena_alloc((size_t)ub * nf * fe->n_fft * 4, &gf));
-        LELE_TRY(ctx->arena_alloc((size_t)ub * nf * bins * 4, &gp));
-        if (!want_logmel) LELE_TRY(ctx->arena_alloc((size_t)ub * nf * nm * 4, &gl));
-        auto blocks = [](int64_t n) { return dim3((unsigned)std::max<int64_t>(1, std::min<int64_t>((n + 255) / 256, 8192))); };
-        for (int64_t u = 0; u < batch; u += ub) {
-            const int64_t nu = std::min<int64_t>(ub, batch - u), rows = nu * nf;
-            const float* up = (const float*)dpcm + u * pcm_len;
-            float* lm = want_logmel ? (float*)out->data + u * nf * nm : (float*)gl;
-            hipLaunchKernelGGL(fe_generic_mean_kernel, dim3((unsigned)((rows + 63) / 64)), dim3(64), 0, ctx->stream, up, rows, nf, pcm_len,
-                               (int)fe->frame_len, (int)fe->hop_len, (float*)gm);
-            hipLaunchKernelGGL(fe_generic_frame_kernel, blocks(rows * fe->n_fft), dim3(256), 0, ctx->stream, up, (const float*)gm,
-                               fe->g_window, rows, nf, pcm_len, (int)fe->frame_len, (int)fe->hop_len, (int)fe->n_fft, (float*)gf);
-            LELE_TRY(fft_rows_power(ctx, (const float*)gf, rows, fe->n_fft, (float*)gp));
-            hipLaunchKernelGGL(fe_generic_mel_kernel, blocks(rows * nm), dim3(256), 0, ctx->stream, (const float*)gp, rows, (int)bins,
-                               (int)nm, fe->g_mstart, fe->g_moff, fe->g_mw, lm);
-            if (!want_logmel) {
-                dim3 lg = blocks(t_lfr * cols);
-                lg.y = (unsigned)nu;
-                hipLaunchKernelGGL(fe_generic_lfr_kernel, lg, dim3(256), 0, ctx->stream, (const float*)lm, nf, nm,
-                                   fe->cfg.lfr_m, fe->cfg.lfr_n, t_lfr, (float*)out->data + u * t_lfr * cols);
-            }
-        }
-        LELE_HIP_CHECK(hipGetLastError());
+        LELE_TRY(fe_generic(fe, (const float*)dpcm, batch, pcm_len, nf, t_lfr, cols, (float*)out->data, want_logmel, dmean));
         if (want_logmel) {
-            if (batch == 1) return set_shape(out_shape, out_rank, {nf, nm});
-            return set_shape(out_shape, out_rank, {batch, nf, nm});
+            if (batch == 1) return set_shape(out_shape, out_rank, {nf, fe->cfg.n_mels});
+            return set_shape(out_shape, out_rank, {batch, nf, fe->cfg.n_mels});
         }
         return 0;
     }
@@ -1085,6 +1133,107 @@ int lele_hip_frontend_logmel(LeleFrontend* fe, const LeleTensor* pcm, LeleBuf* o
     LELE_REQUIRE(fe && pcm && out, "frontend_logmel: NULL argument");
     if (pcm->rank == 2) return fe_run(fe, pcm, pcm->shape[0], pcm->shape[1], out, true, out_shape, out_rank);
     return fe_run(fe, pcm, 1, numel(pcm), out, true, out_shape, out_rank);
+}
+
+/* Segments of one PCM buffer in one launch pair (see lele_hip.h).  Validation first (nothing is launched and `out` is untouched on
+ * failure), then the packed row offsets, then either the segment-aware kernels (default config) or, on the generic path, the
+ * generic kernels once per segment. */
+struct SegLayout {  // host inputs of the table builder below
+    const LeleFrontend* fe;
+    const int64_t* starts;
+    const int64_t* lengths;
+    int64_t count;
+    const int64_t* rows;  // row_offsets
+};
+static void build_seg_table(const void* arg, std::vector<char>& blob) {
+    const SegLayout& L = *(const SegLayout*)arg;
+    std::vector<FeSeg> segs;
+    std::vector<int> blk;
+    for (int64_t i = 0; i < L.count; ++i) {
+        int64_t t = 0, nf = 0;
+        lele_hip_frontend_out_rows(L.fe, L.lengths[i], &t, nullptr, &nf);
+        if (nf == 0) continue;
+        const int64_t nb = (nf + 63) / 64;
+        segs.push_back(FeSeg{L.starts[i], L.lengths[i], nf, t, L.rows[i], (int64_t)blk.size()});
+        blk.insert(blk.end(), (size_t)nb, (int)segs.size() - 1);
+    }
+    blob.resize(segs.size() * sizeof(FeSeg) + blk.size() * sizeof(int));
+    memcpy(blob.data(), segs.data(), segs.size() * sizeof(FeSeg));
+    memcpy(blob.data() + segs.size() * sizeof(FeSeg), blk.data(), blk.size() * sizeof(int));
+}
+
+int lele_hip_frontend_compute_segments(LeleFrontend* fe, const LeleTensor* pcm, const int64_t* starts, const int64_t* lengths, int64_t count,
+                                       LeleBuf* out, int64_t* row_offsets, int64_t* out_shape, int32_t* out_rank) {
+    LELE_REQUIRE(fe && pcm && out && row_offsets, "frontend_compute_segments: NULL argument");
+    LELE_REQUIRE(count >= 0 && (count == 0 || (starts && lengths)), "frontend_compute_segments: bad segment arrays (count %lld)",
+                 (long long)count);
+    LELE_REQUIRE(pcm->dtype == LELE_F32 && pcm->rank == 1, "frontend_compute_segments: pcm must be f32 [N]");
+    const int64_t n = pcm->shape[0];
+    for (int64_t i = 0; i < count; ++i)
+        LELE_REQUIRE(starts[i] >= 0 && lengths[i] >= 0 && starts[i] <= n - lengths[i],
+                     "frontend_compute_segments: segment %lld (start %lld, length %lld) lies outside the %lld samples of pcm", (long long)i,
+                     (long long)starts[i], (long long)lengths[i], (long long)n);
+    int64_t cols = fe->cfg.n_mels * fe->cfg.lfr_m, blocks = 0, max_nf = 0;
+    row_offsets[0] = 0;
+    for (int64_t i = 0; i < count; ++i) {
+        int64_t t = 0, nf = 0;
+        lele_hip_frontend_out_rows(fe, lengths[i], &t, nullptr, &nf);
+        row_offsets[i + 1] = row_offsets[i] + t;
+        blocks += (nf + 63) / 64;
+        max_nf = std::max(max_nf, nf);
+    }
+    const int64_t rows = row_offsets[count];
+    if (rows == 0) {  // no segment holds a frame: TensorView::empty()
+        out->bytes = 0;
+        if (out_rank) *out_rank = 0;
+        return 0;
+    }
+    LELE_REQUIRE(blocks < (int64_t(1) << 31), "frontend_compute_segments: %lld blocks exceed the grid", (long long)blocks);
+    LeleCtx* ctx = fe->ctx;
+    LELE_HIP_CHECK(hipSetDevice(ctx->device));
+    LELE_TRY(ctx->arena_reset());
+    const void* dpcm = nullptr;
+    LELE_TRY(ctx->dev_ptr(pcm, &dpcm));
+    LELE_TRY(out->reserve((size_t)rows * cols * sizeof(float)));
+    float* o = (float*)out->data;
+    if (!fe->fast) {
+        // generic path: correct, not fast -- the generic kernels once per segment (they take equal-length batches only); the arena
+        // scratch of one segment is reused by the next, which the stream orders after it
+        void* dmean = nullptr;
+        LELE_TRY(ctx->get_scratch((size_t)max_nf * sizeof(float), &dmean));
+        const size_t mark = ctx->arena_used;
+        for (int64_t i = 0; i < count; ++i) {
+            int64_t t = 0, nf = 0;
+            lele_hip_frontend_out_rows(fe, lengths[i], &t, nullptr, &nf);
+            if (nf == 0) continue;
+            LELE_TRY(fe_generic(fe, (const float*)dpcm + starts[i], 1, lengths[i], nf, t, cols, o + row_offsets[i] * cols, false, dmean));
+            ctx->arena_used = mark;
+        }
+        return set_shape(out_shape, out_rank, {rows, cols});
+    }
+    // the layout's device table (shape metadata: uploaded once per distinct layout, never rewritten -- safe under graph capture)
+    std::string key((size_t)count * 16, '\0');
+    memcpy(&key[0], starts, (size_t)count * 8);
+    memcpy(&key[(size_t)count * 8], lengths, (size_t)count * 8);
+    const SegLayout lay{fe, starts, lengths, count, row_offsets};
+    const void* table = nullptr;
+    LELE_TRY(fe->seg_tables.get(ctx, std::move(key), build_seg_table, &lay, &table));
+    int64_t nseg = 0;
+    for (int64_t i = 0; i < count; ++i) nseg += lengths[i] >= fe->frame_len;
+    const FeSeg* dsegs = (const FeSeg*)table;
+    const int* dblk = (const int*)(dsegs + nseg);
+    const size_t mel_lds = (size_t)fe->dev.mel_steps * 16 * sizeof(float);
+#define FE_SEG_LAUNCH(MODE, STD)                                                                                                 \
+    hipLaunchKernelGGL((fe_seg_main_kernel<MODE, STD>), dim3((unsigned)blocks), dim3(256), mel_lds, ctx->stream, (const float*)dpcm, \
+                       dsegs, dblk, fe->dev, o)
+    if (fe->dpp_mode == 1) {
+        if (fe->std_mel) FE_SEG_LAUNCH(1, true); else FE_SEG_LAUNCH(1, false);
+    } else {
+        if (fe->std_mel) FE_SEG_LAUNCH(0, true); else FE_SEG_LAUNCH(0, false);
+    }
+#undef FE_SEG_LAUNCH
+    LELE_HIP_CHECK(hipGetLastError());
+    return set_shape(out_shape, out_rank, {rows, cols});
 }
 
 int lele_hip_frontend_set_profiling(LeleFrontend* fe, int on) {

@@ -75,9 +75,36 @@ class SenseVoiceFrontend:
         """pcm [batch, pcm_len] -> [batch, T, n_mels*lfr_m] (one launch pair for the whole batch)"""
         return self._call(_lib.lib().lele_hip_frontend_compute_batch, pcm, out)
 
+    def compute_segments(self, pcm, segments, out=None):
+        """Features of several (start, end) sample ranges of ONE pcm buffer [N] in one launch -- `segments` as apps.vad_segments
+        returns them (any order; overlaps and repeats allowed).  -> (TensorView [R, n_mels*lfr_m], offsets np.int64 [count + 1]):
+        rows offsets[i] .. offsets[i+1] are compute(pcm[start_i:end_i]), bit for bit (0 rows for a range shorter than one frame)."""
+        seg = np.asarray(segments, np.int64).reshape(-1, 2)
+        starts = np.ascontiguousarray(seg[:, 0])
+        lengths = np.ascontiguousarray(seg[:, 1] - seg[:, 0])
+        offsets = np.zeros(len(seg) + 1, np.int64)
+        keep = []
+        t = _lib.as_tensor(unwrap(pcm), keep)
+        sh = _lib.OutShape()
+        out = out or self._out
+        _lib.check(_lib.lib().lele_hip_frontend_compute_segments(self._h, t, _lib.i64_ptr(starts), _lib.i64_ptr(lengths), len(seg), out._h,
+                                                                 _lib.i64_ptr(offsets), sh.shape, C.byref(sh.rank)))
+        if sh.rank.value == 0:
+            return TensorView.empty(), offsets
+        return TensorView(_lib.DevTensor(out, sh.get(), np.float32)), offsets
+
     def logmel(self, pcm, out=None):
         """intermediate log-mel [num_frames, n_mels] (before LFR); test hook"""
         return self._call(_lib.lib().lele_hip_frontend_logmel, pcm, out)
+
+
+def pack(arrays):
+    """list of 1-D PCM arrays -> (pcm f32 [sum of lengths], [(start, end)]): one buffer for compute_segments"""
+    arrays = [np.asarray(a, np.float32).reshape(-1) for a in arrays]
+    ends = np.cumsum([len(a) for a in arrays], dtype=np.int64)
+    starts = ends - np.asarray([len(a) for a in arrays], np.int64)
+    pcm = np.concatenate(arrays) if arrays else np.zeros(0, np.float32)
+    return pcm, [(int(s), int(e)) for s, e in zip(starts, ends)]
 
 
 def _op(ctx, fn, tensors, extra, out=None, dtype=np.float32, prefix=()):
@@ -108,6 +135,15 @@ class Cmvn:  # cmvn.rs
 
     def compute(self, x, out=None):
         return _op(self.ctx, _lib.lib().lele_hip_cmvn, [x], [C.c_float(self.eps)], out)
+
+    def compute_segments(self, x, offsets, out=None):
+        """x [R, D] packed as compute_segments returns it, offsets [count + 1]: each segment normalised with its own statistics (bit
+        for bit compute() on its rows alone; 0-row segments are skipped)"""
+        off = np.ascontiguousarray(offsets, np.int64)
+        if int(off[-1]) == 0:
+            return TensorView.empty()
+        return _op(self.ctx, _lib.lib().lele_hip_cmvn_segments, [x], [_lib.i64_ptr(off), C.c_int64(len(off) - 1), C.c_float(self.eps)],
+                   out)
 
     def apply_with_stats(self, x, mean, std, out=None):
         ctx = _ctx(self.ctx)

@@ -19,6 +19,7 @@
 #include <memory>
 #include <stdexcept>
 #include <string>
+#include <utility>
 #include <vector>
 
 namespace lele {
@@ -1101,6 +1102,23 @@ class SenseVoiceFrontend {  // pipeline.rs:29-193
         check(lele_hip_frontend_compute_batch(h_, &t, out.raw(), sh.dims, &sh.rank));
         return TensorView::from_device(out, sh.vec());
     }
+    // several (start, end) sample ranges of ONE pcm buffer [N] in one launch -> the packed [R, n_mels*lfr_m]; offsets (count + 1,
+    // written) delimit each range's rows, which are compute() of that range bit for bit.  Empty TensorView when no range holds a frame.
+    TensorView compute_segments(const TensorView& pcm, const std::vector<std::pair<int64_t, int64_t>>& segments, Buffer& out,
+                                std::vector<int64_t>& offsets) const {
+        std::vector<int64_t> starts, lengths;
+        for (const auto& s : segments) {
+            starts.push_back(s.first);
+            lengths.push_back(s.second - s.first);
+        }
+        offsets.assign(segments.size() + 1, 0);
+        Shape sh;
+        LeleTensor t = pcm.c();
+        check(lele_hip_frontend_compute_segments(h_, &t, starts.data(), lengths.data(), (int64_t)segments.size(), out.raw(), offsets.data(),
+                                                 sh.dims, &sh.rank));
+        if (sh.rank == 0) return TensorView();
+        return TensorView::from_device(out, sh.vec());
+    }
 
    private:
     LeleFrontend* h_ = nullptr;
@@ -1112,6 +1130,13 @@ struct Cmvn {  // cmvn.rs
         Shape sh;
         LeleTensor t = x.c();
         check(lele_hip_cmvn(detail::ctx(), &t, eps, out.raw(), sh.dims, &sh.rank));
+        return TensorView::from_device(out, sh.vec());
+    }
+    // each segment of a packed x [R, D] (offsets from SenseVoiceFrontend::compute_segments) with its own statistics
+    TensorView compute_segments(const TensorView& x, const std::vector<int64_t>& offsets, Buffer& out) const {
+        Shape sh;
+        LeleTensor t = x.c();
+        check(lele_hip_cmvn_segments(detail::ctx(), &t, offsets.data(), (int64_t)offsets.size() - 1, eps, out.raw(), sh.dims, &sh.rank));
         return TensorView::from_device(out, sh.vec());
     }
 };

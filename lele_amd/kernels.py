@@ -35,6 +35,18 @@ def stft_power_spectrum(input, n_fft, hop_length, win_length, window=None, out=N
     return TensorView(_lib.DevTensor(out, sh.get(), np.float32))
 
 
+def segments_to_padded(x, offsets, t_max=0, pad=0.0, out=None, ctx=None):
+    """packed x [R, D] + offsets [count + 1] (SenseVoiceFrontend.compute_segments) -> ([count, t_max, D], lengths np.int64 [count]):
+    segment b's rows, then `pad`; t_max = 0 takes the longest segment.  The [B, T, D] + speech_lengths form of a padded encoder."""
+    off = np.ascontiguousarray(offsets, np.int64)
+    lengths = np.diff(off)
+    if len(x.shape) != 2:  # every segment empty (TensorView.empty()): R = 0 rows of unknown width
+        raise _lib.LeleError("segments_to_padded: x must be [R, D]")
+    y = _op(ctx, _lib.lib().lele_hip_segments_to_padded, [x], [_lib.i64_ptr(off), C.c_int64(len(off) - 1), C.c_int64(t_max), C.c_float(pad)],
+            out)
+    return y, lengths
+
+
 def _call(fn, tensors, extra=(), out=None, ctx=None, dtype=np.float32):
     """generic C-ABI call: fn(ctx, *tensors, *extra, out, out_shape, out_rank) -> TensorView"""
     return _op(ctx, fn, tensors, list(extra), out, dtype)

@@ -178,6 +178,18 @@ impl Cmvn {
         rt::check(unsafe { ffi::lele_hip_cmvn(rt::ctx(), input.as_c().ptr(), self.eps, keep.slot().raw(), sh.dims(), sh.rank()) });
         TensorView::device_owned(keep, sh.vec())
     }
+    /// beyond upstream: each segment of a packed [R, D] (offsets from `SenseVoiceFrontend::compute_segments`) normalised with its own
+    /// statistics, bit for bit `compute` on its rows alone
+    pub fn compute_segments(&self, input: &TensorView, offsets: &[usize]) -> TensorView<'static> {
+        let off: Vec<i64> = offsets.iter().map(|&o| o as i64).collect();
+        let keep = rt::pooled_slot();
+        let mut sh = Shape::new();
+        rt::check(unsafe {
+            ffi::lele_hip_cmvn_segments(rt::ctx(), input.as_c().ptr(), off.as_ptr(), off.len() as i64 - 1, self.eps, keep.slot().raw(),
+                                        sh.dims(), sh.rank())
+        });
+        TensorView::device_owned(keep, sh.vec())
+    }
     /// cmvn.rs:67-92
     pub fn apply_with_stats(&self, input: &TensorView, mean: &[f32], std: &[f32]) -> TensorView<'static> {
         let (m, s) = (TensorView::from_slice(mean, vec![mean.len()]), TensorView::from_slice(std, vec![std.len()]));
@@ -241,6 +253,26 @@ impl SenseVoiceFrontend {
         let mut sh = Shape::new();
         rt::check(unsafe { ffi::lele_hip_frontend_compute_batch(self.h, pcm.as_c().ptr(), keep.slot().raw(), sh.dims(), sh.rank()) });
         TensorView::device_owned(keep, sh.vec())
+    }
+    /// beyond upstream: several `(start, end)` sample ranges of ONE pcm buffer in one launch (VAD segments, a queue of utterances
+    /// packed back to back) -> (the packed [R, n_mels * lfr_m], row offsets [count + 1]); rows `offsets[i]..offsets[i + 1]` are
+    /// `compute(&pcm[start..end])` of range i, bit for bit (none for a range shorter than one frame)
+    pub fn compute_segments(&self, pcm: &[f32], segments: &[(usize, usize)]) -> (TensorView<'static>, Vec<usize>) {
+        let x = TensorView::from_slice(pcm, vec![pcm.len()]);
+        let starts: Vec<i64> = segments.iter().map(|s| s.0 as i64).collect();
+        let lengths: Vec<i64> = segments.iter().map(|s| s.1 as i64 - s.0 as i64).collect();
+        let mut offsets = vec![0i64; segments.len() + 1];
+        let keep = rt::pooled_slot();
+        let mut sh = Shape::new();
+        rt::check(unsafe {
+            ffi::lele_hip_frontend_compute_segments(self.h, x.as_c().ptr(), starts.as_ptr(), lengths.as_ptr(), segments.len() as i64,
+                                                    keep.slot().raw(), offsets.as_mut_ptr(), sh.dims(), sh.rank())
+        });
+        let offsets = offsets.iter().map(|&o| o as usize).collect();
+        if sh.vec().iter().product::<usize>() == 0 {
+            return (TensorView::empty(), offsets);
+        }
+        (TensorView::device_owned(keep, sh.vec()), offsets)
     }
 }
 impl Drop for SenseVoiceFrontend {
