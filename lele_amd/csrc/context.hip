@@ -342,6 +342,10 @@ int lele_hip_graph_begin(LeleCtx* c) {
         ps.arena_overflow.clear();
         ps.arena_used = 0;
     }
+    // {min, max} pairs published before the capture describe the buffers' contents NOW; a recorded consumer would bake them in and
+    // replay them after the caller has uploaded new contents (quant.hip, find_partials).  Only a producer recorded in this capture
+    // may hand its statistics to a recorded consumer.
+    for (auto& kv : c->buf_of_data) kv.second->rowstat_valid = false;
     LELE_HIP_CHECK(hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
     c->capturing = true;
     for (auto& t : c->lane_tail) t.clear();

@@ -671,10 +671,11 @@ def test_sanm_out_block_is_the_three_calls_bit_for_bit(ctx, orc, b, t, res2, fbi
         got = K.sanm_out_block(av_d, *W, False, qkv_d, fw, fb, koff, pads[0], pads[1], r2, g1, b1, 1e-5, ctx=ctx)
         assert np.array_equal(got[0].numpy(), want[0]), (b, t, rep, float(np.abs(got[0].numpy() - want[0]).max()))
         assert np.array_equal(got[1].numpy(), want[1]), (b, t, rep)
-    if (b, t) == (40, 100):
+    if (b, t) in ((40, 100), (32, 171), (1, 504)) and pads == (5, 5):   # and the production shapes: one launch, and the three calls
         from oracle import plan_ref
         o = plan_ref.PlanRef({"statements": [], "weights": {}, "outputs": [], "inputs": []}, {}).call(
-            "sanm_out_block", [av, w, ws, np.array([128.0], np.float32), bias, False, qkv, fw.arr, None, koff, 5, 5, r2, g1.arr, b1.arr, 1e-5])
+            "sanm_out_block", [av, w, ws, np.array([128.0], np.float32), bias, False, qkv, fw.arr, fb.arr if fbias else None, koff, 5, 5, r2,
+                               g1.arr, b1.arr, 1e-5])
         # against the oracle's sequence the bar is the convolution's (1e-4: the oracle's conv1d restates lele's dot loops, the device's
         # depthwise kernels chain FMAs -- tests/test_conv_rnn.py), everything around it is exact
         from tests.parity import close_f32
@@ -708,7 +709,8 @@ def test_feed_forward_block_and_next_layer_norm_as_one_call(ctx, orc, b, m, nres
         assert np.array_equal(got[0].numpy(), want[0]) and np.array_equal(got[1].numpy(), want[1]), (b, m, nres, rep)
     nxt = K.fused_quantized_linear(K.layer_norm(y, g1, b1, -1, 1e-5, ctx=ctx), *W1, True, ctx=ctx).numpy()
     assert np.array_equal(K.fused_quantized_linear(got[1], *W1, True, ctx=ctx).numpy(), nxt)
-    if (b, m) == (3, 1000):
+    if (b, m, nres) in ((3, 1000, 1), (32, 171, 2), (1, 504, 1)):   # igemm_ask_kernel's epilogue at (32, 171); the two calls at (1, 504)
         h = orc.fused_quantized_linear(xn.numpy(), w1, ws1, [128.0], bias1, relu=True)
         o = orc.fused_quantized_linear(h, w2, ws2, [127.0], bias2) + r1
+        o = o + r2 if r2 is not None else o
         assert np.array_equal(want[0], o) and np.array_equal(want[1], orc.layer_norm(o, g1.arr, b1.arr, -1, 1e-5))
