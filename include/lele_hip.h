@@ -365,6 +365,13 @@ int lele_hip_conv2d_res(LeleCtx* ctx, const LeleTensor* x, const LeleTensor* w, 
  * 2-D convolutions issued on ctx since the last reset, as call count and multiply-accumulate count */
 int lele_hip_conv_stats_reset(LeleCtx* ctx);
 int lele_hip_conv_stats(LeleCtx* ctx, int64_t* calls, int64_t* macs);
+/* The kernel route the most recent f32 GEMM or convolution call on ctx dispatched (matmul, matmul_fused_add, gemm, matmul_view,
+ * conv2d*, conv1d, conv_transpose, the f32 form of conv_integer): its levels joined by '/', e.g. "gemm.tile64x64",
+ * "conv.win3_oct32_osplit" or "conv.gemm_tap/gemm.small"; "" when the result was empty.  Recorded on the host when the call is
+ * issued (a call recorded into a graph reports the route it recorded).  NUL-terminated into buf; an error when cap is too small.
+ * lele_hip_route_names: every level name a route can hold, one per line; host only, no GPU needed. */
+int lele_hip_last_route(LeleCtx* ctx, char* buf, size_t cap);
+int lele_hip_route_names(char* buf, size_t cap);
 /* conv1d (conv1d.rs:837) / conv1d_fused (conv1d.rs:1464: relu != 0).  x [N,C,L], w [C_out,C_in/g,K], pads [left,right] */
 int lele_hip_conv1d(LeleCtx* ctx, const LeleTensor* x, const LeleTensor* w, const LeleTensor* bias,
                     const int64_t* dilations, size_t ndil, int64_t group, const int64_t* pads, size_t npads,

@@ -1452,7 +1452,11 @@ inline WinTile pick_win_tile(int ow, int oh, int positions, int ks, int stride, 
 
 int run_conv2d(LeleCtx* ctx, const LeleTensor* wt, const float* dx, const float* dw, const float* db, ConvGeom g, int act,
                float* out) {
+    ctx->set_route(nullptr);
     if ((int64_t)g.n * g.oc * g.plane == 0) return 0;
+    // no input channels (K = 0): the result is bias + activation (+ residual), which the implicit GEMM's epilogue alone produces
+    // (gemm::launch reads no operand then); every other route assumes at least one channel chunk
+    const bool empty_k = g.K == 0;
     const bool pitched = (g.xbs != 0 && g.xbs != (long long)g.c * g.ih * g.iw) || (g.obs != 0 && g.obs != (long long)g.oc * g.plane);
     if (g.xbs == 0) g.xbs = (long long)g.c * g.ih * g.iw;
     if (g.obs == 0) g.obs = (long long)g.oc * g.plane;
@@ -1484,28 +1488,36 @@ int run_conv2d(LeleCtx* ctx, const LeleTensor* wt, const float* dx, const float*
 #define LELE_DW_LDS(KW) \
     hipLaunchKernelGGL(depthwise_lds_kernel<KW>, lgrid, dim3(256), lds, ctx->stream, dx, dw, db, out, dg, act, (unsigned)planes, \
                        (unsigned)pb, ngroups)
+            static const char* const names[2][4] = {{"conv.dw_lds_k3", "conv.dw_lds_k5", "conv.dw_lds_k7", "conv.dw_lds_k11"},
+                                                    {"conv.dw_lds_k3_direct", "conv.dw_lds_k5_direct", "conv.dw_lds_k7_direct", "conv.dw_lds_k11_direct"}};
             if (g.kw == 3) LELE_DW_LDS(3);
             else if (g.kw == 5) LELE_DW_LDS(5);
             else if (g.kw == 7) LELE_DW_LDS(7);
             else LELE_DW_LDS(11);
+            ctx->set_route(names[dw_direct][g.kw == 3 ? 0 : g.kw == 5 ? 1 : g.kw == 7 ? 2 : 3]);
 #undef LELE_DW_LDS
         } else if (row_ok && g.kw == 3) {
             LELE_DW_ROW(3);
+            ctx->set_route("conv.dw_row4_k3");
         } else if (row_ok && g.kw == 5) {
             LELE_DW_ROW(5);
+            ctx->set_route("conv.dw_row4_k5");
         } else if (row_ok && g.kw == 7) {
             LELE_DW_ROW(7);
+            ctx->set_route("conv.dw_row4_k7");
         } else if (row_ok && g.kw == 11) {
             LELE_DW_ROW(11);
+            ctx->set_route("conv.dw_row4_k11");
 #undef LELE_DW_ROW
         } else {
             hipLaunchKernelGGL(depthwise_conv2d_kernel, dim3(grid_for(total)), dim3(256), 0, ctx->stream, dx, dw, db, out, g, act,
                                (unsigned)total);
+            ctx->set_route("conv.dw_generic");
         }
         if (g.res)
             hipLaunchKernelGGL(conv_residual_kernel, dim3((unsigned)std::min<int64_t>(((int64_t)g.oc * g.plane + 255) / 256, 1024), (unsigned)g.n),
                                dim3(256), 0, ctx->stream, out, g.res, (unsigned)((int64_t)g.oc * g.plane), g.obs, g.rbs);
-    } else if (g.group == 1 &&
+    } else if (g.group == 1 && !empty_k &&
                ((g.kh == 3 && g.kw == 3) ||
                 // 1 x 1: where it measured faster than the tiled GEMM on the Yolo-shaped network at batch 64 (w1_max_oc() and friends above)
                 (g.kh == 1 && g.kw == 1 && g.pt == 0 && g.pl == 0 && g.oh == g.ih && g.ow == g.iw && g.oc <= w1_max_oc() && g.plane >= w1_min_plane() &&
@@ -1590,7 +1602,11 @@ int run_conv2d(LeleCtx* ctx, const LeleTensor* wt, const float* dx, const float*
             else LELE_CW(1, 32);
         }
 #undef LELE_CW
-    } else if (g.group == 1 && g.kh == 3 && g.kw == 3 && g.dh == 1 && g.dw == 1 && g.sh == 2 && g.sw == 2 && g.c % 16 == 0 && g.oc > 16 &&
+        static const char* const names[2][2][3] = {
+            {{"conv.win1_oct32", "conv.win1_oct64", "conv.win1_oct128"}, {"conv.win1_oct32_osplit", "conv.win1_oct64_osplit", "conv.win1_oct128_osplit"}},
+            {{"conv.win3_oct32", "conv.win3_oct64", nullptr}, {"conv.win3_oct32_osplit", "conv.win3_oct64_osplit", nullptr}}};
+        ctx->set_route(names[taps == 9][osplit > 1][oct == 32 ? 0 : oct == 64 ? 1 : 2]);
+    } else if (g.group == 1 && !empty_k && g.kh == 3 && g.kw == 3 && g.dh == 1 && g.dw == 1 && g.sh == 2 && g.sw == 2 && g.c % 16 == 0 && g.oc > 16 &&
                g.ow >= 16 && g.n <= 65535 && (int64_t)g.c * g.ih * g.iw < (int64_t(1) << 31) &&
                (int64_t)g.n * ((g.oc + 63) / 64) * (((int64_t)g.plane + 127) / 128) >= 2 * (int64_t)ctx->num_cus &&
                !lab_env("LELE_HIP_CONV_NO_S2_WINDOW")) {
@@ -1633,7 +1649,9 @@ int run_conv2d(LeleCtx* ctx, const LeleTensor* wt, const float* dx, const float*
             LELE_HIP_CHECK(lele::ensure_dyn_lds(reinterpret_cast<const void*>(kern), C3S2::STAGE));
             hipLaunchKernelGGL(kern, pgrid, dim3(512), C3S2::STAGE, ctx->stream, dx, (const cu32x4*)dwf, epi, tile, ntiles, nocb, osplit, (int)items);
         }
-    } else if (g.group == 1 && g.kh == 3 && g.kw == 3 && g.dh == 1 && g.dw == 1 && g.sh == g.sw && (g.sh == 1 || g.sh == 2) && g.oc <= 16 &&
+        static const char* const names[2][2] = {{"conv.win3s2_oct32", "conv.win3s2_oct64"}, {"conv.win3s2_oct32_osplit", "conv.win3s2_oct64_osplit"}};
+        ctx->set_route(names[osplit > 1][oct == 64]);
+    } else if (g.group == 1 && !empty_k && g.kh == 3 && g.kw == 3 && g.dh == 1 && g.dw == 1 && g.sh == g.sw && (g.sh == 1 || g.sh == 2) && g.oc <= 16 &&
                g.c <= 64 && g.ow >= 16 && g.n <= 65535 &&
                (int64_t)g.n * ((g.ow + 31) / 32) * ((g.oh + 7) / 8) >= 2 * (int64_t)ctx->num_cus) {
         // few channels over a batch: the direct kernel (see conv3x3_direct_kernel).  Measured on the Yolo-shaped network at batch 64
@@ -1678,6 +1696,10 @@ int run_conv2d(LeleCtx* ctx, const LeleTensor* wt, const float* dx, const float*
             else LELE_C3(16, 2);
         }
 #undef LELE_C3
+        static const char* const names[2][2][2] = {
+            {{"conv.direct_ocb8_s1", "conv.direct_ocb8_s1_passes"}, {"conv.direct_ocb8_s2", "conv.direct_ocb8_s2_passes"}},
+            {{"conv.direct_ocb16_s1", "conv.direct_ocb16_s1_passes"}, {"conv.direct_ocb16_s2", "conv.direct_ocb16_s2_passes"}}};
+        ctx->set_route(names[ocb == 16][s_ == 2][icc < g.c]);
     } else {
         ConvWLoad al{dw, g, (int)((((uintptr_t)dw & 15) == 0) && g.K % 4 == 0)};
         ConvEpi epi{out, db, g, act};
@@ -1686,8 +1708,8 @@ int run_conv2d(LeleCtx* ctx, const LeleTensor* wt, const float* dx, const float*
         if (g.kh == 1 && g.kw == 1 && g.sh == 1 && g.sw == 1 && g.pt == 0 && g.pl == 0 && g.oh == g.ih && g.ow == g.iw) {
             // pointwise: B[p][k] = x[img][grp*ICg + k][p] is a plain column-major operand; batch b = img*G + grp
             gemm::LoadKRow bl{dx, g.group == 1 ? (int64_t)g.xbs : img_elems, (int64_t)g.plane, g.plane, g.K};
-            gemm::launch(ctx->stream, al, bl, epi, g.ocg, g.plane, g.K, g.n * g.group, ctx->num_cus);
-        } else if (g.icg % 4 == 0) {
+            ctx->set_route("conv.gemm_pw", gemm::launch(ctx->stream, al, bl, epi, g.ocg, g.plane, g.K, g.n * g.group, ctx->num_cus));
+        } else if (g.icg % 4 == 0 && !empty_k) {
             // tap-major K: weights permuted to [OC][tap][ic] once (cached when the caller declared them immutable)
             const int khw = g.kh * g.kw;
             const size_t wbytes = (size_t)g.oc * g.K * 4;
@@ -1710,10 +1732,10 @@ int run_conv2d(LeleCtx* ctx, const LeleTensor* wt, const float* dx, const float*
             }
             ConvWLoad alt{(const float*)dwt, g, 1};  // hipMalloc / arena chunks are 16-B aligned and K % 4 == 0
             ConvXLoadTap bl{dx, g, make_fastdiv(g.ow, g.plane), make_fastdiv(g.icg, g.K), make_fastdiv(g.kw, khw)};
-            gemm::launch(ctx->stream, alt, bl, epi, g.ocg, g.plane, g.K, g.n * g.group, ctx->num_cus);
+            ctx->set_route("conv.gemm_tap", gemm::launch(ctx->stream, alt, bl, epi, g.ocg, g.plane, g.K, g.n * g.group, ctx->num_cus));
         } else {
             ConvXLoad bl{dx, g, make_fastdiv(g.ow, g.plane), make_fastdiv(g.kh * g.kw, g.K), make_fastdiv(g.kw, g.kh * g.kw)};
-            gemm::launch(ctx->stream, al, bl, epi, g.ocg, g.plane, g.K, g.n * g.group, ctx->num_cus);
+            ctx->set_route("conv.gemm_generic", gemm::launch(ctx->stream, al, bl, epi, g.ocg, g.plane, g.K, g.n * g.group, ctx->num_cus));
         }
     }
     LELE_HIP_CHECK(hipGetLastError());
@@ -2138,7 +2160,9 @@ int ci_run(LeleCtx* ctx, ConvGeom g, const LeleTensor* w, float w_zp, const floa
     LeleTensor wv = *w;
     wv.mem = LELE_MEM_DEVICE;  // the centred copy is what run_conv2d sees (its own weight cache keys on the pointer below)
     wv.data = dwc;
-    return run_conv2d(ctx, &wv, (const float*)xc, dwc, nullptr, gp, LELE_ACT_NONE, out);
+    LELE_TRY(run_conv2d(ctx, &wv, (const float*)xc, dwc, nullptr, gp, LELE_ACT_NONE, out));
+    ctx->route[0] = "ci.f32";
+    return 0;
 }
 
 }  // namespace
@@ -2407,6 +2431,7 @@ int lele_hip_conv_transpose(LeleCtx* ctx, const LeleTensor* x, const LeleTensor*
     if (bias) LELE_TRY(ctx->dev_ptr(bias, &db));
     const int64_t total = (int64_t)g.n * g.oc * oh * ow;
     LELE_TRY(out->reserve((size_t)total * 4));
+    ctx->set_route(nullptr);
     if (total == 0) return set_shape(out_shape, out_rank, {(int64_t)g.n, (int64_t)g.oc, oh, ow});
     if (lab_env("LELE_HIP_CONVT_GATHER")) {  // reference gather kernel, kept for A/B checks
         hipLaunchKernelGGL(conv_transpose_kernel, dim3(grid_for(total)), dim3(256), 0, ctx->stream, (const float*)dx,
@@ -2444,7 +2469,7 @@ int lele_hip_conv_transpose(LeleCtx* ctx, const LeleTensor* x, const LeleTensor*
         gemm::LoadKRow bl{(const float*)dx, (int64_t)g.c * plane_in, (int64_t)plane_in, plane_in, g.c};
         ConvTKsEpi epi{(float*)out->data, (const float*)db, make_fastdiv(g.iw, plane_in), make_fastdiv(taps, mrows), make_fastdiv(g.kw, taps),
                        g.oc, g.oh, g.ow, g.kh, g.kw, g.iw, plane_in, taps};
-        gemm::launch(ctx->stream, al, bl, epi, mrows, plane_in, g.c, g.n, ctx->num_cus);
+        ctx->set_route("convt.ks", gemm::launch(ctx->stream, al, bl, epi, mrows, plane_in, g.c, g.n, ctx->num_cus));
         LELE_HIP_CHECK(hipGetLastError());
         return set_shape(out_shape, out_rank, {(int64_t)g.n, (int64_t)g.oc, oh, ow});
     }
@@ -2469,6 +2494,7 @@ int lele_hip_conv_transpose(LeleCtx* ctx, const LeleTensor* x, const LeleTensor*
     }
     auto mod = [](int v, int m) { return ((v % m) + m) % m; };
     size_t woff = 0;
+    ctx->set_route("convt.phase");  // one GEMM per phase (their own tiles each): the route names no GEMM kernel
     for (int py = 0; py < g.sh; ++py)
         for (int px = 0; px < g.sw; ++px) {
             const int nj = py < g.oh ? (g.oh - py + g.sh - 1) / g.sh : 0, ni = px < g.ow ? (g.ow - px + g.sw - 1) / g.sw : 0;
@@ -2493,6 +2519,7 @@ int lele_hip_conv_transpose(LeleCtx* ctx, const LeleTensor* x, const LeleTensor*
                 hipLaunchKernelGGL(convt_fill_phase_kernel, dim3(grid_for((int64_t)g.n * g.oc * nj * ni)), dim3(256), 0,
                                    ctx->stream, (float*)out->data, (const float*)db, g.n, g.oc, g.oh, g.ow, py, px, g.sh,
                                    g.sw, nj, ni);
+                ctx->set_route("convt.phase_fill");
                 continue;
             }
             if (!have_w)

@@ -65,10 +65,27 @@ int run_matmul(LeleCtx* ctx, const float* da, const float* db, const MmShape& s,
                       (int)(aligned16(da) && s.k % 4 == 0)};
     gemm::LoadKRow bl{db, s.batch_b == 1 ? 0 : s.k * s.n, s.n, (int)s.n, (int)s.k};
     gemm::EpiAffine epi{out, s.m * s.n, (int)s.m, (int)s.n, alpha, beta, c, cmode, clen};
-    gemm::launch(ctx->stream, al, bl, epi, (int)s.m, (int)s.n, (int)s.k, (int)s.fb, ctx->num_cus);
+    ctx->set_route(nullptr, gemm::launch(ctx->stream, al, bl, epi, (int)s.m, (int)s.n, (int)s.k, (int)s.fb, ctx->num_cus));
     LELE_HIP_CHECK(hipGetLastError());
     return 0;
 }
+
+// every name lele_hip_last_route can report (one level of a route each; a route joins its levels with '/')
+const char* const kRouteNames[] = {
+    "gemm.thin_n", "gemm.thin_m", "gemm.small", "gemm.tile256x128", "gemm.tile128x128", "gemm.tile64x256", "gemm.tile64x64",
+    "gemm.tile32x128", "gemm.k0",
+    "conv.dw_lds_k3", "conv.dw_lds_k5", "conv.dw_lds_k7", "conv.dw_lds_k11",
+    "conv.dw_lds_k3_direct", "conv.dw_lds_k5_direct", "conv.dw_lds_k7_direct", "conv.dw_lds_k11_direct",
+    "conv.dw_row4_k3", "conv.dw_row4_k5", "conv.dw_row4_k7", "conv.dw_row4_k11", "conv.dw_generic",
+    "conv.win3_oct32", "conv.win3_oct64", "conv.win3_oct32_osplit", "conv.win3_oct64_osplit",
+    "conv.win1_oct32", "conv.win1_oct64", "conv.win1_oct128", "conv.win1_oct32_osplit", "conv.win1_oct64_osplit", "conv.win1_oct128_osplit",
+    "conv.win3s2_oct32", "conv.win3s2_oct64", "conv.win3s2_oct32_osplit", "conv.win3s2_oct64_osplit",
+    "conv.direct_ocb8_s1", "conv.direct_ocb16_s1", "conv.direct_ocb8_s2", "conv.direct_ocb16_s2",
+    "conv.direct_ocb8_s1_passes", "conv.direct_ocb16_s1_passes", "conv.direct_ocb8_s2_passes", "conv.direct_ocb16_s2_passes",
+    "conv.gemm_pw", "conv.gemm_tap", "conv.gemm_generic",
+    "convt.ks", "convt.phase", "convt.phase_fill",
+    "ci.f32",
+};
 
 }  // namespace
 
@@ -157,14 +174,16 @@ int lele_hip_gemm(LeleCtx* ctx, const LeleTensor* a, const LeleTensor* b, const 
     gemm::LoadKRow a_km{fa, 0, m, (int)m, (int)k};
     gemm::LoadKRow b_kn{fb, 0, n, (int)n, (int)k};
     gemm::LoadRowK b_nk{fb, 0, k, (int)n, (int)k, (int)(aligned16(fb) && k % 4 == 0)};
+    const char* r;
     if (!trans_a && !trans_b)
-        gemm::launch(ctx->stream, a_mk, b_kn, epi, (int)m, (int)n, (int)k, 1, ctx->num_cus);
+        r = gemm::launch(ctx->stream, a_mk, b_kn, epi, (int)m, (int)n, (int)k, 1, ctx->num_cus);
     else if (!trans_a && trans_b)
-        gemm::launch(ctx->stream, a_mk, b_nk, epi, (int)m, (int)n, (int)k, 1, ctx->num_cus);
+        r = gemm::launch(ctx->stream, a_mk, b_nk, epi, (int)m, (int)n, (int)k, 1, ctx->num_cus);
     else if (trans_a && !trans_b)
-        gemm::launch(ctx->stream, a_km, b_kn, epi, (int)m, (int)n, (int)k, 1, ctx->num_cus);
+        r = gemm::launch(ctx->stream, a_km, b_kn, epi, (int)m, (int)n, (int)k, 1, ctx->num_cus);
     else
-        gemm::launch(ctx->stream, a_km, b_nk, epi, (int)m, (int)n, (int)k, 1, ctx->num_cus);
+        r = gemm::launch(ctx->stream, a_km, b_nk, epi, (int)m, (int)n, (int)k, 1, ctx->num_cus);
+    ctx->set_route(nullptr, r);
     LELE_HIP_CHECK(hipGetLastError());
     return set_shape(out_shape, out_rank, {m, n});
 }
@@ -197,6 +216,7 @@ int lele_hip_matmul_view(LeleCtx* ctx, const LeleTensor* a, const LeleMatView* a
     LELE_TRY(ctx->dev_ptr(a, &da));
     LELE_TRY(ctx->dev_ptr(b, &db));
     LELE_TRY(out->reserve((size_t)total * 4));
+    ctx->set_route(nullptr);
     if (total) {
         const float* pa = (const float*)da + av->offset;
         const float* pb = (const float*)db + bv->offset;
@@ -213,14 +233,35 @@ int lele_hip_matmul_view(LeleCtx* ctx, const LeleTensor* a, const LeleMatView* a
         gemm::LoadRowK b_nk{pb, bv->stride_outer, bv->stride_col, (int)n, (int)k,
                             (int)(aligned16(pb) && bv->stride_col % 4 == 0 && bv->stride_outer % 4 == 0 && bv->stride_inner % 4 == 0), bi, bv->stride_inner};
         const bool a_k = av->stride_col == 1, b_n = bv->stride_col == 1;
-        if (a_k && b_n) gemm::launch(ctx->stream, a_rk, b_kn, epi, (int)m, (int)n, (int)k, (int)fb, ctx->num_cus);
-        else if (a_k && !b_n) gemm::launch(ctx->stream, a_rk, b_nk, epi, (int)m, (int)n, (int)k, (int)fb, ctx->num_cus);
-        else if (!a_k && b_n) gemm::launch(ctx->stream, a_kr, b_kn, epi, (int)m, (int)n, (int)k, (int)fb, ctx->num_cus);
-        else gemm::launch(ctx->stream, a_kr, b_nk, epi, (int)m, (int)n, (int)k, (int)fb, ctx->num_cus);
+        const char* r;
+        if (a_k && b_n) r = gemm::launch(ctx->stream, a_rk, b_kn, epi, (int)m, (int)n, (int)k, (int)fb, ctx->num_cus);
+        else if (a_k && !b_n) r = gemm::launch(ctx->stream, a_rk, b_nk, epi, (int)m, (int)n, (int)k, (int)fb, ctx->num_cus);
+        else if (!a_k && b_n) r = gemm::launch(ctx->stream, a_kr, b_kn, epi, (int)m, (int)n, (int)k, (int)fb, ctx->num_cus);
+        else r = gemm::launch(ctx->stream, a_kr, b_nk, epi, (int)m, (int)n, (int)k, (int)fb, ctx->num_cus);
+        ctx->set_route(nullptr, r);
         LELE_HIP_CHECK(hipGetLastError());
         stat_publish(out, epi.blockstat, nstat, total);
     }
     return set_shape_v(out_shape, out_rank, std::vector<int64_t>(out_dims, out_dims + out_dims_rank));
+}
+
+int lele_hip_last_route(LeleCtx* ctx, char* buf, size_t cap) {
+    LELE_REQUIRE(ctx && (buf || cap == 0), "last_route: NULL argument");
+    std::string r;
+    for (const char* level : ctx->route)
+        if (level) r += (r.empty() ? "" : "/") + std::string(level);
+    LELE_REQUIRE(r.size() < cap, "last_route: %zu bytes do not hold the %zu-character name", cap, r.size());
+    memcpy(buf, r.c_str(), r.size() + 1);
+    return 0;
+}
+
+int lele_hip_route_names(char* buf, size_t cap) {
+    LELE_REQUIRE(buf || cap == 0, "route_names: NULL buffer");
+    std::string all;
+    for (const char* n : kRouteNames) all += (all.empty() ? "" : "\n") + std::string(n);
+    LELE_REQUIRE(all.size() < cap, "route_names: %zu bytes do not hold the %zu-character list", cap, all.size());
+    memcpy(buf, all.c_str(), all.size() + 1);
+    return 0;
 }
 
 }  // extern "C"

@@ -13,6 +13,7 @@
 // Global -> register -> LDS with the next tile's loads in flight during the MFMAs (double-buffered LDS,
 // one __syncthreads per K tile).
 #pragma once
+#include <algorithm>
 #include <cstdlib>
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -561,6 +562,20 @@ __global__ __launch_bounds__(256) void gemm_f32_thin_kernel(AL al, BL bl, EPI ep
     }
 }
 
+// ---------------------------------------------------------------------------------------------- empty K
+// K = 0: the product is all zeros and the result is the epilogue alone (zeros, beta*C, bias + activation) -- what the reference's
+// GEMM with Accum::Replace gives.  No operand is read: with K = 0 the loaders' clamp to k = K - 1 would address before the operand,
+// and an empty host operand is not even staged on the device.
+template <class EPI>
+__global__ __launch_bounds__(256) void gemm_f32_epilogue_kernel(EPI epi, int M, int N) {
+    const int batch = blockIdx.y;
+    const int64_t total = (int64_t)M * N;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+        const int row = (int)(i / N), col = (int)(i % N);
+        epi.store(batch, row, col, 0.0f, epi.load(batch, row, col));
+    }
+}
+
 template <int BM, int BN, int WM, int WN, int BK, int OCC = 1, class AL, class BL, class EPI>
 inline void launch_tile(hipStream_t st, const AL& al, const BL& bl, const EPI& epi, int M, int N, int K, int batch) {
     constexpr size_t lds = (size_t)2 * (BM + BN) * (BK + 4) * sizeof(float);
@@ -580,22 +595,30 @@ inline int64_t small_kernel_blocks(int M, int N, int K, int batch, int num_cus) 
     return (int64_t)((N + 31) / 32) * ((M + 31) / 32) * batch;
 }
 
+// Returns the name of the kernel it launched (lele_hip_last_route, lele_hip_route_names: string literals, so a caller may keep the
+// pointer), or nullptr when the result is empty and nothing was launched.
 template <class AL, class BL, class EPI>
-inline void launch(hipStream_t st, const AL& al, const BL& bl, const EPI& epi, int M, int N, int K, int batch,
-                   int num_cus) {
-    if (M <= 0 || N <= 0 || batch <= 0) return;
+inline const char* launch(hipStream_t st, const AL& al, const BL& bl, const EPI& epi, int M, int N, int K, int batch,
+                          int num_cus) {
+    if (M <= 0 || N <= 0 || batch <= 0) return nullptr;
+    if (K <= 0) {
+        const int64_t total = (int64_t)M * N;
+        const unsigned blocks = (unsigned)std::min<int64_t>((total + 255) / 256, 1024);
+        hipLaunchKernelGGL((gemm_f32_epilogue_kernel<EPI>), dim3(blocks, batch), dim3(256), 0, st, epi, M, N);
+        return "gemm.k0";
+    }
     static const int force = lab_env("LELE_HIP_GEMM_FORCE") ? atoi(lab_env("LELE_HIP_GEMM_FORCE")) : -1;  // A/B experiments
     if (force >= 0) {
         switch (force) {
-            case 0: launch_tile<128, 128, 2, 4, 16, 4>(st, al, bl, epi, M, N, K, batch); return;
-            case 1: launch_tile<64, 256, 2, 4, 16, 4>(st, al, bl, epi, M, N, K, batch); return;
-            case 2: launch_tile<64, 64, 2, 2, 16>(st, al, bl, epi, M, N, K, batch); return;
-            case 3: launch_tile<32, 128, 1, 4, 16>(st, al, bl, epi, M, N, K, batch); return;
-            case 4: launch_tile<256, 128, 4, 2, 16, 4>(st, al, bl, epi, M, N, K, batch); return;
+            case 0: launch_tile<128, 128, 2, 4, 16, 4>(st, al, bl, epi, M, N, K, batch); return "gemm.tile128x128";
+            case 1: launch_tile<64, 256, 2, 4, 16, 4>(st, al, bl, epi, M, N, K, batch); return "gemm.tile64x256";
+            case 2: launch_tile<64, 64, 2, 2, 16>(st, al, bl, epi, M, N, K, batch); return "gemm.tile64x64";
+            case 3: launch_tile<32, 128, 1, 4, 16>(st, al, bl, epi, M, N, K, batch); return "gemm.tile32x128";
+            case 4: launch_tile<256, 128, 4, 2, 16, 4>(st, al, bl, epi, M, N, K, batch); return "gemm.tile256x128";
             case 5: {
                 dim3 grid((N + 31) / 32, (M + 31) / 32, batch);
                 hipLaunchKernelGGL((gemm_f32_small_kernel<AL, BL, EPI>), grid, dim3(256), 0, st, al, bl, epi, M, N, K);
-                return;
+                return "gemm.small";
             }
             default: break;
         }
@@ -607,18 +630,18 @@ inline void launch(hipStream_t st, const AL& al, const BL& bl, const EPI& epi, i
     if (!wants_stats && K >= 8 && force < 0) {
         if (N <= 4 && M >= 8 && !AL::kRowFast) {
             hipLaunchKernelGGL((gemm_f32_thin_kernel<false, AL, BL, EPI>), dim3((M + 3) / 4, batch), dim3(256), 0, st, al, bl, epi, M, N, K);
-            return;
+            return "gemm.thin_n";
         }
         if (M <= 4 && N >= 8 && !BL::kRowFast) {
             hipLaunchKernelGGL((gemm_f32_thin_kernel<true, AL, BL, EPI>), dim3((N + 3) / 4, batch), dim3(256), 0, st, al, bl, epi, M, N, K);
-            return;
+            return "gemm.thin_m";
         }
     }
     // too few 64x64 tiles to fill the chip: 32x32 tiles with a 4-way split of K (latency-optimised, see above)
     if ((int64_t)((M + 63) / 64) * ((N + 63) / 64) * batch < 2 * (int64_t)num_cus && K >= 16) {
         dim3 grid((N + 31) / 32, (M + 31) / 32, batch);
         hipLaunchKernelGGL((gemm_f32_small_kernel<AL, BL, EPI>), grid, dim3(256), 0, st, al, bl, epi, M, N, K);
-        return;
+        return "gemm.small";
     }
     struct Cand {
         int bm, bn;
@@ -640,11 +663,11 @@ inline void launch(hipStream_t st, const AL& al, const BL& bl, const EPI& epi, i
         }
     }
     switch (best) {
-        case 0: launch_tile<128, 128, 2, 4, 16, 4>(st, al, bl, epi, M, N, K, batch); break;  // 8 waves of 64x32
-        case 1: launch_tile<64, 256, 2, 4, 16, 4>(st, al, bl, epi, M, N, K, batch); break;  // 8 waves of 32x64
-        case 4: launch_tile<256, 128, 4, 2, 16, 4>(st, al, bl, epi, M, N, K, batch); break;  // 8 waves, 61 KB LDS, 2 per CU
-        case 2: launch_tile<64, 64, 2, 2, 16>(st, al, bl, epi, M, N, K, batch); break;
-        default: launch_tile<32, 128, 1, 4, 16>(st, al, bl, epi, M, N, K, batch); break;
+        case 0: launch_tile<128, 128, 2, 4, 16, 4>(st, al, bl, epi, M, N, K, batch); return "gemm.tile128x128";  // 8 waves of 64x32
+        case 1: launch_tile<64, 256, 2, 4, 16, 4>(st, al, bl, epi, M, N, K, batch); return "gemm.tile64x256";  // 8 waves of 32x64
+        case 4: launch_tile<256, 128, 4, 2, 16, 4>(st, al, bl, epi, M, N, K, batch); return "gemm.tile256x128";  // 8 waves, 61 KB LDS, 2 per CU
+        case 2: launch_tile<64, 64, 2, 2, 16>(st, al, bl, epi, M, N, K, batch); return "gemm.tile64x64";
+        default: launch_tile<32, 128, 1, 4, 16>(st, al, bl, epi, M, N, K, batch); return "gemm.tile32x128";
     }
 }
 

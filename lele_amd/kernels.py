@@ -650,6 +650,21 @@ def conv_stats(ctx=None):
     return calls.value, macs.value
 
 
+def last_route(ctx=None):
+    """name of the kernel route the last f32 GEMM or convolution call on the context dispatched, its levels joined by '/'
+    (lele_hip_last_route: recorded by the library at the launch site, e.g. "conv.gemm_tap/gemm.small"); "" for an empty result"""
+    buf = C.create_string_buffer(256)
+    _lib.check(_lib.lib().lele_hip_last_route(_ctx(ctx)._h, buf, C.c_size_t(len(buf))))
+    return buf.value.decode()
+
+
+def route_names():
+    """every level name last_route() can report (lele_hip_route_names: host only, no GPU needed)"""
+    buf = C.create_string_buffer(8192)
+    _lib.check(_lib.lib().lele_hip_route_names(buf, C.c_size_t(len(buf))))
+    return buf.value.decode().split("\n")
+
+
 def print_conv_stats(ctx=None):  # conv2d.rs:75
     calls, macs = conv_stats(ctx)
     print("conv stats: %d convolution calls, %.3f GMAC" % (calls, macs * 1e-9))

@@ -394,7 +394,8 @@ RES_CASES = [
     (8, 96, 12, 12, 200, 3, 1, 1, 0),       # tiled GEMM, 16-byte stores
     (4, 24, 9, 7, 40, 3, 1, 1, 2),          # tiled / small GEMM, scalar stores
     (64, 130, 20, 20, 200, 1, 1, 1, 2),     # pointwise tiled GEMM
-    (48, 16, 48, 48, 8, 3, 1, 1, 2),        # direct small-channel kernel
+    (48, 16, 48, 48, 8, 3, 1, 1, 2),        # window kernel, 5-16 output channels (narrow form)
+    (48, 8, 48, 48, 8, 3, 1, 1, 2),         # direct small-channel kernel
     (2, 128, 17, 17, 128, 3, 1, 128, 2),    # depthwise (+ the separate add)
     (1, 16, 33, 29, 24, 3, 1, 2, 1),        # grouped
 ]

@@ -34,8 +34,9 @@ def test_debug_library_carries_the_assertions_and_the_whole_abi():
 def test_parity_cases_run_clean_on_the_bounds_asserting_build():
     _dbg_lib()
     env = dict(os.environ, LELE_HIP_LIBRARY="liblele_hip_dbg.so")
-    r = subprocess.run([sys.executable, "-m", "pytest", "tests/test_gemm.py", "tests/test_conv_rnn.py", "tests/test_channel_views.py", "-m", "gpu", "-x", "-q",
-                        "-p", "no:cacheprovider"], cwd=ROOT, env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=1500)
-    tail = r.stdout[-3000:]
-    assert r.returncode == 0 and "bounds assertion failed" not in r.stdout, tail
-    assert " passed" in tail
+    for files, limit in ((["tests/test_gemm.py", "tests/test_conv_rnn.py", "tests/test_channel_views.py"], 1500), (["tests/test_f32_routes.py"], 900)):
+        r = subprocess.run([sys.executable, "-m", "pytest"] + files + ["-m", "gpu", "-x", "-q", "-p", "no:cacheprovider"], cwd=ROOT, env=env,
+                           stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=limit)
+        tail = r.stdout[-3000:]
+        assert r.returncode == 0 and "bounds assertion failed" not in r.stdout, tail
+        assert " passed" in tail
