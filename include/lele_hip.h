@@ -561,6 +561,42 @@ int lele_hip_attention_view(LeleCtx* ctx, const LeleTensor* q, const LeleMatView
                             int64_t t_k, int64_t dh, const LeleTensor* scale_or_null, const LeleMatView* out_view,
                             const int64_t* out_dims, int32_t out_dims_rank, LeleBuf* out, int64_t* out_shape, int32_t* out_rank);
 
+/* ---- The packed batch behind the front-end: x [R, D] + row_offsets (host, count + 1 values from 0 to R, non-decreasing, checked
+ * before anything is launched: a failing call leaves `out` as it was), the layout lele_hip_frontend_compute_segments and
+ * lele_hip_cmvn_segments produce.  Every segment is computed exactly as if it ran alone -- the reference is batch 1 throughout
+ * (examples/sensevoice/src/main.rs) -- and 0-row segments are skipped.  A layout's device tables are uploaded once and never rewritten,
+ * so a graph may record these calls after the layout has run once.  Row-wise operators (layer_norm, add, add3) take [R, D] as it is. */
+
+/* fused_quantized_linear (quantization.rs:77-169) with every segment as a batch slice of its own (quantization.rs:104-128: one dynamic
+ * range per slice): rows of segment i are, bit for bit, lele_hip_fused_quantized_linear of input[off[i]:off[i+1]] alone as a rank-2
+ * tensor.  input f32 [R, K] -> out [R, N].  Producer-side row statistics of `input` are not read. */
+int lele_hip_fused_quantized_linear_segments(LeleCtx* ctx, const LeleTensor* input, const int64_t* row_offsets, int64_t count,
+                                             const LeleTensor* weight_int8, const LeleTensor* weight_scale, const LeleTensor* weight_zero,
+                                             const LeleTensor* bias_or_null, int apply_relu, LeleBuf* out, int64_t* out_shape,
+                                             int32_t* out_rank);
+/* lele_hip_attention_view per segment: qkv f32 [R, P] holds Q, K, V of `heads` heads of width dh at columns q_offset, k_offset,
+ * v_offset (head h at + h * dh); for every segment and head softmax(Q K^T * scale) V over THAT SEGMENT's rows only, queries and keys
+ * alike (gemm.rs:112-222, norm.rs:8) -> out [R, heads * dh], heads merged.  Supported: dh == 128, every segment <= 512 rows, q_offset,
+ * k_offset and P multiples of 4; anything else is an error that names the offending segment.  A segment runs the kernel
+ * lele_hip_attention_view picks for it ALONE among its 16-row and 32-row forms (16 rows per workgroup while heads * ceil(len / 32) is
+ * below half the CUs: then the segment's result is that call's bit for bit), so it does not depend on the rest of the batch.  At most
+ * 9 launches a call, whatever the number of segments: one per key-tile class present (8), one more for the class that rule splits.
+ * LELE_HIP_ATTENTION_EXACT=1 selects the f32-MFMA arithmetic as it does there. */
+int lele_hip_attention_segments(LeleCtx* ctx, const LeleTensor* qkv, int64_t q_offset, int64_t k_offset, int64_t v_offset, int64_t heads,
+                                int64_t dh, const int64_t* row_offsets, int64_t count, const LeleTensor* scale_or_null, LeleBuf* out,
+                                int64_t* out_shape, int32_t* out_rank);
+/* lele_hip_depthwise_conv1d_tlc (conv1d.rs:837 between two transposes) per segment: x f32 [R, P], channels [x_offset, x_offset + C),
+ * w [C, 1, K], pad_left + pad_right == K - 1 (rows are kept) -> out [R, C].  A segment ends where its rows end: taps outside it are
+ * skipped, so segment i is bit for bit the dense entry point on it alone as [1, len, P], segments shorter than the stencil included. */
+int lele_hip_depthwise_conv1d_tlc_segments(LeleCtx* ctx, const LeleTensor* x, int64_t x_offset, const int64_t* row_offsets, int64_t count,
+                                           const LeleTensor* w, const LeleTensor* bias_or_null, int64_t pad_left, int64_t pad_right,
+                                           int relu, int add_input, LeleBuf* out, int64_t* out_shape, int32_t* out_rank);
+/* concat along time (manipulation.rs:108-207) per segment: `prefix` [p, D] rows, then the segment's rows, for every segment, empty ones
+ * included -> out [R + p * count, D]; out_offsets (host, count + 1, written) = row_offsets[i] + p * i.  An exact copy: the prompt
+ * embeddings a SenseVoice-shaped encoder puts in front of every utterance. */
+int lele_hip_segments_prepend(LeleCtx* ctx, const LeleTensor* x, const int64_t* row_offsets, int64_t count, const LeleTensor* prefix,
+                              LeleBuf* out, int64_t* out_offsets, int64_t* out_shape, int32_t* out_rank);
+
 #ifdef __cplusplus
 }
 #endif

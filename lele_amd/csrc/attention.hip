@@ -46,6 +46,9 @@ struct AttnArgs {
     int nqb;           // query blocks per (batch, head)
     const float* scale;
     float* stat;       // [batch_outer][batch_inner * nqb][2] or NULL
+    // packed batch (lele_hip_attention_segments): workgroup b's {first row, rows, query block, head} of ITS segment; the outer batch
+    // index is then the segment's first row and the *_so strides are row strides.  NULL for the dense entry point.
+    const int4* work;
 #ifdef LELE_HIP_LAB
     int ablate;        // lab switch LELE_HIP_ATTN_ABLATE (timing experiments, results wrong): skip parts of the batch kernel
     long long* dbg;    // lab switch LELE_HIP_ATTN_STAMPS: cycle-counter stamps (tools/attention_stamps.py), or NULL
@@ -106,15 +109,23 @@ constexpr int kSPad = 4;   // LDS row padding (floats)
 // pair up: wave w owns row tile w & 1 throughout; in phase 1 it takes every second key tile of that row tile (three each for the six
 // tiles of a 10 s utterance: balanced, where RT = 1 leaves two of four waves with half the work), in phase 3 two of the four
 // 32-dim output tiles, fed by ONE set of P fragments.  K and V are read half as often.
-template <int NT, int RT, bool EXACT>
+// SEG: the workgroup finds its (segment, head, row block) and that segment's length in a.work (a per-layout work list of one key-tile
+// class: every segment of a launch has tpad == 32 NT, so a segment runs the instantiation the dense call picks for it alone).
+template <int NT, int RT, bool EXACT, bool SEG = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void attention_kernel(AttnArgs a) {
     extern __shared__ __attribute__((aligned(16))) float s_sp[];  // S, then P: [32 * RT][tpad + 4]
     __shared__ float s_mm[4][2];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int hv = lane >> 5, l31 = lane & 31;
+    int4 wk = {0, 0, 0, 0};
+    if constexpr (SEG) {
+        wk = a.work[blockIdx.x];
+        a.tq = a.tk = wk.y;
+        a.tpad = (wk.y + 63) & ~63;
+    }
     const int pitch = a.tpad + kSPad;
-    const int qb = blockIdx.x % a.nqb, bh = blockIdx.x / a.nqb;
-    const int bi = bh % a.batch_inner, bo = bh / a.batch_inner;
+    const int qb = SEG ? wk.z : blockIdx.x % a.nqb, bh = blockIdx.x / a.nqb;
+    const int bi = SEG ? wk.w : bh % a.batch_inner, bo = SEG ? wk.x : bh / a.batch_inner;
     const int i0 = qb * 32 * RT;
     const int rt = RT == 2 ? (wave & 1) : 0;   // this wave's row tile
     // its first key tile and the stride between its key tiles.  With one row tile the six key tiles of a 10 s utterance leave two
@@ -359,15 +370,21 @@ __device__ __forceinline__ void mm6_16(const Split3& a, const Split3& b, f32x4v&
     acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(LELE_BF(a.h), LELE_BF(b.h), acc, 0, 0, 0);
 }
 
-template <int NT, int NW, bool EXACT>
+template <int NT, int NW, bool EXACT, bool SEG = false>  // SEG: as attention_kernel's, query blocks of 16 rows
 __global__ __launch_bounds__(64 * NW) void attention16_kernel(AttnArgs a) {
     extern __shared__ __attribute__((aligned(16))) float s_sp[];  // S, then P: [16][tpad + 4]
     __shared__ float s_mm[NW][2];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int r16 = lane & 15, g = lane >> 4;
+    int4 wk = {0, 0, 0, 0};
+    if constexpr (SEG) {
+        wk = a.work[blockIdx.x];
+        a.tq = a.tk = wk.y;
+        a.tpad = (wk.y + 63) & ~63;
+    }
     const int pitch = a.tpad + kSPad;
-    const int qb = blockIdx.x % a.nqb, bh = blockIdx.x / a.nqb;
-    const int bi = bh % a.batch_inner, bo = bh / a.batch_inner;
+    const int qb = SEG ? wk.z : blockIdx.x % a.nqb, bh = blockIdx.x / a.nqb;
+    const int bi = SEG ? wk.w : bh % a.batch_inner, bo = SEG ? wk.x : bh / a.batch_inner;
     const int i0 = qb * 16;
     const float* qp = a.q + bo * a.q_so + bi * a.q_si;
     const float* kp = a.k + bo * a.k_so + bi * a.k_si;
@@ -1004,6 +1021,130 @@ int lele_hip_attention_view(LeleCtx* ctx, const LeleTensor* q, const LeleMatView
         out->rowstat_valid = true;
     }
     return set_shape_v(out_shape, out_rank, std::vector<int64_t>(out_dims, out_dims + out_dims_rank));
+}
+
+namespace {
+// Work lists of a layout: {first row, rows, query block, head} per query block of every head of every non-empty segment, one list per
+// (key-tile class c = tpad / 64 in 1 .. 8, block height), class after class, the 16-row list of a class before its 32-row list.  A
+// segment takes the block height lele_hip_attention_view picks for it ALONE -- 16 rows while heads x ceil(len / 32) stays below half
+// the CUs (every SenseVoice-shaped utterance: 4 heads, <= 16 blocks), else 32 -- so its result does not depend on what else is in the
+// batch, and under the 16-row rule it is the dense call's on the segment alone bit for bit.  The host recounts the lists' lengths.
+struct SegWorkArg {
+    const int64_t* off;
+    int64_t count;
+    int heads, half_cus;
+};
+inline bool seg_rows16(int64_t len, int heads, int half_cus) { return heads * ((len + 31) / 32) < half_cus; }
+void build_attn_work(const void* arg, std::vector<char>& blob) {
+    const SegWorkArg& a = *(const SegWorkArg*)arg;
+    std::vector<int> w;
+    for (int c = 1; c <= 8; ++c)
+        for (int tall = 0; tall < 2; ++tall)
+            for (int64_t i = 0; i < a.count; ++i) {
+                const int64_t len = a.off[i + 1] - a.off[i];
+                if (len == 0 || (len + 63) / 64 != c || seg_rows16(len, a.heads, a.half_cus) != (tall == 0)) continue;
+                const int qrows = tall ? 32 : 16;
+                for (int h = 0; h < a.heads; ++h)
+                    for (int qb = 0; qb < (int)((len + qrows - 1) / qrows); ++qb) {
+                        const int e[4] = {(int)a.off[i], (int)len, qb, h};
+                        w.insert(w.end(), e, e + 4);
+                    }
+            }
+    blob.resize(w.size() * 4);
+    if (!w.empty()) memcpy(blob.data(), w.data(), blob.size());
+}
+}  // namespace
+
+/* softmax(Q K^T scale) V of every segment of a packed qkv [R, P] over that segment's rows only, heads merged in the result: the
+ * 16-row and 32-row kernels of lele_hip_attention_view behind a block locator, one launch per (key-tile class, block height) present
+ * in the layout: at most 9 (8 classes, and the height rule splits at most one of them for a given number of heads). */
+int lele_hip_attention_segments(LeleCtx* ctx, const LeleTensor* qkv, int64_t q_offset, int64_t k_offset, int64_t v_offset, int64_t heads,
+                                int64_t dh, const int64_t* row_offsets, int64_t count, const LeleTensor* scale, LeleBuf* out,
+                                int64_t* out_shape, int32_t* out_rank) {
+    LELE_REQUIRE(ctx && qkv && out, "attention_segments: NULL argument");
+    int64_t rows = 0, p = 0, tmax = 0;
+    LELE_TRY(seg_offsets(qkv, row_offsets, count, &rows, &p, &tmax, "attention_segments"));
+    LELE_REQUIRE(!scale || (scale->dtype == LELE_F32 && numel(scale) == 1), "attention_segments: the scale must be one f32 value");
+    LELE_REQUIRE(heads >= 1 && heads < (1 << 20) && dh == kDh, "attention_segments: unsupported geometry (head dimension %lld, %lld heads)", (long long)dh,
+                 (long long)heads);
+    const int64_t d = heads * dh;
+    LELE_REQUIRE(q_offset >= 0 && k_offset >= 0 && v_offset >= 0 && q_offset + d <= p && k_offset + d <= p && v_offset + d <= p,
+                 "attention_segments: Q / K / V columns [%lld, %lld, %lld) + %lld leave the row (%lld)", (long long)q_offset, (long long)k_offset,
+                 (long long)v_offset, (long long)d, (long long)p);
+    LELE_REQUIRE(q_offset % 4 == 0 && k_offset % 4 == 0 && p % 4 == 0, "attention_segments: unsupported geometry (Q / K rows are not 16-byte aligned)");
+    const int half_cus = ctx->num_cus / 2;
+    int64_t blocks[9][2] = {};
+    for (int64_t i = 0; i < count; ++i) {
+        const int64_t len = row_offsets[i + 1] - row_offsets[i];
+        LELE_REQUIRE(len <= 512, "attention_segments: segment %lld has %lld rows, at most 512 are supported", (long long)i, (long long)len);
+        if (!len) continue;
+        if (seg_rows16(len, (int)heads, half_cus)) blocks[(len + 63) / 64][0] += heads * ((len + 15) / 16);
+        else blocks[(len + 63) / 64][1] += heads * ((len + 31) / 32);
+    }
+    LELE_REQUIRE(rows < (int64_t(1) << 31) && heads * ((rows + 15) / 16 + count) < (int64_t(1) << 31), "attention_segments: too many blocks");
+    LELE_HIP_CHECK(hipSetDevice(ctx->device));
+    const void* work = nullptr;
+    if (rows > 0) {
+        const SegWorkArg arg{row_offsets, count, (int)heads, half_cus};
+        LELE_TRY(layout_table(ctx, "attn", heads, half_cus, row_offsets, count, build_attn_work, &arg, &work));
+    }
+    LELE_TRY(ctx->arena_reset());
+    const void *dq = nullptr, *dsc = nullptr;
+    if (rows > 0) LELE_TRY(ctx->dev_ptr(qkv, &dq));
+    if (scale) LELE_TRY(ctx->dev_ptr(scale, &dsc));
+    LELE_REQUIRE(rows == 0 || aligned16(dq), "attention_segments: unsupported geometry (Q / K rows are not 16-byte aligned)");
+    LELE_TRY(out->reserve((size_t)rows * d * 4));
+    if (rows == 0) return set_shape(out_shape, out_rank, {rows, d});
+    AttnArgs a{};
+    a.q = (const float*)dq + q_offset;
+    a.k = (const float*)dq + k_offset;
+    a.v = (const float*)dq + v_offset;
+    a.o = (float*)out->data;
+    // "outer batch index" = the segment's first row: the outer strides are the row strides
+    a.q_so = a.k_so = a.v_so = p, a.q_sr = a.k_sr = a.v_sr = p, a.q_si = a.k_si = a.v_si = dh;
+    a.o_so = a.o_sr = d, a.o_si = dh;
+    a.batch_inner = (int)heads;
+    a.nqb = 1;
+    a.scale = (const float*)dsc;
+    const char* ex_env = getenv("LELE_HIP_ATTENTION_EXACT");
+    const bool exact = ex_env && *ex_env && atoi(ex_env) != 0;
+    const int4* wp = (const int4*)work;
+    for (int c = 1; c <= 8; ++c)
+        for (int tall = 0; tall < 2; ++tall) {
+            if (!blocks[c][tall]) continue;
+            a.work = wp;
+            wp += blocks[c][tall];
+            a.tq = a.tk = a.tpad = 64 * c;  // (every workgroup takes its own from the work list)
+            const size_t lds = (size_t)(tall ? 32 : 16) * (64 * c + kSPad) * 4;
+            const dim3 grid((unsigned)blocks[c][tall]);
+#define LELE_ATTN_SEG1(KERN_)                                                                               \
+    do {                                                                                                    \
+        auto kern = KERN_;                                                                                  \
+        if (lds > 60 * 1024) LELE_HIP_CHECK(ensure_dyn_lds(reinterpret_cast<const void*>(kern), (int)lds)); \
+        hipLaunchKernelGGL(kern, grid, dim3(256), lds, ctx->stream, a);                                     \
+    } while (0)
+#define LELE_ATTN_SEG(NT_)                                                         \
+    do {                                                                           \
+        if (!tall && exact) LELE_ATTN_SEG1((attention16_kernel<NT_, 4, true, true>));  \
+        else if (!tall) LELE_ATTN_SEG1((attention16_kernel<NT_, 4, false, true>));     \
+        else if (exact) LELE_ATTN_SEG1((attention_kernel<NT_, 1, true, true>));        \
+        else LELE_ATTN_SEG1((attention_kernel<NT_, 1, false, true>));                  \
+    } while (0)
+            switch (c) {
+                case 1: LELE_ATTN_SEG(2); break;
+                case 2: LELE_ATTN_SEG(4); break;
+                case 3: LELE_ATTN_SEG(6); break;
+                case 4: LELE_ATTN_SEG(8); break;
+                case 5: LELE_ATTN_SEG(10); break;
+                case 6: LELE_ATTN_SEG(12); break;
+                case 7: LELE_ATTN_SEG(14); break;
+                default: LELE_ATTN_SEG(16); break;
+            }
+#undef LELE_ATTN_SEG
+#undef LELE_ATTN_SEG1
+        }
+    LELE_HIP_CHECK(hipGetLastError());
+    return set_shape(out_shape, out_rank, {rows, d});
 }
 
 }  // extern "C"

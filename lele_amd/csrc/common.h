@@ -260,6 +260,15 @@ int live_contexts(int device);  // context.hip: contexts of this process alive o
 int fft_twiddles(LeleCtx* ctx, int64_t n, const float** tw_re, const float** tw_im);  // features_ops.hip: fft.rs:136-157 on the device
 int fft_rows_power(LeleCtx* ctx, const float* rows_in, int64_t rows, int64_t n_fft, float* out_power);
 
+// features_ops.hip: the packed layout of the *_segments entry points.  seg_offsets checks x f32 [R, D] and the host offsets (from 0 to
+// R, non-decreasing) before anything is launched; offsets_table is their device copy, layout_table any further table derived from
+// them (`tag` names the kind, p0 / p1 what else the builder depends on), both in ctx->seg_tables: one per distinct layout, never
+// rewritten.  A miss may drop the tables no capture uses, so an op takes ONE table per call and puts all it needs into it.
+int seg_offsets(const LeleTensor* x, const int64_t* off, int64_t count, int64_t* r, int64_t* d, int64_t* tmax, const char* who);
+int offsets_table(LeleCtx* ctx, const int64_t* off, int64_t count, const void** out);
+int layout_table(LeleCtx* ctx, const char tag[4], int64_t p0, int64_t p1, const int64_t* off, int64_t count,
+                 void (*build)(const void* arg, std::vector<char>& blob), const void* arg, const void** out);
+
 // quant.hip: dynamic-quantisation parameters of the joint range of several device arrays (16 bytes on the device)
 struct QParamsDev {
     float scale, zp, inv_scale;

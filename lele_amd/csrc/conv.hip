@@ -15,6 +15,7 @@
 // Activation matches the x86 epilogue: polynomial SiLU for the first plane&~7 positions of each (n, oc) plane,
 // libm form for the tail (avx/math.rs:344-365).
 #include "common.h"
+#include "tlc_core.h"
 #include "gemm_core.h"
 #include "simd_math.h"
 
@@ -447,45 +448,12 @@ __global__ __launch_bounds__(256) void dwconv1d_tlc_kernel(const float* __restri
     // Workgroup b runs on XCD b % 8, each with its own L2: in launch order the time tiles next to each other -- whose windows overlap
     // by KW - 1 rows -- sit on different XCDs and every one of them fetches the shared rows again (counters: 25 MB read for the
     // 11 MB of v on a configs[3] shard).  Re-labelled so that every XCD walks one contiguous range of (utterance, time tile, channels).
-    const unsigned G = gridDim.x, xcd = blockIdx.x & 7u, gbase = G >> 3, grem = G & 7u;
-    const unsigned logical = xcd * gbase + (xcd < grem ? xcd : grem) + (blockIdx.x >> 3);
-    const unsigned i = logical * 256u + threadIdx.x;
+    const unsigned i = tlc_xcd_index(total);
     if (i >= total) return;
     const unsigned ch = i % (unsigned)c, r = i / (unsigned)c;
     const unsigned tile = r % tiles_t, b = r / tiles_t;
-    const int t0 = (int)tile * TT;
-    const float* xp = x + ((size_t)b * t_in) * pitch + ch;
-    float xs[KW + TT - 1], wv[KW];
-#pragma unroll
-    for (int j = 0; j < KW + TT - 1; ++j) {
-        const int t = t0 - pl + j;
-        xs[j] = xp[(size_t)min(max(t, 0), t_in - 1) * pitch];
-    }
-#pragma unroll
-    for (int j = 0; j < KW; ++j) wv[j] = w[ch * KW + j];
-    const float bv = bias ? bias[ch] : 0.0f;
-    float* op = out + ((size_t)b * t_out) * c + ch;
-#pragma unroll
-    for (int q = 0; q < TT; ++q) {
-        float acc = 0.0f;
-#pragma unroll
-        for (int j = 0; j < KW; ++j) {
-            const int t = t0 + q - pl + j;
-            const float f = fmaf_(xs[q + j], wv[j], acc);
-            acc = (t >= 0 && t < t_in) ? f : acc;
-        }
-        if (bias) acc = acc + bv;
-        if (relu) acc = acc > 0.0f ? acc : 0.0f;
-        // the FSMN residual (memory + input): x[t0 + q] sits at window index q + pl (the host checks pl <= KW - 1);
-        // a separate unrolled select keeps the index a compile-time constant per (q, pl) pair
-        if (add_input) {
-            float xv = 0.0f;
-#pragma unroll
-            for (int j = 0; j < KW; ++j) xv = (j == pl) ? xs[q + j] : xv;
-            acc = acc + xv;
-        }
-        if (t0 + q < t_out) op[(size_t)(t0 + q) * c] = acc;
-    }
+    tlc_tile<KW, TT>(x + ((size_t)b * t_in) * pitch + ch, w, bias, out + ((size_t)b * t_out) * c + ch, ch, (int)tile * TT, t_in, t_out, c, pitch,
+                     pl, relu, add_input);
 }
 
 // conv_transpose (group 1): gather form of the reference's GEMM + col2im scatter (conv2d.rs:3060-3126)

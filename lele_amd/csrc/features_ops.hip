@@ -333,6 +333,9 @@ int feature_2d(const LeleTensor* x, int64_t* t, int64_t* d, const char* who) {
     return 2;
 }
 
+}  // namespace
+
+namespace lele {
 // the packed layout of cmvn_segments / segments_to_padded: x [R, D] f32, row_offsets[0] == 0, non-decreasing, row_offsets[count] == R
 int seg_offsets(const LeleTensor* x, const int64_t* off, int64_t count, int64_t* r, int64_t* d, int64_t* tmax, const char* who) {
     LELE_REQUIRE(x->dtype == LELE_F32 && x->rank == 2, "%s: x must be f32 [R, D]", who);
@@ -348,7 +351,7 @@ int seg_offsets(const LeleTensor* x, const int64_t* off, int64_t count, int64_t*
     }
     return 0;
 }
-void build_offsets(const void* arg, std::vector<char>& blob) {
+static void build_offsets(const void* arg, std::vector<char>& blob) {
     const std::string& key = *(const std::string*)arg;
     blob.assign(key.begin(), key.end());
 }
@@ -358,9 +361,16 @@ int offsets_table(LeleCtx* ctx, const int64_t* off, int64_t count, const void** 
     return ctx->seg_tables.get(ctx, key, build_offsets, &key, out);
 }
 
-}  // namespace
-
-namespace lele {
+// a further per-layout table (work lists, row -> segment maps) beside the offsets: keyed by a 4-byte tag + the parameters the
+// builder depends on + the offsets themselves (never the length of a plain offsets key, which is a multiple of 8)
+int layout_table(LeleCtx* ctx, const char tag[4], int64_t p0, int64_t p1, const int64_t* off, int64_t count,
+                 void (*build)(const void* arg, std::vector<char>& blob), const void* arg, const void** out) {
+    std::string key(tag, 4);
+    key.append((const char*)&p0, 8);
+    key.append((const char*)&p1, 8);
+    key.append((const char*)off, (size_t)(count + 1) * 8);
+    return ctx->seg_tables.get(ctx, std::move(key), build, arg, out);
+}
 // the per-stage twiddle tables of the radix-2 network (fft.rs:136-157), on the device: [n - 1] values each, stage by stage
 int fft_twiddles(LeleCtx* ctx, int64_t n, const float** tw_re, const float** tw_im) {
     FftTables t;

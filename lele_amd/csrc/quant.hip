@@ -86,6 +86,53 @@ __global__ __launch_bounds__(256) void qminmax_kernel(const float* __restrict__ 
     }
 }
 
+// The same for a packed batch: grid.y = segment, whose slice is the rows off[y] .. off[y + 1] of x [R, k] (an empty segment leaves
+// the neutral pair, which nobody reads).  min / max are order-independent, so a segment's pair is qminmax_kernel's on it alone.
+__global__ __launch_bounds__(256) void qminmax_seg_kernel(const float* __restrict__ x, const int64_t* __restrict__ off, int64_t k,
+                                                          float* __restrict__ partial /*[segments][blocks][2]*/) {
+    const int64_t r0 = off[blockIdx.y], slice_len = (off[blockIdx.y + 1] - r0) * k;
+    const float* p = x + r0 * k;
+    float mn = 3.40282347e+38f, mx = -3.40282347e+38f;
+    auto upd = [&](float v) {
+        mn = v < mn ? v : mn;
+        mx = v > mx ? v : mx;
+    };
+    // as qminmax_kernel: scalar head up to the segment's first 16-byte boundary, float4 body, scalar tail
+    const int64_t head = std::min<int64_t>(slice_len, (int64_t)((4 - (((uintptr_t)p >> 2) & 3)) & 3));
+    const int64_t nvec = (slice_len - head) / 4;
+    const int64_t gtid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, gstride = (int64_t)gridDim.x * blockDim.x;
+    if (gtid < head) upd(p[gtid]);
+    const float4* pv = reinterpret_cast<const float4*>(p + head);
+    for (int64_t i = gtid; i < nvec; i += gstride) {
+        const float4 v = pv[i];
+        upd(v.x);
+        upd(v.y);
+        upd(v.z);
+        upd(v.w);
+    }
+    for (int64_t i = head + nvec * 4 + gtid; i < slice_len; i += gstride) upd(p[i]);
+    for (int o = 32; o > 0; o >>= 1) {
+        const float a = __shfl_xor(mn, o), b = __shfl_xor(mx, o);
+        mn = a < mn ? a : mn;
+        mx = b > mx ? b : mx;
+    }
+    __shared__ float smn[4], smx[4];
+    if ((threadIdx.x & 63) == 0) {
+        smn[threadIdx.x >> 6] = mn;
+        smx[threadIdx.x >> 6] = mx;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int w = 1; w < 4; ++w) {
+            mn = smn[w] < mn ? smn[w] : mn;
+            mx = smx[w] > mx ? smx[w] : mx;
+        }
+        float* o = partial + ((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * 2;
+        o[0] = mn;
+        o[1] = mx;
+    }
+}
+
 // Two instructions that do on their own what the reference spells out in several (probed on gfx950: profiles/r05_cvt_pk_u8_probe.txt):
 //   * v_cvt_pk_u8_f32 rounds to nearest EVEN and saturates to [0, 255] (0.5 -> 0, 1.5 -> 2, 2.5 -> 2, 254.5 -> 254, 255.5 and
 //     +inf -> 255, negative values and NaN -> 0): _mm256_round_ps(.., NEAREST) + the clamp + the pack in one -- no rintf in front;
@@ -139,7 +186,8 @@ __device__ __forceinline__ float quant_one(float v, const QParams& q, bool simd_
 }
 
 // ------------------------------------------------------------------------------------------ 2. rows -> i8
-// MODE 0: dynamic quantisation with prm[row / m] (fused linear: SIMD body = first k&~7 elements of EACH ROW)
+// MODE 0: dynamic quantisation with prm[row / m] -- prm[row_seg[row]] for a packed batch of unequal segments, whose parameters the
+//         pairs are partial[row_seg[row]][nblk] -- (fused linear: SIMD body = first k&~7 elements of EACH ROW)
 // MODE 1: the input already holds u8 values as f32 (mat_mul_integer): q = sat_u8(round-nearest-even(x))
 // One wave per row; writes q-128 as i8 into [rows][kp] (zero padded = contributes 0) and the exact sum of (q-128).
 // MODE 0 with `partial` != NULL: the slice's {scale, zp} are derived here from the min/max partials (every wave
@@ -150,7 +198,8 @@ __global__ __launch_bounds__(256) void qrows_kernel(const float* __restrict__ x,
                                                     QParams* __restrict__ prm, int8_t* __restrict__ aq,
                                                     int* __restrict__ row_sums, const float* __restrict__ partial,
                                                     int nblk, unsigned* __restrict__ zero_slice = nullptr,
-                                                    int* __restrict__ zero_rows = nullptr) {
+                                                    int* __restrict__ zero_rows = nullptr,
+                                                    const int* __restrict__ row_seg = nullptr /* packed batch: row -> segment (= slice) */) {
     const int lane = threadIdx.x & 63;
     const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (row >= rows) return;
@@ -178,7 +227,7 @@ __global__ __launch_bounds__(256) void qrows_kernel(const float* __restrict__ x,
     }
     QParams q;
     if (MODE == 0) {
-        const int64_t slice = row / m;
+        const int64_t slice = row_seg ? row_seg[row] : row / m;
         if (partial) {
             float mn = 3.40282347e+38f, mx = -3.40282347e+38f;
             // {min, max} pairs as 8-byte loads, all of a trip's loads in flight together (clamped index: a repeated pair changes
@@ -207,7 +256,9 @@ __global__ __launch_bounds__(256) void qrows_kernel(const float* __restrict__ x,
             mn = wave_allreduce64(mn, [](float cur, float a) { return a < cur ? a : cur; });
             mx = wave_allreduce64(mx, [](float cur, float a) { return a > cur ? a : cur; });
             q = make_qparams(mn, mx);
-            if (lane == 0 && row == slice * m) prm[slice] = q;
+            // the slice's first row publishes (a packed batch: the first row of its segment)
+            const bool first = row_seg ? (row == 0 || row_seg[row - 1] != (int)slice) : row == slice * m;
+            if (lane == 0 && first) prm[slice] = q;
         } else {
             q = prm[slice];
         }
@@ -367,6 +418,7 @@ struct IgemmEpi {
     int8_t* q_out = nullptr;        // EM 2: the result quantised with its slice's range, as q - 128, [rows][n]
     int* q_rowsum = nullptr;        // EM 2: sum over the row of (q - 128), accumulated over column blocks
     QParams* q_prm = nullptr;       // EM 2: the slices' parameters, published for the next GEMM's epilogue
+    const int* row_seg = nullptr;   // packed batch (lele_hip_fused_quantized_linear_segments): row -> segment, the slice of prm[]
     // Everything that depends only on the row (slice parameters, row-sum term, output row pointer) or only on the
     // column (column sum, weight scale, bias) is computed once per row / column of a thread's tile, not per element.
     struct RowCtx {
@@ -382,7 +434,7 @@ struct IgemmEpi {
         int zp_a = zp_a_fixed;
         float ds = 1.0f;
         if (prm) {
-            const QParams q = prm[rows == m ? 0u : (unsigned)row / (unsigned)m];
+            const QParams q = prm[row_seg ? (unsigned)row_seg[row] : (rows == m ? 0u : (unsigned)row / (unsigned)m)];
             zp_a = q.zp_i;
             ds = q.scale;
         }
@@ -1577,6 +1629,94 @@ int lele_hip_fused_quantized_linear(LeleCtx* ctx, const LeleTensor* input, const
                                     const LeleTensor* bias, int apply_relu, LeleBuf* out, int64_t* out_shape,
                                     int32_t* out_rank) {
     return fql_impl(ctx, input, weight_int8, weight_scale, weight_zero, bias, apply_relu, nullptr, nullptr, out, out_shape, out_rank);
+}
+
+// row -> segment map behind the offsets, in one table: [int64 off[count + 1]][int row_seg[R]]
+static void build_rowseg(const void* arg, std::vector<char>& blob) {
+    const auto& a = *(const std::pair<const int64_t*, int64_t>*)arg;
+    const int64_t* off = a.first;
+    const int64_t count = a.second, r = off[count];
+    blob.resize((size_t)(count + 1) * 8 + (size_t)r * 4);
+    memcpy(blob.data(), off, (size_t)(count + 1) * 8);
+    int* rs = (int*)(blob.data() + (size_t)(count + 1) * 8);
+    for (int64_t i = 0; i < count; ++i)
+        for (int64_t row = off[i]; row < off[i + 1]; ++row) rs[row] = (int)i;
+}
+
+/* Packed batch: every segment of input [R, K] is a batch slice of its own (quantization.rs:104-128).  Three things know about
+ * segments -- the range pass (one {min, max} per segment), the row quantiser's parameter lookup and the epilogue's row_ctx, the last
+ * two through a row -> segment map -- and the integer sums are exact, so a segment's rows are the dense entry point's on it alone. */
+int lele_hip_fused_quantized_linear_segments(LeleCtx* ctx, const LeleTensor* input, const int64_t* row_offsets, int64_t count,
+                                             const LeleTensor* weight_int8, const LeleTensor* weight_scale, const LeleTensor* weight_zero,
+                                             const LeleTensor* bias, int apply_relu, LeleBuf* out, int64_t* out_shape, int32_t* out_rank) {
+    LELE_REQUIRE(ctx && input && weight_int8 && weight_scale && out, "fused_quantized_linear_segments: NULL argument");
+    int64_t rows = 0, k = 0, tmax = 0;
+    LELE_TRY(seg_offsets(input, row_offsets, count, &rows, &k, &tmax, "fused_quantized_linear_segments"));
+    LELE_REQUIRE(weight_int8->rank >= 2, "fused_quantized_linear: rank >= 2 required");
+    const int64_t kw = weight_int8->shape[weight_int8->rank - 2], n = weight_int8->shape[weight_int8->rank - 1];
+    LELE_REQUIRE(k == kw, "fused_quantized_linear: K mismatch (%lld vs %lld)", (long long)k, (long long)kw);
+    const int64_t ws_len = numel(weight_scale);
+    LELE_REQUIRE(ws_len >= 1, "fused_quantized_linear: empty weight_scale");
+    LELE_REQUIRE(ws_len <= 1 || ws_len >= n, "fused_quantized_linear: weight_scale has %lld entries for N=%lld", (long long)ws_len, (long long)n);
+    const int64_t blen = bias ? numel(bias) : 0;
+    LELE_REQUIRE(blen == 0 || blen >= n, "fused_quantized_linear: bias has %lld entries for N=%lld", (long long)blen, (long long)n);
+    LELE_REQUIRE(rows < (int64_t(1) << 31) && count < (int64_t(1) << 31), "fused_quantized_linear_segments: more than 2^31 rows or segments");
+    LELE_HIP_CHECK(hipSetDevice(ctx->device));
+    const void* tab = nullptr;
+    if (rows > 0 && n > 0 && k > 0) {
+        const std::pair<const int64_t*, int64_t> arg{row_offsets, count};
+        LELE_TRY(layout_table(ctx, "qseg", 0, 0, row_offsets, count, build_rowseg, &arg, &tab));
+    }
+    if (rows == 0 || n == 0 || k == 0) {
+        LELE_TRY(out->reserve((size_t)rows * n * 4));
+        return set_shape(out_shape, out_rank, {rows, n});
+    }
+    const int64_t* doff = (const int64_t*)tab;
+    const int* drowseg = (const int*)((const char*)tab + (size_t)(count + 1) * 8);
+    LELE_TRY(ctx->arena_reset());
+    const void *dx = nullptr, *dws = nullptr, *db = nullptr;
+    LELE_TRY(ctx->dev_ptr(input, &dx));
+    LELE_TRY(ctx->dev_ptr(weight_scale, &dws));
+    if (blen) LELE_TRY(ctx->dev_ptr(bias, &db));
+    float wz = 0.0f;
+    LELE_TRY(weight_zero_of(ctx, weight_zero, &wz));
+    // 1. one range per segment: {min, max} partials only, which the row quantiser's waves reduce themselves (as in the dense chain: one
+    // launch fewer).  Enough blocks for every thread of the LONGEST segment to stream ~4 float4, at most 128 pairs a segment (a row's
+    // wave reads its segment's pairs in one trip); the surplus blocks of a shorter segment leave the neutral pair.
+    const int nblk = (int)std::max<int64_t>(1, std::min<int64_t>(128, (tmax * k + 4095) / 4096));
+    void *prm = nullptr, *partial = nullptr;
+    LELE_TRY(ctx->arena_alloc((size_t)count * sizeof(QParams), &prm));
+    LELE_TRY(ctx->arena_alloc((size_t)count * nblk * 8, &partial));
+    LELE_TRY(qprof_mark(ctx, 0));
+    for (int64_t c0 = 0; c0 < count; c0 += 65535) {  // grid.y limit
+        const int64_t nc = std::min<int64_t>(65535, count - c0);
+        hipLaunchKernelGGL(qminmax_seg_kernel, dim3(nblk, (unsigned)nc), dim3(256), 0, ctx->stream, (const float*)dx, doff + c0, k,
+                           (float*)partial + c0 * nblk * 2);
+    }
+    LELE_TRY(qprof_mark(ctx, 1));
+    // 2. rows -> i8 with their segment's parameters, 3. the tiled i8 GEMM whose epilogue looks the segment up per row
+    const int kp = (int)((k + 15) & ~int64_t(15));
+    PackedW pw;
+    LELE_TRY(packed_weights_of(ctx, weight_int8, (int)k, (int)n, kp, &pw));
+    void *aq = nullptr, *rs = nullptr;
+    LELE_TRY(ctx->arena_alloc((size_t)rows * kp, &aq));
+    LELE_TRY(ctx->arena_alloc((size_t)rows * 4, &rs));
+    // every fallible step is behind us: `out` is as it was until here (reserve clears any producer-side statistics of `out`;
+    // those of `input` describe equal slices and are not read)
+    LELE_TRY(out->reserve((size_t)rows * n * 4));
+    if (rows <= 2048 || kp <= 2048)  // as the dense chain chooses: the whole row in flight at once
+        hipLaunchKernelGGL((qrows_kernel<0, true>), dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, ctx->stream, (const float*)dx, rows, (int)k, kp,
+                           (int)rows, (QParams*)prm, (int8_t*)aq, (int*)rs, (const float*)partial, nblk, (unsigned*)nullptr, (int*)nullptr, drowseg);
+    else
+        hipLaunchKernelGGL((qrows_kernel<0, false>), dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, ctx->stream, (const float*)dx, rows, (int)k, kp,
+                           (int)rows, (QParams*)prm, (int8_t*)aq, (int*)rs, (const float*)partial, nblk, (unsigned*)nullptr, (int*)nullptr, drowseg);
+    LELE_TRY(qprof_mark(ctx, 2));
+    IgemmEpi epi{(float*)out->data, rows, n, (int)rows, (int)k, (const int*)rs, pw.col_sums, (const QParams*)prm, 0,
+                 (int)wz, (const float*)dws, (int)ws_len, blen ? (const float*)db : nullptr, apply_relu};
+    epi.row_seg = drowseg;
+    LELE_TRY(launch_igemm(ctx, (const int8_t*)aq, pw.wt, rows, (int)n, kp, 0, (int)rows, epi));
+    LELE_TRY(qprof_mark(ctx, 3));
+    return set_shape(out_shape, out_rank, {rows, n});
 }
 
 int lele_hip_binary(LeleCtx* ctx, int op, const LeleTensor* a, const LeleTensor* b, LeleBuf* out, int64_t* out_shape, int32_t* out_rank);

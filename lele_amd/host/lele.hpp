@@ -976,6 +976,46 @@ inline TensorView depthwise_conv1d_tlc(const TensorView& x, const TensorView& w,
     check(lele_hip_depthwise_conv1d_tlc(ctx(), &tx, x_offset, &tw, ob.p, pad_left, pad_right, relu, add_input, out.raw(), sh.dims, &sh.rank));
     LELE_RET(out, LELE_F32);
 }
+// ---- the packed batch: x [R, D] + offsets (count + 1 values from 0 to R), every segment computed as if it ran alone (lele_hip.h)
+inline TensorView fused_quantized_linear_segments(const TensorView& input, const std::vector<int64_t>& offsets, const TensorView& weight_int8,
+                                                  const TensorView& weight_scale, const TensorView& weight_zero, const TensorView* bias,
+                                                  bool apply_relu, Buffer& out) {
+    Shape sh;
+    LeleTensor a = input.c(), b = weight_int8.c(), s = weight_scale.c(), z = weight_zero.c();
+    Opt ob(bias);
+    check(lele_hip_fused_quantized_linear_segments(ctx(), &a, offsets.data(), (int64_t)offsets.size() - 1, &b, &s, &z, ob.p, apply_relu,
+                                                   out.raw(), sh.dims, &sh.rank));
+    LELE_RET(out, LELE_F32);
+}
+inline TensorView attention_segments(const TensorView& qkv, const std::vector<int64_t>& offsets, int64_t q_offset, int64_t k_offset,
+                                     int64_t v_offset, int64_t heads, int64_t dh, const TensorView* scale, Buffer& out) {
+    Shape sh;
+    LeleTensor t = qkv.c();
+    Opt os(scale);
+    check(lele_hip_attention_segments(ctx(), &t, q_offset, k_offset, v_offset, heads, dh, offsets.data(), (int64_t)offsets.size() - 1, os.p,
+                                      out.raw(), sh.dims, &sh.rank));
+    LELE_RET(out, LELE_F32);
+}
+inline TensorView depthwise_conv1d_tlc_segments(const TensorView& x, const std::vector<int64_t>& offsets, const TensorView& w,
+                                                const TensorView* bias, int64_t pad_left, int64_t pad_right, bool relu, int64_t x_offset,
+                                                bool add_input, Buffer& out) {
+    Shape sh;
+    LeleTensor tx = x.c(), tw = w.c();
+    Opt ob(bias);
+    check(lele_hip_depthwise_conv1d_tlc_segments(ctx(), &tx, x_offset, offsets.data(), (int64_t)offsets.size() - 1, &tw, ob.p, pad_left,
+                                                 pad_right, relu, add_input, out.raw(), sh.dims, &sh.rank));
+    LELE_RET(out, LELE_F32);
+}
+// `prefix` [p, D] in front of every segment; out_offsets receives offsets[i] + p * i
+inline TensorView segments_prepend(const TensorView& x, const std::vector<int64_t>& offsets, const TensorView& prefix, Buffer& out,
+                                   std::vector<int64_t>& out_offsets) {
+    Shape sh;
+    LeleTensor tx = x.c(), tp = prefix.c();
+    out_offsets.assign(offsets.size(), 0);
+    check(lele_hip_segments_prepend(ctx(), &tx, offsets.data(), (int64_t)offsets.size() - 1, &tp, out.raw(), out_offsets.data(), sh.dims,
+                                    &sh.rank));
+    LELE_RET(out, LELE_F32);
+}
 // view operators: shape bookkeeping only (shape.rs:2-52, 105-185)
 inline TensorView reshape(const TensorView& x, const std::vector<int64_t>& target) {
     const int64_t total = x.size();

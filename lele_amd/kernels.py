@@ -1185,6 +1185,78 @@ def depthwise_conv1d_tlc(input, weights, bias=None, pad_left=0, pad_right=0, rel
         C.c_int(int(bool(add_input))), out._h, sh.shape, C.byref(sh.rank)))
     return TensorView(_lib.DevTensor(out, sh.get(), np.float32))
 
+
+# ------------------------------------------------------------------------------------------- the packed batch (x [R, D] + offsets)
+def _offsets(offsets):
+    off = np.ascontiguousarray(offsets, np.int64)
+    if off.ndim != 1 or off.size < 1:
+        raise _lib.LeleError("offsets must hold count + 1 values")
+    return off
+
+
+def fused_quantized_linear_segments(input, offsets, weight_int8, weight_scale, weight_zero, bias, apply_relu=False, out=None, ctx=None):
+    """fused_quantized_linear with every segment of the packed input [R, K] as a batch slice of its own (one dynamic range per
+    segment): rows offsets[i] .. offsets[i + 1] are, bit for bit, fused_quantized_linear of that range alone -> [R, N]"""
+    ctx = _ctx(ctx)
+    keep = []
+    out = out or ctx.buf()
+    sh = _lib.OutShape()
+    off = _offsets(offsets)
+    _lib.check(_lib.lib().lele_hip_fused_quantized_linear_segments(
+        ctx._h, _t(input, keep), _lib.i64_ptr(off), C.c_int64(len(off) - 1), _t(weight_int8, keep), _t(weight_scale, keep),
+        _t(weight_zero, keep), _t(bias, keep), C.c_int(int(apply_relu)), out._h, sh.shape, C.byref(sh.rank)))
+    return TensorView(_lib.DevTensor(out, sh.get(), np.float32))
+
+
+def attention_segments(qkv, offsets, heads, dh, scale=None, q_offset=0, k_offset=None, v_offset=None, out=None, ctx=None):
+    """softmax(Q K^T * scale) V per segment and head over that segment's rows only: qkv [R, P] holds Q | K | V at the column offsets
+    (default: the packed projection, 0, heads * dh, 2 * heads * dh) -> [R, heads * dh], heads merged.  dh == 128, segments of at most
+    512 rows; anything else raises (there is no fallback)."""
+    ctx = _ctx(ctx)
+    keep = []
+    out = out or ctx.buf()
+    sh = _lib.OutShape()
+    off = _offsets(offsets)
+    d = int(heads) * int(dh)
+    k_offset = q_offset + d if k_offset is None else k_offset
+    v_offset = k_offset + d if v_offset is None else v_offset
+    _lib.check(_lib.lib().lele_hip_attention_segments(
+        ctx._h, _t(qkv, keep), C.c_int64(int(q_offset)), C.c_int64(int(k_offset)), C.c_int64(int(v_offset)), C.c_int64(int(heads)),
+        C.c_int64(int(dh)), _lib.i64_ptr(off), C.c_int64(len(off) - 1), _t(scale, keep), out._h, sh.shape, C.byref(sh.rank)))
+    return TensorView(_lib.DevTensor(out, sh.get(), np.float32))
+
+
+def depthwise_conv1d_tlc_segments(input, offsets, weights, bias=None, pad_left=0, pad_right=0, relu=False, x_offset=0, add_input=False,
+                                  out=None, ctx=None):
+    """depthwise_conv1d_tlc per segment of the packed input [R, P] (pad_left + pad_right == K - 1): a segment ends where its rows end,
+    bit for bit the dense call on it alone as [1, len, P] -> [R, C]"""
+    ctx = _ctx(ctx)
+    keep = []
+    out = out or ctx.buf()
+    sh = _lib.OutShape()
+    off = _offsets(offsets)
+    _lib.check(_lib.lib().lele_hip_depthwise_conv1d_tlc_segments(
+        ctx._h, _lib.as_tensor(unwrap(input), keep), C.c_int64(int(x_offset)), _lib.i64_ptr(off), C.c_int64(len(off) - 1),
+        _lib.as_tensor(unwrap(weights), keep), _lib.as_tensor(unwrap(bias), keep), C.c_int64(int(pad_left)), C.c_int64(int(pad_right)),
+        C.c_int(int(bool(relu))), C.c_int(int(bool(add_input))), out._h, sh.shape, C.byref(sh.rank)))
+    return TensorView(_lib.DevTensor(out, sh.get(), np.float32))
+
+
+def segments_prepend(x, offsets, prefix, out=None, ctx=None):
+    """`prefix` [p, D] rows in front of every segment (empty ones too) of the packed x [R, D] -> ([R + p * count, D], offsets' np.int64
+    with offsets'[i] = offsets[i] + p * i)"""
+    ctx = _ctx(ctx)
+    keep = []
+    out = out or ctx.buf()
+    sh = _lib.OutShape()
+    off = _offsets(offsets)
+    new_off = np.zeros(len(off), np.int64)
+    _lib.check(_lib.lib().lele_hip_segments_prepend(
+        ctx._h, _lib.as_tensor(unwrap(x), keep), _lib.i64_ptr(off), C.c_int64(len(off) - 1), _lib.as_tensor(unwrap(prefix), keep), out._h,
+        _lib.i64_ptr(new_off), sh.shape, C.byref(sh.rank)))
+    return TensorView(_lib.DevTensor(out, sh.get(), np.float32)), new_off
+
+
 # ------------------------------------------------------------------------------------------- ConvInteger family
 def conv_integer(input, weights, x_zero_point=None, w_zero_point=None, dilations=(), group=1, pads=(), strides=(), out=None,
                  ctx=None):

@@ -170,6 +170,56 @@ class Encoder:
             x = self.layer(x, i, None if taps is None else taps.get(i))
         return self.head(x)
 
+    # ---- the packed batch: utterances of different lengths as x [R, D] + offsets, each computed exactly as if it ran alone
+    def qls(self, x, off, p, relu, slot):
+        return self.K.fused_quantized_linear_segments(x, off, p.w, p.scale, p.zero, p.bias, relu, out=self.ws[slot], ctx=self.ctx)
+
+    def layer_segments(self, x, off, i, taps=None):
+        """Encoder.layer on a packed batch [R, d_in]: the same node list with one C-ABI call per node; the split / transposes /
+        matmul / softmax / matmul are attention_segments and the transpose / conv / transpose / add is depthwise_conv1d_tlc_segments
+        (the substitutions the compiler makes for dense plans).  taps: as Encoder.layer, every node's input and output"""
+        K, ctx, ws, L = self.K, self.ctx, self.ws, self.layers[i]
+        xin = x
+        xn = K.layer_norm(xin, L.ln1[0], L.ln1[1], -1, 1e-5, out=ws[1], ctx=ctx)
+        qkv = self.qls(xn, off, L.qkv, False, 2)                                # [R,1536]
+        mem = K.depthwise_conv1d_tlc_segments(qkv, off, L.fsmn, None, FSMN_K // 2, FSMN_K // 2, x_offset=2 * D, add_input=True,
+                                              out=ws[7], ctx=ctx)              # FSMN memory + v
+        av = K.attention_segments(qkv, off, HEADS, DH, self.scale, out=ws[5], ctx=ctx)        # [R,512], heads merged
+        att = self.qls(av, off, L.out, False, 8)
+        if taps is not None:
+            taps.update(x=xin.numpy(), xn=xn.numpy(), qkv=qkv.numpy(), mem=mem.numpy(), av=av.numpy(), att=att.numpy())
+        slot_x = 11 if i % 2 == 0 else 12
+        if L.d_in == D:
+            am = K.add(att, mem, out=ws[9], ctx=ctx)
+            x = K.add(am, xin, out=ws[slot_x], ctx=ctx)
+            if taps is not None:
+                taps.update(am=am.numpy())
+        else:  # the first layer changes width (560 -> 512): no residual
+            x = K.add(att, mem, out=ws[slot_x], ctx=ctx)
+        xn = K.layer_norm(x, L.ln2[0], L.ln2[1], -1, 1e-5, out=ws[1], ctx=ctx)
+        h = self.qls(xn, off, L.ffn1, True, 2)
+        h2 = self.qls(h, off, L.ffn2, False, 3)
+        y = K.add(x, h2, out=ws[13 if i % 2 == 0 else 14], ctx=ctx)
+        if taps is not None:
+            taps.update(x1=x.numpy(), xn2=xn.numpy(), h=h.numpy(), h2=h2.numpy(), y=y.numpy())
+        return y
+
+    def forward_segments(self, feats, offsets, taps=None):
+        """feats: packed [R, 560] device tensor (compute_segments -> Cmvn.compute_segments), offsets [count + 1] -> (logits
+        [R + 4 * count, VOCAB], offsets' with offsets'[i] = offsets[i] + 4 * i): every utterance gets the four prompt rows and runs
+        through the encoder exactly as if it were alone.  taps: {layer index: dict} to fill, plus "embed" / "head" for the two ends"""
+        K, ctx, ws = self.K, self.ctx, self.ws
+        x, off = K.segments_prepend(feats, offsets, self.prompt, out=ws[0], ctx=ctx)      # prompt [1, 4, 560]: four rows
+        if taps is not None and "embed" in taps:
+            taps["embed"].update(x=x.numpy())
+        for i in range(len(self.layers)):
+            x = self.layer_segments(x, off, i, None if taps is None else taps.get(i))
+        xn = K.layer_norm(x, self.ln_out[0], self.ln_out[1], -1, 1e-5, out=ws[1], ctx=ctx)
+        logits = self.qls(xn, off, self.ctc, False, 2)
+        if taps is not None and "head" in taps:
+            taps["head"].update(x=x.numpy(), xn=xn.numpy(), logits=logits.numpy())
+        return logits, off
+
 
 def encoder_arrays(enc):
     """the Encoder's weights as plain numpy arrays, in the layout oracle/sensevoice_ref.py consumes"""
