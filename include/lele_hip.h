@@ -365,9 +365,10 @@ int lele_hip_conv2d_res(LeleCtx* ctx, const LeleTensor* x, const LeleTensor* w, 
  * 2-D convolutions issued on ctx since the last reset, as call count and multiply-accumulate count */
 int lele_hip_conv_stats_reset(LeleCtx* ctx);
 int lele_hip_conv_stats(LeleCtx* ctx, int64_t* calls, int64_t* macs);
-/* The kernel route the most recent f32 GEMM or convolution call on ctx dispatched (matmul, matmul_fused_add, gemm, matmul_view,
- * conv2d*, conv1d, conv_transpose, the f32 form of conv_integer): its levels joined by '/', e.g. "gemm.tile64x64",
- * "conv.win3_oct32_osplit" or "conv.gemm_tap/gemm.small"; "" when the result was empty.  Recorded on the host when the call is
+/* The kernel route the most recent f32 GEMM, convolution or attention call on ctx dispatched (matmul, matmul_fused_add, gemm,
+ * matmul_view, conv2d*, conv1d, conv_transpose, the f32 form of conv_integer, attention_view, attention_segments): its levels joined
+ * by '/', e.g. "gemm.tile64x64", "conv.win3_oct32_osplit", "conv.gemm_tap/gemm.small" or "attn.rows16/attn.nt6" (the kernel, then its
+ * key-tile class; "attn.flash" and the packed form's "attn.seg" have one level); "" when the result was empty.  Recorded on the host when the call is
  * issued (a call recorded into a graph reports the route it recorded).  NUL-terminated into buf; an error when cap is too small.
  * lele_hip_route_names: every level name a route can hold, one per line; host only, no GPU needed. */
 int lele_hip_last_route(LeleCtx* ctx, char* buf, size_t cap);

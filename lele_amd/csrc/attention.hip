@@ -997,16 +997,22 @@ int lele_hip_attention_view(LeleCtx* ctx, const LeleTensor* q, const LeleMatView
         auto kern = attention_flash_kernel;
         LELE_HIP_CHECK(ensure_dyn_lds(reinterpret_cast<const void*>(kern), FA_LDS));
         hipLaunchKernelGGL(kern, grid, dim3(512), FA_LDS, ctx->stream, a);
-    } else
-    switch (a.tpad / 64) {
-        case 1: LELE_ATTN_NT(2); break;
-        case 2: LELE_ATTN_NT(4); break;
-        case 3: LELE_ATTN_NT(6); break;
-        case 4: LELE_ATTN_NT(8); break;
-        case 5: LELE_ATTN_NT(10); break;
-        case 6: LELE_ATTN_NT(12); break;
-        case 7: LELE_ATTN_NT(14); break;
-        default: LELE_ATTN_NT(16); break;
+        ctx->set_route("attn.flash");
+    } else {
+        static const char* const kernel_names[2][3] = {{"attn.rows16", "attn.rows32", "attn.rows64"},
+                                                       {"attn.rows16_exact", "attn.rows32_exact", "attn.rows64_exact"}};
+        static const char* const class_names[8] = {"attn.nt2", "attn.nt4", "attn.nt6", "attn.nt8", "attn.nt10", "attn.nt12", "attn.nt14", "attn.nt16"};
+        ctx->set_route(kernel_names[exact][rows16 ? 0 : (rt == 2 ? 2 : 1)], class_names[a.tpad / 64 - 1]);
+        switch (a.tpad / 64) {
+            case 1: LELE_ATTN_NT(2); break;
+            case 2: LELE_ATTN_NT(4); break;
+            case 3: LELE_ATTN_NT(6); break;
+            case 4: LELE_ATTN_NT(8); break;
+            case 5: LELE_ATTN_NT(10); break;
+            case 6: LELE_ATTN_NT(12); break;
+            case 7: LELE_ATTN_NT(14); break;
+            default: LELE_ATTN_NT(16); break;
+        }
     }
 #undef LELE_ATTN_NT
 #undef LELE_ATTN
@@ -1094,6 +1100,7 @@ int lele_hip_attention_segments(LeleCtx* ctx, const LeleTensor* qkv, int64_t q_o
     if (scale) LELE_TRY(ctx->dev_ptr(scale, &dsc));
     LELE_REQUIRE(rows == 0 || aligned16(dq), "attention_segments: unsupported geometry (Q / K rows are not 16-byte aligned)");
     LELE_TRY(out->reserve((size_t)rows * d * 4));
+    ctx->set_route(nullptr);
     if (rows == 0) return set_shape(out_shape, out_rank, {rows, d});
     AttnArgs a{};
     a.q = (const float*)dq + q_offset;
@@ -1108,6 +1115,7 @@ int lele_hip_attention_segments(LeleCtx* ctx, const LeleTensor* qkv, int64_t q_o
     a.scale = (const float*)dsc;
     const char* ex_env = getenv("LELE_HIP_ATTENTION_EXACT");
     const bool exact = ex_env && *ex_env && atoi(ex_env) != 0;
+    ctx->set_route(exact ? "attn.seg_exact" : "attn.seg");  // one name: a layout may take several launches
     const int4* wp = (const int4*)work;
     for (int c = 1; c <= 8; ++c)
         for (int tall = 0; tall < 2; ++tall) {

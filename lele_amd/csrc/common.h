@@ -139,9 +139,10 @@ struct LeleCtx {
     // reset_conv_stats / print_conv_stats: 2-D convolutions issued since the last reset
     int64_t conv_calls = 0, conv_macs = 0;
 
-    // lele_hip_last_route: the kernel route the last f32 GEMM or convolution call dispatched, as string literals stored at the
-    // launch site -- a wrapper that re-shaped the call first (route[0], "ci.f32"), the operator's own choice (route[1], e.g.
-    // "conv.gemm_tap") and the GEMM core's (route[2], what gemm::launch returned); unused levels are nullptr
+    // lele_hip_last_route: the kernel route the last f32 GEMM, convolution or attention call dispatched, as string literals stored
+    // at the launch site -- a wrapper that re-shaped the call first (route[0], "ci.f32"), the operator's own choice (route[1], e.g.
+    // "conv.gemm_tap", "attn.rows32") and the GEMM core's (route[2], what gemm::launch returned; for attention the key-tile class,
+    // "attn.nt6"); unused levels are nullptr
     const char* route[3] = {nullptr, nullptr, nullptr};
     void set_route(const char* op, const char* core = nullptr) {
         route[0] = nullptr;

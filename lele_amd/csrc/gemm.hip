@@ -85,6 +85,11 @@ const char* const kRouteNames[] = {
     "conv.gemm_pw", "conv.gemm_tap", "conv.gemm_generic",
     "convt.ks", "convt.phase", "convt.phase_fill",
     "ci.f32",
+    // lele_hip_attention_view: the kernel, then its key-tile class (softmax registers per lane = tpad / 32); the one-pass kernel has
+    // no classes.  lele_hip_attention_segments: one name for the launches of a layout
+    "attn.flash", "attn.rows16", "attn.rows32", "attn.rows64", "attn.rows16_exact", "attn.rows32_exact", "attn.rows64_exact",
+    "attn.nt2", "attn.nt4", "attn.nt6", "attn.nt8", "attn.nt10", "attn.nt12", "attn.nt14", "attn.nt16",
+    "attn.seg", "attn.seg_exact",
 };
 
 }  // namespace

@@ -522,8 +522,9 @@ def test_labels_cover_every_route_name():
     names = K.route_names()
     assert len(names) == len(set(names)) and all(re.fullmatch(r"[a-z0-9]+\.[a-z0-9_]+", s) for s in names), names
     used = {lvl for case in CASES for lvl in case["label"].split("/")}
-    assert not used - set(names), "labels the library cannot report: %s" % sorted(used - set(names))
-    assert not set(names) - used - {"gemm.k0"}, "routes no case reaches: %s" % sorted(set(names) - used)   # gemm.k0: test_empty_k
+    mine = {s for s in names if not s.startswith("attn.")}   # the attn. names: tests/test_attention_routes.py, the same two assertions
+    assert not used - mine, "labels the library cannot report: %s" % sorted(used - mine)
+    assert not mine - used - {"gemm.k0"}, "routes no case reaches: %s" % sorted(mine - used)   # gemm.k0: test_empty_k
 
 
 def test_tolerances_stay_within_the_derived_constant():
