@@ -368,8 +368,15 @@ int lele_hip_conv_stats(LeleCtx* ctx, int64_t* calls, int64_t* macs);
 /* The kernel route the most recent f32 GEMM, convolution or attention call on ctx dispatched (matmul, matmul_fused_add, gemm,
  * matmul_view, conv2d*, conv1d, conv_transpose, the f32 form of conv_integer, attention_view, attention_segments): its levels joined
  * by '/', e.g. "gemm.tile64x64", "conv.win3_oct32_osplit", "conv.gemm_tap/gemm.small" or "attn.rows16/attn.nt6" (the kernel, then its
- * key-tile class; "attn.flash" and the packed form's "attn.seg" have one level); "" when the result was empty.  Recorded on the host when the call is
- * issued (a call recorded into a graph reports the route it recorded).  NUL-terminated into buf; an error when cap is too small.
+ * key-tile class; "attn.flash" and the packed form's "attn.seg" have one level); "" when the result was empty.
+ * The data-movement calls report theirs as well: the strided copy engine behind strided_copy and concat ("copy.w4", "copy.w8",
+ * "copy.vec16", "copy.tile_w4", "copy.tile_w8", then "copy.i64" under 64-bit indexing; concat: its last launch), resize_nearest
+ * ("resize.up2" / "up4" / "up8" / "resize.generic"), max_pool2d ("pool.lds" or "pool.lds_sep", then "pool.pb1" / "pool.pbn" for one or
+ * several planes per workgroup; "pool.direct", "pool.direct_i64"), topk ("topk.rank", "topk.select_lds", "topk.select_l2"),
+ * copy_pitched ("cpitch.w16" / "w4" / "w1"), and one fixed name each for pad, gather, gather_elements, adaptive_avg_pool1d,
+ * transpose_cp_pitched, range_f32, range_i64, fill and cast ("pad.index", "gather.rows", "gather.elements", "apool.window",
+ * "tcp.tile32", "range.f32", "range.i64", "fill.words", "cast.convert"), so the route never names an earlier call.  Recorded on the
+ * host when the call is issued (a call recorded into a graph reports the route it recorded).  NUL-terminated into buf; an error when cap is too small.
  * lele_hip_route_names: every level name a route can hold, one per line; host only, no GPU needed. */
 int lele_hip_last_route(LeleCtx* ctx, char* buf, size_t cap);
 int lele_hip_route_names(char* buf, size_t cap);

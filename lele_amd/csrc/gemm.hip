@@ -90,6 +90,14 @@ const char* const kRouteNames[] = {
     "attn.flash", "attn.rows16", "attn.rows32", "attn.rows64", "attn.rows16_exact", "attn.rows32_exact", "attn.rows64_exact",
     "attn.nt2", "attn.nt4", "attn.nt6", "attn.nt8", "attn.nt10", "attn.nt12", "attn.nt14", "attn.nt16",
     "attn.seg", "attn.seg_exact",
+    // manip.hip: the strided copy engine (copy.i64: a second level, 64-bit indexing), resize, max-pool (pool.pb1 / pool.pbn: one or
+    // several planes per workgroup of the LDS kernels), top-k, the pitched copy; one fixed name for every entry that has no choice
+    "copy.w4", "copy.w8", "copy.vec16", "copy.tile_w4", "copy.tile_w8", "copy.i64",
+    "resize.up2", "resize.up4", "resize.up8", "resize.generic",
+    "pool.lds", "pool.lds_sep", "pool.direct", "pool.direct_i64", "pool.pb1", "pool.pbn",
+    "topk.rank", "topk.select_lds", "topk.select_l2",
+    "cpitch.w16", "cpitch.w4", "cpitch.w1",
+    "pad.index", "gather.rows", "gather.elements", "apool.window", "tcp.tile32", "range.f32", "range.i64", "fill.words", "cast.convert",
 };
 
 }  // namespace

@@ -367,7 +367,7 @@ __global__ __launch_bounds__(256) void max_pool2d_lds_kernel(const float* __rest
 }
 
 // topk over the last axis (conv2d.rs:1385-1435): stable sort by value => rank(i) = #{j : v_j beats v_i, or ties with
-// j < i}.  One block per row, O(n^2 / threads) comparisons; rows of the sizes lele uses (<= 8400) take microseconds.
+// j < i}; a NaN ranks below everything, NaNs among themselves by index.  Rows of at most 1024 elements, or k > 1024.
 __global__ __launch_bounds__(256) void topk_kernel(const float* __restrict__ x, int64_t n, int64_t k, int largest,
                                                    float* __restrict__ values, float* __restrict__ indices) {
     // grid (ceil(n / 256), rows): every thread ranks ONE element by streaming the row through LDS in 2048-element chunks;
@@ -395,7 +395,16 @@ __global__ __launch_bounds__(256) void topk_kernel(const float* __restrict__ x, 
             const int before = (int)(i - c0);
             int add = 0;
             const float4* c4 = reinterpret_cast<const float4*>(chunk);
-            if (before >= 2048) {
+            if (v != v) {
+                // a NaN ranks below every non-NaN and after the NaNs of lower index (what the select kernels' key 0 and the stable
+                // sort give): no comparison with it holds, so count by class.  A padding slot sits at 4 t + e >= cn > before.
+                for (int t = 0; t < nq; ++t) {
+                    const float4 u = c4[t];
+                    const float uu[4] = {u.x, u.y, u.z, u.w};
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) add += (uu[e] == uu[e] || 4 * t + e < before) ? 1 : 0;
+                }
+            } else if (before >= 2048) {
 #pragma unroll 8
                 for (int t = 0; t < nq; ++t) {
                     const float4 u = c4[t];
@@ -436,95 +445,6 @@ __global__ __launch_bounds__(256) void topk_kernel(const float* __restrict__ x, 
     }
 }
 
-// Long rows (n > 2048): prefilter.  If t0 is the k-th best of the first 2048 elements, anything strictly worse than t0
-// already has k elements ahead of it and cannot be in the top k -- and it can never outrank a survivor either, so the
-// survivors' ranks depend on survivors only.  Three small kernels: threshold, compaction (value + original index, the
-// index keeps the tie-break "lower index first"), rank among the survivors.
-__global__ __launch_bounds__(256) void topk_threshold_kernel(const float* __restrict__ x, int64_t n, int64_t k, int largest,
-                                                             float* __restrict__ t0, int* __restrict__ count) {
-    // grid (32, rows): 2048 sample elements, FOUR lanes per element (each scans a quarter of the sample held in LDS; the four
-    // partial ranks meet by shuffle) -- the serial 2048-step scan per element was the longest kernel of the YOLO post-processing
-    __shared__ __attribute__((aligned(16))) float chunk[2048];
-    const float* row = x + (int64_t)blockIdx.y * n;
-    const int m = (int)(n < 2048 ? n : 2048);
-    for (int t = threadIdx.x; t < 2048; t += 256) chunk[t] = t < m ? row[t] : __builtin_nanf("");
-    __syncthreads();
-    const int e = blockIdx.x * 64 + (threadIdx.x >> 2), part = threadIdx.x & 3;
-    const float v = chunk[e < 2048 ? e : 2047];
-    int rank = 0;
-    const float4* c4 = reinterpret_cast<const float4*>(chunk) + 128 * part;
-#pragma unroll 4
-    for (int t = 0; t < 128; ++t) {
-        const float4 u = c4[t];
-        const float uu[4] = {u.x, u.y, u.z, u.w};
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const bool beats = largest ? (uu[q] > v) : (uu[q] < v);
-            rank += (beats || (uu[q] == v && 512 * part + 4 * t + q < e)) ? 1 : 0;
-        }
-    }
-    rank += __shfl_xor(rank, 1);
-    rank += __shfl_xor(rank, 2);
-    if (part == 0 && e < m && rank == k - 1) t0[blockIdx.y] = v;  // exactly one element of the sample has this rank
-}
-__global__ void topk_init_kernel(int64_t rows, int largest, float* __restrict__ t0, int* __restrict__ count) {
-    const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (r < rows) {
-        count[r] = 0;
-        t0[r] = largest ? -INFINITY : INFINITY;  // stays when the sample holds fewer than k elements: keep everything
-    }
-}
-__global__ __launch_bounds__(256) void topk_compact_kernel(const float* __restrict__ x, int64_t n, int largest,
-                                                           const float* __restrict__ t0, int* __restrict__ count,
-                                                           float* __restrict__ cv, int* __restrict__ ci) {
-    const int64_t rowi = blockIdx.y, i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
-    const float v = x[rowi * n + i], t = t0[rowi];
-    const bool keep = largest ? !(v < t) : !(v > t);
-    if (keep) {
-        const int pos = atomicAdd(&count[rowi], 1);
-        cv[rowi * n + pos] = v;
-        ci[rowi * n + pos] = (int)i;
-    }
-}
-__global__ __launch_bounds__(256) void topk_rank_kernel(const float* __restrict__ cv, const int* __restrict__ ci, int64_t n,
-                                                        int64_t k, int largest, const int* __restrict__ count,
-                                                        float* __restrict__ values, float* __restrict__ indices) {
-    // 64 candidates per workgroup, four lanes each: lane `part` ranks its candidate against every fourth survivor of the
-    // LDS chunk, the partial ranks meet by shuffle
-    __shared__ float sv[1024];
-    __shared__ int si[1024];
-    const int64_t rowi = blockIdx.y;
-    const int m = count[rowi];
-    if ((int64_t)blockIdx.x * 64 >= m) return;  // uniform per workgroup
-    const int j = blockIdx.x * 64 + (threadIdx.x >> 2), part = threadIdx.x & 3;
-    const bool in = j < m;
-    const float v = in ? cv[rowi * n + j] : 0.0f;
-    const int vi = in ? ci[rowi * n + j] : 0;
-    int rank = 0;
-    for (int c0 = 0; c0 < m; c0 += 1024) {
-        __syncthreads();
-        for (int t = threadIdx.x; t < 1024; t += 256) {
-            const bool live = c0 + t < m;
-            sv[t] = live ? cv[rowi * n + c0 + t] : __builtin_nanf("");
-            si[t] = live ? ci[rowi * n + c0 + t] : 0;
-        }
-        __syncthreads();
-#pragma unroll 4
-        for (int t = part; t < 1024; t += 4) {
-            const float u = sv[t];
-            const bool beats = largest ? (u > v) : (u < v);
-            rank += (beats || (u == v && si[t] < vi)) ? 1 : 0;
-        }
-    }
-    rank += __shfl_xor(rank, 1);
-    rank += __shfl_xor(rank, 2);
-    if (in && part == 0 && rank < k) {
-        values[rowi * k + rank] = v;
-        indices[rowi * k + rank] = (float)vi;
-    }
-}
-
 // out[n][p][c] = x[n][c][p] for one image-pitched operand and result: 32 x 32 tiles through LDS, reads along p, writes along c
 __global__ __launch_bounds__(256) void transpose_cp_kernel(const float* __restrict__ x, float* __restrict__ out, int c, int pos, long long xbs, long long obs) {
     __shared__ float t[32][33];
@@ -543,9 +463,8 @@ __global__ __launch_bounds__(256) void transpose_cp_kernel(const float* __restri
     }
 }
 
-// Long rows, one workgroup per row: RADIX SELECT.  The prefilter above keeps everything at least as good as the k-th best of the
-// first 2048 elements -- ~n k / 2048 survivors, ranked against each other in O(m^2): 0.51 ms for the [64, 24000] -> 300 selection
-// of a Yolo26n-seg tail.  Here the k-th best value itself is found by four 8-bit histogram passes over order-preserving integer
+// Long rows, one workgroup per row: RADIX SELECT.  Ranking every element against the whole row (topk_kernel above) is O(n^2).
+// Here the k-th best value itself is found by four 8-bit histogram passes over order-preserving integer
 // images of the values (the histogram bin that holds the k-th element fixes 8 more bits of it each pass), the elements better
 // than it plus the first ties in index order are collected (exactly k of them: the stable sort's "lower index first" among equal
 // values), and only those k are ranked.  Five sweeps of an L2-resident row and k^2 comparisons, no atomics on global memory, a
@@ -710,6 +629,16 @@ __global__ void cast_kernel(const S* __restrict__ in, D* __restrict__ out, int64
         out[i] = (D)in[i];
 }
 
+// f32 -> i64 with Rust's `as i64` (utils.rs:84-101): truncation toward zero, saturating, NaN -> 0.  A plain (int64_t)v is undefined
+// in C++ outside [-2^63, 2^63) and for a NaN
+__global__ void cast_f32_i64_kernel(const float* __restrict__ in, int64_t* __restrict__ out, int64_t n) {
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        const float v = in[i];
+        const float c = fminf(fmaxf(v, -9223372036854775808.0f), 9223371487098961920.0f);  // [-2^63, 2^63 - 2^39]: every float in range
+        out[i] = (v != v) ? (int64_t)0 : v >= 9223372036854775808.0f ? INT64_MAX : (int64_t)c;
+    }
+}
+
 // f32 -> u8 with Rust's `as u8` (src/tensor.rs:92-97, TensorView::reinterpret_as_u8): truncation toward zero, saturating, NaN -> 0
 __global__ void cast_f32_u8_kernel(const float* __restrict__ in, uint8_t* __restrict__ out, int64_t n) {
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
@@ -726,6 +655,8 @@ struct Word16 {
 
 // Canonicalise the descriptor before launching: drop unit dims, merge dims that are contiguous on both sides, move
 // 16-byte words when the innermost dim allows it, and index in 32 bits when everything fits.
+// Records the route (lele_hip_last_route): copy.tile_w4 / copy.tile_w8, copy.vec16, copy.w4 / copy.w8, then copy.i64 when the
+// strided kernel indexes in 64 bits; nothing for an empty copy.
 int launch_copy(LeleCtx* ctx, const void* in, void* out, int64_t numel, const CopyDesc& d0, size_t esize) {
     if (numel == 0) return 0;
     CopyDesc d{};
@@ -798,11 +729,13 @@ int launch_copy(LeleCtx* ctx, const void* in, void* out, int64_t numel, const Co
                 else
                     hipLaunchKernelGGL(transpose_tile_kernel<uint32_t>, tgrid, dim3(256), 0, ctx->stream, (const uint32_t*)in,
                                        (uint32_t*)out, d, tj);
+                ctx->set_route(esize == 8 ? "copy.tile_w8" : "copy.tile_w4");
                 LELE_HIP_CHECK(hipGetLastError());
                 return 0;
             }
         }
     }
+    ctx->set_route(vec ? "copy.vec16" : esize == 8 ? "copy.w8" : "copy.w4", i32 ? nullptr : "copy.i64");
     const dim3 grid(grid_for(numel)), block(256);
 #define LELE_COPY(W, I) \
     hipLaunchKernelGGL((strided_copy_kernel<W, I>), grid, block, 0, ctx->stream, (const W*)in, (W*)out, numel, d)
@@ -874,6 +807,7 @@ int lele_hip_strided_copy(LeleCtx* ctx, const LeleTensor* x, const int64_t* out_
     const void* dx = nullptr;
     LELE_TRY(ctx->dev_ptr(x, &dx));
     LELE_TRY(out->reserve((size_t)n * es));
+    ctx->set_route(nullptr);
     LELE_TRY(launch_copy(ctx, dx, out->data, n, d, es));
     return set_shape_v(out_shape, out_rank, std::vector<int64_t>(out_shape_in, out_shape_in + rank));
 }
@@ -901,6 +835,7 @@ int lele_hip_concat(LeleCtx* ctx, const LeleTensor* const* inputs, size_t ninput
     std::vector<int64_t> ostr = strides_of(oshape.data(), rank);
     LELE_TRY(ctx->arena_reset());
     LELE_TRY(out->reserve((size_t)n * es));
+    ctx->set_route(nullptr);  // (each launch_copy overwrites it: the route of the last non-empty input)
     int64_t pos = 0;
     for (size_t i = 0; i < ninputs; ++i) {
         const LeleTensor* t = inputs[i];
@@ -948,6 +883,7 @@ int lele_hip_pad(LeleCtx* ctx, const LeleTensor* x, const int64_t* pads, int32_t
     const void* dx = nullptr;
     LELE_TRY(ctx->dev_ptr(x, &dx));
     LELE_TRY(out->reserve((size_t)n * es));
+    ctx->set_route(n ? "pad.index" : nullptr);
     if (n) {
         if (es == 8)
             hipLaunchKernelGGL(pad_kernel<uint64_t>, dim3(grid_for(n)), dim3(256), 0, ctx->stream, (const uint64_t*)dx,
@@ -992,6 +928,7 @@ int lele_hip_gather(LeleCtx* ctx, const LeleTensor* data, const LeleTensor* indi
     LELE_TRY(ctx->dev_ptr(data, &dd));
     LELE_TRY(ctx->dev_ptr(indices, &di));
     LELE_TRY(out->reserve((size_t)total * es));
+    ctx->set_route(total ? "gather.rows" : nullptr);
     if (total) {
         const dim3 g(grid_for(total)), b(256);
 #define LELE_GATHER(W, I)                                                                                          \
@@ -1044,6 +981,7 @@ int lele_hip_gather_elements(LeleCtx* ctx, const LeleTensor* x, const LeleTensor
     LELE_TRY(ctx->dev_ptr(x, &dx));
     LELE_TRY(ctx->dev_ptr(indices, &di));
     LELE_TRY(out->reserve((size_t)total * 4));
+    ctx->set_route(total ? "gather.elements" : nullptr);
     if (total) {
         hipLaunchKernelGGL(gather_elements_kernel, dim3(grid_for(total)), dim3(256), 0, ctx->stream, (const float*)dx,
                            (const float*)di, (float*)out->data, total, d, ctx->deverr_dev);
@@ -1070,6 +1008,7 @@ int lele_hip_adaptive_avg_pool1d(LeleCtx* ctx, const LeleTensor* x, int64_t outp
     const void* dx = nullptr;
     LELE_TRY(ctx->dev_ptr(x, &dx));
     LELE_TRY(out->reserve((size_t)total * 4));
+    ctx->set_route(total ? "apool.window" : nullptr);
     if (total) {
         hipLaunchKernelGGL(adaptive_avg_pool1d_kernel, dim3(grid_for(total)), dim3(256), 0, ctx->stream, (const float*)dx,
                            (float*)out->data, channels, in_len, output_len);
@@ -1110,6 +1049,7 @@ static int resize_nearest_entry(LeleCtx* ctx, const LeleTensor* x, int64_t out_h
     }
     const long long xbs_ = pv && pv->x_pitch ? pv->x_pitch : in_img, obs_ = pv && pv->out_pitch ? pv->out_pitch : out_img;
     const int64_t up = x->shape[2] > 0 && out_h % x->shape[2] == 0 ? out_h / x->shape[2] : 0;
+    ctx->set_route(nullptr);
     if (total && asymmetric && (up == 2 || up == 4 || up == 8) && out_w == up * x->shape[3] && x->shape[3] % 4 == 0 && x->shape[0] <= 65535 &&
         in_img / 4 < (int64_t(1) << 32) && ((((uintptr_t)dx) | ((uintptr_t)dst)) & 15) == 0 && xbs_ % 4 == 0 && obs_ % 4 == 0) {
         const unsigned quads = (unsigned)(in_img / 4);
@@ -1120,8 +1060,10 @@ static int resize_nearest_entry(LeleCtx* ctx, const LeleTensor* x, int64_t out_h
             hipLaunchKernelGGL(resize_up_kernel<4>, ugrid, dim3(256), 0, ctx->stream, (const float*)dx, dst, quads, (int)(x->shape[3] / 4), xbs_, obs_);
         else
             hipLaunchKernelGGL(resize_up_kernel<8>, ugrid, dim3(256), 0, ctx->stream, (const float*)dx, dst, quads, (int)(x->shape[3] / 4), xbs_, obs_);
+        ctx->set_route(up == 2 ? "resize.up2" : up == 4 ? "resize.up4" : "resize.up8");
         LELE_HIP_CHECK(hipGetLastError());
     } else if (total) {
+        ctx->set_route("resize.generic");
         hipLaunchKernelGGL(resize_nearest_kernel, dim3(grid_for(total)), dim3(256), 0, ctx->stream, (const float*)dx, dst, planes,
                            (int)x->shape[2], (int)x->shape[3], (int)out_h, (int)out_w, asymmetric, (int)x->shape[1],
                            (long long)(pv && pv->x_pitch ? pv->x_pitch : in_img), (long long)(pv && pv->out_pitch ? pv->out_pitch : out_img));
@@ -1180,6 +1122,7 @@ static int max_pool2d_entry(LeleCtx* ctx, const LeleTensor* x, const int64_t* ke
         LELE_TRY(out->reserve((size_t)total * 4));
         dst = (float*)out->data;
     }
+    ctx->set_route(nullptr);
     if (total) {
         const int64_t in_total = planes * plane_in;
         // whole planes in LDS when (input + output plane) fit 48 KB: as many planes per workgroup as keep >= 4 workgroups per CU
@@ -1195,10 +1138,13 @@ static int max_pool2d_entry(LeleCtx* ctx, const LeleTensor* x, const int64_t* ke
             const size_t lds = (size_t)(((ppb * plane_in + 3) & ~int64_t(3)) + ppb * plane_out + (separable ? ppb * d.in_h * d.out_w : 0)) * 4;
             hipLaunchKernelGGL(max_pool2d_lds_kernel, dim3((unsigned)((d.channels + ppb - 1) / ppb), (unsigned)x->shape[0]), dim3(256), lds,
                                ctx->stream, (const float*)dx, dst, d, (int)ppb, (int)separable);
+            ctx->set_route(separable ? "pool.lds_sep" : "pool.lds", ppb > 1 ? "pool.pbn" : "pool.pb1");
         } else if (total < (int64_t(1) << 31) && in_total < (int64_t(1) << 31)) {
             hipLaunchKernelGGL(max_pool2d_kernel<int32_t>, dim3(grid_for(total)), dim3(256), 0, ctx->stream, (const float*)dx, dst, planes, d);
+            ctx->set_route("pool.direct");
         } else {
             hipLaunchKernelGGL(max_pool2d_kernel<int64_t>, dim3(grid_for(total)), dim3(256), 0, ctx->stream, (const float*)dx, dst, planes, d);
+            ctx->set_route("pool.direct_i64");
         }
         LELE_HIP_CHECK(hipGetLastError());
     }
@@ -1232,6 +1178,7 @@ int lele_hip_transpose_cp_pitched(LeleCtx* ctx, const LeleTensor* x, const LeleP
     LELE_TRY(ctx->dev_ptr(x, &dx));
     void* dst = nullptr;
     LELE_TRY(lele::pitched_out(out, pitch, images, per, 4, &dst));
+    ctx->set_route(images * per ? "tcp.tile32" : nullptr);
     if (images * per) {
         LELE_REQUIRE(images <= 65535 && (c + 31) / 32 <= 65535 && pos < (int64_t(1) << 31) && c < (int64_t(1) << 31), "transpose_cp_pitched: tensor too large");
         hipLaunchKernelGGL(transpose_cp_kernel, dim3((unsigned)((pos + 31) / 32), (unsigned)((c + 31) / 32), (unsigned)images), dim3(256), 0, ctx->stream,
@@ -1257,12 +1204,14 @@ int lele_hip_copy_pitched(LeleCtx* ctx, const LeleTensor* x, const LelePitch* pi
     LELE_TRY(ctx->dev_ptr(x, &dx));
     void* dst = nullptr;
     LELE_TRY(lele::pitched_out(out, pitch, images, per, es, &dst));
+    ctx->set_route(nullptr);
     if (images * per) {
         LELE_REQUIRE(images <= 65535, "copy_pitched: more than 65535 images");
         const size_t row = (size_t)per * es, sp = (size_t)(pitch->x_pitch ? pitch->x_pitch : per) * es,
                      dp = (size_t)(pitch->out_pitch ? pitch->out_pitch : per) * es;
         const int w = ((((uintptr_t)dx) | ((uintptr_t)dst) | row | sp | dp) & 15) == 0 ? 16
                       : ((((uintptr_t)dx) | ((uintptr_t)dst) | row | sp | dp) & 3) == 0 ? 4 : 1;
+        ctx->set_route(w == 16 ? "cpitch.w16" : w == 4 ? "cpitch.w4" : "cpitch.w1");
         const unsigned chunks = (unsigned)std::max<size_t>(1, std::min<size_t>((row / w + 2047) / 2048, 4096));
         const dim3 cgrid(chunks, (unsigned)images);
         if (w == 16)
@@ -1292,6 +1241,7 @@ int lele_hip_topk(LeleCtx* ctx, const LeleTensor* x, int64_t k, int largest, Lel
     LELE_TRY(ctx->dev_ptr(x, &dx));
     LELE_TRY(out_values->reserve((size_t)rows * kk * 4));
     LELE_TRY(out_indices->reserve((size_t)rows * kk * 4));
+    ctx->set_route(nullptr);
     if (rows * kk) {
         const dim3 tgrid((unsigned)((n + 255) / 256), (unsigned)rows);
         if (n > 1024 && kk <= 1024 && n < (int64_t(1) << 31) && rows < (int64_t(1) << 31)) {  // long rows: radix select, a workgroup per row
@@ -1300,28 +1250,16 @@ int lele_hip_topk(LeleCtx* ctx, const LeleTensor* x, int64_t k, int largest, Lel
                 LELE_HIP_CHECK(lele::ensure_dyn_lds(reinterpret_cast<const void*>(kern), TOPK_STAGE_MAX * 4));  // (the opt-in is remembered per kernel: ask for the most)
                 hipLaunchKernelGGL(kern, dim3((unsigned)rows), dim3(TOPK_TPB), (size_t)n * 4, ctx->stream, (const float*)dx, n, (int)kk, largest,
                                    (float*)out_values->data, (float*)out_indices->data);
+                ctx->set_route("topk.select_lds");
             } else {
+                ctx->set_route("topk.select_l2");
                 hipLaunchKernelGGL(topk_select_kernel<false>, dim3((unsigned)rows), dim3(TOPK_TPB), 0, ctx->stream, (const float*)dx, n, (int)kk,
                                    largest, (float*)out_values->data, (float*)out_indices->data);
             }
-        } else if (n <= 4096 || kk > 1024 || n >= (int64_t(1) << 31)) {
+        } else {  // short rows, k > 1024 (the select kernels keep k candidates in LDS), or a row of 2^31 elements and more
             hipLaunchKernelGGL(topk_kernel, tgrid, dim3(256), 0, ctx->stream, (const float*)dx, n, kk, largest,
                                (float*)out_values->data, (float*)out_indices->data);
-        } else {  // prefilter on the first 2048 elements, then rank the survivors only
-            void *t0 = nullptr, *cnt = nullptr, *cv = nullptr, *ci = nullptr;
-            LELE_TRY(ctx->arena_alloc((size_t)rows * 4, &t0));
-            LELE_TRY(ctx->arena_alloc((size_t)rows * 4, &cnt));
-            LELE_TRY(ctx->arena_alloc((size_t)rows * n * 4, &cv));
-            LELE_TRY(ctx->arena_alloc((size_t)rows * n * 4, &ci));
-            hipLaunchKernelGGL(topk_init_kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, ctx->stream, rows, largest,
-                               (float*)t0, (int*)cnt);
-            hipLaunchKernelGGL(topk_threshold_kernel, dim3(32, (unsigned)rows), dim3(256), 0, ctx->stream, (const float*)dx, n, kk,
-                               largest, (float*)t0, (int*)cnt);
-            hipLaunchKernelGGL(topk_compact_kernel, tgrid, dim3(256), 0, ctx->stream, (const float*)dx, n, largest,
-                               (const float*)t0, (int*)cnt, (float*)cv, (int*)ci);
-            const dim3 rgrid((unsigned)((n + 63) / 64), (unsigned)rows);
-            hipLaunchKernelGGL(topk_rank_kernel, rgrid, dim3(256), 0, ctx->stream, (const float*)cv, (const int*)ci, n, kk,
-                               largest, (const int*)cnt, (float*)out_values->data, (float*)out_indices->data);
+            ctx->set_route("topk.rank");
         }
         LELE_HIP_CHECK(hipGetLastError());
     }
@@ -1334,6 +1272,7 @@ int lele_hip_range_f32(LeleCtx* ctx, float start, float delta, int64_t n, LeleBu
     LELE_REQUIRE(ctx && out && n >= 0, "range: bad argument");
     LELE_HIP_CHECK(hipSetDevice(ctx->device));
     LELE_TRY(out->reserve((size_t)n * 4));
+    ctx->set_route(n ? "range.f32" : nullptr);
     if (n) {
         hipLaunchKernelGGL(range_kernel, dim3(grid_for(n)), dim3(256), 0, ctx->stream, start, delta, n, (float*)out->data);
         LELE_HIP_CHECK(hipGetLastError());
@@ -1345,6 +1284,7 @@ int lele_hip_range_i64(LeleCtx* ctx, int64_t start, int64_t delta, int64_t n, Le
     LELE_REQUIRE(ctx && out && n >= 0, "range_i64: bad argument");
     LELE_HIP_CHECK(hipSetDevice(ctx->device));
     LELE_TRY(out->reserve((size_t)n * 8));
+    ctx->set_route(n ? "range.i64" : nullptr);
     if (n) {
         hipLaunchKernelGGL(range_i64_kernel, dim3(grid_for(n)), dim3(256), 0, ctx->stream, start, delta, n,
                            (int64_t*)out->data);
@@ -1363,6 +1303,7 @@ int lele_hip_fill(LeleCtx* ctx, const int64_t* shape, int32_t rank, int32_t dtyp
     int64_t n = 1;
     for (int i = 0; i < rank; ++i) n *= shape[i];
     LELE_TRY(out->reserve((size_t)n * es));
+    ctx->set_route(n ? "fill.words" : nullptr);
     if (n) {
         if (es == 8)
             hipLaunchKernelGGL(fill_kernel<uint64_t>, dim3(grid_for(n)), dim3(256), 0, ctx->stream, (uint64_t*)out->data,
@@ -1386,9 +1327,11 @@ int lele_hip_cast(LeleCtx* ctx, const LeleTensor* x, int32_t to_dtype, LeleBuf* 
     LELE_TRY(ctx->dev_ptr(x, &dx));
     LELE_TRY(out->reserve((size_t)n * dtype_size(to_dtype)));
     const dim3 g(grid_for(n)), b(256);
+    ctx->set_route(n ? "cast.convert" : nullptr);
     if (n) {
 #define LELE_CAST(S, D) hipLaunchKernelGGL((cast_kernel<S, D>), g, b, 0, ctx->stream, (const S*)dx, (D*)out->data, n)
-        if (x->dtype == LELE_F32 && to_dtype == LELE_I64) LELE_CAST(float, int64_t);
+        if (x->dtype == LELE_F32 && to_dtype == LELE_I64)
+            hipLaunchKernelGGL(cast_f32_i64_kernel, g, b, 0, ctx->stream, (const float*)dx, (int64_t*)out->data, n);
         else if (x->dtype == LELE_I64 && to_dtype == LELE_F32) LELE_CAST(int64_t, float);
         else if (x->dtype == LELE_I32 && to_dtype == LELE_F32) LELE_CAST(int32_t, float);
         else if (x->dtype == LELE_I32 && to_dtype == LELE_I64) LELE_CAST(int32_t, int64_t);

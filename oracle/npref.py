@@ -229,7 +229,10 @@ def max_pool2d(x, kernel, strides=(), pads=(), dilations=(), ceil_mode=False):  
     out = np.full((n, c, oh, ow), -np.inf, np.float32)
     for a in range(kh):
         for b in range(kw):
-            out = np.maximum(out, xp[:, :, a * dh:a * dh + oh * sh:sh, b * dw:b * dw + ow * sw:sw])
+            # `if val > max_val` (conv2d.rs:1242): a NaN never wins, the first of equal values (+0 before -0) stays.  A padded cell
+            # is skipped upstream; as -inf it never wins either
+            tap = xp[:, :, a * dh:a * dh + oh * sh:sh, b * dw:b * dw + ow * sw:sw]
+            out = np.where(tap > out, tap, out)
     return out
 
 

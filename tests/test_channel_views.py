@@ -482,8 +482,8 @@ def test_pitched_kernels_vs_oracle(ctx):
     assert np.array_equal(r.numpy(), wide[:, 3:19] + wide[:, 20:36])
     assert np.array_equal(K.mul(a, wide[:, 20:36].copy(), ctx=ctx).numpy(), wide[:, 3:19] * wide[:, 20:36])
     # max-pool: `if val > max_val` (conv2d.rs:1230-1247) -- a NaN never wins and the first of equal values stays, so a window that
-    # holds +0 then -0 gives +0.  The numpy reference (np.maximum) propagates NaN: compared on clean data; the special values are
-    # checked by hand where they sit, and pitched == dense on everything.
+    # holds +0 then -0 gives +0.  npref.max_pool2d restates that comparison (tests/test_manip_routes.py pins it on a literal scan):
+    # the special values are compared with it by bits, checked by hand where they sit, and pitched == dense on everything.
     wz = wide.copy()
     wz[0, 5, 3, 3:5] = [0.0, -0.0]
     wz[0, 5, 1:6, 1:7] = np.minimum(wz[0, 5, 1:6, 1:7], 0.0) - (wz[0, 5, 1:6, 1:7] != 0) * 1.0   # everything else around them negative
@@ -496,6 +496,7 @@ def test_pitched_kernels_vs_oracle(ctx):
         dense = K.max_pool2d(np.ascontiguousarray(wz[:, 4:20]), kk, ss, pp, ctx=ctx).numpy()
         got = K.max_pool2d(srcz.channels(4, 20), kk, ss, pp, ctx=ctx).numpy()
         assert np.array_equal(got.view(np.uint32), dense.view(np.uint32)), kk
+        assert np.array_equal(dense.view(np.uint32), npref.max_pool2d(wz[:, 4:20], kk, ss, pp).view(np.uint32)), kk
         ob = ctx.buf()
         ob.reserve(4 * n * 20 * want.shape[2] * want.shape[3])
         got = K.max_pool2d(srcz.channels(4, 20), kk, ss, pp, out=ob, out_window=(2 * want.shape[2] * want.shape[3], 20 * want.shape[2] * want.shape[3]), ctx=ctx)
