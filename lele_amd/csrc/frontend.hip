@@ -41,6 +41,7 @@ struct FeDev {                 // device tables (all owned by LeleFrontend)
     int mel_steps;             // total steps (rows of melw)
     int n_mels;
     int lfr_m, lfr_n;
+    int tile_dma;              // aligned runs of the fused kernels are staged by direct-to-LDS loads (LELE_HIP_FE_TILE_DMA, default 1)
 };
 
 // Which 64-frame block of which utterance a workgroup takes.  compute / compute_batch: block x of utterance y of the grid (equal-length
@@ -151,6 +152,23 @@ struct TwLds {  // twiddle accessor over the LDS copy (phase B: per-lane indices
     __device__ __forceinline__ float2 at(int i) const { return t[i]; }
 };
 
+// One direct-to-LDS load of 16 bytes per lane (global_load_lds_dwordx4): LDS address = lds_dst (wave-uniform) + 16 * lane.  The
+// compiler's builtin, not inline assembly: a volatile asm statement counts as a write to all memory, after which the pass loop's
+// scalar table loads become vector loads (190 registers, two waves a SIMD); the builtin's own cost of that kind is what
+// fe_const_table below takes back.  The compiler also counts it: the block's __syncthreads() waits for it by itself.
+__device__ __forceinline__ void fe_dma16(const void* gsrc, __attribute__((address_space(3))) char* lds_dst) {
+    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)gsrc, lds_dst, 16, 0, 0);
+}
+
+// A table that no kernel writes, seen through the constant address space.  The pass loop reads its wave-uniform twiddles with scalar
+// loads; the compiler grants those to a plain global pointer only while nothing before the load may have written memory, and it
+// counts a direct-to-LDS load as such a write.  A constant-space pointer needs no such proof.
+__device__ __forceinline__ const float* fe_const_table(const float* t, int pass) {
+    auto c = (const __attribute__((address_space(4))) float*)t;
+    asm("" : "+s"(c) : "s"(pass));  // opaque, or the two casts fold away; tied to the pass, or the loads leave the loop and their 58 SGPRs spill
+    return (const float*)c;
+}
+
 template <int MODE>
 __device__ __forceinline__ float lane_rot_prev(float v, int p) {
     // value of lane (p-1) mod 16 inside this 16-lane row
@@ -194,47 +212,88 @@ __device__ __forceinline__ void fe_main_body(const float* __restrict__ pcm, int6
     __shared__ int s_moff[kMaxMelRounds + 1];
     constexpr int kTwBase = LOWREG ? 31 : 0;
 
-    for (int i = threadIdx.x; i < 511 - kTwBase; i += 256) s_tw[i] = tb.tw[i + kTwBase];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int g = lane >> 4, p = lane & 15;
+    constexpr int kVecPerRow = fe::kHop / 4;
+    constexpr int kVecs = kRows * kVecPerRow;
+    constexpr int kIters = (kVecs + 255) / 256;
+    constexpr bool kTwDma = FUSED && !LOWREG;  // the whole 4 KiB twiddle table by four direct-to-LDS loads
+    // FUSED: the block's run [64*blockIdx.x*hop, +66 hops) goes into the LDS tile as [hop row][offset] -- the layout and bank argument of
+    // fe_frame_sum_kernel -- as RAW samples (the x32768 is in the sum chain below).  The tile is a copy, so where the run is 16-byte
+    // aligned it is made by direct-to-LDS loads: no staging registers, no ds_write, half a dozen address instructions a KiB.  A wave
+    // instruction fills 64 consecutive 16-byte slots of the tile; a row is 41 slots (40 of data + the pad slot), and lane l of
+    // instruction u of wave w owns slot i = (4u + w)*64 + l = 256u + threadIdx.x.  Slot i sits in row i / 41, so its data are the 16
+    // bytes at 16 * (i - i / 41) of the run (a pad slot fetches the first vector of the next row; nothing reads it).  42 instructions
+    // cover slots 0 .. 2687; the last slot the sums read is 65*41 + 19 = 2684 (frame 63 ends half-way through row 65), so nothing
+    // is written past the tile.  They are the first thing the kernel issues: no table load and no window coefficient stands between
+    // the workgroup's start and its first HBM request.
+    // Bounds: the source offset is clamped in 32-bit arithmetic RELATIVE TO THE RUN's first sample: `rem` = samples of the utterance from
+    // there on (wave-uniform, at least one frame; capped far above the run's 10 560 so that it fits an int), and a slot that would end
+    // past it fetches the utterance's last four samples instead.  No lane reads outside its utterance; slots that are clamped only
+    // ever feed frames >= num_frames, whose sums are discarded.
+    const bool tile_dma = FUSED && !LOWREG && aligned16 && tb.tile_dma;  // wave-uniform (LELE_HIP_FE_TILE_DMA=0: register staging everywhere)
+    float4 st[FUSED ? kIters : 1];
+    if constexpr (FUSED) {
+        const float* run = pcm + (int64_t)bl.y() * utt_stride + (int64_t)bl.x() * FR * fe::kHop;
+        const int64_t rem64 = utt_stride - (int64_t)bl.x() * FR * fe::kHop;
+        const int rem = (int)(rem64 < (1 << 20) ? rem64 : (1 << 20));
+        if (tile_dma) {
+            constexpr int kSlotsPerRow = kSumPitch / 4;
+            constexpr int kDma = (FR - 1 + 2) * kSlotsPerRow + (fe::kFrame - 2 * fe::kHop) / 4;  // slots the sums read: 2685
+            constexpr int kDmaInstr = (kDma + 63) / 64;
+            static_assert(kDmaInstr * 64 * 4 <= kXFloats, "the tile DMA stays inside s_x");
+            auto* tile_lds = (__attribute__((address_space(3))) char*)s_x;
+            static_assert(kSlotsPerRow == 41 && kDmaInstr * 64 * 1599 < (1 << 24), "i / 41 == (i * 1599) >> 16 for every slot");
+            const unsigned last = 4u * (unsigned)rem - 16u;  // rem is a multiple of 4 here (aligned16) and >= kFrame
+            const int wave_s = __builtin_amdgcn_readfirstlane(wave);  // the LDS destination is a scalar operand
+#pragma unroll
+            for (int u = 0; 4 * u < kDmaInstr; ++u) {
+                const unsigned i = 256u * u + threadIdx.x;
+                const unsigned ob = 16u * (i - ((i * 1599u) >> 16));
+                if (4 * u + 3 < kDmaInstr || 4 * u + wave_s < kDmaInstr)
+                    fe_dma16(reinterpret_cast<const char*>(run) + (ob < last ? ob : last), tile_lds + (4 * u + wave_s) * 1024);
+            }
+        }
+        if (kTwDma && wave == 3) {  // s_tw: 511 entries + the pad = 4 KiB (the device table is padded to 512 too)
+            auto* tw_lds = (__attribute__((address_space(3))) char*)s_tw;
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+                fe_dma16(reinterpret_cast<const char*>(tb.tw) + 1024 * k + 16 * lane, tw_lds + 1024 * k);
+        }
+        if (!tile_dma) {
+            // register staging (unaligned runs -- most compute_segments blocks): 256 threads, all loads of a thread issued before the
+            // first use
+#pragma unroll
+            for (int u = 0; u < kIters; ++u) {
+                const int idx = u * 256 + (int)threadIdx.x;
+                int o = 4 * idx;
+                if (o + 3 >= rem) o = aligned16 ? ((rem - 4) & ~3) : (rem - 4);
+                const float* src = run + o;
+                if (aligned16)
+                    st[u] = *reinterpret_cast<const float4*>(src);
+                else
+                    st[u] = make_float4(src[0], src[1], src[2], src[3]);
+            }
+        }
+    }
+    if (!kTwDma)
+        for (int i = threadIdx.x; i < 511 - kTwBase; i += 256) s_tw[i] = tb.tw[i + kTwBase];
     if (!STDMEL)
         for (int i = threadIdx.x; i < tb.mel_steps * 16; i += 256) s_melw[i] = tb.melw[i];
     if (threadIdx.x < tb.mel_rounds * 16) s_mstart[threadIdx.x] = tb.mel_start[threadIdx.x];
     if (threadIdx.x <= tb.mel_rounds) s_moff[threadIdx.x] = tb.mel_step_off[threadIdx.x];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int g = lane >> 4, p = lane & 15;
     if (FUSED) {
-        // stage the run [64*blockIdx.x*hop, +66 hops) as [hop row][offset] (x32768, exact) -- same layout and bank
-        // argument as fe_frame_sum_kernel, 256 threads, all loads of a thread issued before the first use
-        const float* ubase = pcm + (int64_t)bl.y() * utt_stride;
-        const int64_t s0 = (int64_t)bl.x() * FR * fe::kHop;
-        constexpr int kVecPerRow = fe::kHop / 4;
-        constexpr int kVecs = kRows * kVecPerRow;
-        constexpr int kIters = (kVecs + 255) / 256;
-        float4 st[kIters];
+        if (!tile_dma) {
 #pragma unroll
-        for (int u = 0; u < kIters; ++u) {
-            const int idx = u * 256 + (int)threadIdx.x;
-            int64_t sidx = s0 + 4 * (int64_t)idx;
-            if (sidx + 3 >= utt_stride) sidx = aligned16 ? ((utt_stride - 4) & ~int64_t(3)) : (utt_stride - 4);
-            if (sidx < 0) sidx = 0;
-            const float* src = ubase + sidx;
-            if (aligned16)
-                st[u] = *reinterpret_cast<const float4*>(src);
-            else
-                st[u] = make_float4(src[0], src[1], src[2], src[3]);
-        }
-#pragma unroll
-        for (int u = 0; u < kIters; ++u) {
-            const int idx = u * 256 + (int)threadIdx.x;
-            if (idx < kVecs) {
-                float4 xv = st[u];
-                xv.x *= 32768.0f;
-                xv.y *= 32768.0f;
-                xv.z *= 32768.0f;
-                xv.w *= 32768.0f;
-                const int row = idx / kVecPerRow, c = idx - row * kVecPerRow;
-                *reinterpret_cast<float4*>(&s_x[row * kSumPitch + 4 * c]) = xv;
+            for (int u = 0; u < kIters; ++u) {
+                const int idx = u * 256 + (int)threadIdx.x;
+                if (idx < kVecs) {
+                    const int row = idx / kVecPerRow, c = idx - row * kVecPerRow;
+                    *reinterpret_cast<float4*>(&s_x[row * kSumPitch + 4 * c]) = st[u];
+                }
             }
         }
+        __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0): this wave's direct-to-LDS loads have landed; the barrier covers the others'
         __syncthreads();
     }
     // window coefficients and the first pass's samples are requested before the sums / barrier below, so that their
@@ -269,8 +328,12 @@ __device__ __forceinline__ void fe_main_body(const float* __restrict__ pcm, int6
     };
     issue_loads(0);
     if (FUSED) {
-        constexpr int kVecPerRow = fe::kHop / 4;
-        if (wave == 0 && lane < FR) {  // raw_frame.iter().sum() (pipeline.rs:115): one lane per frame, 400 adds in index order
+        // raw_frame.iter().sum() (pipeline.rs:115) over the scaled samples (pipeline.rs:90-112): one lane per frame, 400 steps in index
+        // order.  The tile holds RAW samples: x * 32768 is exact (a power of two), so `sum + x * 32768` rounds once -- which is what one
+        // fused multiply-add does: the same bits, and the scaling costs no instruction (the argument of the pass body's x * 32768 - mean;
+        // like it, it breaks only where x * 2^15 overflows)
+        // (wave 0 always: rotating the summing wave with the block index measured the same, docs/experiments.md)
+        if (wave == 0 && lane < FR) {
             float sum = 0.0f;
 #pragma unroll
             for (int seg = 0; seg < 3; ++seg) {
@@ -279,10 +342,10 @@ __device__ __forceinline__ void fe_main_body(const float* __restrict__ pcm, int6
 #pragma unroll 10
                 for (int k = 0; k < nvec; ++k) {
                     const float4 r = *reinterpret_cast<const float4*>(rowp + 4 * k);
-                    sum = sum + r.x;
-                    sum = sum + r.y;
-                    sum = sum + r.z;
-                    sum = sum + r.w;
+                    sum = __builtin_fmaf(r.x, 32768.0f, sum);
+                    sum = __builtin_fmaf(r.y, 32768.0f, sum);
+                    sum = __builtin_fmaf(r.z, 32768.0f, sum);
+                    sum = __builtin_fmaf(r.w, 32768.0f, sum);
                 }
             }
             s_mean[lane] = sum / (float)fe::kFrame;  // pipeline.rs:116
@@ -334,7 +397,7 @@ __device__ __forceinline__ void fe_main_body(const float* __restrict__ pcm, int6
 
         // 5. FFT stages 1..5 (wave-uniform twiddles straight from the table)
         fe::cf a[fe::kRegs];
-        fe::phase_a_fast(xin, a, tb.tw_re, tb.tw_im);
+        fe::phase_a_fast(xin, a, fe_const_table(tb.tw_re, pass), fe_const_table(tb.tw_im, pass));
 
         float pw[2][8];
         float p256 = 0.0f;
@@ -921,6 +984,10 @@ int lele_hip_frontend_create(LeleCtx* ctx, const LeleFeatureConfig* cfg, LeleFro
     fe->dpp_mode = env ? atoi(env) : 1;  // 1: DPP row_ror (default), 0: __shfl (ds_bpermute)
     const char* envf = lab_env("LELE_HIP_FE_FUSED");
     fe->fused = envf ? atoi(envf) != 0 : true;
+    // product switch: 0 = aligned runs take the register staging of unaligned ones -- same bits, the A/B handle and
+    // the on-device cross-check of the direct-to-LDS tile
+    const char* envd = getenv("LELE_HIP_FE_TILE_DMA");
+    d.tile_dma = envd && *envd ? atoi(envd) != 0 : 1;
     *out = fe;
     return 0;
 }
