@@ -76,6 +76,7 @@ int lele_hip_ctx_create(int device, LeleCtx** out);
 int lele_hip_ctx_destroy(LeleCtx* ctx);
 int lele_hip_sync(LeleCtx* ctx);
 void* lele_hip_ctx_stream(LeleCtx* ctx); /* hipStream_t */
+int lele_hip_ctx_num_cus(LeleCtx* ctx);  /* compute units of the ctx's device, as the dispatch thresholds read them; 0 for NULL */
 /* hipGraph capture of an op sequence.  lele's generated forward() is a fixed sequence of kernel calls per input shape
  * (src/compiler/mod.rs:1291-1303); at SenseVoice's token counts every call is launch-latency bound, so the sequence is
  * recorded once and replayed as ONE graph launch.  Between begin and end every lele_hip_* op on this ctx is recorded
@@ -375,7 +376,14 @@ int lele_hip_conv_stats(LeleCtx* ctx, int64_t* calls, int64_t* macs);
  * several planes per workgroup; "pool.direct", "pool.direct_i64"), topk ("topk.rank", "topk.select_lds", "topk.select_l2"),
  * copy_pitched ("cpitch.w16" / "w4" / "w1"), and one fixed name each for pad, gather, gather_elements, adaptive_avg_pool1d,
  * transpose_cp_pitched, range_f32, range_i64, fill and cast ("pad.index", "gather.rows", "gather.elements", "apool.window",
- * "tcp.tile32", "range.f32", "range.i64", "fill.words", "cast.convert"), so the route never names an earlier call.  Recorded on the
+ * "tcp.tile32", "range.f32", "range.i64", "fill.words", "cast.convert").
+ * So do the element-wise, reduce and norm calls: unary ("unary.vec4", or "unary.w1" when a pointer is not 16-byte aligned), binary
+ * ("bin.fast" for the float4 patterns, else "bin.flat_f32" / "bin.index_f32" / "bin.flat_i64" / "bin.index_i64": equal shapes or the index
+ * walk; add3 with broadcasting operands: its second add), binary_pitched ("binp.vec4" / "binp.w1"), where ("where.index"), clip
+ * ("clip.w1"), reduce ("reduce.seq", min / max over a contiguous last axis "reduce.rows16", few long rows "reduce.parts"), layer_norm and
+ * softmax / softmax_scaled ("ln.reg8" / "reg16" / "reg32" and "softmax.reg8" / "reg16" / "reg32" by row length, then "rows.rpb2" / "rpb4" /
+ * "rpb8" for the rows a block holds; "ln.stream", "softmax.stream" past 1024 elements), rms_norm ("rms.stream"), batch_norm ("bn.w1"),
+ * add3 ("add3.vec4" / "add3.w1"), halves_pow_add_sqrt ("hpas.w1").  The route never names an earlier call.  Recorded on the
  * host when the call is issued (a call recorded into a graph reports the route it recorded).  NUL-terminated into buf; an error when cap is too small.
  * lele_hip_route_names: every level name a route can hold, one per line; host only, no GPU needed. */
 int lele_hip_last_route(LeleCtx* ctx, char* buf, size_t cap);

@@ -327,6 +327,7 @@ int lele_hip_sync(LeleCtx* c) {
 }
 
 void* lele_hip_ctx_stream(LeleCtx* c) { return c ? (void*)c->stream : nullptr; }
+int lele_hip_ctx_num_cus(LeleCtx* c) { return c ? c->num_cus : 0; }
 
 /* ---- hipGraph capture of an op sequence -------------------------------------------------------------------------- */
 int lele_hip_graph_begin(LeleCtx* c) {

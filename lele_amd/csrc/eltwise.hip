@@ -107,8 +107,12 @@ __device__ __forceinline__ float binary_apply<float>(int op, float a, float b) {
         case B_MUL: return a * b;
         case B_DIV: return a / b;
         case B_POW: return powf(a, b);
-        case B_MAX: return fmaxf(a, b);
-        case B_MIN: return fminf(a, b);
+        // `a.max(b)` (math.rs:1935, 1971) as LLVM lowers f32::max for x86: maxss with the operands swapped, then a select on `a`
+        // unordered -- the other operand for a NaN, and of equal values (+0 / -0) the FIRST operand.  Rust leaves the zero unspecified
+        // and the reference was not run on that pair: this rests on reading the code generation, not on a measurement.  fmaxf orders
+        // the zeros instead (max(-0, +0) = +0).  The reference has no element-wise min; B_MIN (ONNX Min) is the mirror image
+        case B_MAX: return a != a ? b : (b > a ? b : a);
+        case B_MIN: return a != a ? b : (b < a ? b : a);
         case B_EQUAL: return a == b ? 1.0f : 0.0f;
         case B_LESS: return a < b ? 1.0f : 0.0f;
         case B_GREATER: return a > b ? 1.0f : 0.0f;
@@ -215,9 +219,8 @@ __global__ void halves_pow_add_sqrt_kernel(const float* __restrict__ x, float* _
 // (a + b) + c element-wise on equal shapes: the two consecutive residual adds of a transformer block in one pass, same
 // rounding order as two `add` kernels
 __global__ __launch_bounds__(256) void add3_kernel(const float* __restrict__ a, const float* __restrict__ b, const float* __restrict__ c,
-                                                   float* __restrict__ out, int64_t n) {
+                                                   float* __restrict__ out, int64_t n, int vec /* all four pointers 16-byte aligned */) {
     const int64_t gtid = (int64_t)blockIdx.x * 256 + threadIdx.x, gstride = (int64_t)gridDim.x * 256;
-    const bool vec = ((((uintptr_t)a | (uintptr_t)b | (uintptr_t)c | (uintptr_t)out) & 15) == 0);
     const int64_t nvec = vec ? n >> 2 : 0;
     for (int64_t i = gtid; i < nvec; i += gstride) {
         const float4 x = reinterpret_cast<const float4*>(a)[i], y = reinterpret_cast<const float4*>(b)[i], z = reinterpret_cast<const float4*>(c)[i];
@@ -655,8 +658,11 @@ int lele_hip_unary(LeleCtx* ctx, int op, const LeleTensor* x, LeleBuf* out, int6
     const void* dx = nullptr;
     LELE_TRY(ctx->dev_ptr(x, &dx));
     LELE_TRY(out->reserve((size_t)len * 4));
+    ctx->set_route(nullptr);
     if (len) {
-        if ((((uintptr_t)dx | (uintptr_t)out->data) & 15) == 0)
+        const bool vec = (((uintptr_t)dx | (uintptr_t)out->data) & 15) == 0;
+        ctx->set_route(vec ? "unary.vec4" : "unary.w1");
+        if (vec)
             hipLaunchKernelGGL(unary_vec4_kernel, dim3(grid_for((len + 3) / 4)), dim3(256), 0, ctx->stream, op,
                                (const float*)dx, (float*)out->data, len);
         else
@@ -688,11 +694,15 @@ int lele_hip_binary(LeleCtx* ctx, int op, const LeleTensor* a, const LeleTensor*
     LELE_TRY(ctx->dev_ptr(a, &da));
     LELE_TRY(ctx->dev_ptr(b, &db));
     LELE_TRY(out->reserve((size_t)n * es));
+    ctx->set_route(nullptr);
     if (n) {
         const int same = (numel(a) == n && numel(b) == n) ? 1 : 0;
         OperandMap ma, mb;
-        if (a->dtype == LELE_F32 && n < (int64_t(1) << 32) && (((uintptr_t)out->data) & 15) == 0 &&
-            binary_fast_map(bc, bc.astride, da, n, numel(a), &ma) && binary_fast_map(bc, bc.bstride, db, n, numel(b), &mb))
+        const bool fast = a->dtype == LELE_F32 && n < (int64_t(1) << 32) && (((uintptr_t)out->data) & 15) == 0 &&
+                          binary_fast_map(bc, bc.astride, da, n, numel(a), &ma) && binary_fast_map(bc, bc.bstride, db, n, numel(b), &mb);
+        // the flat form of binary_kernel (both operands full) skips the index walk
+        ctx->set_route(fast ? "bin.fast" : a->dtype == LELE_F32 ? (same ? "bin.flat_f32" : "bin.index_f32") : (same ? "bin.flat_i64" : "bin.index_i64"));
+        if (fast)
             hipLaunchKernelGGL(binary_fast_kernel, dim3(grid_for((n + 7) / 8)), dim3(256), 0, ctx->stream, op, (const float*)da,
                                (const float*)db, (float*)out->data, (unsigned)n, ma, mb);
         else if (a->dtype == LELE_F32)
@@ -725,11 +735,13 @@ int lele_hip_binary_pitched(LeleCtx* ctx, int op, const LeleTensor* a, const Lel
     LELE_TRY(ctx->dev_ptr(b, &db));
     float* dst = nullptr;
     LELE_TRY(lele::pitched_out(out, pitch, images, per, 4, (void**)&dst));
+    ctx->set_route(nullptr);
     if (images * per) {
         const long long pa = pitch->x_pitch ? pitch->x_pitch : per, pb = pitch->y_pitch ? pitch->y_pitch : per,
                         po = pitch->out_pitch ? pitch->out_pitch : per;
         const int vec = ((((uintptr_t)da) | ((uintptr_t)db) | ((uintptr_t)dst)) & 15) == 0 && pa % 4 == 0 && pb % 4 == 0 && po % 4 == 0;
         const unsigned chunks = (unsigned)std::max<int64_t>(1, std::min<int64_t>((per + 2047) / 2048, 4096));
+        ctx->set_route(vec ? "binp.vec4" : "binp.w1");
         hipLaunchKernelGGL(binary_pitched_kernel, dim3(chunks, (unsigned)images), dim3(256), 0, ctx->stream, op, (const float*)da,
                            (const float*)db, dst, (unsigned)per, pa, pb, po, vec);
         LELE_HIP_CHECK(hipGetLastError());
@@ -755,6 +767,7 @@ int lele_hip_where(LeleCtx* ctx, const LeleTensor* cond, const LeleTensor* x, co
     LELE_TRY(ctx->dev_ptr(x, &dx));
     LELE_TRY(ctx->dev_ptr(y, &dy));
     LELE_TRY(out->reserve((size_t)n * 4));
+    ctx->set_route(n ? "where.index" : nullptr);
     if (n) {
         hipLaunchKernelGGL(where_kernel, dim3(grid_for(n)), dim3(256), 0, ctx->stream, (const float*)dc,
                            (const float*)dx, (const float*)dy, (float*)out->data, n, bc);
@@ -772,6 +785,7 @@ int lele_hip_clip(LeleCtx* ctx, const LeleTensor* x, int has_min, float min_v, i
     const void* dx = nullptr;
     LELE_TRY(ctx->dev_ptr(x, &dx));
     LELE_TRY(out->reserve((size_t)len * 4));
+    ctx->set_route(len ? "clip.w1" : nullptr);
     if (len) {
         hipLaunchKernelGGL(clip_kernel, dim3(grid_for(len)), dim3(256), 0, ctx->stream, (const float*)dx,
                            has_min ? min_v : -3.40282347e+38f, has_max ? max_v : 3.40282347e+38f, (float*)out->data,
@@ -819,6 +833,7 @@ int lele_hip_reduce(LeleCtx* ctx, int op, const LeleTensor* x, const int64_t* ax
     const void* dx = nullptr;
     LELE_TRY(ctx->dev_ptr(x, &dx));
     LELE_TRY(out->reserve((size_t)on * 4));
+    ctx->set_route(nullptr);
     if (on) {
         bool rows_first = (op == R_MAX || op == R_MIN) && rd.rank_red == 1 && rd.red_stride[0] == 1 && rd.red_count >= 16 && on < (int64_t(1) << 34);
         int64_t expect = rd.red_count;  // the kept dims must be laid out row after row: output o starts at o * red_count
@@ -830,18 +845,22 @@ int lele_hip_reduce(LeleCtx* ctx, int op, const LeleTensor* x, const int64_t* ax
             const int64_t per = std::max<int64_t>(8192, (rd.red_count + 1023) / 1024);
             const int pieces = (int)((rd.red_count + per - 1) / per);
             void *pv = nullptr, *pa = nullptr;
+            ctx->set_route("reduce.parts");
             LELE_TRY(ctx->arena_alloc((size_t)on * pieces * 4, &pv));
             LELE_TRY(ctx->arena_alloc((size_t)on * pieces * 8, &pa));
             hipLaunchKernelGGL(reduce_minmax_part_kernel, dim3((unsigned)pieces, (unsigned)on), dim3(256), 0, ctx->stream, op, (const float*)dx,
                                (float*)pv, (long long*)pa, rd.red_count, per);
             hipLaunchKernelGGL(reduce_minmax_merge_kernel, dim3((unsigned)on), dim3(64), 0, ctx->stream, op, (const float*)pv, (const long long*)pa,
                                (float*)out->data, pieces, rd.red_count);
-        } else if (rows_first)
+        } else if (rows_first) {
+            ctx->set_route("reduce.rows16");
             hipLaunchKernelGGL(reduce_minmax_last_kernel, dim3((unsigned)((on + 15) / 16)), dim3(256), 0, ctx->stream, op, (const float*)dx,
                                (float*)out->data, on, rd.red_count);
-        else
+        } else {
+            ctx->set_route("reduce.seq");
             hipLaunchKernelGGL(reduce_kernel, dim3((unsigned)((on + 63) / 64)), dim3(64), 0, ctx->stream, op,
                                (const float*)dx, (float*)out->data, on, rd);
+        }
         LELE_HIP_CHECK(hipGetLastError());
     }
     return set_shape_v(out_shape, out_rank, oshape);
@@ -864,9 +883,13 @@ int lele_hip_layer_norm(LeleCtx* ctx, const LeleTensor* x, const LeleTensor* sca
     LELE_TRY(ctx->dev_ptr(scale, &dg));
     LELE_TRY(ctx->dev_ptr(bias, &db));
     LELE_TRY(out->reserve((size_t)outer * norm * 4));
+    ctx->set_route(nullptr);
     if (outer * norm) {
         // rows that fit 32 registers per lane take the single-pass kernel; few rows -> fewer rows per block (more CUs)
         const int rpb = outer >= 4096 ? 8 : (outer >= 1024 ? 4 : 2);
+        const char* rows = rpb == 8 ? "rows.rpb8" : rpb == 4 ? "rows.rpb4" : "rows.rpb2";
+        if (norm <= 1024) ctx->set_route(norm <= 256 ? "ln.reg8" : norm <= 512 ? "ln.reg16" : "ln.reg32", rows);
+        else ctx->set_route("ln.stream");
         const dim3 rgrid((unsigned)((outer + rpb - 1) / rpb)), rblock(32 * rpb);
         // row statistics for a dynamic quantisation that may read this result next (common.h, LeleBuf::rowstat)
         float* rs = nullptr;
@@ -913,6 +936,7 @@ int lele_hip_rms_norm(LeleCtx* ctx, const LeleTensor* x, const LeleTensor* weigh
     LELE_TRY(ctx->dev_ptr(x, &dx));
     LELE_TRY(ctx->dev_ptr(weight, &dw));
     LELE_TRY(out->reserve((size_t)outer * norm * 4));
+    ctx->set_route(outer * norm ? "rms.stream" : nullptr);
     if (outer * norm) {
         hipLaunchKernelGGL(rms_norm_kernel, dim3((unsigned)((outer + 7) / 8)), dim3(256), 0, ctx->stream,
                            (const float*)dx, (const float*)dw, (float*)out->data, norm, outer, epsilon);
@@ -939,8 +963,12 @@ static int softmax_impl(LeleCtx* ctx, const LeleTensor* x, const LeleTensor* sca
     LELE_TRY(ctx->dev_ptr(x, &dx));
     if (scale) LELE_TRY(ctx->dev_ptr(scale, &dsc));
     LELE_TRY(out->reserve((size_t)outer * len * 4));
+    ctx->set_route(nullptr);
     if (outer * len) {
         const int rpb = outer >= 4096 ? 8 : (outer >= 1024 ? 4 : 2);
+        const char* rows = rpb == 8 ? "rows.rpb8" : rpb == 4 ? "rows.rpb4" : "rows.rpb2";
+        if (len <= 1024) ctx->set_route(len <= 256 ? "softmax.reg8" : len <= 512 ? "softmax.reg16" : "softmax.reg32", rows);
+        else ctx->set_route("softmax.stream");
         const dim3 rgrid((unsigned)((outer + rpb - 1) / rpb)), rblock(32 * rpb);
         if (len <= 256)
             hipLaunchKernelGGL(softmax_reg_kernel<8>, rgrid, rblock, 0, ctx->stream, (const float*)dx, (float*)out->data,
@@ -993,9 +1021,12 @@ int lele_hip_add3(LeleCtx* ctx, const LeleTensor* a, const LeleTensor* b, const 
     LELE_TRY(ctx->dev_ptr(b, &db));
     LELE_TRY(ctx->dev_ptr(c, &dc));
     LELE_TRY(out->reserve((size_t)n * 4));
+    ctx->set_route(nullptr);
     if (n) {
+        const int vec = (((uintptr_t)da | (uintptr_t)db | (uintptr_t)dc | (uintptr_t)out->data) & 15) == 0;
+        ctx->set_route(vec ? "add3.vec4" : "add3.w1");
         hipLaunchKernelGGL(add3_kernel, dim3(grid_for((n + 3) / 4)), dim3(256), 0, ctx->stream, (const float*)da, (const float*)db,
-                           (const float*)dc, (float*)out->data, n);
+                           (const float*)dc, (float*)out->data, n, vec);
         LELE_HIP_CHECK(hipGetLastError());
     }
     return set_shape_v(out_shape, out_rank, std::vector<int64_t>(a->shape, a->shape + a->rank));
@@ -1030,6 +1061,7 @@ int lele_hip_halves_pow_add_sqrt(LeleCtx* ctx, const LeleTensor* x, int32_t axis
     const void* dx;
     LELE_TRY(ctx->dev_ptr(x, &dx));
     LELE_TRY(out->reserve((size_t)n * 4));
+    ctx->set_route(n ? "hpas.w1" : nullptr);
     if (n) {
         hipLaunchKernelGGL(halves_pow_add_sqrt_kernel, dim3(grid_for(n)), dim3(256), 0, ctx->stream, (const float*)dx, (float*)out->data,
                            dim, a0, b0, len, inner, n, *(const float*)exp_lo->data, *(const float*)exp_hi->data);
@@ -1058,6 +1090,7 @@ int lele_hip_batch_norm(LeleCtx* ctx, const LeleTensor* x, const LeleTensor* sca
     LELE_TRY(ctx->dev_ptr(mean, &dm));
     LELE_TRY(ctx->dev_ptr(var, &dv));
     LELE_TRY(out->reserve((size_t)n * 4));
+    ctx->set_route(n ? "bn.w1" : nullptr);
     if (n) {
         hipLaunchKernelGGL(batch_norm_kernel, dim3(grid_for(n)), dim3(256), 0, ctx->stream, (const float*)dx,
                            (const float*)ds, (const float*)db, (const float*)dm, (const float*)dv, epsilon, c, inner, n,

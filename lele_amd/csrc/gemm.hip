@@ -98,6 +98,12 @@ const char* const kRouteNames[] = {
     "topk.rank", "topk.select_lds", "topk.select_l2",
     "cpitch.w16", "cpitch.w4", "cpitch.w1",
     "pad.index", "gather.rows", "gather.elements", "apool.window", "tcp.tile32", "range.f32", "range.i64", "fill.words", "cast.convert",
+    // eltwise.hip: the kernel, and for the register-resident norm kernels a second level for the rows a block holds (rows.rpb2 / 4 / 8)
+    "unary.vec4", "unary.w1", "bin.fast", "bin.flat_f32", "bin.index_f32", "bin.flat_i64", "bin.index_i64", "binp.vec4", "binp.w1",
+    "where.index", "clip.w1", "reduce.seq", "reduce.rows16", "reduce.parts",
+    "ln.reg8", "ln.reg16", "ln.reg32", "ln.stream", "softmax.reg8", "softmax.reg16", "softmax.reg32", "softmax.stream",
+    "rows.rpb2", "rows.rpb4", "rows.rpb8",
+    "rms.stream", "bn.w1", "add3.vec4", "add3.w1", "hpas.w1",
 };
 
 }  // namespace

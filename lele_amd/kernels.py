@@ -651,12 +651,18 @@ def conv_stats(ctx=None):
 
 
 def last_route(ctx=None):
-    """name of the kernel route the last f32 GEMM, convolution, attention or data-movement call on the context dispatched, its levels
-    joined by '/' (lele_hip_last_route: recorded by the library at the launch site, e.g. "conv.gemm_tap/gemm.small",
-    "attn.rows16/attn.nt6", "copy.tile_w4", "pool.lds_sep/pool.pbn", "topk.select_lds"); "" for an empty result, which launches nothing"""
+    """name of the kernel route the last f32 GEMM, convolution, attention, data-movement, element-wise, reduce or norm call on the
+    context dispatched, its levels joined by '/' (lele_hip_last_route: recorded by the library at the launch site, e.g.
+    "conv.gemm_tap/gemm.small", "attn.rows16/attn.nt6", "copy.tile_w4", "pool.lds_sep/pool.pbn", "topk.select_lds", "bin.fast",
+    "reduce.parts", "ln.reg16/rows.rpb4"); "" for an empty result, which launches nothing"""
     buf = C.create_string_buffer(256)
     _lib.check(_lib.lib().lele_hip_last_route(_ctx(ctx)._h, buf, C.c_size_t(len(buf))))
     return buf.value.decode()
+
+
+def num_cus(ctx=None):
+    """compute units of the context's device: the count the library's dispatch thresholds read"""
+    return int(_lib.lib().lele_hip_ctx_num_cus(_ctx(ctx)._h))
 
 
 def route_names():

@@ -8,6 +8,16 @@ import numpy as np
 
 
 # ---- src/kernels/math.rs: broadcast_binary_op (69-264) and the ops built on it --------------------------------
+def _i64_divmod(a, b):
+    """i64 `/` and `%` in integer arithmetic only (a detour through float64 is wrong beyond 2^53): the quotient truncates toward zero,
+    the remainder takes the dividend's sign; a zero divisor gives 0 for both (the device library's choice where the reference panics)"""
+    a, b = np.broadcast_arrays(np.asarray(a, np.int64), np.asarray(b, np.int64))
+    bs = np.where(b == 0, 1, b)
+    q = np.floor_divide(a, bs)
+    q = q + (((a - q * bs) != 0) & ((a < 0) != (bs < 0)))   # floor -> truncation
+    return np.where(b == 0, 0, q).astype(np.int64), np.where(b == 0, 0, a - q * bs).astype(np.int64)
+
+
 def binary(name, a, b):
     a, b = np.asarray(a), np.asarray(b)
     with np.errstate(all="ignore"):
@@ -19,14 +29,20 @@ def binary(name, a, b):
             return a * b  # math.rs:611
         if name == "div":
             if a.dtype == np.int64:
-                return np.where(b == 0, 0, np.trunc(a / np.where(b == 0, 1, b))).astype(np.int64)
+                return _i64_divmod(a, b)[0]
             return a / b  # math.rs:1106
+        if name == "mod" and a.dtype == np.int64:
+            return _i64_divmod(a, b)[1]
         if name == "pow":
             return np.power(a.astype(np.float64), b.astype(np.float64)).astype(np.float32)  # f32::powf (libm)
+        # f32::max (math.rs:1922): the other operand when one is a NaN; of equal values (+0 / -0) LLVM's x86 lowering keeps the
+        # FIRST operand (maxss with the operands swapped, then a select on `a` unordered).  Rust leaves that zero unspecified and the
+        # reference was not run on the pair: a reading of the code generation, written out because np.fmax's choice between the
+        # zeros depends on the numpy build.  min (no element-wise min upstream) is the mirror image
         if name == "max":
-            return np.fmax(a, b)  # f32::max: NaN-ignoring, math.rs:1922
+            return np.where(np.isnan(a), b, np.where(b > a, b, a)).astype(a.dtype)
         if name == "min":
-            return np.fmin(a, b)
+            return np.where(np.isnan(a), b, np.where(b < a, b, a)).astype(a.dtype)
         if name == "equal":
             return (a == b).astype(a.dtype)  # 1.0 / 0.0, math.rs:1193
         if name == "less":
@@ -53,7 +69,8 @@ def clip(x, lo=None, hi=None):  # math.rs:1984-2010
     x = np.asarray(x, np.float32)
     lo = np.float32(-3.40282347e+38) if lo is None else np.float32(lo)
     hi = np.float32(3.40282347e+38) if hi is None else np.float32(hi)
-    return np.minimum(np.maximum(x, lo), hi)
+    with np.errstate(invalid="ignore"):   # f32::clamp: `if x < lo { lo } else if x > hi { hi } else { x }` -- a NaN and a -0 at a bound stay
+        return np.where(x < lo, lo, np.where(x > hi, hi, x)).astype(np.float32)
 
 
 def unary_exact(name, x):

@@ -324,7 +324,9 @@ def batch_norm(x, scale, bias, mean, var, eps=1e-5):
     x = _f32(x)
     shape = x.shape
     c = shape[1] if len(shape) > 1 else shape[0]
-    outer = shape[0]
+    # rank 1: upstream walks shape[0] * shape[0] elements of a shape[0]-element tensor (norm.rs:370-372, out of bounds); only its first
+    # row exists, and that is what is restated -- the C routine must not be handed the rest
+    outer = shape[0] if len(shape) > 1 else 1
     inner = int(np.prod(shape[2:], dtype=np.int64)) if len(shape) > 2 else 1
     out = np.empty_like(x)
     lib().orc_batch_norm(_p(x), _p(_f32(scale)), _p(_f32(bias)), _p(_f32(mean)), _p(_f32(var)), f(eps), i64(outer),
