@@ -612,6 +612,24 @@ int lele_hip_depthwise_conv1d_tlc_segments(LeleCtx* ctx, const LeleTensor* x, in
  * embeddings a SenseVoice-shaped encoder puts in front of every utterance. */
 int lele_hip_segments_prepend(LeleCtx* ctx, const LeleTensor* x, const int64_t* row_offsets, int64_t count, const LeleTensor* prefix,
                               LeleBuf* out, int64_t* out_offsets, int64_t* out_shape, int32_t* out_rank);
+/* lele_hip_lstm / lele_hip_gru (rnn.rs:67, 246) over `count` INDEPENDENT sequences: segment i is the rows [off[i], off[i+1]) of
+ * x f32 [R, I] and runs exactly as if it went through the single call alone as [len, 1, I] with its own initial state -- y, h and c
+ * are that call's bit for bit, whatever the neighbours, the position or `count` (W x of all R rows is one MFMA GEMM of ONE fixed tile
+ * form, the recurrence keeps the single call's summation order).  w [1, 4H, I] / [1, 3H, I], r [1, 4H, H] / [1, 3H, H], bias 8H / 6H
+ * values or NULL; initial_h / initial_c hold count * H values (segment i at i * H) or are NULL (zeros).  out_y [R, H] (y_shape),
+ * out_h / out_c [1, count, H].  A 0-row segment writes no y row and its final state is its initial state.  out_h / out_c may be the
+ * buffers initial_h / initial_c live in: N streams fed chunk by chunk (row_offsets = 0, 1, .., N) keep their state on the device.
+ * One 1024-thread workgroup walks a group of up to NS segments in lockstep; info_or_null receives {kernel form: 0 = nothing launched
+ * (R == 0), 1 = recurrent weights held in registers (H / S in {16, 32, 64}), 2 = streamed from the transposed copy in L2; NS}.
+ * Everything is checked before anything is launched or resized: a failing call leaves every out buffer as it was. */
+int lele_hip_lstm_segments(LeleCtx* ctx, const LeleTensor* x, const int64_t* row_offsets, int64_t count, const LeleTensor* w,
+                           const LeleTensor* r, const LeleTensor* bias_or_null, const LeleTensor* initial_h_or_null,
+                           const LeleTensor* initial_c_or_null, LeleBuf* out_y, LeleBuf* out_h, LeleBuf* out_c, int64_t* y_shape,
+                           int32_t* y_rank, int32_t* info_or_null);
+int lele_hip_gru_segments(LeleCtx* ctx, const LeleTensor* x, const int64_t* row_offsets, int64_t count, const LeleTensor* w,
+                          const LeleTensor* r, const LeleTensor* bias_or_null, const LeleTensor* initial_h_or_null,
+                          int linear_before_reset, LeleBuf* out_y, LeleBuf* out_h, int64_t* y_shape, int32_t* y_rank,
+                          int32_t* info_or_null);
 
 #ifdef __cplusplus
 }

@@ -1016,6 +1016,33 @@ inline TensorView segments_prepend(const TensorView& x, const std::vector<int64_
                                     &sh.rank));
     LELE_RET(out, LELE_F32);
 }
+// lstm / gru over independent sequences (segment i = rows offsets[i] .. offsets[i + 1] of x [R, I], each bit for bit the single call on
+// it alone): y [R, H], h / c [1, count, H]; initial_h / initial_c hold count * H values; out_h / out_c may be their buffers (state in
+// place).  info, if given, receives {kernel form 0 / 1 / 2, segments a workgroup walks}.
+inline LstmOut lstm_segments(const TensorView& x, const std::vector<int64_t>& offsets, const TensorView& w, const TensorView& r,
+                             const TensorView* bias, const TensorView* initial_h, const TensorView* initial_c, Buffer& out_y, Buffer& out_h,
+                             Buffer& out_c, int32_t* info = nullptr) {
+    Shape sh;
+    LeleTensor tx = x.c(), tw = w.c(), tr = r.c();
+    Opt ob(bias), oh(initial_h), oc(initial_c);
+    const int64_t count = (int64_t)offsets.size() - 1;
+    check(lele_hip_lstm_segments(ctx(), &tx, offsets.data(), count, &tw, &tr, ob.p, oh.p, oc.p, out_y.raw(), out_h.raw(), out_c.raw(), sh.dims,
+                                 &sh.rank, info));
+    const std::vector<int64_t> ys = sh.vec(), hs = {1, count, ys.back()};
+    return {TensorView::from_device(out_y, ys), TensorView::from_device(out_h, hs), TensorView::from_device(out_c, hs)};
+}
+inline GruOut gru_segments(const TensorView& x, const std::vector<int64_t>& offsets, const TensorView& w, const TensorView& r,
+                           const TensorView* bias, const TensorView* initial_h, bool linear_before_reset, Buffer& out_y, Buffer& out_h,
+                           int32_t* info = nullptr) {
+    Shape sh;
+    LeleTensor tx = x.c(), tw = w.c(), tr = r.c();
+    Opt ob(bias), oh(initial_h);
+    const int64_t count = (int64_t)offsets.size() - 1;
+    check(lele_hip_gru_segments(ctx(), &tx, offsets.data(), count, &tw, &tr, ob.p, oh.p, linear_before_reset, out_y.raw(), out_h.raw(), sh.dims,
+                                &sh.rank, info));
+    const std::vector<int64_t> ys = sh.vec();
+    return {TensorView::from_device(out_y, ys), TensorView::from_device(out_h, {1, count, ys.back()})};
+}
 // view operators: shape bookkeeping only (shape.rs:2-52, 105-185)
 inline TensorView reshape(const TensorView& x, const std::vector<int64_t>& target) {
     const int64_t total = x.size();

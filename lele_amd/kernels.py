@@ -1264,6 +1264,48 @@ def segments_prepend(x, offsets, prefix, out=None, ctx=None):
     return TensorView(_lib.DevTensor(out, sh.get(), np.float32)), new_off
 
 
+def _rnn_info(info, words):
+    if info is not None:
+        info["form"], info["streams_per_workgroup"] = int(words[0]), int(words[1])
+
+
+def lstm_segments(x, row_offsets, w, r, bias=None, initial_h=None, initial_c=None, outs=None, info=None, ctx=None):
+    """lstm over independent sequences: segment i = rows row_offsets[i] .. row_offsets[i + 1] of the packed x [R, I], bit for bit
+    lstm() of that range alone with its own initial state (initial_h / initial_c hold count * H values) ->
+    (Y [R, H], H_n [1, count, H], C_n [1, count, H]).  outs[1] / outs[2] may be the buffers of initial_h / initial_c (state in place);
+    info (a dict) receives {"form": 0 nothing launched / 1 register-stationary / 2 streamed, "streams_per_workgroup"}."""
+    ctx = _ctx(ctx)
+    keep = []
+    oy, oh, oc = outs if outs else (ctx.buf(), ctx.buf(), ctx.buf())
+    sh = _lib.OutShape()
+    off = _offsets(row_offsets)
+    words = (C.c_int32 * 2)()
+    t = [_lib.as_tensor(unwrap(v), keep) for v in (w, r, bias, initial_h, initial_c)]
+    _lib.check(_lib.lib().lele_hip_lstm_segments(ctx._h, _lib.as_tensor(unwrap(x), keep), _lib.i64_ptr(off), C.c_int64(len(off) - 1), *t,
+                                                 oy._h, oh._h, oc._h, sh.shape, C.byref(sh.rank), words))
+    _rnn_info(info, words)
+    ys = sh.get()
+    hs = (1, len(off) - 1, ys[-1])
+    return (TensorView(_lib.DevTensor(oy, ys, np.float32)), TensorView(_lib.DevTensor(oh, hs, np.float32)),
+            TensorView(_lib.DevTensor(oc, hs, np.float32)))
+
+
+def gru_segments(x, row_offsets, w, r, bias=None, initial_h=None, linear_before_reset=False, outs=None, info=None, ctx=None):
+    """gru over independent sequences, as lstm_segments -> (Y [R, H], H_n [1, count, H])"""
+    ctx = _ctx(ctx)
+    keep = []
+    oy, oh = outs if outs else (ctx.buf(), ctx.buf())
+    sh = _lib.OutShape()
+    off = _offsets(row_offsets)
+    words = (C.c_int32 * 2)()
+    t = [_lib.as_tensor(unwrap(v), keep) for v in (w, r, bias, initial_h)]
+    _lib.check(_lib.lib().lele_hip_gru_segments(ctx._h, _lib.as_tensor(unwrap(x), keep), _lib.i64_ptr(off), C.c_int64(len(off) - 1), *t,
+                                                C.c_int(int(bool(linear_before_reset))), oy._h, oh._h, sh.shape, C.byref(sh.rank), words))
+    _rnn_info(info, words)
+    ys = sh.get()
+    return TensorView(_lib.DevTensor(oy, ys, np.float32)), TensorView(_lib.DevTensor(oh, (1, len(off) - 1, ys[-1]), np.float32))
+
+
 # ------------------------------------------------------------------------------------------- ConvInteger family
 def conv_integer(input, weights, x_zero_point=None, w_zero_point=None, dilations=(), group=1, pads=(), strides=(), out=None,
                  ctx=None):
