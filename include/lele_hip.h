@@ -383,7 +383,10 @@ int lele_hip_conv_stats(LeleCtx* ctx, int64_t* calls, int64_t* macs);
  * ("clip.w1"), reduce ("reduce.seq", min / max over a contiguous last axis "reduce.rows16", few long rows "reduce.parts"), layer_norm and
  * softmax / softmax_scaled ("ln.reg8" / "reg16" / "reg32" and "softmax.reg8" / "reg16" / "reg32" by row length, then "rows.rpb2" / "rpb4" /
  * "rpb8" for the rows a block holds; "ln.stream", "softmax.stream" past 1024 elements), rms_norm ("rms.stream"), batch_norm ("bn.w1"),
- * add3 ("add3.vec4" / "add3.w1"), halves_pow_add_sqrt ("hpas.w1").  The route never names an earlier call.  Recorded on the
+ * add3 ("add3.vec4" / "add3.w1"), halves_pow_add_sqrt ("hpas.w1").  And the recurrent calls: lstm / gru ("rnn.lstm" / "rnn.gru", then
+ * the GEMM kernel of W x: "gemm.thin_m", "gemm.small", a tile, "gemm.k0" for I = 0; nothing more for T = 0), lstm_segments / gru_segments
+ * ("rnns.lstm" / "rnns.gru", then "rnns.reg16" / "reg32" / "reg64" for recurrent weights in registers or "rnns.stream1" / "stream2" /
+ * "stream4" / "stream8" for the streamed form by the width of its members' register tile).  The route never names an earlier call.  Recorded on the
  * host when the call is issued (a call recorded into a graph reports the route it recorded).  NUL-terminated into buf; an error when cap is too small.
  * lele_hip_route_names: every level name a route can hold, one per line; host only, no GPU needed. */
 int lele_hip_last_route(LeleCtx* ctx, char* buf, size_t cap);

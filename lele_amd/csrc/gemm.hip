@@ -104,6 +104,10 @@ const char* const kRouteNames[] = {
     "ln.reg8", "ln.reg16", "ln.reg32", "ln.stream", "softmax.reg8", "softmax.reg16", "softmax.reg32", "softmax.stream",
     "rows.rpb2", "rows.rpb4", "rows.rpb8",
     "rms.stream", "bn.w1", "add3.vec4", "add3.w1", "hpas.w1",
+    // rnn.hip: the single calls name the GEMM kernel of W x as their second level (none for T == 0); the packed calls name the form of
+    // rnn_seg_kernel: recurrent weights in registers in slices of 16 / 32 / 64, or streamed with 1 / 2 / 4 / 8 members a register tile
+    "rnn.lstm", "rnn.gru", "rnns.lstm", "rnns.gru",
+    "rnns.reg16", "rnns.reg32", "rnns.reg64", "rnns.stream1", "rnns.stream2", "rnns.stream4", "rnns.stream8",
 };
 
 }  // namespace

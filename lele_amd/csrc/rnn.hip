@@ -17,8 +17,9 @@
 //   lele_hip_lstm_segments / lele_hip_gru_segments: the same over a packed batch of INDEPENDENT sequences (x [R, I] + row offsets),
 //   every segment bit for bit the single call on it alone.  W x of all R rows is one GEMM of one FIXED tile form (a route that moved
 //   with R would make a segment's bits depend on its neighbours); one workgroup per group of up to NS segments walks them in
-//   lockstep (rnn_seg_kernel below), with the recurrent weights in registers where a thread's slice is 16, 32 or 64 values (H = 128)
-//   and streamed from the transposed copy otherwise.  DESIGN.md 3.5b.
+//   lockstep (rnn_seg_kernel below), with the recurrent weights in registers where a thread's slice is 16, 32 or 64 values (LSTM H = 64
+//   and 128, GRU H = 96 and 128) and streamed from the transposed copy otherwise.  DESIGN.md 3.5b.
+//   Every entry point records its route (lele_hip_last_route): rnn.lstm / rnn.gru + the GEMM kernel of W x; rnns.lstm / rnns.gru + the form.
 #include "common.h"
 #include "gemm_core.h"
 #include "simd_math.h"
@@ -196,12 +197,14 @@ int run_rnn(LeleCtx* ctx, const char* name, const LeleTensor* x, const LeleTenso
     LELE_TRY(y->reserve((size_t)T * H * 4));
     LELE_TRY(hn->reserve((size_t)H * 4));
     if (MODE == 0) LELE_TRY(cn->reserve((size_t)H * 4));
+    const char* wx_route = nullptr;  // lele_hip_last_route: rnn.lstm / rnn.gru, then the GEMM kernel of W x (none for T == 0)
     if (T > 0) {
         gemm::LoadRowK al{(const float*)dx, 0, I, (int)T, (int)I, (int)((((uintptr_t)dx & 15) == 0) && I % 4 == 0)};
         gemm::LoadRowK bl{(const float*)dw, 0, I, (int)G, (int)I, (int)((((uintptr_t)dw & 15) == 0) && I % 4 == 0)};
         gemm::EpiAffine epi{(float*)wx, 0, (int)T, (int)G, 1.0f, 0.0f, nullptr, gemm::C_NONE, 1};
-        gemm::launch(ctx->stream, al, bl, epi, (int)T, (int)G, (int)I, 1, ctx->num_cus);
+        wx_route = gemm::launch(ctx->stream, al, bl, epi, (int)T, (int)G, (int)I, 1, ctx->num_cus);
     }
+    ctx->set_route(MODE == 0 ? "rnn.lstm" : "rnn.gru", wx_route);
     if (!have_rt)
         hipLaunchKernelGGL(transpose_kernel, dim3((unsigned)((H + 31) / 32), (unsigned)((G + 31) / 32)), dim3(32, 8), 0,
                            ctx->stream, (const float*)dr, (float*)rt, (int)G, (int)H);
@@ -462,7 +465,9 @@ int run_rnn_segments(LeleCtx* ctx, const char* name, const LeleTensor* x, const 
     LELE_REQUIRE(R <= (int64_t)65535 * 64 && count < (int64_t(1) << 31) / 8 && I < (int64_t(1) << 31), "%s: tensor too large", name);
     // the form and the group width follow from the shapes alone (never from the data, the lengths or the position of a segment)
     int ks = (H % S == 0 && (int64_t)S * G <= kRnnThreads) ? (int)(H / S) : 0;
-    if (ks != 16 && ks != 32 && ks != 64) ks = 0;
+    // S = min(H, max(1, 1024 / G)) leaves four register-stationary shapes: LSTM H = 64 (KS = 16) and 128 (KS = 64), GRU H = 96 (KS = 32)
+    // and 128 (KS = 64); no H gives the LSTM slices of 32 or the GRU slices of 16 (tests/test_rnn_routes.py enumerates H)
+    if (ks != (MODE == 0 ? 16 : 32) && ks != 64) ks = 0;
     if (const char* f = lab_env("LELE_HIP_RNN_SEG_FORM"))  // A/B timing (tools/rnn_segments_bench.py): 2 = streamed for every shape
         if (atoi(f) == 2) ks = 0;
     int ns = 1;
@@ -520,6 +525,7 @@ int run_rnn_segments(LeleCtx* ctx, const char* name, const LeleTensor* x, const 
         info[0] = R == 0 ? 0 : ks ? 1 : 2;
         info[1] = ns;
     }
+    ctx->set_route(nullptr);
     if (R == 0) {  // every segment is empty: the final state is the initial state (no kernel)
         LeleBuf* outs[2] = {hn, MODE == 0 ? cn : nullptr};
         const void* init[2] = {dh0, dc0};
@@ -552,14 +558,29 @@ int run_rnn_segments(LeleCtx* ctx, const char* name, const LeleTensor* x, const 
 #define LELE_RNN_SEG(NSV, KSV)                                                                                                     \
     LELE_TRY((launch_rnn_seg<MODE, NSV, KSV>(ctx, ngroups, lds_bytes, (const float*)wx, rw, (const float*)db, (const float*)dh0,  \
                                              (const float*)dc0, (float*)y->data, (float*)hn->data, cnd, (const int4*)groups, ns, (int)H, S)))
-    if (ks == 64) LELE_RNN_SEG(2, 64);  // the register-stationary form walks its members two at a time, whatever ns is
-    else if (ks == 32) LELE_RNN_SEG(2, 32);
-    else if (ks == 16) LELE_RNN_SEG(2, 16);
-    else if (ns == 1) LELE_RNN_SEG(1, 0);  // the streamed form: the members' chains share every load of R^T
-    else if (ns == 2) LELE_RNN_SEG(2, 0);
-    else if (ns <= 4) LELE_RNN_SEG(4, 0);
-    else LELE_RNN_SEG(8, 0);
+    constexpr int KS_SMALL = MODE == 0 ? 16 : 32;
+    const char* form = nullptr;  // lele_hip_last_route: rnns.lstm / rnns.gru, then the kernel form
+    if (ks == 64) {  // the register-stationary form walks its members two at a time, whatever ns is
+        LELE_RNN_SEG(2, 64);
+        form = "rnns.reg64";
+    } else if (ks == KS_SMALL) {
+        LELE_RNN_SEG(2, KS_SMALL);
+        form = MODE == 0 ? "rnns.reg16" : "rnns.reg32";
+    } else if (ns == 1) {  // the streamed form: the members' chains share every load of R^T
+        LELE_RNN_SEG(1, 0);
+        form = "rnns.stream1";
+    } else if (ns == 2) {
+        LELE_RNN_SEG(2, 0);
+        form = "rnns.stream2";
+    } else if (ns <= 4) {
+        LELE_RNN_SEG(4, 0);
+        form = "rnns.stream4";
+    } else {
+        LELE_RNN_SEG(8, 0);
+        form = "rnns.stream8";
+    }
 #undef LELE_RNN_SEG
+    ctx->set_route(MODE == 0 ? "rnns.lstm" : "rnns.gru", form);
     return set_shape(y_shape, y_rank, {R, H});
 }
 
