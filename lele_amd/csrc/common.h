@@ -7,10 +7,13 @@
 #include <stdio.h>
 #include <string.h>
 
+#include <array>
+#include <initializer_list>
 #include <map>
 #include <mutex>
 #include <set>
 #include <string>
+#include <tuple>
 #include <utility>
 #include <vector>
 
@@ -96,6 +99,37 @@ struct DevTables {
     void release();  // frees every table (the owner's streams are idle)
 };
 
+// The pre-packed forms a LELE_MEM_WEIGHT tensor is cached in (LeleCtx::weight_form)
+enum class WeightForm : int {
+    Raw,          // the tensor's own bytes, uploaded (dev_ptr)
+    FftTwiddles,  // re | im tables of an n-point FFT (no source tensor); {n}
+    I8Packed,     // i8 [N][Kp] | column sums
+    I8Frag,       // i8 fragment-major | column sums
+    ConvTapMajor,
+    ConvDirect,      // {ocb}
+    ConvWindowFrag,  // {taps, packed bytes: the padding tiles depend on the channel block}
+    ConvTPhase,      // {sh, sw, dh, dw, pt, pl}
+    ConvTKernelStride,
+    CiCentred,  // w - w_zp; {bit pattern of w_zp}
+    CiI8Frag,   // i8 fragments | per-channel sums
+    CiNotU8,    // verdict "not u8 codes": an entry without memory
+    RnnRT,
+};
+// Two calls share a cached form if and only if source pointer, source bytes, form and every parameter the packed bytes depend on
+// (each as itself, zero-filled) are equal.
+using WeightKey = std::tuple<const void*, size_t, WeightForm, std::array<int64_t, 6>>;
+inline WeightKey weight_key(const void* src, size_t src_bytes, WeightForm form, std::initializer_list<int64_t> params = {}) {
+    std::array<int64_t, 6> p{};
+    size_t i = 0;
+    for (int64_t v : params) p.at(i++) = v;
+    return WeightKey(src, src_bytes, form, p);
+}
+inline WeightKey weight_key(const LeleTensor* t, WeightForm form, std::initializer_list<int64_t> params = {}) {
+    return weight_key(t->data, (size_t)lele::numel(t) * lele::dtype_size(t->dtype), form, params);
+}
+// where the second array of a two-array form starts in its allocation
+inline size_t weight_second(size_t first_bytes) { return (first_bytes + 255) & ~size_t(255); }
+
 struct LeleCtx {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -105,8 +139,31 @@ struct LeleCtx {
     char* arena = nullptr;
     size_t arena_cap = 0, arena_used = 0;
     std::vector<void*> arena_overflow;  // freed at the next reset
-    // LELE_MEM_WEIGHT cache: (host ptr, bytes, tag) -> device copy (tag distinguishes pre-packed forms)
-    std::map<std::tuple<const void*, size_t, int>, void*> weights;
+    // LELE_MEM_WEIGHT cache: WeightKey -> device memory of that form.  Read and written by context.hip alone: ops go through
+    // weight_form, which publishes an entry only after the launches that fill it were enqueued without error, so a call that fails
+    // half-way leaves nothing half-made behind; drop_weights forgets a source tensor whatever forms it was cached in.
+    std::map<WeightKey, void*> weights;
+    // The form `key` in `bytes` of device memory at *out.  A hit returns the cached pointer and calls nothing.  A miss calls
+    // fill(ptr), which enqueues on `stream` whatever packs the buffer and returns 0 or an error: on cacheable memory of its own
+    // (refused while capturing; kept only if fill returned 0), otherwise on arena memory, every call.
+    template <class Fill>
+    int weight_form(bool cacheable, const WeightKey& key, size_t bytes, void** out, Fill&& fill) {
+        bool hit = false;
+        LELE_TRY(weight_take(cacheable, key, bytes, out, &hit));
+        if (hit) return 0;
+        const int rc = fill(*out);
+        return cacheable ? weight_publish(key, *out, rc) : rc;
+    }
+    template <class Fill>  // ... of tensor t: cacheable if the caller declared it immutable
+    int weight_form(const LeleTensor* t, WeightForm form, std::initializer_list<int64_t> params, size_t bytes, void** out, Fill&& fill) {
+        return weight_form(t->mem == LELE_MEM_WEIGHT, weight_key(t, form, params), bytes, out, fill);
+    }
+    int weight_take(bool cacheable, const WeightKey& key, size_t bytes, void** out, bool* hit);  // weight_form's halves
+    int weight_publish(const WeightKey& key, void* d, int fill_rc);
+    // a verdict about an immutable tensor that needs no memory (WeightForm::CiNotU8); never recorded while capturing
+    bool weight_noted(const LeleTensor* t, WeightForm form) const;
+    void note_weight(const LeleTensor* t, WeightForm form);
+    void drop_weights(const void* src);  // frees every form of the tensor at `src` (its streams are idle)
     // device address -> the LeleBuf that owns it (kept current by LeleBuf::reserve), for the row-statistics side channel
     std::map<const void*, LeleBuf*> buf_of_data;
     // scratch that ops may keep across calls (grown on demand)

@@ -187,21 +187,15 @@ int LeleCtx::dev_ptr(const LeleTensor* t, const void** out) {
         *out = t->data;
         return 0;
     }
-    if (t->mem == LELE_MEM_WEIGHT) {
-        auto key = std::make_tuple(t->data, bytes, 0);
-        auto it = weights.find(key);
-        if (it != weights.end()) {
-            *out = it->second;
+    if (t->mem == LELE_MEM_WEIGHT) {  // the raw upload: its own capture message and a synchronous copy
+        const WeightKey key = weight_key(t, WeightForm::Raw);
+        LELE_REQUIRE(!capturing || weights.count(key), "graph capture: weight %p is not cached yet; run the sequence once before capturing it",
+                     t->data);
+        return weight_form(true, key, bytes, const_cast<void**>(out), [&](void* d) {
+            LELE_HIP_CHECK(hipMemcpyAsync(d, t->data, bytes, hipMemcpyHostToDevice, stream));
+            LELE_HIP_CHECK(hipStreamSynchronize(stream));
             return 0;
-        }
-        LELE_REQUIRE(!capturing, "graph capture: weight %p is not cached yet; run the sequence once before capturing it", t->data);
-        void* d = nullptr;
-        LELE_HIP_CHECK(hipMalloc(&d, bytes));
-        LELE_HIP_CHECK(hipMemcpyAsync(d, t->data, bytes, hipMemcpyHostToDevice, stream));
-        LELE_HIP_CHECK(hipStreamSynchronize(stream));
-        weights[key] = d;
-        *out = d;
-        return 0;
+        });
     }
     LELE_REQUIRE(!capturing, "graph capture: LELE_MEM_HOST inputs cannot be captured; pass device tensors or weights");
     void* d = nullptr;
@@ -210,6 +204,50 @@ int LeleCtx::dev_ptr(const LeleTensor* t, const void** out) {
     LELE_HIP_CHECK(hipMemcpyAsync(d, t->data, bytes, hipMemcpyHostToDevice, stream));
     *out = d;
     return 0;
+}
+
+int LeleCtx::weight_take(bool cacheable, const WeightKey& key, size_t bytes, void** out, bool* hit) {
+    *hit = false;
+    if (!cacheable) return arena_alloc(std::max<size_t>(bytes, 16), out);
+    auto it = weights.find(key);
+    if (it != weights.end()) {
+        *out = it->second;
+        *hit = true;
+        return 0;
+    }
+    LELE_REQUIRE(!capturing, "graph capture: this op must run once eagerly first (it allocates or synchronises)");
+    LELE_HIP_CHECK(hipMalloc(out, std::max<size_t>(bytes, 16)));
+    return 0;
+}
+
+int LeleCtx::weight_publish(const WeightKey& key, void* d, int fill_rc) {
+    if (fill_rc == 0)
+        weights[key] = d;
+    else
+        (void)hipFree(d);
+    return fill_rc;
+}
+
+bool LeleCtx::weight_noted(const LeleTensor* t, WeightForm form) const {
+    return t->mem == LELE_MEM_WEIGHT && weights.count(weight_key(t, form)) != 0;
+}
+
+void LeleCtx::note_weight(const LeleTensor* t, WeightForm form) {
+    if (t->mem == LELE_MEM_WEIGHT && !capturing) weights[weight_key(t, form)] = nullptr;
+}
+
+void LeleCtx::drop_weights(const void* src) {
+    for (auto it = weights.begin(); it != weights.end();) {
+        if (std::get<0>(it->first) != src) {
+            ++it;
+            continue;
+        }
+        if (it->second) {
+            (void)hipFree(it->second);
+            ++generation;
+        }
+        it = weights.erase(it);
+    }
 }
 
 int LeleBuf::reserve(size_t n) {

@@ -1418,6 +1418,19 @@ inline WinTile pick_win_tile(int ow, int oh, int positions, int ks, int stride, 
     return WinTile{btw, bth, (ow + btw - 1) / btw, (unsigned)(((1u << 20) + btw - 1) / btw)};
 }
 
+// the window kernels' weights: split-bf16 fragments for ceil(OC / 32) tiles (conv_wfrag_kernel) in `wbytes`, which round them up to
+// whole blocks of `oct` channels (the padding tiles are zeros)
+int window_frags(LeleCtx* ctx, const LeleTensor* wt, const float* dw, const ConvGeom& g, int taps, int oct, size_t wbytes, void** dwf) {
+    return ctx->weight_form(wt, WeightForm::ConvWindowFrag, {taps, (int64_t)wbytes}, wbytes, dwf, [&](void* d) {
+        const int oc_pad = ((g.oc + oct - 1) / oct) * oct;
+        LELE_HIP_CHECK(hipMemsetAsync(d, 0, wbytes, ctx->stream));
+        hipLaunchKernelGGL(conv_wfrag_kernel, dim3(grid_for((int64_t)(oc_pad / 32) * (g.c / 16) * taps * 64)), dim3(256), 0, ctx->stream, dw,
+                           (cu32x4*)d, g.oc, g.c, taps);
+        LELE_HIP_CHECK(hipGetLastError());
+        return 0;
+    });
+}
+
 int run_conv2d(LeleCtx* ctx, const LeleTensor* wt, const float* dx, const float* dw, const float* db, ConvGeom g, int act,
                float* out) {
     ctx->set_route(nullptr);
@@ -1515,25 +1528,7 @@ int run_conv2d(LeleCtx* ctx, const LeleTensor* wt, const float* dx, const float*
         const size_t wbytes = oct == 128 ? (size_t)(((g.oc + 127) / 128) * 4) * (g.c / 16) * taps * 3 * 1024  // whole blocks: the padding tiles are zeros
                                          : (size_t)((g.oc + 31) / 32) * (g.c / 16) * taps * 3 * 1024 + (size_t)(g.c / 16) * taps * 3 * 1024;  // (+ one padding tile)
         void* dwf = nullptr;
-        const bool cacheable = wt->mem == LELE_MEM_WEIGHT;
-        auto key = std::make_tuple((const void*)wt->data, wbytes, 330 + taps);
-        auto it = cacheable ? ctx->weights.find(key) : ctx->weights.end();
-        if (it != ctx->weights.end()) {
-            dwf = it->second;
-        } else {
-            if (cacheable) {
-                LELE_REQUIRE(!ctx->capturing, "graph capture: this op must run once eagerly first (it allocates or synchronises)");
-                LELE_HIP_CHECK(hipMalloc(&dwf, wbytes));
-                ctx->weights[key] = dwf;
-            } else {
-                LELE_TRY(ctx->arena_alloc(wbytes, &dwf));
-            }
-            // fragments for ceil(OC / 32) tiles, rounded up to whole blocks (the padding tiles are zeros)
-            const int oc_pad = ((g.oc + oct - 1) / oct) * oct;
-            LELE_HIP_CHECK(hipMemsetAsync(dwf, 0, wbytes, ctx->stream));
-            hipLaunchKernelGGL(conv_wfrag_kernel, dim3(grid_for((int64_t)(oc_pad / 32) * (g.c / 16) * taps * 64)), dim3(256), 0, ctx->stream, dw,
-                               (cu32x4*)dwf, g.oc, g.c, taps);
-        }
+        LELE_TRY(window_frags(ctx, wt, dw, g, taps, oct, wbytes, &dwf));
         // a 1 x 1 convolution has no rows: its plane is ONE row, cut into tiles of 256 positions (only the last one has padding)
         if (taps == 1) {
             g.ih = g.oh = 1;
@@ -1583,24 +1578,7 @@ int run_conv2d(LeleCtx* ctx, const LeleTensor* wt, const float* dx, const float*
         const int oct = ((g.oc + 31) / 32) * 32 < ((g.oc + 63) / 64) * 64 ? 32 : 64;
         const size_t wbytes = (size_t)((g.oc + 31) / 32) * (g.c / 16) * 9 * 3 * 1024 + (oct == 64 ? (size_t)(g.c / 16) * 9 * 3 * 1024 : 0);
         void* dwf = nullptr;
-        const bool cacheable = wt->mem == LELE_MEM_WEIGHT;
-        auto key = std::make_tuple((const void*)wt->data, wbytes, 330 + 9);
-        auto it = cacheable ? ctx->weights.find(key) : ctx->weights.end();
-        if (it != ctx->weights.end()) {
-            dwf = it->second;
-        } else {
-            if (cacheable) {
-                LELE_REQUIRE(!ctx->capturing, "graph capture: this op must run once eagerly first (it allocates or synchronises)");
-                LELE_HIP_CHECK(hipMalloc(&dwf, wbytes));
-                ctx->weights[key] = dwf;
-            } else {
-                LELE_TRY(ctx->arena_alloc(wbytes, &dwf));
-            }
-            const int oc_pad = ((g.oc + oct - 1) / oct) * oct;
-            LELE_HIP_CHECK(hipMemsetAsync(dwf, 0, wbytes, ctx->stream));
-            hipLaunchKernelGGL(conv_wfrag_kernel, dim3(grid_for((int64_t)(oc_pad / 32) * (g.c / 16) * 9 * 64)), dim3(256), 0, ctx->stream, dw,
-                               (cu32x4*)dwf, g.oc, g.c, 9);
-        }
+        LELE_TRY(window_frags(ctx, wt, dw, g, 9, oct, wbytes, &dwf));
         ConvEpi epi{out, db, g, act};
         const WinTile tile = pick_win_tile(g.ow, g.oh, 128, 3, 2, C3S2::POS, (int64_t)g.n * ((g.oc + oct - 1) / oct), ctx->num_cus);
         const int ntiles = tile.tiles_x * ((g.oh + tile.th - 1) / tile.th), nblocks = (g.oc + oct - 1) / oct;
@@ -1629,21 +1607,11 @@ int run_conv2d(LeleCtx* ctx, const LeleTensor* wt, const float* dx, const float*
         const int ocb = g.oc <= 8 ? 8 : 16;
         const size_t wbytes = (size_t)g.c * 9 * ocb * 4;
         void* dwq = nullptr;
-        const bool cacheable = wt->mem == LELE_MEM_WEIGHT;
-        auto key = std::make_tuple((const void*)wt->data, wbytes, 310 + ocb);
-        auto it = cacheable ? ctx->weights.find(key) : ctx->weights.end();
-        if (it != ctx->weights.end()) {
-            dwq = it->second;
-        } else {
-            if (cacheable) {
-                LELE_REQUIRE(!ctx->capturing, "graph capture: this op must run once eagerly first (it allocates or synchronises)");
-                LELE_HIP_CHECK(hipMalloc(&dwq, wbytes));
-                ctx->weights[key] = dwq;
-            } else {
-                LELE_TRY(ctx->arena_alloc(wbytes, &dwq));
-            }
-            hipLaunchKernelGGL(conv3x3_wperm_kernel, dim3(grid_for((int64_t)g.c * 9 * ocb)), dim3(256), 0, ctx->stream, dw, (float*)dwq, g.oc, g.c, ocb);
-        }
+        LELE_TRY(ctx->weight_form(wt, WeightForm::ConvDirect, {ocb}, wbytes, &dwq, [&](void* d) {
+            hipLaunchKernelGGL(conv3x3_wperm_kernel, dim3(grid_for((int64_t)g.c * 9 * ocb)), dim3(256), 0, ctx->stream, dw, (float*)d, g.oc, g.c, ocb);
+            LELE_HIP_CHECK(hipGetLastError());
+            return 0;
+        }));
         const int s_ = g.sh, ph = 7 * s_ + 3, pp = 31 * s_ + 3 + 1;
         int icc = g.c;
         while ((size_t)icc * ph * pp * 4 > 36 * 1024) icc = (icc + 1) / 2;  // the window of `icc` channels per LDS pass: four workgroups a CU
@@ -1682,22 +1650,11 @@ int run_conv2d(LeleCtx* ctx, const LeleTensor* wt, const float* dx, const float*
             const int khw = g.kh * g.kw;
             const size_t wbytes = (size_t)g.oc * g.K * 4;
             void* dwt = nullptr;
-            const bool cacheable = wt->mem == LELE_MEM_WEIGHT;
-            auto key = std::make_tuple((const void*)wt->data, wbytes, 301);
-            auto it = cacheable ? ctx->weights.find(key) : ctx->weights.end();
-            if (it != ctx->weights.end()) {
-                dwt = it->second;
-            } else {
-                if (cacheable) {
-                    LELE_REQUIRE(!ctx->capturing, "graph capture: this op must run once eagerly first (it allocates or synchronises)");
-                    LELE_HIP_CHECK(hipMalloc(&dwt, wbytes));
-                    ctx->weights[key] = dwt;
-                } else {
-                    LELE_TRY(ctx->arena_alloc(wbytes, &dwt));
-                }
-                hipLaunchKernelGGL(conv_wperm_kernel, dim3(grid_for((int64_t)g.oc * g.K)), dim3(256), 0, ctx->stream, dw,
-                                   (float*)dwt, g.oc, g.icg, khw);
-            }
+            LELE_TRY(ctx->weight_form(wt, WeightForm::ConvTapMajor, {}, wbytes, &dwt, [&](void* d) {
+                hipLaunchKernelGGL(conv_wperm_kernel, dim3(grid_for((int64_t)g.oc * g.K)), dim3(256), 0, ctx->stream, dw, (float*)d, g.oc, g.icg, khw);
+                LELE_HIP_CHECK(hipGetLastError());
+                return 0;
+            }));
             ConvWLoad alt{(const float*)dwt, g, 1};  // hipMalloc / arena chunks are 16-B aligned and K % 4 == 0
             ConvXLoadTap bl{dx, g, make_fastdiv(g.ow, g.plane), make_fastdiv(g.icg, g.K), make_fastdiv(g.kw, khw)};
             ctx->set_route("conv.gemm_tap", gemm::launch(ctx->stream, alt, bl, epi, g.ocg, g.plane, g.K, g.n * g.group, ctx->num_cus));
@@ -1991,29 +1948,15 @@ int centred_weights(LeleCtx* ctx, const LeleTensor* w, float w_zp, const float**
         *out = (const float*)dw;
         return 0;
     }
-    const size_t bytes = (size_t)numel(w) * 4;
-    int zbits;
+    uint32_t zbits;
     memcpy(&zbits, &w_zp, 4);
-    auto key = std::make_tuple((const void*)w->data, bytes, 500 + (zbits & 0x7fffff));
-    const bool cacheable = w->mem == LELE_MEM_WEIGHT;
-    if (cacheable) {
-        auto it = ctx->weights.find(key);
-        if (it != ctx->weights.end()) {
-            *out = (const float*)it->second;
-            return 0;
-        }
-    }
-    LELE_TRY(ctx->dev_ptr(w, &dw));
     void* adj = nullptr;
-    if (cacheable) {
-        LELE_REQUIRE(!ctx->capturing, "graph capture: this op must run once eagerly first (it allocates or synchronises)");
-        LELE_HIP_CHECK(hipMalloc(&adj, std::max<size_t>(bytes, 16)));
-        ctx->weights[key] = adj;
-    } else {
-        LELE_TRY(ctx->arena_alloc(std::max<size_t>(bytes, 16), &adj));
-    }
-    hipLaunchKernelGGL(ci_sub_kernel, dim3(grid_for(numel(w))), dim3(256), 0, ctx->stream, (const float*)dw, numel(w), w_zp,
-                       (float*)adj);
+    LELE_TRY(ctx->weight_form(w, WeightForm::CiCentred, {zbits}, (size_t)numel(w) * 4, &adj, [&](void* d) {
+        LELE_TRY(ctx->dev_ptr(w, &dw));
+        hipLaunchKernelGGL(ci_sub_kernel, dim3(grid_for(numel(w))), dim3(256), 0, ctx->stream, (const float*)dw, numel(w), w_zp, (float*)d);
+        LELE_HIP_CHECK(hipGetLastError());
+        return 0;
+    }));
     *out = (const float*)adj;
     return 0;
 }
@@ -2032,41 +1975,27 @@ int ci_run(LeleCtx* ctx, ConvGeom g, const LeleTensor* w, float w_zp, const floa
               !lab_env("LELE_HIP_CONV_INTEGER_F32");
     const int cp = (g.c + 31) & ~31, chunks = cp / 32, tiles = (g.oc + 31) / 32;
     const size_t fbytes = (size_t)tiles * taps * chunks * 1024, wbytes = fbytes + (size_t)g.oc * 4;
-    const bool cacheable = w->mem == LELE_MEM_WEIGHT;
-    const auto key = std::make_tuple((const void*)w->data, wbytes, 520);
-    const auto key_not = std::make_tuple((const void*)w->data, wbytes, 521);  // verdict "not u8 codes" of an immutable tensor (a 16-byte marker)
+    // the weights must be u8 codes: a host array, scanned when the fragments are made (once per immutable tensor, every call otherwise);
+    // the verdict "not u8 codes" of an immutable tensor is remembered too
+    if (i8 && ctx->weight_noted(w, WeightForm::CiNotU8)) i8 = false;
     void* fw = nullptr;
-    if (i8) {  // the weights must be u8 codes: a host array, scanned once per immutable tensor (every call otherwise)
-        auto it = cacheable ? ctx->weights.find(key) : ctx->weights.end();
-        if (it != ctx->weights.end()) {
-            fw = it->second;
-        } else if (cacheable && ctx->weights.count(key_not)) {
-            i8 = false;
-        } else {
+    if (i8) {
+        const int rc = ctx->weight_form(w, WeightForm::CiI8Frag, {}, wbytes, &fw, [&](void* d) {
             const float* hw = (const float*)w->data;
             const int64_t nw = numel(w);
             for (int64_t i = 0; i < nw && i8; ++i) i8 = code(hw[i]);
-            if (!i8 && cacheable && !ctx->capturing) {
-                void* marker = nullptr;
-                LELE_HIP_CHECK(hipMalloc(&marker, 16));
-                ctx->weights[key_not] = marker;
-            }
-        }
-    }
-    if (i8) {
-        if (!fw) {
+            if (!i8) return -1;  // not an error: the f32 route below
             const void* dw = nullptr;
             LELE_TRY(ctx->dev_ptr(w, &dw));
-            if (cacheable) {
-                LELE_REQUIRE(!ctx->capturing, "graph capture: this op must run once eagerly first (it allocates or synchronises)");
-                LELE_HIP_CHECK(hipMalloc(&fw, wbytes));
-                ctx->weights[key] = fw;
-            } else {
-                LELE_TRY(ctx->arena_alloc(wbytes, &fw));
-            }
             hipLaunchKernelGGL(ci8_wfrag_kernel, dim3(grid_for((int64_t)tiles * taps * chunks * 64)), dim3(256), 0, ctx->stream, (const float*)dw, g.oc, g.c,
-                               taps, chunks, (ci_v4i*)fw, (int*)((char*)fw + fbytes));
-        }
+                               taps, chunks, (ci_v4i*)d, (int*)((char*)d + fbytes));
+            LELE_HIP_CHECK(hipGetLastError());
+            return 0;
+        });
+        if (!i8) ctx->note_weight(w, WeightForm::CiNotU8);
+        else LELE_TRY(rc);
+    }
+    if (i8) {
         void *img = nullptr, *ts = nullptr;
         LELE_TRY(ctx->arena_alloc((size_t)g.n * spatial * cp + 512, &img));
         LELE_TRY(ctx->arena_alloc((size_t)g.n * spatial * 4, &ts));
@@ -2413,22 +2342,12 @@ int lele_hip_conv_transpose(LeleCtx* ctx, const LeleTensor* x, const LeleTensor*
         const int taps = g.kh * g.kw, mrows = g.oc * taps, plane_in = g.ih * g.iw;
         const size_t wb = (size_t)g.c * mrows * 4;
         void* dwk = nullptr;
-        const bool cache_k = w->mem == LELE_MEM_WEIGHT;
-        auto kkey = std::make_tuple((const void*)w->data, wb, 450);
-        auto kit = cache_k ? ctx->weights.find(kkey) : ctx->weights.end();
-        if (kit != ctx->weights.end()) {
-            dwk = kit->second;
-        } else {
-            if (cache_k) {
-                LELE_REQUIRE(!ctx->capturing, "graph capture: this op must run once eagerly first (it allocates or synchronises)");
-                LELE_HIP_CHECK(hipMalloc(&dwk, std::max<size_t>(wb, 16)));
-                ctx->weights[kkey] = dwk;
-            } else {
-                LELE_TRY(ctx->arena_alloc(std::max<size_t>(wb, 16), &dwk));
-            }
-            hipLaunchKernelGGL(convt_wks_kernel, dim3(grid_for((int64_t)g.c * mrows)), dim3(256), 0, ctx->stream, (const float*)dwp, (float*)dwk,
-                               g.c, g.oc, taps);
-        }
+        LELE_TRY(ctx->weight_form(w, WeightForm::ConvTKernelStride, {}, wb, &dwk, [&](void* d) {
+            hipLaunchKernelGGL(convt_wks_kernel, dim3(grid_for((int64_t)g.c * mrows)), dim3(256), 0, ctx->stream, (const float*)dwp, (float*)d, g.c,
+                               g.oc, taps);
+            LELE_HIP_CHECK(hipGetLastError());
+            return 0;
+        }));
         ConvGeom q{};
         q.group = 1;
         q.ocg = mrows;
@@ -2444,41 +2363,42 @@ int lele_hip_conv_transpose(LeleCtx* ctx, const LeleTensor* x, const LeleTensor*
     // per-phase weights: one buffer holding every phase's [OC][K_phase] block (each tap belongs to exactly one phase)
     const size_t wbytes = (size_t)g.c * g.oc * g.kh * g.kw * 4;
     const int tap_major = g.c % 4 == 0;
+    // the taps of a phase along one axis: the first, their spacing and their number
+    auto phase_taps = [](int p, int pad, int k, int dil, int stride, int* t0, int* st, int* nt) {
+        *t0 = -1, *st = 1, *nt = 0;
+        for (int t = 0; t < k; ++t)
+            if ((((p + pad - t * dil) % stride) + stride) % stride == 0) {
+                if (*nt == 0) *t0 = t;
+                if (*nt == 1) *st = t - *t0;
+                ++*nt;
+            }
+    };
+    // the phase structure depends on stride / dilation / pad-begin, so they are part of the key
     void* dwt = nullptr;
-    const bool cacheable = w->mem == LELE_MEM_WEIGHT;
-    // the phase structure depends on stride / dilation / pad-begin, so they are part of the cache tag
-    const int tag = 400 + ((g.sh * 31 + g.sw) * 31 + g.dh) * 31 + g.dw + 7919 * (g.pt * 64 + g.pl);
-    auto key = std::make_tuple((const void*)w->data, wbytes, tag);
-    auto it = cacheable ? ctx->weights.find(key) : ctx->weights.end();
-    const bool have_w = it != ctx->weights.end();
-    if (have_w) {
-        dwt = it->second;
-    } else if (cacheable) {
-        LELE_REQUIRE(!ctx->capturing, "graph capture: this op must run once eagerly first (it allocates or synchronises)");
-        LELE_HIP_CHECK(hipMalloc(&dwt, std::max<size_t>(wbytes, 16)));
-        ctx->weights[key] = dwt;
-    } else {
-        LELE_TRY(ctx->arena_alloc(std::max<size_t>(wbytes, 16), &dwt));
-    }
-    auto mod = [](int v, int m) { return ((v % m) + m) % m; };
+    LELE_TRY(ctx->weight_form(w, WeightForm::ConvTPhase, {g.sh, g.sw, g.dh, g.dw, g.pt, g.pl}, wbytes, &dwt, [&](void* d) {
+        size_t woff = 0;
+        for (int py = 0; py < g.sh; ++py)
+            for (int px = 0; px < g.sw; ++px) {
+                int a0, sa, na, b0, sb, nb;
+                phase_taps(py, g.pt, g.kh, g.dh, g.sh, &a0, &sa, &na);
+                phase_taps(px, g.pl, g.kw, g.dw, g.sw, &b0, &sb, &nb);
+                const int kp = g.c * na * nb;
+                if (kp)
+                    hipLaunchKernelGGL(convt_wphase_kernel, dim3(grid_for((int64_t)g.oc * kp)), dim3(256), 0, ctx->stream, (const float*)dwp,
+                                       (float*)d + woff, g.c, g.oc, g.kh, g.kw, a0, sa, na, b0, sb, nb, tap_major);
+                woff += (size_t)g.oc * kp;
+            }
+        LELE_HIP_CHECK(hipGetLastError());
+        return 0;
+    }));
     size_t woff = 0;
     ctx->set_route("convt.phase");  // one GEMM per phase (their own tiles each): the route names no GEMM kernel
     for (int py = 0; py < g.sh; ++py)
         for (int px = 0; px < g.sw; ++px) {
             const int nj = py < g.oh ? (g.oh - py + g.sh - 1) / g.sh : 0, ni = px < g.ow ? (g.ow - px + g.sw - 1) / g.sw : 0;
-            int a0 = -1, sa = 1, na = 0, b0 = -1, sb = 1, nb = 0;
-            for (int a = 0; a < g.kh; ++a)
-                if (mod(py + g.pt - a * g.dh, g.sh) == 0) {
-                    if (na == 0) a0 = a;
-                    if (na == 1) sa = a - a0;
-                    ++na;
-                }
-            for (int b = 0; b < g.kw; ++b)
-                if (mod(px + g.pl - b * g.dw, g.sw) == 0) {
-                    if (nb == 0) b0 = b;
-                    if (nb == 1) sb = b - b0;
-                    ++nb;
-                }
+            int a0, sa, na, b0, sb, nb;
+            phase_taps(py, g.pt, g.kh, g.dh, g.sh, &a0, &sa, &na);
+            phase_taps(px, g.pl, g.kw, g.dw, g.sw, &b0, &sb, &nb);
             const int kp = g.c * na * nb;
             float* wph = (float*)dwt + woff;
             woff += (size_t)g.oc * kp;
@@ -2490,9 +2410,6 @@ int lele_hip_conv_transpose(LeleCtx* ctx, const LeleTensor* x, const LeleTensor*
                 ctx->set_route("convt.phase_fill");
                 continue;
             }
-            if (!have_w)
-                hipLaunchKernelGGL(convt_wphase_kernel, dim3(grid_for((int64_t)g.oc * kp)), dim3(256), 0, ctx->stream,
-                                   (const float*)dwp, wph, g.c, g.oc, g.kh, g.kw, a0, sa, na, b0, sb, nb, tap_major);
             ConvGeom q{};
             q.n = g.n;
             q.c = g.c;

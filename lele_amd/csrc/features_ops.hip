@@ -213,13 +213,11 @@ struct FftTables {
     const float* tw_im;
 };
 
-// twiddle tables per n are immutable: cache them in the ctx weight map under a synthetic key
+// twiddle tables per n are immutable: one cached form without a source tensor, re | im
 int get_fft_tables(LeleCtx* ctx, int64_t n, FftTables* out) {
-    static const char tag_re = 0, tag_im = 0;
-    auto key_re = std::make_tuple((const void*)&tag_re, (size_t)n, 101);
-    auto key_im = std::make_tuple((const void*)&tag_im, (size_t)n, 102);
-    auto it = ctx->weights.find(key_re);
-    if (it == ctx->weights.end()) {
+    const size_t im_at = weight_second((size_t)n * 4);
+    void* d = nullptr;
+    LELE_TRY(ctx->weight_form(true, weight_key(nullptr, 0, WeightForm::FftTwiddles, {n}), im_at + (size_t)n * 4, &d, [&](void* p) {
         std::vector<float> re, im;
         for (int64_t size = 2; size <= n; size *= 2) {  // fft.rs:136-157
             const int64_t half = size / 2, step = n / size;
@@ -231,20 +229,12 @@ int get_fft_tables(LeleCtx* ctx, int64_t n, FftTables* out) {
         }
         re.push_back(0.f);
         im.push_back(0.f);
-        void *dre = nullptr, *dim = nullptr;
-        LELE_REQUIRE(!ctx->capturing, "graph capture: this op must run once eagerly first (it allocates or synchronises)");
-        LELE_HIP_CHECK(hipMalloc(&dre, re.size() * 4));
-        LELE_REQUIRE(!ctx->capturing, "graph capture: this op must run once eagerly first (it allocates or synchronises)");
-        LELE_HIP_CHECK(hipMalloc(&dim, im.size() * 4));
-        LELE_REQUIRE(!ctx->capturing, "graph capture: this op must run once eagerly first (it allocates or synchronises)");
-        LELE_HIP_CHECK(hipMemcpy(dre, re.data(), re.size() * 4, hipMemcpyHostToDevice));
-        LELE_REQUIRE(!ctx->capturing, "graph capture: this op must run once eagerly first (it allocates or synchronises)");
-        LELE_HIP_CHECK(hipMemcpy(dim, im.data(), im.size() * 4, hipMemcpyHostToDevice));
-        ctx->weights[key_re] = dre;
-        ctx->weights[key_im] = dim;
-    }
-    out->tw_re = (const float*)ctx->weights[key_re];
-    out->tw_im = (const float*)ctx->weights[key_im];
+        LELE_HIP_CHECK(hipMemcpy(p, re.data(), re.size() * 4, hipMemcpyHostToDevice));
+        LELE_HIP_CHECK(hipMemcpy((char*)p + im_at, im.data(), im.size() * 4, hipMemcpyHostToDevice));
+        return 0;
+    }));
+    out->tw_re = (const float*)d;
+    out->tw_im = (const float*)((const char*)d + im_at);
     return 0;
 }
 

@@ -851,71 +851,48 @@ struct PackedW {
     int* col_sums;
 };
 
-int get_packed_weights(LeleCtx* ctx, const LeleTensor* w, const float* dw, int64_t nbatch, int k, int n, int kp,
-                       PackedW* out, bool cacheable) {
-    // cache key: the caller's pointer (host pointer for LELE_MEM_WEIGHT, device pointer otherwise) + size
-    auto key_w = std::make_tuple((const void*)w->data, (size_t)numel(w) * 4, 201);
-    auto key_s = std::make_tuple((const void*)w->data, (size_t)numel(w) * 4, 202);
-    if (cacheable) {
-        auto it = ctx->weights.find(key_w);
-        if (it != ctx->weights.end()) {
-            out->wt = (int8_t*)it->second;
-            out->col_sums = (int*)ctx->weights[key_s];
-            return 0;
-        }
-    }
-    void *dwt = nullptr, *dcs = nullptr;
-    if (cacheable) {
-        LELE_REQUIRE(!ctx->capturing, "graph capture: this op must run once eagerly first (it allocates or synchronises)");
-        LELE_HIP_CHECK(hipMalloc(&dwt, (size_t)nbatch * n * kp));
-        LELE_REQUIRE(!ctx->capturing, "graph capture: this op must run once eagerly first (it allocates or synchronises)");
-        LELE_HIP_CHECK(hipMalloc(&dcs, (size_t)nbatch * n * 4));
-        ctx->weights[key_w] = dwt;
-        ctx->weights[key_s] = dcs;
-    } else {
-        LELE_TRY(ctx->arena_alloc((size_t)nbatch * n * kp, &dwt));
-        LELE_TRY(ctx->arena_alloc((size_t)nbatch * n * 4, &dcs));
-    }
-    LELE_HIP_CHECK(hipMemsetAsync(dcs, 0, (size_t)nbatch * n * 4, ctx->stream));
-    for (int64_t b = 0; b < nbatch; ++b)
-        hipLaunchKernelGGL(wpack_kernel, dim3((unsigned)((n + 63) / 64), (unsigned)((kp + 63) / 64)), dim3(256), 0, ctx->stream,
-                           dw + b * (int64_t)k * n, k, n, kp, (int8_t*)dwt + b * (int64_t)n * kp, (int*)dcs + b * n);
-    LELE_HIP_CHECK(hipGetLastError());
-    out->wt = (int8_t*)dwt;
-    out->col_sums = (int*)dcs;
+// weights as i8 [N][Kp] | column sums, of `nbatch` matrices: one cached form for declared-immutable weights, packed into the arena per
+// call otherwise.  dw is the f32-encoded source on the device; NULL has it uploaded when (and only when) the form is packed.
+int packed_weights_of(LeleCtx* ctx, const LeleTensor* w, const float* dw, int64_t nbatch, int k, int n, int kp, PackedW* out) {
+    const size_t sums_at = weight_second((size_t)nbatch * n * kp);
+    void* d = nullptr;
+    LELE_TRY(ctx->weight_form(w, WeightForm::I8Packed, {}, sums_at + (size_t)nbatch * n * 4, &d, [&](void* p) {
+        const void* src = dw;
+        if (!src) LELE_TRY(ctx->dev_ptr(w, &src));
+        int* dcs = (int*)((char*)p + sums_at);
+        LELE_HIP_CHECK(hipMemsetAsync(dcs, 0, (size_t)nbatch * n * 4, ctx->stream));
+        for (int64_t b = 0; b < nbatch; ++b)
+            hipLaunchKernelGGL(wpack_kernel, dim3((unsigned)((n + 63) / 64), (unsigned)((kp + 63) / 64)), dim3(256), 0, ctx->stream,
+                               (const float*)src + b * (int64_t)k * n, k, n, kp, (int8_t*)p + b * (int64_t)n * kp, dcs + b * n);
+        LELE_HIP_CHECK(hipGetLastError());
+        return 0;
+    }));
+    out->wt = (int8_t*)d;
+    out->col_sums = (int*)((char*)d + sums_at);
     return 0;
 }
 
-
-// fragment-major packed weights for the one-pass kernel (cached like PackedW; tags 203 / 204)
+// fragment-major packed weights | column sums for the one-pass kernel (cached like PackedW)
 struct FragW {
     int8_t* wf;
     int* col_sums;
 };
-int get_frag_weights(LeleCtx* ctx, const LeleTensor* w, int k, int n, int ks, int nt, FragW* out) {
-    auto key_w = std::make_tuple((const void*)w->data, (size_t)numel(w) * 4, 203);
-    auto key_s = std::make_tuple((const void*)w->data, (size_t)numel(w) * 4, 204);
-    auto it = ctx->weights.find(key_w);
-    if (it != ctx->weights.end()) {
-        out->wf = (int8_t*)it->second;
-        out->col_sums = (int*)ctx->weights[key_s];
+int frag_weights_of(LeleCtx* ctx, const LeleTensor* w, int k, int n, int kp, FragW* out) {
+    const int ks = kp / 32, nt = (n + 31) / 32;
+    const size_t sums_at = weight_second((size_t)nt * ks * 1024);
+    void* d = nullptr;
+    LELE_TRY(ctx->weight_form(w, WeightForm::I8Frag, {}, sums_at + (size_t)n * 4, &d, [&](void* p) {
+        const void* dw = nullptr;
+        LELE_TRY(ctx->dev_ptr(w, &dw));  // the f32-encoded matrix (an immutable one is uploaded and cached as WeightForm::Raw)
+        const int64_t threads = (int64_t)nt * 32 * ks * 2;
+        hipLaunchKernelGGL(wpack_frag_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, ctx->stream, (const float*)dw, k, n, ks,
+                           nt, (int8_t*)p);
+        LELE_TRY(launch_wcolsum(ctx, (const float*)dw, k, n, (int*)((char*)p + sums_at)));
+        LELE_HIP_CHECK(hipGetLastError());
         return 0;
-    }
-    LELE_REQUIRE(!ctx->capturing, "graph capture: this op must run once eagerly first (it allocates or synchronises)");
-    const void* dw = nullptr;
-    LELE_TRY(ctx->dev_ptr(w, &dw));  // the f32-encoded matrix (uploaded and cached under tag 0)
-    void *dwf = nullptr, *dcs = nullptr;
-    LELE_HIP_CHECK(hipMalloc(&dwf, (size_t)nt * ks * 1024));
-    LELE_HIP_CHECK(hipMalloc(&dcs, (size_t)n * 4));
-    const int64_t threads = (int64_t)nt * 32 * ks * 2;
-    hipLaunchKernelGGL(wpack_frag_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, ctx->stream, (const float*)dw, k, n, ks,
-                       nt, (int8_t*)dwf);
-    LELE_TRY(launch_wcolsum(ctx, (const float*)dw, k, n, (int*)dcs));
-    LELE_HIP_CHECK(hipGetLastError());
-    ctx->weights[key_w] = dwf;
-    ctx->weights[key_s] = dcs;
-    out->wf = (int8_t*)dwf;
-    out->col_sums = (int*)dcs;
+    }));
+    out->wf = (int8_t*)d;
+    out->col_sums = (int*)((char*)d + sums_at);
     return 0;
 }
 
@@ -1100,24 +1077,6 @@ bool rs_fits(LeleCtx* ctx, int64_t rows, int64_t n, int kp) { return kp == 512 &
 // the register-stationary kernels read residuals and write results 16 bytes at a time: a device tensor that does not start on a
 // 16-byte boundary (a view into a larger buffer) takes the tiled route instead (host tensors are staged into the aligned arena)
 bool rs_aligned(const LeleTensor* t) { return !t || t->mem != LELE_MEM_DEVICE || (((uintptr_t)t->data) & 15) == 0; }
-// weights in fragment order + column sums: cached for declared-immutable weights, packed into the arena per call otherwise
-int frag_weights_of(LeleCtx* ctx, const LeleTensor* w, int k, int n, int kp, FragW* out) {
-    const int ks = kp / 32, nt = (n + 31) / 32;
-    if (w->mem == LELE_MEM_WEIGHT) return get_frag_weights(ctx, w, k, n, ks, nt, out);
-    const void* dw = nullptr;
-    LELE_TRY(ctx->dev_ptr(w, &dw));
-    void *dwf = nullptr, *dcs = nullptr;
-    LELE_TRY(ctx->arena_alloc((size_t)nt * ks * 1024, &dwf));
-    LELE_TRY(ctx->arena_alloc((size_t)n * 4, &dcs));
-    const int64_t threads = (int64_t)nt * 32 * ks * 2;
-    hipLaunchKernelGGL(wpack_frag_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, ctx->stream, (const float*)dw, k, n, ks, nt,
-                       (int8_t*)dwf);
-    LELE_TRY(launch_wcolsum(ctx, (const float*)dw, k, n, (int*)dcs));
-    LELE_HIP_CHECK(hipGetLastError());
-    out->wf = (int8_t*)dwf;
-    out->col_sums = (int*)dcs;
-    return 0;
-}
 // f32 rows -> fragment-major i8 [ceil(rows / 32)][kp / 32][1024] in the arena (+ row sums unless rs == NULL)
 int launch_qrows_frag(LeleCtx* ctx, const float* dx, int64_t rows, int k, int kp, int m, QParams* prm, int8_t* af, int* rs,
                       const float* partial, int nblk, unsigned* zero_slice) {
@@ -1421,15 +1380,6 @@ int weight_zero_of(LeleCtx* ctx, const LeleTensor* weight_zero, float* wz) {
     return 0;
 }
 
-// weights as i8 [N][Kp] + column sums (cached for declared-immutable weights)
-int packed_weights_of(LeleCtx* ctx, const LeleTensor* weight_int8, int k, int n, int kp, PackedW* pw) {
-    const bool cacheable = weight_int8->mem == LELE_MEM_WEIGHT;  // only declared-immutable weights are cached
-    auto key_w = std::make_tuple((const void*)weight_int8->data, (size_t)numel(weight_int8) * 4, 201);
-    if (cacheable && ctx->weights.count(key_w)) return get_packed_weights(ctx, weight_int8, nullptr, 1, k, n, kp, pw, true);
-    const void* dw = nullptr;
-    LELE_TRY(ctx->dev_ptr(weight_int8, &dw));
-    return get_packed_weights(ctx, weight_int8, (const float*)dw, 1, k, n, kp, pw, cacheable);
-}
 }  // namespace
 
 extern "C" {
@@ -1592,7 +1542,7 @@ static int fql_impl(LeleCtx* ctx, const LeleTensor* input, const LeleTensor* wei
     // ---- three-kernel chain: rows -> i8 (+ row sums) in HBM, then the tiled i8 GEMM
     const int kp = (int)((k + 15) & ~int64_t(15));
     PackedW pw;
-    LELE_TRY(packed_weights_of(ctx, weight_int8, (int)k, (int)n, kp, &pw));
+    LELE_TRY(packed_weights_of(ctx, weight_int8, nullptr, 1, (int)k, (int)n, kp, &pw));
     void *aq = nullptr, *rs = nullptr;
     LELE_TRY(ctx->arena_alloc((size_t)rows * kp, &aq));
     LELE_TRY(ctx->arena_alloc((size_t)rows * 4, &rs));
@@ -1697,7 +1647,7 @@ int lele_hip_fused_quantized_linear_segments(LeleCtx* ctx, const LeleTensor* inp
     // 2. rows -> i8 with their segment's parameters, 3. the tiled i8 GEMM whose epilogue looks the segment up per row
     const int kp = (int)((k + 15) & ~int64_t(15));
     PackedW pw;
-    LELE_TRY(packed_weights_of(ctx, weight_int8, (int)k, (int)n, kp, &pw));
+    LELE_TRY(packed_weights_of(ctx, weight_int8, nullptr, 1, (int)k, (int)n, kp, &pw));
     void *aq = nullptr, *rs = nullptr;
     LELE_TRY(ctx->arena_alloc((size_t)rows * kp, &aq));
     LELE_TRY(ctx->arena_alloc((size_t)rows * 4, &rs));
@@ -2024,8 +1974,8 @@ static int ffn_impl(LeleCtx* ctx, const LeleTensor* input, const LeleTensor* w1_
     }
     const int kp1 = (int)((k1 + 15) & ~int64_t(15)), kp2 = (int)n1;
     PackedW pw1, pw2;
-    LELE_TRY(packed_weights_of(ctx, w1_int8, (int)k1, (int)n1, kp1, &pw1));
-    LELE_TRY(packed_weights_of(ctx, w2_int8, (int)k2, (int)n2, kp2, &pw2));
+    LELE_TRY(packed_weights_of(ctx, w1_int8, nullptr, 1, (int)k1, (int)n1, kp1, &pw1));
+    LELE_TRY(packed_weights_of(ctx, w2_int8, nullptr, 1, (int)k2, (int)n2, kp2, &pw2));
     LELE_TRY(ctx->arena_alloc((size_t)rows * kp1, &aq1));
     LELE_TRY(ctx->arena_alloc((size_t)rows * 4, &rs1));
     LELE_TRY(ctx->arena_alloc((size_t)rows * kp2, &aq2));
@@ -2137,17 +2087,10 @@ int lele_hip_prepare_weights(LeleCtx* ctx, const uint8_t* b_u8, int64_t k, int64
 }
 int lele_hip_prepared_destroy(LelePrepared* p) {
     if (!p) return 0;
-    // the cached device copies stay with the ctx (freed at ctx_destroy); drop the keys so a recycled host address cannot alias
+    // free every cached form of this matrix, so a recycled host address cannot alias
     LeleCtx* c = p->ctx;
     (void)hipStreamSynchronize(c->stream);
-    for (int tag : {0, 201, 202, 203, 204}) {
-        auto it = c->weights.find(std::make_tuple((const void*)p->host.data(), p->host.size() * 4, tag));
-        if (it != c->weights.end()) {
-            (void)hipFree(it->second);
-            ++c->generation;
-            c->weights.erase(it);
-        }
-    }
+    c->drop_weights(p->host.data());
     delete p;
     return 0;
 }
@@ -2259,8 +2202,7 @@ int lele_hip_mat_mul_integer_with_scale_bias(LeleCtx* ctx, const LeleTensor* a, 
     if (bias) LELE_TRY(ctx->dev_ptr(bias, &dbi));
     const int kp = (int)((k + 15) & ~int64_t(15));
     PackedW pw;
-    LELE_TRY(get_packed_weights(ctx, b, (const float*)db, batch_b, (int)k, (int)n, kp, &pw,
-                                b->mem == LELE_MEM_WEIGHT));
+    LELE_TRY(packed_weights_of(ctx, b, (const float*)db, batch_b, (int)k, (int)n, kp, &pw));
     const int64_t rows_a = batch_a * m;
     void *aq = nullptr, *rs = nullptr;
     LELE_TRY(ctx->arena_alloc((size_t)rows_a * kp, &aq));

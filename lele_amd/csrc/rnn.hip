@@ -144,6 +144,39 @@ __global__ __launch_bounds__(kRnnThreads) void rnn_kernel(const float* __restric
     }
 }
 
+// what lele_hip_lstm / _gru and their *_segments forms check alike: W [1, G, I], R [1, G, H], the bias and the initial state of
+// `states` sequences; gives H, G = gates * H, the k-slices S a gate row is summed in and the LDS bytes of one sequence
+template <int MODE>
+int check_rnn_weights(const char* name, const LeleTensor* w, const LeleTensor* r, const LeleTensor* bias, const LeleTensor* h0,
+                      const LeleTensor* c0, int64_t I, int64_t states, int64_t* Hp, int64_t* Gp, int* Sp, size_t* lds_bytes) {
+    constexpr int NG = MODE == 0 ? 4 : 3;
+    const int64_t H = w->shape[1] / NG, G = NG * H;
+    LELE_REQUIRE(w->shape[1] == G && w->shape[2] == I, "%s: W shape mismatch", name);
+    LELE_REQUIRE(r->shape[0] == 1 && r->shape[1] == G && r->shape[2] == H, "%s: R shape mismatch", name);
+    if (bias) LELE_REQUIRE(numel(bias) == 2 * G, "%s: bias must hold %lld values", name, (long long)(2 * G));
+    if (h0) LELE_REQUIRE(numel(h0) == states * H, "%s: initial_h must hold %lld values", name, (long long)(states * H));
+    if (c0) LELE_REQUIRE(numel(c0) == states * H, "%s: initial_c must hold %lld values", name, (long long)(states * H));
+    LELE_REQUIRE(H >= 1, "%s: hidden_size must be positive", name);
+    int S = (int)std::max<int64_t>(1, kRnnThreads / G);
+    S = (int)std::min<int64_t>(S, H);
+    *lds_bytes = (size_t)(2 * H + (int64_t)S * G) * 4;
+    LELE_REQUIRE(*lds_bytes <= 160 * 1024, "%s: hidden_size %lld exceeds the LDS-resident state limit", name, (long long)H);
+    *Hp = H;
+    *Gp = G;
+    *Sp = S;
+    return 0;
+}
+
+// R transposed: once per weight when the caller declared it immutable (a streaming model calls this for every chunk)
+int rnn_rt(LeleCtx* ctx, const LeleTensor* r, const void* dr, int64_t G, int64_t H, void** rt) {
+    return ctx->weight_form(r, WeightForm::RnnRT, {}, (size_t)G * H * 4, rt, [&](void* d) {
+        hipLaunchKernelGGL(transpose_kernel, dim3((unsigned)((H + 31) / 32), (unsigned)((G + 31) / 32)), dim3(32, 8), 0, ctx->stream,
+                           (const float*)dr, (float*)d, (int)G, (int)H);
+        LELE_HIP_CHECK(hipGetLastError());
+        return 0;
+    });
+}
+
 template <int MODE>
 int run_rnn(LeleCtx* ctx, const char* name, const LeleTensor* x, const LeleTensor* w, const LeleTensor* r,
             const LeleTensor* bias, const LeleTensor* h0, const LeleTensor* c0, LeleBuf* y, LeleBuf* hn, LeleBuf* cn,
@@ -155,17 +188,11 @@ int run_rnn(LeleCtx* ctx, const char* name, const LeleTensor* x, const LeleTenso
     LELE_REQUIRE(x->dtype == LELE_F32 && w->dtype == LELE_F32 && r->dtype == LELE_F32, "%s: f32 tensors required", name);
     LELE_REQUIRE(w->shape[0] == 1, "%s: Only num_directions=1 supported", name);  // rnn.rs:86, 266
     LELE_REQUIRE(x->shape[1] == 1, "%s: Only batch_size=1 supported", name);     // rnn.rs:89, 269
-    const int64_t T = x->shape[0], I = x->shape[2], H = w->shape[1] / NG, G = NG * H;
-    LELE_REQUIRE(w->shape[1] == G && w->shape[2] == I, "%s: W shape mismatch", name);
-    LELE_REQUIRE(r->shape[0] == 1 && r->shape[1] == G && r->shape[2] == H, "%s: R shape mismatch", name);
-    if (bias) LELE_REQUIRE(numel(bias) == 2 * G, "%s: bias must hold %lld values", name, (long long)(2 * G));
-    if (h0) LELE_REQUIRE(numel(h0) == H, "%s: initial_h must hold %lld values", name, (long long)H);
-    if (c0) LELE_REQUIRE(numel(c0) == H, "%s: initial_c must hold %lld values", name, (long long)H);
-    LELE_REQUIRE(H >= 1, "%s: hidden_size must be positive", name);
-    int S = (int)std::max<int64_t>(1, kRnnThreads / G);
-    S = (int)std::min<int64_t>(S, H);
-    const size_t lds_bytes = (size_t)(2 * H + (int64_t)S * G) * 4;
-    LELE_REQUIRE(lds_bytes <= 160 * 1024, "%s: hidden_size %lld exceeds the LDS-resident state limit", name, (long long)H);
+    const int64_t T = x->shape[0], I = x->shape[2];
+    int64_t H = 0, G = 0;
+    int S = 0;
+    size_t lds_bytes = 0;
+    LELE_TRY(check_rnn_weights<MODE>(name, w, r, bias, h0, c0, I, 1, &H, &G, &S, &lds_bytes));
     LELE_HIP_CHECK(hipSetDevice(ctx->device));
     LELE_TRY(ctx->arena_reset());
     const void *dx = nullptr, *dw = nullptr, *dr = nullptr, *db = nullptr, *dh0 = nullptr, *dc0 = nullptr;
@@ -177,23 +204,7 @@ int run_rnn(LeleCtx* ctx, const char* name, const LeleTensor* x, const LeleTenso
     if (c0) LELE_TRY(ctx->dev_ptr(c0, &dc0));
     void *wx = nullptr, *rt = nullptr;
     LELE_TRY(ctx->arena_alloc((size_t)std::max<int64_t>(1, T * G) * 4, &wx));
-    // R transposed: once per weight when the caller declared it immutable (a streaming model calls this for every chunk)
-    const bool r_cacheable = r->mem == LELE_MEM_WEIGHT;
-    const auto r_key = std::make_tuple((const void*)r->data, (size_t)G * H * 4, 601);
-    bool have_rt = false;
-    if (r_cacheable) {
-        auto it = ctx->weights.find(r_key);
-        if (it != ctx->weights.end()) {
-            rt = it->second;
-            have_rt = true;
-        } else {
-            LELE_REQUIRE(!ctx->capturing, "graph capture: this op must run once eagerly first (it allocates or synchronises)");
-            LELE_HIP_CHECK(hipMalloc(&rt, (size_t)G * H * 4));
-            ctx->weights[r_key] = rt;
-        }
-    } else {
-        LELE_TRY(ctx->arena_alloc((size_t)G * H * 4, &rt));
-    }
+    LELE_TRY(rnn_rt(ctx, r, dr, G, H, &rt));
     LELE_TRY(y->reserve((size_t)T * H * 4));
     LELE_TRY(hn->reserve((size_t)H * 4));
     if (MODE == 0) LELE_TRY(cn->reserve((size_t)H * 4));
@@ -205,9 +216,6 @@ int run_rnn(LeleCtx* ctx, const char* name, const LeleTensor* x, const LeleTenso
         wx_route = gemm::launch(ctx->stream, al, bl, epi, (int)T, (int)G, (int)I, 1, ctx->num_cus);
     }
     ctx->set_route(MODE == 0 ? "rnn.lstm" : "rnn.gru", wx_route);
-    if (!have_rt)
-        hipLaunchKernelGGL(transpose_kernel, dim3((unsigned)((H + 31) / 32), (unsigned)((G + 31) / 32)), dim3(32, 8), 0,
-                           ctx->stream, (const float*)dr, (float*)rt, (int)G, (int)H);
     LELE_HIP_CHECK(ensure_dyn_lds(reinterpret_cast<const void*>(&rnn_kernel<MODE>), 160 * 1024));
     hipLaunchKernelGGL(rnn_kernel<MODE>, dim3(1), dim3(kRnnThreads), lds_bytes, ctx->stream, (const float*)wx,
                        (const float*)rt, (const float*)db, (const float*)dh0, (const float*)dc0, (float*)y->data,
@@ -451,17 +459,10 @@ int run_rnn_segments(LeleCtx* ctx, const char* name, const LeleTensor* x, const 
     LELE_REQUIRE(w->rank == 3 && r->rank == 3, "%s: expected W [1,%dH,I], R [1,%dH,H]", name, NG, NG);
     LELE_REQUIRE(w->dtype == LELE_F32 && r->dtype == LELE_F32, "%s: f32 tensors required", name);
     LELE_REQUIRE(w->shape[0] == 1, "%s: Only num_directions=1 supported", name);  // rnn.rs:86, 266
-    const int64_t H = w->shape[1] / NG, G = NG * H;
-    LELE_REQUIRE(w->shape[1] == G && w->shape[2] == I, "%s: W shape mismatch", name);
-    LELE_REQUIRE(r->shape[0] == 1 && r->shape[1] == G && r->shape[2] == H, "%s: R shape mismatch", name);
-    if (bias) LELE_REQUIRE(numel(bias) == 2 * G, "%s: bias must hold %lld values", name, (long long)(2 * G));
-    if (h0) LELE_REQUIRE(numel(h0) == count * H, "%s: initial_h must hold %lld values", name, (long long)(count * H));
-    if (c0) LELE_REQUIRE(numel(c0) == count * H, "%s: initial_c must hold %lld values", name, (long long)(count * H));
-    LELE_REQUIRE(H >= 1, "%s: hidden_size must be positive", name);
-    int S = (int)std::max<int64_t>(1, kRnnThreads / G);
-    S = (int)std::min<int64_t>(S, H);
-    const size_t seg_bytes = (size_t)(2 * H + (int64_t)S * G) * 4;
-    LELE_REQUIRE(seg_bytes <= 160 * 1024, "%s: hidden_size %lld exceeds the LDS-resident state limit", name, (long long)H);
+    int64_t H = 0, G = 0;
+    int S = 0;
+    size_t seg_bytes = 0;
+    LELE_TRY(check_rnn_weights<MODE>(name, w, r, bias, h0, c0, I, count, &H, &G, &S, &seg_bytes));
     LELE_REQUIRE(R <= (int64_t)65535 * 64 && count < (int64_t(1) << 31) / 8 && I < (int64_t(1) << 31), "%s: tensor too large", name);
     // the form and the group width follow from the shapes alone (never from the data, the lengths or the position of a segment)
     int ks = (H % S == 0 && (int64_t)S * G <= kRnnThreads) ? (int)(H / S) : 0;
@@ -496,26 +497,9 @@ int run_rnn_segments(LeleCtx* ctx, const char* name, const LeleTensor* x, const 
     if (h0 && count > 0) LELE_TRY(ctx->dev_ptr(h0, &dh0));
     if (c0 && count > 0) LELE_TRY(ctx->dev_ptr(c0, &dc0));
     void *wx = nullptr, *rt = nullptr;
-    bool have_rt = true;
     if (R > 0) {
         LELE_TRY(ctx->arena_alloc((size_t)(R * G) * 4, &wx));
-        if (ks == 0) {  // R transposed, under lele_hip_lstm's cache rule and key
-            const auto r_key = std::make_tuple((const void*)r->data, (size_t)G * H * 4, 601);
-            have_rt = false;
-            if (r->mem == LELE_MEM_WEIGHT) {
-                auto it = ctx->weights.find(r_key);
-                if (it != ctx->weights.end()) {
-                    rt = it->second;
-                    have_rt = true;
-                } else {
-                    LELE_REQUIRE(!ctx->capturing, "graph capture: this op must run once eagerly first (it allocates or synchronises)");
-                    LELE_HIP_CHECK(hipMalloc(&rt, (size_t)G * H * 4));
-                    ctx->weights[r_key] = rt;
-                }
-            } else {
-                LELE_TRY(ctx->arena_alloc((size_t)G * H * 4, &rt));
-            }
-        }
+        if (ks == 0) LELE_TRY(rnn_rt(ctx, r, dr, G, H, &rt));  // the streamed form reads R transposed
     }
     const size_t state_bytes = (size_t)(count * H) * 4;
     LELE_TRY(y->reserve((size_t)(R * H) * 4));
@@ -548,9 +532,6 @@ int run_rnn_segments(LeleCtx* ctx, const char* name, const LeleTensor* x, const 
         const unsigned blocks = (unsigned)std::min<int64_t>((R * G + 255) / 256, 1024);
         hipLaunchKernelGGL((gemm::gemm_f32_epilogue_kernel<gemm::EpiAffine>), dim3(blocks, 1), dim3(256), 0, ctx->stream, epi, (int)R, (int)G);
     }
-    if (!have_rt)
-        hipLaunchKernelGGL(transpose_kernel, dim3((unsigned)((H + 31) / 32), (unsigned)((G + 31) / 32)), dim3(32, 8), 0, ctx->stream,
-                           (const float*)dr, (float*)rt, (int)G, (int)H);
     const unsigned ngroups = (unsigned)((count + ns - 1) / ns);
     const size_t lds_bytes = seg_bytes * ns;
     const float* rw = ks ? (const float*)dr : (const float*)rt;
