@@ -951,22 +951,20 @@ int launch_range(LeleCtx* ctx, const float* dx, int64_t slices, int64_t slice_le
     return 0;
 }
 
-int launch_igemm(LeleCtx* ctx, const int8_t* aq, const int8_t* wt, int64_t rows, int n, int kp, int64_t b_stride,
-                 int m_per_batch, const IgemmEpi& epi_in) {
+int launch_igemm(LeleCtx* ctx, const int8_t* aq, const int8_t* wt, int64_t rows, int n, int kp, int m_per_batch, const IgemmEpi& epi_in) {
     if (rows == 0 || n == 0) return 0;
     IgemmEpi epi = epi_in;
     epi.flags = lab_int("LELE_HIP_IGEMM_FLAGS", 0);
     LELE_REQUIRE(rows < (int64_t(1) << 31), "quantized GEMM: more than 2^31 rows");
     const int64_t b128 = ((rows + 127) / 128) * ((n + 127) / 128);
-    // batched B needs every block to stay inside one batch slice: tiles never straddle slices when BM divides m,
-    // otherwise fall back to one launch per slice (handled by the caller passing rows == m)
+    // (the kernels' b_stride stays 0: a batched B is one launch per slice, issued by the caller with rows == m)
 #define IGEMM_LAUNCH(BM_, BN_, WM_, WN_, BKB_, OCC_)                                                                         \
     do {                                                                                                                  \
         constexpr size_t lds = (size_t)2 * ((BM_) + (BN_)) * ((BKB_) + 16);                                               \
         auto kern = igemm_kernel<BM_, BN_, WM_, WN_, BKB_, OCC_>;                                                          \
         if (lds > 64 * 1024) LELE_HIP_CHECK(ensure_dyn_lds(reinterpret_cast<const void*>(kern), (int)lds));               \
         dim3 grid((n + (BN_)-1) / (BN_), (unsigned)((rows + (BM_)-1) / (BM_)));                                           \
-        hipLaunchKernelGGL(kern, grid, dim3((WM_) * (WN_) * 64), lds, ctx->stream, aq, wt, rows, n, kp, b_stride,          \
+        hipLaunchKernelGGL(kern, grid, dim3((WM_) * (WN_) * 64), lds, ctx->stream, aq, wt, rows, n, kp, (int64_t)0,        \
                            m_per_batch, epi);                                                                             \
     } while (0)
     const int64_t b64 = ((rows + 63) / 64) * ((n + 63) / 64);
@@ -989,11 +987,12 @@ int launch_igemm(LeleCtx* ctx, const int8_t* aq, const int8_t* wt, int64_t rows,
     else
 #endif
     // compute-bound shapes (igemm_big.h): long K in whole 128-byte steps, at least half a chip of 256 x 256 results, 16-byte rows
-    if (b_stride == 0 && kp % 128 == 0 && kp >= 1024 && n % 4 == 0 && lab_int("LELE_HIP_IGEMM_BIG", 1) != 0 &&
+    if (kp % 128 == 0 && kp >= 1024 && n % 4 == 0 && lab_int("LELE_HIP_IGEMM_BIG", 1) != 0 &&
         rows * kp < (int64_t(1) << 32) && (int64_t)n * kp < (int64_t(1) << 32) &&
         ((rows + 255) / 256) * (((int64_t)n + 255) / 256) * 2 >= (int64_t)ctx->num_cus && ((((uintptr_t)epi.out) | ((uintptr_t)epi.res1) | ((uintptr_t)epi.res2)) & 15) == 0 &&
         !epi.blockstat) {
         dim3 grid((unsigned)((n + 255) / 256), (unsigned)((rows + 255) / 256));
+#ifdef LELE_HIP_LAB
         if (lab_int("LELE_HIP_IGEMM_BIG", 1) == 2) {   // (lab) four waves of 128 x 128
             auto kern = igemm_big_kernel<2>;
             LELE_HIP_CHECK(ensure_dyn_lds(reinterpret_cast<const void*>(kern), BG_LDS));
@@ -1002,7 +1001,9 @@ int launch_igemm(LeleCtx* ctx, const int8_t* aq, const int8_t* wt, int64_t rows,
             auto kern = igemm_big_kernel<4>;
             LELE_HIP_CHECK(ensure_dyn_lds(reinterpret_cast<const void*>(kern), BG_LDS));
             hipLaunchKernelGGL(kern, grid, dim3(512), BG_LDS, ctx->stream, aq, wt, rows, n, kp, epi);
-        } else {
+        } else
+#endif
+        {
             auto kern = igemm_big_kernel<4, true>;
             LELE_HIP_CHECK(ensure_dyn_lds(reinterpret_cast<const void*>(kern), BG_LDS));
             hipLaunchKernelGGL(kern, grid, dim3(512), BG_LDS, ctx->stream, aq, wt, rows, n, kp, epi);
@@ -1011,10 +1012,10 @@ int launch_igemm(LeleCtx* ctx, const int8_t* aq, const int8_t* wt, int64_t rows,
         // small problem (SenseVoice at M = 504): 32x32 tiles, K split over the four waves, operands straight from L2
         dim3 grid((unsigned)((n + 31) / 32), (unsigned)((rows + 31) / 32));
         if (kp <= 512)
-            hipLaunchKernelGGL((gemm::igemm_small_kernel<IgemmEpi, 4>), grid, dim3(256), 0, ctx->stream, aq, wt, rows, n, kp, b_stride,
+            hipLaunchKernelGGL((gemm::igemm_small_kernel<IgemmEpi, 4>), grid, dim3(256), 0, ctx->stream, aq, wt, rows, n, kp, (int64_t)0,
                                m_per_batch, epi);
         else
-            hipLaunchKernelGGL((gemm::igemm_small_kernel<IgemmEpi, 16>), grid, dim3(256), 0, ctx->stream, aq, wt, rows, n, kp, b_stride,
+            hipLaunchKernelGGL((gemm::igemm_small_kernel<IgemmEpi, 16>), grid, dim3(256), 0, ctx->stream, aq, wt, rows, n, kp, (int64_t)0,
                                m_per_batch, epi);
     } else if (b128 >= 2 * ctx->num_cus) {
         // 128-byte K tiles (74 KB of LDS, 2 workgroups per CU): half as many barriers and twice the bytes in flight per K step.
@@ -1023,12 +1024,12 @@ int launch_igemm(LeleCtx* ctx, const int8_t* aq, const int8_t* wt, int64_t rows,
         IGEMM_LAUNCH(128, 128, 2, 4, 128, 1);
     } else if (rows <= 32) {
         IGEMM_LAUNCH(32, 128, 1, 4, 64, 1);
-    } else if (((rows + 127) / 128) * ((n + 63) / 64) >= ctx->num_cus) {
-        // narrow results over many rows (out projection, second feed-forward layer: N = 512 over a batch of utterances): 128 x 64
-        // tiles, eight waves, 128-byte K tiles -- 40.0 us against 45.9 us with 64 x 64 tiles at K = 2048, 16.3 against 16.8 at K = 512
-        IGEMM_LAUNCH(128, 64, 4, 2, 128, 4);
     } else {
-        IGEMM_LAUNCH(64, 64, 2, 2, 64, 1);
+        // narrow results over many rows (out projection, second feed-forward layer: N = 512 over a batch of utterances): 128 x 64
+        // tiles, eight waves, 128-byte K tiles -- 40.0 us against 45.9 us with 64 x 64 tiles at K = 2048, 16.3 against 16.8 at K = 512.
+        // (They always cover the chip here: b64 >= 2 CUs and ceil(rows / 64) <= 2 ceil(rows / 128) give ceil(rows / 128) * ceil(n / 64)
+        // >= CUs, so the 64 x 64 tile that once stood behind this one is the lab's LELE_HIP_IGEMM_TILE=5 only.)
+        IGEMM_LAUNCH(128, 64, 4, 2, 128, 4);
     }
 #undef IGEMM_LAUNCH
     LELE_HIP_CHECK(hipGetLastError());
@@ -1039,24 +1040,15 @@ int launch_igemm(LeleCtx* ctx, const int8_t* aq, const int8_t* wt, int64_t rows,
 int launch_igemm_hidden(LeleCtx* ctx, int em, const int8_t* aq, const int8_t* wt, int64_t rows, int n, int kp, int m, const IgemmEpi& epi) {
     constexpr size_t lds = (size_t)2 * (128 + 128) * (128 + 16);
     const dim3 grid((n + 127) / 128, (unsigned)((rows + 127) / 128));
-    if (em == 1) {
-        auto kern = igemm_kernel<128, 128, 2, 4, 128, 1, 1>;
-        LELE_HIP_CHECK(ensure_dyn_lds(reinterpret_cast<const void*>(kern), (int)lds));
-        hipLaunchKernelGGL(kern, grid, dim3(512), lds, ctx->stream, aq, wt, rows, n, kp, (int64_t)0, m, epi);
-    } else {
-        auto kern = igemm_kernel<128, 128, 2, 4, 128, 1, 2>;
-        LELE_HIP_CHECK(ensure_dyn_lds(reinterpret_cast<const void*>(kern), (int)lds));
-        hipLaunchKernelGGL(kern, grid, dim3(512), lds, ctx->stream, aq, wt, rows, n, kp, (int64_t)0, m, epi);
-    }
+    auto kern = em == 1 ? igemm_kernel<128, 128, 2, 4, 128, 1, 1> : igemm_kernel<128, 128, 2, 4, 128, 1, 2>;
+    LELE_HIP_CHECK(ensure_dyn_lds(reinterpret_cast<const void*>(kern), (int)lds));
+    hipLaunchKernelGGL(kern, grid, dim3(512), lds, ctx->stream, aq, wt, rows, n, kp, (int64_t)0, m, epi);
     LELE_HIP_CHECK(hipGetLastError());
     return 0;
 }
 
-// ---- register-stationary route (igemm_rs.h): K padded to exactly 512 or 2048 bytes, enough 32 x 32 tiles to fill the chip
-int rs_kp(int64_t k) {
-    const int64_t kp = (k + 31) & ~int64_t(31);
-    return kp == 512 || kp == 2048 ? (int)kp : 0;
-}
+// ---- register-stationary route (igemm_rs.h): K padded to exactly 512 bytes (2048 inside the feed-forward block), enough 32 x 32 tiles to fill the chip
+bool pads_to_512(int64_t k) { return ((k + 31) & ~int64_t(31)) == 512; }
 // enough 32 x 32 tiles, 16-byte stores, 32-bit byte offsets into the result.  (Round 3 asked for 8 tiles per CU: below that the
 // quantising pass + small-problem GEMM were faster.  With the rows quantised inside the kernel the route needs no pass in front, and
 // one 30 s utterance -- 16 row tiles x 48-64 column tiles -- gains 7 % per forward on it: 2 tiles per CU.)
@@ -1073,20 +1065,17 @@ bool rs_enabled(LeleCtx* ctx, int64_t rows, int64_t n, int per_cu = 2) {
 // the quantising loaders (igemm_rs.h, FQ): whole 512-element rows read as float4s.  LELE_HIP_IGEMM_RS_FQ=0 (lab build) keeps the
 // separate qrows_frag_kernel pass for A/B timing; both give the same bits.
 bool rs_fq(int64_t k, const void* dx) { return k == 512 && (((uintptr_t)dx) & 15) == 0 && lab_int("LELE_HIP_IGEMM_RS_FQ", 1) != 0; }
-bool rs_fits(LeleCtx* ctx, int64_t rows, int64_t n, int kp) { return kp == 512 && n >= lab_int("LELE_HIP_IGEMM_RS_MIN_N", 1024) && rs_enabled(ctx, rows, n); }
+bool rs_fits(LeleCtx* ctx, int64_t rows, int64_t n, int64_t k) { return pads_to_512(k) && n >= lab_int("LELE_HIP_IGEMM_RS_MIN_N", 1024) && rs_enabled(ctx, rows, n); }
 // the register-stationary kernels read residuals and write results 16 bytes at a time: a device tensor that does not start on a
 // 16-byte boundary (a view into a larger buffer) takes the tiled route instead (host tensors are staged into the aligned arena)
 bool rs_aligned(const LeleTensor* t) { return !t || t->mem != LELE_MEM_DEVICE || (((uintptr_t)t->data) & 15) == 0; }
-// f32 rows -> fragment-major i8 [ceil(rows / 32)][kp / 32][1024] in the arena (+ row sums unless rs == NULL)
-int launch_qrows_frag(LeleCtx* ctx, const float* dx, int64_t rows, int k, int kp, int m, QParams* prm, int8_t* af, int* rs,
-                      const float* partial, int nblk, unsigned* zero_slice) {
+// f32 rows, K <= 512 -> fragment-major i8 [ceil(rows / 32)][16][1024] in the arena (+ row sums unless rs == NULL)
+int launch_qrows_frag(LeleCtx* ctx, const float* dx, int64_t rows, int k, int m, QParams* prm, int8_t* af, int* rs, const float* partial,
+                      int nblk, unsigned* zero_slice) {
     const int64_t nrt = (rows + 31) / 32;
-    if (kp == 512)  // a wave per two rows: 4 tiles' worth of workgroups per tile
-        hipLaunchKernelGGL((qrows_frag_kernel<32, 1>), dim3((unsigned)(4 * nrt)), dim3(256), 0, ctx->stream, dx, (unsigned)rows, k, m, prm, af, rs,
-                           partial, nblk, zero_slice);
-    else
-        hipLaunchKernelGGL((qrows_frag_kernel<128, 4>), dim3((unsigned)(4 * nrt)), dim3(256), 0, ctx->stream, dx, (unsigned)rows, k, m, prm, af, rs,
-                           partial, nblk, zero_slice);
+    // a wave per two rows: 4 tiles' worth of workgroups per tile
+    hipLaunchKernelGGL((qrows_frag_kernel<32, 1>), dim3((unsigned)(4 * nrt)), dim3(256), 0, ctx->stream, dx, (unsigned)rows, k, m, prm, af, rs,
+                       partial, nblk, zero_slice);
     LELE_HIP_CHECK(hipGetLastError());
     return 0;
 }
@@ -1302,9 +1291,13 @@ int launch_ask(LeleCtx* ctx, const int8_t* af, const int8_t* wf, int64_t rows, c
         else if (nres == 1) LELE_ASK(1, true);
         else LELE_ASK(2, true);
     } else {
+#ifdef LELE_HIP_LAB
         if (nres == 0) LELE_ASK(0, false);
         else if (nres == 1) LELE_ASK(1, false);
         else LELE_ASK(2, false);
+#else
+        LELE_REQUIRE(false, "launch_ask: the form without a LayerNorm is built into the lab library only");
+#endif
     }
 #undef LELE_ASK
     LELE_HIP_CHECK(hipGetLastError());
@@ -1365,224 +1358,293 @@ void find_partials(LeleCtx* ctx, const LeleTensor* input, int64_t batch, int64_t
     }
 }
 
-// weight_zero.data.first() as i32 (quantization.rs:100); fetched on the host: it is a scalar attribute
-int weight_zero_of(LeleCtx* ctx, const LeleTensor* weight_zero, float* wz) {
-    *wz = 0.0f;
-    if (weight_zero && numel(weight_zero) > 0) {
-        if (weight_zero->mem == LELE_MEM_DEVICE) {
-            LELE_HIP_CHECK(hipMemcpyAsync(wz, weight_zero->data, 4, hipMemcpyDeviceToHost, ctx->stream));
-            LELE_REQUIRE(!ctx->capturing, "graph capture: this op must run once eagerly first (it allocates or synchronises)");
-            LELE_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-        } else {
-            *wz = *(const float*)weight_zero->data;
-        }
+// `.data.first()` of a zero point (quantization.rs:100), 0 where absent or empty, fetched on the host; callers take it `as i32`
+int first_scalar_of(LeleCtx* ctx, const LeleTensor* t, float* v) {
+    *v = 0.0f;
+    if (!t || numel(t) == 0) return 0;
+    if (t->mem != LELE_MEM_DEVICE) {
+        *v = *(const float*)t->data;
+        return 0;
     }
+    LELE_HIP_CHECK(hipMemcpyAsync(v, t->data, 4, hipMemcpyDeviceToHost, ctx->stream));
+    LELE_REQUIRE(!ctx->capturing, "graph capture: this op must run once eagerly first (it allocates or synchronises)");
+    LELE_HIP_CHECK(hipStreamSynchronize(ctx->stream));
     return 0;
 }
 
-}  // namespace
-
-extern "C" {
-
-// the LayerNorm epilogue of igemm_as_kernel: whole 512-wide rows in a workgroup, no ReLU, f32 scale / bias of at least 512 values
-static bool as_ln_ok(LeleCtx* ctx, int64_t rows, int64_t n, int apply_relu, const LeleTensor* g, const LeleTensor* b) {
-    return env_int("LELE_HIP_LN_FUSED", 1) != 0 && n == 512 && !apply_relu && as_two(ctx, rows, (int)n) && g->dtype == LELE_F32 &&
-           b->dtype == LELE_F32 && numel(g) >= 512 && numel(b) >= 512;
+// ------------------------------------------------------------------------------------------ one quantised linear, described
+struct QW {  // a layer's weight tensors as the C ABI passes them
+    const LeleTensor *w, *scale, *zero, *bias;
+};
+// input [.., m, k] x weight [.., kw, n]: `batch` slices of m rows, each quantised with its own range
+struct QCall {
+    int64_t batch = 1, m = 0, k = 0, kw = 0, n = 0, rows = 0, ws_len = 0, blen = 0;
+    std::vector<int64_t> shp;  // the result: the input's shape with n as its last extent
+    // weight_scale: one value or one per column; bias: none or one per column
+    bool lens_ok() const { return ws_len >= 1 && (ws_len <= 1 || ws_len >= n) && (blen == 0 || blen >= n); }
+};
+// the extents as the tensors give them, nothing judged (ranks >= 2)
+QCall call_dims(const LeleTensor* input, const QW& w) {
+    QCall c;
+    c.m = input->shape[input->rank - 2], c.k = input->shape[input->rank - 1];
+    c.kw = w.w->shape[w.w->rank - 2], c.n = w.w->shape[w.w->rank - 1];
+    for (int i = 0; i + 2 < input->rank; ++i) c.batch *= input->shape[i];
+    c.rows = c.batch * c.m;
+    c.ws_len = w.scale ? numel(w.scale) : 0, c.blen = w.bias ? numel(w.bias) : 0;
+    c.shp.assign(input->shape, input->shape + input->rank - 1);
+    c.shp.push_back(c.n);
+    return c;
 }
+// ... and judged: `who` names the operator in the messages
+int describe_call(const char* who, const LeleTensor* input, const QW& w, QCall* c) {
+    LELE_REQUIRE(input->rank >= 2 && w.w->rank >= 2, "%s: rank >= 2 required", who);
+    *c = call_dims(input, w);
+    LELE_REQUIRE(c->k == c->kw, "%s: K mismatch (%lld vs %lld)", who, (long long)c->k, (long long)c->kw);
+    LELE_REQUIRE(c->ws_len >= 1, "%s: empty weight_scale", who);
+    LELE_REQUIRE(c->ws_len <= 1 || c->ws_len >= c->n, "%s: weight_scale has %lld entries for N=%lld", who, (long long)c->ws_len, (long long)c->n);
+    LELE_REQUIRE(c->blen == 0 || c->blen >= c->n, "%s: bias has %lld entries for N=%lld", who, (long long)c->blen, (long long)c->n);
+    return 0;
+}
+// an f32 residual of the result's shape [.., m, n] (leading unit dimensions aside): folded into the GEMM's store
+bool res_same_shape(const LeleTensor* input, int64_t n, const LeleTensor* t) {
+    int64_t on = n;
+    for (int i = 0; i + 1 < input->rank; ++i) on *= input->shape[i];
+    if (t->dtype != LELE_F32 || numel(t) != on || t->rank > input->rank) return false;
+    for (int d = 0; d < t->rank; ++d)
+        if (t->shape[t->rank - 1 - d] != (d == 0 ? n : input->shape[input->rank - 1 - d])) return false;
+    return true;
+}
+bool aligned16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
+// where dev_ptr will put a tensor, as far as alignment goes: a device tensor stays, anything else is staged on a 256-byte boundary
+const void* staged_addr(const LeleTensor* t) { return t->mem == LELE_MEM_DEVICE ? t->data : nullptr; }
+
 // a LayerNorm over the last axis that the caller wants behind the linear: done in the GEMM's launch where a workgroup holds whole
 // rows of the result (`done` says whether it was; the caller runs lele_hip_layer_norm otherwise)
 struct LnReq {
     const LeleTensor* g;
     const LeleTensor* b;
     float eps;
-    LeleBuf* out;
+    LeleBuf* out;  // never the linear's own `out` (every entry point that takes a LayerNorm requires two buffers)
     bool done = false;
-    // optionally the FSMN memory block as the first residual (lele_hip_sanm_out_block): only honoured together with the LayerNorm,
-    // `done` then covers both
-    const LeleTensor* fs_x = nullptr;   // [B, T, P]
-    const LeleTensor* fs_w = nullptr;   // [512, 1, 11]
-    const LeleTensor* fs_b = nullptr;
+    // optionally the FSMN memory block as the first residual, COMPUTED IN THE KERNEL (lele_hip_sanm_out_block): the request then
+    // carries no res1, and is only made where fql_route answers AsLnFsmn
+    const LeleTensor *fs_x = nullptr, *fs_w = nullptr, *fs_b = nullptr;  // [B, T, P], [512, 1, 11], 512 or none
     int64_t fs_pl = 0, fs_off = 0;
 };
-static int fql_impl(LeleCtx* ctx, const LeleTensor* input, const LeleTensor* weight_int8, const LeleTensor* weight_scale,
-                    const LeleTensor* weight_zero, const LeleTensor* bias, int apply_relu, const LeleTensor* res1,
-                    const LeleTensor* res2, LeleBuf* out, int64_t* out_shape, int32_t* out_rank, LnReq* ln = nullptr) {
-    LELE_REQUIRE(ctx && input && weight_int8 && weight_scale && out, "fused_quantized_linear: NULL argument");
-    LELE_REQUIRE(input->rank >= 2 && weight_int8->rank >= 2, "fused_quantized_linear: rank >= 2 required");
-    LELE_HIP_CHECK(hipSetDevice(ctx->device));
-    const int64_t m = input->shape[input->rank - 2], k = input->shape[input->rank - 1];
-    const int64_t kw = weight_int8->shape[weight_int8->rank - 2], n = weight_int8->shape[weight_int8->rank - 1];
-    LELE_REQUIRE(k == kw, "fused_quantized_linear: K mismatch (%lld vs %lld)", (long long)k, (long long)kw);
-    int64_t batch = 1;
-    for (int i = 0; i + 2 < input->rank; ++i) batch *= input->shape[i];
-    const int64_t ws_len = numel(weight_scale);
-    LELE_REQUIRE(ws_len >= 1, "fused_quantized_linear: empty weight_scale");
-    LELE_REQUIRE(ws_len <= 1 || ws_len >= n, "fused_quantized_linear: weight_scale has %lld entries for N=%lld",
-                 (long long)ws_len, (long long)n);
-    const int64_t blen = bias ? numel(bias) : 0;
-    LELE_REQUIRE(blen == 0 || blen >= n, "fused_quantized_linear: bias has %lld entries for N=%lld", (long long)blen,
-                 (long long)n);
-    std::vector<int64_t> shp(input->shape, input->shape + input->rank - 1);
-    shp.push_back(n);
-    const int64_t rows = batch * m;
-    LELE_TRY(out->reserve((size_t)rows * n * 4));
-    if (rows == 0 || n == 0) return set_shape_v(out_shape, out_rank, shp);
-    LELE_TRY(ctx->arena_reset());
-    const void *dx = nullptr, *dws = nullptr, *db = nullptr;
-    LELE_TRY(ctx->dev_ptr(input, &dx));
-    LELE_TRY(ctx->dev_ptr(weight_scale, &dws));
-    if (blen) LELE_TRY(ctx->dev_ptr(bias, &db));
-    const void *dr1 = nullptr, *dr2 = nullptr;
-    if (res1) LELE_TRY(ctx->dev_ptr(res1, &dr1));
-    if (res2) LELE_TRY(ctx->dev_ptr(res2, &dr2));
+struct QReq {  // what the caller wants around the product
+    int relu = 0;
+    const LeleTensor *res1 = nullptr, *res2 = nullptr;  // same-shape residuals (res_same_shape), added in this order
+    LnReq* ln = nullptr;
+};
+// one layer, validated and staged: what a route's body reads
+struct QLayer {
+    QCall c;
+    const LeleTensor* weight = nullptr;
+    const float *x = nullptr, *ws = nullptr, *bias = nullptr;  // x NULL: the layer's operand exists in i8 only; bias NULL: none
+    const float *res1 = nullptr, *res2 = nullptr;
     float wz = 0.0f;
-    LELE_TRY(weight_zero_of(ctx, weight_zero, &wz));
-    const float* partial = nullptr;
+    int relu = 0;
+    QParams* prm = nullptr;          // per slice, filled by whichever kernel reduces the range partials first
+    const float* partial = nullptr;  // {min, max} pairs of x, nblk a slice
     int nblk = 0;
-    find_partials(ctx, input, batch, m, k, &partial, &nblk);
-    void* prm = nullptr;
-    LELE_TRY(ctx->arena_alloc((size_t)batch * sizeof(QParams), &prm));
-    LELE_TRY(qprof_mark(ctx, 0));
-    if (!partial) LELE_TRY(launch_range(ctx, (const float*)dx, batch, m * k, (QParams*)prm, nullptr, nullptr, &partial, &nblk));
-    LELE_TRY(qprof_mark(ctx, 1));
-
-    LELE_REQUIRE(!(ln && ln->fs_x) || (as_fits(ctx, rows, n, k, dx) && rs_aligned(res2) && (((uintptr_t)out->data) & 15) == 0),
-                 "internal: the memory block was requested on a route that cannot compute it");
-    // ---- register-stationary route (igemm_rs.h): rows -> i8 in fragment order, then the barrier-free GEMM
-    if (const int kprs = rs_kp(k); rs_fits(ctx, rows, n, kprs) && rs_aligned(res1) && rs_aligned(res2) && (((uintptr_t)out->data) & 15) == 0) {
-        FragW fw;
-        LELE_TRY(frag_weights_of(ctx, weight_int8, (int)k, (int)n, kprs, &fw));
-        const int64_t nrt = (rows + 31) / 32;
-        void *af = nullptr, *rs = nullptr;
-        // K = 512 exactly, 16-byte aligned rows: the GEMM's loader waves quantise the f32 rows themselves (igemm_rs.h, FQ) with
-        // parameters they reduce from the {min, max} partials at the start of the kernel: nothing is launched in front of it
-        const bool fq = rs_fq(k, dx) && rs_max_slices(ctx, rows, n, m) <= RS_MAXSL;
-        if (!fq) {
-            LELE_TRY(ctx->arena_alloc((size_t)nrt * kprs * 32, &af));
-            if (kprs == 512) LELE_TRY(ctx->arena_alloc((size_t)rows * 4, &rs));  // K = 2048: the GEMM sums the rows it loads anyway
-            LELE_TRY(launch_qrows_frag(ctx, (const float*)dx, rows, (int)k, kprs, (int)m, (QParams*)prm, (int8_t*)af, (int*)rs, partial, nblk, nullptr));
-        }
-        LELE_TRY(qprof_mark(ctx, 2));
-        IgemmEpi epi{(float*)out->data, rows, n, (int)m, (int)k, (const int*)rs, fw.col_sums, (const QParams*)prm, 0,
-                     (int)wz, (const float*)dws, (int)ws_len, blen ? (const float*)db : nullptr, apply_relu, (const float*)dr1,
-                     (const float*)dr2};
-        const int64_t nstat = nrt * ((n + 31) / 32);
-        if (kprs == 512 && batch == 1 && nstat <= 4096) {  // {min, max} per tile for a single-slice consumer (LeleBuf::rowstat kind 1)
-            LELE_TRY(out->reserve_rowstat(nstat));
-            if ((size_t)nstat <= out->rowstat_cap) epi.blockstat = out->rowstat;
-        }
-        RsFq fqa;
-        if (fq) fqa.x = (const float*)dx, fqa.partial = partial, fqa.nblk = nblk;
-        if (kprs == 512) LELE_TRY(launch_rs(ctx, 0, (const int8_t*)af, fw.wf, rows, (int)n, nullptr, epi, fqa));
-        else LELE_TRY(launch_rs_ks4(ctx, (const int8_t*)af, fw.wf, rows, (int)n, epi));
-        LELE_TRY(qprof_mark(ctx, 3));
-        if (epi.blockstat) {
-            out->rowstat_rows = nstat;
-            out->rowstat_len = rows * n;
-            out->rowstat_kind = 1;
-            out->rowstat_valid = true;
-        }
-        return set_shape_v(out_shape, out_rank, shp);
-    }
-
-    // ---- activations stationary (igemm_rs.h): few column tiles, K = 512 -- quantise and multiply in one kernel
-    if (as_fits(ctx, rows, n, k, dx) && rs_aligned(res1) && rs_aligned(res2) && (((uintptr_t)out->data) & 15) == 0) {
-        FragW fw;
-        LELE_TRY(frag_weights_of(ctx, weight_int8, (int)k, (int)n, 512, &fw));
-        LELE_TRY(qprof_mark(ctx, 2));
-        IgemmEpi epi{(float*)out->data, rows, n, (int)m, (int)k, nullptr, fw.col_sums, (const QParams*)prm, 0,
-                     (int)wz, (const float*)dws, (int)ws_len, blen ? (const float*)db : nullptr, apply_relu, (const float*)dr1,
-                     (const float*)dr2};
-        const int64_t nstat = ((rows + 31) / 32) * ((n + 31) / 32);
-        if (batch == 1 && nstat <= 4096) {
-            LELE_TRY(out->reserve_rowstat(nstat));
-            if ((size_t)nstat <= out->rowstat_cap) epi.blockstat = out->rowstat;
-        }
-        AsLn aln;
-        const bool fuse_ln = ln && as_ln_ok(ctx, rows, n, apply_relu, ln->g, ln->b) && ln->out != out;
-        LELE_REQUIRE(!(ln && ln->fs_x) || fuse_ln, "internal: the memory block was requested on a route that cannot compute it");
-        if (fuse_ln && ln->fs_x) {
-            const void *fx = nullptr, *fwp = nullptr, *fbp = nullptr;
-            LELE_TRY(ctx->dev_ptr(ln->fs_x, &fx));
-            LELE_TRY(ctx->dev_ptr(ln->fs_w, &fwp));
-            if (ln->fs_b) LELE_TRY(ctx->dev_ptr(ln->fs_b, &fbp));
-            aln.fs_x = (const float*)fx + ln->fs_off, aln.fs_pitch = (int)ln->fs_x->shape[2], aln.fs_w = (const float*)fwp;
-            aln.fs_b = (const float*)fbp, aln.fs_pl = (int)ln->fs_pl;
-        }
-        if (fuse_ln) {
-            const void *dg = nullptr, *dbeta = nullptr;
-            LELE_TRY(ctx->dev_ptr(ln->g, &dg));
-            LELE_TRY(ctx->dev_ptr(ln->b, &dbeta));
-            LELE_TRY(ln->out->reserve((size_t)rows * n * 4));
-            LELE_TRY(ln->out->reserve_rowstat(rows));
-            aln.g = (const float*)dg, aln.b = (const float*)dbeta, aln.eps = ln->eps, aln.out = (float*)ln->out->data;
-            aln.rowstat = (size_t)rows <= ln->out->rowstat_cap ? ln->out->rowstat : nullptr;
-            epi.out = (float*)out->data;  // (a first reserve of ln->out cannot move `out`: they are different buffers)
-        }
-        LELE_TRY(launch_as(ctx, (const float*)dx, fw.wf, rows, (int)n, partial, nblk, (QParams*)prm, epi, fuse_ln ? &aln : nullptr));
-        if (fuse_ln) {
-            ln->done = true;
-            if (aln.rowstat) {   // as lele_hip_layer_norm leaves them: one {min, max} pair per row
-                ln->out->rowstat_rows = rows;
-                ln->out->rowstat_len = n;
-                ln->out->rowstat_kind = 0;
-                ln->out->rowstat_valid = true;
-            }
-        }
-        LELE_TRY(qprof_mark(ctx, 3));
-        if (epi.blockstat) {
-            out->rowstat_rows = nstat;
-            out->rowstat_len = rows * n;
-            out->rowstat_kind = 1;
-            out->rowstat_valid = true;
-        }
-        return set_shape_v(out_shape, out_rank, shp);
-    }
-
-    // ---- three-kernel chain: rows -> i8 (+ row sums) in HBM, then the tiled i8 GEMM
-    const int kp = (int)((k + 15) & ~int64_t(15));
-    PackedW pw;
-    LELE_TRY(packed_weights_of(ctx, weight_int8, nullptr, 1, (int)k, (int)n, kp, &pw));
-    void *aq = nullptr, *rs = nullptr;
-    LELE_TRY(ctx->arena_alloc((size_t)rows * kp, &aq));
-    LELE_TRY(ctx->arena_alloc((size_t)rows * 4, &rs));
-    if (rows <= 2048 || (kp <= 2048 && !lab_int("LELE_HIP_QROWS_STREAM", 0)))  // the whole row in flight at once (8 x 16 bytes per lane)
-        hipLaunchKernelGGL((qrows_kernel<0, true>), dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, ctx->stream, (const float*)dx,
-                           rows, (int)k, kp, (int)m, (QParams*)prm, (int8_t*)aq, (int*)rs, partial, nblk, (unsigned*)nullptr, (int*)nullptr);
-    else
-        hipLaunchKernelGGL((qrows_kernel<0, false>), dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, ctx->stream, (const float*)dx,
-                           rows, (int)k, kp, (int)m, (QParams*)prm, (int8_t*)aq, (int*)rs, partial, nblk, (unsigned*)nullptr, (int*)nullptr);
-    LELE_TRY(qprof_mark(ctx, 2));
-    IgemmEpi epi{(float*)out->data, rows, n, (int)m, (int)k, (const int*)rs, pw.col_sums, (const QParams*)prm, 0,
-                 (int)wz, (const float*)dws, (int)ws_len, blen ? (const float*)db : nullptr, apply_relu, (const float*)dr1,
-                 (const float*)dr2};
-    // small-problem kernel: publish one {min, max} pair per workgroup next to the result (for the linear that may follow)
-    const int64_t b64 = ((rows + 63) / 64) * ((n + 63) / 64), nstat = ((rows + 31) / 32) * ((n + 31) / 32);
-    const bool stats = b64 < 2 * (int64_t)ctx->num_cus && nstat <= 4096;
-    if (stats) {
-        LELE_TRY(out->reserve_rowstat(nstat));
-        if ((size_t)nstat <= out->rowstat_cap) epi.blockstat = out->rowstat;
-    }
-    LELE_TRY(launch_igemm(ctx, (const int8_t*)aq, pw.wt, rows, (int)n, kp, 0, (int)m, epi));
-    LELE_TRY(qprof_mark(ctx, 3));
-    if (epi.blockstat) {
-        out->rowstat_rows = nstat;
-        out->rowstat_len = rows * n;
-        out->rowstat_kind = 1;
-        out->rowstat_valid = true;
-    }
-    return set_shape_v(out_shape, out_rank, shp);
+    LeleBuf* out = nullptr;
+};
+IgemmEpi make_epi(const QLayer& l, float* out, const int* row_sums, const int* col_sums) {
+    return IgemmEpi{out, l.c.rows, l.c.n, (int)l.c.m, (int)l.c.k, row_sums, col_sums, l.prm, 0, (int)l.wz, l.ws, (int)l.c.ws_len, l.bias, l.relu,
+                    l.res1, l.res2};
 }
 
-int lele_hip_fused_quantized_linear(LeleCtx* ctx, const LeleTensor* input, const LeleTensor* weight_int8,
-                                    const LeleTensor* weight_scale, const LeleTensor* weight_zero,
-                                    const LeleTensor* bias, int apply_relu, LeleBuf* out, int64_t* out_shape,
-                                    int32_t* out_rank) {
-    return fql_impl(ctx, input, weight_int8, weight_scale, weight_zero, bias, apply_relu, nullptr, nullptr, out, out_shape, out_rank);
+// {min, max} of every 32 x 32 tile of the result, left next to it for a single-slice consumer (LeleBuf::rowstat kind 1, at most 4096
+// pairs): attached before the launch, published after it
+int64_t tiles32(const QCall& c) { return ((c.rows + 31) / 32) * ((c.n + 31) / 32); }
+int attach_blockstat(LeleBuf* out, const QCall& c, IgemmEpi* epi) {
+    const int64_t nstat = tiles32(c);
+    if (nstat > 4096) return 0;
+    LELE_TRY(out->reserve_rowstat(nstat));
+    if ((size_t)nstat <= out->rowstat_cap) epi->blockstat = out->rowstat;
+    return 0;
+}
+void publish_blockstat(LeleBuf* out, const QCall& c, const IgemmEpi& epi) {
+    if (!epi.blockstat) return;
+    out->rowstat_rows = tiles32(c), out->rowstat_len = c.rows * c.n;
+    out->rowstat_kind = 1, out->rowstat_valid = true;
+}
+
+// the LayerNorm epilogue of igemm_as_kernel / igemm_ask_kernel: whole 512-wide rows in a workgroup, no ReLU, f32 scale / bias of >= 512
+bool as_ln_ok(LeleCtx* ctx, int64_t rows, int64_t n, int apply_relu, const LeleTensor* g, const LeleTensor* b) {
+    return env_int("LELE_HIP_LN_FUSED", 1) != 0 && n == 512 && !apply_relu && as_two(ctx, rows, (int)n) && g->dtype == LELE_F32 &&
+           b->dtype == LELE_F32 && numel(g) >= 512 && numel(b) >= 512;
+}
+// the request as the kernel takes it: scale and bias staged, ln->out sized, room for its row statistics
+int attach_ln(LeleCtx* ctx, const LnReq* ln, const QCall& c, AsLn* aln) {
+    const void *dg = nullptr, *dbeta = nullptr;
+    LELE_TRY(ctx->dev_ptr(ln->g, &dg));
+    LELE_TRY(ctx->dev_ptr(ln->b, &dbeta));
+    LELE_TRY(ln->out->reserve((size_t)c.rows * c.n * 4));
+    LELE_TRY(ln->out->reserve_rowstat(c.rows));
+    aln->g = (const float*)dg, aln->b = (const float*)dbeta, aln->eps = ln->eps, aln->out = (float*)ln->out->data;
+    aln->rowstat = (size_t)c.rows <= ln->out->rowstat_cap ? ln->out->rowstat : nullptr;
+    return 0;
+}
+// ... and after the launch: as lele_hip_layer_norm leaves them, one {min, max} pair per row
+void publish_ln(LnReq* ln, const QCall& c, const AsLn& aln) {
+    ln->done = true;
+    if (!aln.rowstat) return;
+    ln->out->rowstat_rows = c.rows, ln->out->rowstat_len = c.n;
+    ln->out->rowstat_kind = 0, ln->out->rowstat_valid = true;
+}
+// ... and where no kernel took it: the call it stands for, on the sum in `out`
+int finish_ln(LeleCtx* ctx, const LnReq& ln, LeleBuf* out, const int64_t* sh, int32_t r) {
+    if (ln.done) return 0;
+    const LeleTensor x1{out->data, sh, r, LELE_F32, LELE_MEM_DEVICE};
+    int64_t sh2[LELE_MAX_RANK];
+    int32_t r2 = 0;
+    return lele_hip_layer_norm(ctx, &x1, ln.g, ln.b, -1, ln.eps, ln.out, sh2, &r2);
+}
+
+// rows -> i8 [rows][kp] + row sums in HBM, for the tiled kernels.  prefetch: the whole row in flight at once (8 x 16 bytes per lane)
+int launch_qrows(LeleCtx* ctx, bool prefetch, const float* x, int64_t rows, int k, int kp, int m, QParams* prm, int8_t* aq, int* rs,
+                 const float* partial, int nblk, unsigned* zero_slice, int* zero_rows, const int* row_seg) {
+    auto kern = prefetch ? qrows_kernel<0, true> : qrows_kernel<0, false>;
+    hipLaunchKernelGGL(kern, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, ctx->stream, x, rows, k, kp, m, prm, aq, rs, partial, nblk, zero_slice,
+                       zero_rows, row_seg);
+    LELE_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------ the dense linear: route, then body
+enum class QRoute {
+    RsFq,      // register-stationary (igemm_rs_kernel), its loader waves quantise the f32 rows: one launch
+    RsFrag,    // register-stationary behind qrows_frag_kernel (K < 512 padded, or rows not 16-byte aligned)
+    As,        // activation-stationary (igemm_as_kernel): quantise and multiply in one kernel
+    AsLn,      // ... with the requested LayerNorm in its epilogue
+    AsLnFsmn,  // ... and the FSMN memory block computed in the kernel as the first residual
+    Tiled,     // rows -> i8 in HBM (qrows_kernel), then the tiled i8 GEMM (launch_igemm)
+};
+// The one place that chooses.  dx: the staged input; dout: out->data after its reserve (the one-pass kernels move 16 bytes at a
+// time).  A LayerNorm that the chosen kernel cannot take is left to the caller (LnReq::done stays false).
+QRoute fql_route(LeleCtx* ctx, const QCall& c, const QReq& rq, const void* dx, const void* dout) {
+    const bool aligned = rs_aligned(rq.res1) && rs_aligned(rq.res2) && aligned16(dout);
+    if (aligned && rs_fits(ctx, c.rows, c.n, c.k))
+        // K = 512 exactly, 16-byte aligned rows: the loaders reduce their parameters from the {min, max} partials, nothing runs in front
+        return rs_fq(c.k, dx) && rs_max_slices(ctx, c.rows, c.n, c.m) <= RS_MAXSL ? QRoute::RsFq : QRoute::RsFrag;
+    if (aligned && as_fits(ctx, c.rows, c.n, c.k, dx)) {
+        if (!rq.ln || !as_ln_ok(ctx, c.rows, c.n, rq.relu, rq.ln->g, rq.ln->b)) return QRoute::As;
+        return rq.ln->fs_x ? QRoute::AsLnFsmn : QRoute::AsLn;
+    }
+    return QRoute::Tiled;
+}
+
+// rows -> i8 in fragment order (unless the loaders do it), then the barrier-free GEMM (igemm_rs.h)
+int run_rs(LeleCtx* ctx, const QLayer& l, bool fq) {
+    const QCall& c = l.c;
+    FragW fw;
+    LELE_TRY(frag_weights_of(ctx, l.weight, (int)c.k, (int)c.n, 512, &fw));
+    void *af = nullptr, *rs = nullptr;
+    RsFq fqa;
+    if (fq) {
+        fqa.x = l.x, fqa.partial = l.partial, fqa.nblk = l.nblk;
+    } else {
+        LELE_TRY(ctx->arena_alloc((size_t)((c.rows + 31) / 32) * 512 * 32, &af));
+        LELE_TRY(ctx->arena_alloc((size_t)c.rows * 4, &rs));
+        LELE_TRY(launch_qrows_frag(ctx, l.x, c.rows, (int)c.k, (int)c.m, l.prm, (int8_t*)af, (int*)rs, l.partial, l.nblk, nullptr));
+    }
+    LELE_TRY(qprof_mark(ctx, 2));
+    IgemmEpi epi = make_epi(l, (float*)l.out->data, (const int*)rs, fw.col_sums);
+    if (c.batch == 1) LELE_TRY(attach_blockstat(l.out, c, &epi));
+    LELE_TRY(launch_rs(ctx, 0, (const int8_t*)af, fw.wf, c.rows, (int)c.n, nullptr, epi, fqa));
+    LELE_TRY(qprof_mark(ctx, 3));
+    publish_blockstat(l.out, c, epi);
+    return 0;
+}
+
+// few column tiles, K = 512: quantise and multiply in one kernel, with the LayerNorm (and the memory block) where the route says so
+int run_as(LeleCtx* ctx, const QLayer& l, QRoute route, LnReq* ln) {
+    const QCall& c = l.c;
+    FragW fw;
+    LELE_TRY(frag_weights_of(ctx, l.weight, (int)c.k, (int)c.n, 512, &fw));
+    LELE_TRY(qprof_mark(ctx, 2));
+    IgemmEpi epi = make_epi(l, (float*)l.out->data, nullptr, fw.col_sums);
+    if (c.batch == 1) LELE_TRY(attach_blockstat(l.out, c, &epi));
+    AsLn aln;
+    if (route == QRoute::AsLnFsmn) {  // the kernel's res1 is the memory block of fs_x (epi.res1 is not read), epi.res2 the caller's residual
+        const void *fx = nullptr, *fwp = nullptr, *fbp = nullptr;
+        LELE_TRY(ctx->dev_ptr(ln->fs_x, &fx));
+        LELE_TRY(ctx->dev_ptr(ln->fs_w, &fwp));
+        if (ln->fs_b) LELE_TRY(ctx->dev_ptr(ln->fs_b, &fbp));
+        aln.fs_x = (const float*)fx + ln->fs_off, aln.fs_pitch = (int)ln->fs_x->shape[2], aln.fs_w = (const float*)fwp;
+        aln.fs_b = (const float*)fbp, aln.fs_pl = (int)ln->fs_pl;
+    }
+    const bool fuse_ln = route != QRoute::As;
+    if (fuse_ln) LELE_TRY(attach_ln(ctx, ln, c, &aln));  // (a first reserve of ln->out cannot move `out`: they are different buffers)
+    LELE_TRY(launch_as(ctx, l.x, fw.wf, c.rows, (int)c.n, l.partial, l.nblk, l.prm, epi, fuse_ln ? &aln : nullptr));
+    if (fuse_ln) publish_ln(ln, c, aln);
+    LELE_TRY(qprof_mark(ctx, 3));
+    publish_blockstat(l.out, c, epi);
+    return 0;
+}
+
+// three-kernel chain: rows -> i8 (+ row sums) in HBM, then the tiled i8 GEMM
+int run_tiled(LeleCtx* ctx, const QLayer& l) {
+    const QCall& c = l.c;
+    const int kp = (int)((c.k + 15) & ~int64_t(15));
+    PackedW pw;
+    LELE_TRY(packed_weights_of(ctx, l.weight, nullptr, 1, (int)c.k, (int)c.n, kp, &pw));
+    void *aq = nullptr, *rs = nullptr;
+    LELE_TRY(ctx->arena_alloc((size_t)c.rows * kp, &aq));
+    LELE_TRY(ctx->arena_alloc((size_t)c.rows * 4, &rs));
+    LELE_TRY(launch_qrows(ctx, c.rows <= 2048 || (kp <= 2048 && !lab_int("LELE_HIP_QROWS_STREAM", 0)), l.x, c.rows, (int)c.k, kp, (int)c.m, l.prm,
+                          (int8_t*)aq, (int*)rs, l.partial, l.nblk, nullptr, nullptr, nullptr));
+    LELE_TRY(qprof_mark(ctx, 2));
+    IgemmEpi epi = make_epi(l, (float*)l.out->data, (const int*)rs, pw.col_sums);
+    // small-problem kernel: publish one {min, max} pair per workgroup next to the result (for the linear that may follow)
+    if (((c.rows + 63) / 64) * ((c.n + 63) / 64) < 2 * (int64_t)ctx->num_cus) LELE_TRY(attach_blockstat(l.out, c, &epi));
+    LELE_TRY(launch_igemm(ctx, (const int8_t*)aq, pw.wt, c.rows, (int)c.n, kp, (int)c.m, epi));
+    LELE_TRY(qprof_mark(ctx, 3));
+    publish_blockstat(l.out, c, epi);
+    return 0;
+}
+
+// validate, reserve, stage, range pass, then the route's body.  The order is observable: the reserve clears the statistics `out`
+// published (it may be the producer of `input`'s) before find_partials looks for them.
+int fql_impl(LeleCtx* ctx, const LeleTensor* input, const QW& w, const QReq& rq, LeleBuf* out, int64_t* out_shape, int32_t* out_rank) {
+    LELE_REQUIRE(ctx && input && w.w && w.scale && out, "fused_quantized_linear: NULL argument");
+    QLayer l;
+    LELE_TRY(describe_call("fused_quantized_linear", input, w, &l.c));
+    const QCall& c = l.c;
+    LELE_HIP_CHECK(hipSetDevice(ctx->device));
+    LELE_TRY(out->reserve((size_t)c.rows * c.n * 4));
+    if (c.rows == 0 || c.n == 0) return set_shape_v(out_shape, out_rank, c.shp);
+    LELE_TRY(ctx->arena_reset());
+    const void *dx = nullptr, *dws = nullptr, *db = nullptr, *dr1 = nullptr, *dr2 = nullptr;
+    LELE_TRY(ctx->dev_ptr(input, &dx));
+    LELE_TRY(ctx->dev_ptr(w.scale, &dws));
+    if (c.blen) LELE_TRY(ctx->dev_ptr(w.bias, &db));
+    if (rq.res1) LELE_TRY(ctx->dev_ptr(rq.res1, &dr1));
+    if (rq.res2) LELE_TRY(ctx->dev_ptr(rq.res2, &dr2));
+    LELE_TRY(first_scalar_of(ctx, w.zero, &l.wz));
+    find_partials(ctx, input, c.batch, c.m, c.k, &l.partial, &l.nblk);
+    void* prm = nullptr;
+    LELE_TRY(ctx->arena_alloc((size_t)c.batch * sizeof(QParams), &prm));
+    l.weight = w.w, l.x = (const float*)dx, l.ws = (const float*)dws, l.bias = (const float*)db, l.relu = rq.relu;
+    l.res1 = (const float*)dr1, l.res2 = (const float*)dr2, l.prm = (QParams*)prm, l.out = out;
+    LELE_TRY(qprof_mark(ctx, 0));
+    if (!l.partial) LELE_TRY(launch_range(ctx, l.x, c.batch, c.m * c.k, l.prm, nullptr, nullptr, &l.partial, &l.nblk));
+    LELE_TRY(qprof_mark(ctx, 1));
+    const QRoute route = fql_route(ctx, c, rq, dx, out->data);
+    switch (route) {
+        case QRoute::RsFq:
+        case QRoute::RsFrag: LELE_TRY(run_rs(ctx, l, route == QRoute::RsFq)); break;
+        case QRoute::As:
+        case QRoute::AsLn:
+        case QRoute::AsLnFsmn: LELE_TRY(run_as(ctx, l, route, rq.ln)); break;
+        case QRoute::Tiled: LELE_TRY(run_tiled(ctx, l)); break;
+    }
+    return set_shape_v(out_shape, out_rank, c.shp);
 }
 
 // row -> segment map behind the offsets, in one table: [int64 off[count + 1]][int row_seg[R]]
-static void build_rowseg(const void* arg, std::vector<char>& blob) {
+void build_rowseg(const void* arg, std::vector<char>& blob) {
     const auto& a = *(const std::pair<const int64_t*, int64_t>*)arg;
     const int64_t* off = a.first;
     const int64_t count = a.second, r = off[count];
@@ -1591,6 +1653,206 @@ static void build_rowseg(const void* arg, std::vector<char>& blob) {
     int* rs = (int*)(blob.data() + (size_t)(count + 1) * 8);
     for (int64_t i = 0; i < count; ++i)
         for (int64_t row = off[i]; row < off[i + 1]; ++row) rs[row] = (int)i;
+}
+
+// can igemm_as_kernel compute depthwise_conv1d_tlc(v_src, .., add_input = 1) of the projection's rows itself: v_src [B, T, P] with B * T
+// the projection's rows and T its slice length, 512 channels from a 16-byte aligned offset, k = 11 with the output as long as the input
+bool fsmn_fits(const QCall& c, const LeleTensor* v_src, const LeleTensor* fsmn_w, const LeleTensor* fsmn_bias, int64_t x_offset,
+               int64_t pad_left, int64_t pad_right) {
+    return v_src->rank == 3 && v_src->dtype == LELE_F32 && fsmn_w->rank == 3 && fsmn_w->dtype == LELE_F32 && fsmn_w->shape[0] == 512 &&
+           fsmn_w->shape[1] == 1 && fsmn_w->shape[2] == 11 && v_src->shape[0] * v_src->shape[1] == c.rows && v_src->shape[1] == c.m && c.m >= 32 &&
+           x_offset >= 0 && x_offset % 4 == 0 && x_offset + 512 <= v_src->shape[2] && v_src->shape[2] % 4 == 0 && rs_aligned(v_src) &&
+           pad_left == 5 && pad_right == 5 && (!fsmn_bias || (fsmn_bias->dtype == LELE_F32 && numel(fsmn_bias) >= 512)) &&
+           v_src->shape[2] * c.rows < (int64_t(1) << 30);
+}
+
+// ------------------------------------------------------------------------------------------ the feed-forward block: route, then body
+enum class FfnRoute {
+    Unfused,  // the two calls it stands for, an f32 hidden layer between them
+    Rs,       // register-stationary: K = 512 into exactly 2048 hidden columns, written as i8 in the second product's fragment order
+    Tiled,    // the hidden layer's product twice on the tiled kernel (range, then quantise), the second GEMM on its i8 rows
+};
+// c1: the first layer as call_dims gives it (nothing validated yet: what does not fit the fused forms runs the two calls, which raise)
+FfnRoute ffn_route(LeleCtx* ctx, const LeleTensor* input, const QCall& c1, int64_t k2, int64_t n2, const LeleTensor* res1, const LeleTensor* res2) {
+    const int64_t rows = c1.rows, n1 = c1.n;
+    if (env_int("LELE_HIP_FFN_FUSED", 1) == 0 || c1.kw != c1.k || k2 != n1 || rows >= (int64_t(1) << 31) || !c1.lens_ok() || n2 < 1)
+        return FfnRoute::Unfused;
+    // (the second product's threshold is ONE tile per CU: at one 30 s utterance -- 16 x 16 tiles -- the fused block replaces ffn1 with an f32
+    // hidden layer | row quantisation | small-problem GEMM: a configs[2] forward 5.33 -> 5.05 ms, round 6)
+    const bool rs = pads_to_512(c1.k) && n1 == 2048 && rs_enabled(ctx, rows, n1) && rs_enabled(ctx, rows, n2, 1) && rs_aligned(res1) && rs_aligned(res2);
+    // tiled: a hidden layer of whole 128-column tiles (= whole SIMD bodies of its quantiser), slices of at least one tile of rows,
+    // enough tiles to fill the chip
+    const bool tiled = n1 % 128 == 0 && c1.m >= 128 && ((rows + 127) / 128) * (n1 / 128) >= 2 * (int64_t)ctx->num_cus;
+    if (!rs && !tiled) return FfnRoute::Unfused;
+    if (res1 && !(res_same_shape(input, n2, res1) && (!res2 || res_same_shape(input, n2, res2)))) return FfnRoute::Unfused;
+    return rs ? FfnRoute::Rs : FfnRoute::Tiled;
+}
+
+// the second product of the register-stationary form
+enum class FfnSecond {
+    Ks4,    // one column tile a workgroup over a range of row tiles (igemm_rs_ks4_kernel)
+    Ask,    // one row tile a workgroup with all 512 columns (igemm_ask_kernel): lab only
+    AskLn,  // ... and the requested LayerNorm in its epilogue
+};
+FfnSecond ffn_second(LeleCtx* ctx, const QCall& c2, int relu2, const LnReq* ln, const void* dout) {
+    if (!ask_fits(ctx, c2.rows, c2.n, c2.k) || !aligned16(dout)) return FfnSecond::Ks4;
+    if (ln && as_ln_ok(ctx, c2.rows, c2.n, relu2, ln->g, ln->b)) return FfnSecond::AskLn;
+#ifdef LELE_HIP_LAB
+    if (lab_int("LELE_HIP_IGEMM_ASK_ALWAYS", 0) != 0) return FfnSecond::Ask;
+#endif
+    return FfnSecond::Ks4;
+}
+
+int ffn_unfused(LeleCtx* ctx, const LeleTensor* input, const QW& w1, const QW& w2, const QReq& rq, LeleBuf* out, int64_t* out_shape, int32_t* out_rank) {
+    LeleBuf* hid = nullptr;
+    LELE_TRY(ctx->tmp_buf(2, &hid));
+    int64_t sh[LELE_MAX_RANK];
+    int32_t r = 0;
+    LELE_TRY(fql_impl(ctx, input, w1, QReq{1}, hid, sh, &r));
+    LeleTensor h{hid->data, sh, r, LELE_F32, LELE_MEM_DEVICE};
+    if (rq.res1) return lele_hip_fused_quantized_linear_residual(ctx, &h, w2.w, w2.scale, w2.zero, w2.bias, rq.relu, rq.res1, rq.res2, out, out_shape, out_rank);
+    return fql_impl(ctx, &h, w2, QReq{rq.relu}, out, out_shape, out_rank);
+}
+
+// l1.partial: the {min, max} pairs of the input; both layers' parameters are reduced inside the kernels
+int ffn_rs(LeleCtx* ctx, const QLayer& l1, const QLayer& l2, LnReq* ln) {
+    const QCall &c1 = l1.c, &c2 = l2.c;
+    const int64_t rows = c1.rows, nrt = (rows + 31) / 32;
+    FragW fw1, fw2;
+    LELE_TRY(frag_weights_of(ctx, l1.weight, (int)c1.k, (int)c1.n, 512, &fw1));
+    LELE_TRY(frag_weights_of(ctx, l2.weight, (int)c2.k, (int)c2.n, 2048, &fw2));
+    void *af1 = nullptr, *rs1 = nullptr, *hid = nullptr, *hmax = nullptr;
+    // both passes of the first product quantise the f32 rows in their loader waves, with parameters reduced inside the kernels; the
+    // range pass leaves four maxima a workgroup (plain stores: nothing to clear) which the quantise pass's loaders reduce
+    const bool fq = rs_fq(c1.k, l1.x) && rs_max_slices(ctx, rows, c1.n, c1.m) <= 4;
+    LELE_TRY(ctx->arena_alloc((size_t)nrt * 2048 * 32, &hid));
+    LELE_TRY(ctx->arena_alloc((size_t)c1.batch * 4, &hmax));
+    RsFq fqa;
+    if (fq) {
+        int ncb = 0, nrr = 0;
+        rs_grid(ctx, rows, c1.n, &ncb, &nrr);
+        void* hpart = nullptr;
+        LELE_TRY(ctx->arena_alloc((size_t)ncb * nrr * 16, &hpart));
+        fqa.x = l1.x, fqa.partial = l1.partial, fqa.nblk = l1.nblk, fqa.hpart = (unsigned*)hpart;
+        fqa.sync = rs_sync_counters(ctx, rows, c1.n);
+    } else {
+        LELE_TRY(ctx->arena_alloc((size_t)nrt * 512 * 32, &af1));
+        LELE_TRY(ctx->arena_alloc((size_t)rows * 4, &rs1));
+        // rows -> i8 for the first product; the same launch clears the per-slice maxima the range pass adds into
+        LELE_TRY(launch_qrows_frag(ctx, l1.x, rows, (int)c1.k, (int)c1.m, l1.prm, (int8_t*)af1, (int*)rs1, l1.partial, l1.nblk, (unsigned*)hmax));
+    }
+    LELE_TRY(qprof_mark(ctx, 2));
+    // (tests) LELE_HIP_FFN_ONE_LAUNCH=2: fail instead of falling back to the two launches, so that a test of the one-launch form tests it
+    LELE_REQUIRE(env_int("LELE_HIP_FFN_ONE_LAUNCH", 1) != 2 || fqa.sync,
+                 "fused_ffn_quantized: LELE_HIP_FFN_ONE_LAUNCH=2, but this call cannot take the one-launch form (K = 512 exactly, 16-byte aligned "
+                 "rows, at most 4 slices and %d row tiles a workgroup, lane 0 of the only context of the device, counters made before a capture)",
+                 RS_NS_BOTH);
+    IgemmEpi e1 = make_epi(l1, nullptr, (const int*)rs1, fw1.col_sums);
+    e1.slice_max = (unsigned*)hmax;
+    if (fqa.sync) {  // both passes in one launch (igemm_rs.h, EM 3)
+        e1.q_prm = l2.prm;
+        LELE_TRY(launch_rs(ctx, 3, nullptr, fw1.wf, rows, (int)c1.n, (int8_t*)hid, e1, fqa));
+    } else {
+        LELE_TRY(launch_rs(ctx, 1, (const int8_t*)af1, fw1.wf, rows, (int)c1.n, nullptr, e1, fqa));   // range of the ReLU result per slice
+        e1.q_prm = l2.prm;
+        LELE_TRY(launch_rs(ctx, 2, (const int8_t*)af1, fw1.wf, rows, (int)c1.n, (int8_t*)hid, e1, fqa));  // the result again, as the next operand
+    }
+    const IgemmEpi e2 = make_epi(l2, (float*)l2.out->data, nullptr, fw2.col_sums);
+    const FfnSecond second = ffn_second(ctx, c2, l2.relu, ln, l2.out->data);
+    if (second == FfnSecond::Ks4) {
+        LELE_TRY(launch_rs_ks4(ctx, (const int8_t*)hid, fw2.wf, rows, (int)c2.n, e2));
+    } else {
+        AsLn aln;
+        if (second == FfnSecond::AskLn) LELE_TRY(attach_ln(ctx, ln, c2, &aln));
+        LELE_TRY(launch_ask(ctx, (const int8_t*)hid, fw2.wf, rows, e2, second == FfnSecond::AskLn ? &aln : nullptr));
+        if (second == FfnSecond::AskLn) publish_ln(ln, c2, aln);
+    }
+    return qprof_mark(ctx, 3);
+}
+
+int ffn_tiled(LeleCtx* ctx, const QLayer& l1, const QLayer& l2) {
+    const QCall &c1 = l1.c, &c2 = l2.c;
+    const int64_t rows = c1.rows;
+    const int kp1 = (int)((c1.k + 15) & ~int64_t(15)), kp2 = (int)c1.n;
+    PackedW pw1, pw2;
+    LELE_TRY(packed_weights_of(ctx, l1.weight, nullptr, 1, (int)c1.k, (int)c1.n, kp1, &pw1));
+    LELE_TRY(packed_weights_of(ctx, l2.weight, nullptr, 1, (int)c2.k, (int)c2.n, kp2, &pw2));
+    void *aq1 = nullptr, *rs1 = nullptr, *aq2 = nullptr, *rs2 = nullptr, *hmax = nullptr;
+    LELE_TRY(ctx->arena_alloc((size_t)rows * kp1, &aq1));
+    LELE_TRY(ctx->arena_alloc((size_t)rows * 4, &rs1));
+    LELE_TRY(ctx->arena_alloc((size_t)rows * kp2, &aq2));
+    LELE_TRY(ctx->arena_alloc((size_t)rows * 4, &rs2));
+    LELE_TRY(ctx->arena_alloc((size_t)c1.batch * 4, &hmax));
+    // rows -> i8 for the first GEMM; the same launch clears the accumulators of the two hidden-layer passes
+    LELE_TRY(launch_qrows(ctx, kp1 <= 2048 && !lab_int("LELE_HIP_QROWS_STREAM", 0), l1.x, rows, (int)c1.k, kp1, (int)c1.m, l1.prm, (int8_t*)aq1,
+                          (int*)rs1, l1.partial, l1.nblk, (unsigned*)hmax, (int*)rs2, nullptr));
+    LELE_TRY(qprof_mark(ctx, 2));
+    IgemmEpi e1 = make_epi(l1, nullptr, (const int*)rs1, pw1.col_sums);
+    e1.slice_max = (unsigned*)hmax;
+    LELE_TRY(launch_igemm_hidden(ctx, 1, (const int8_t*)aq1, pw1.wt, rows, (int)c1.n, kp1, (int)c1.m, e1));
+    e1.q_out = (int8_t*)aq2;
+    e1.q_rowsum = (int*)rs2;
+    e1.q_prm = l2.prm;
+    LELE_TRY(launch_igemm_hidden(ctx, 2, (const int8_t*)aq1, pw1.wt, rows, (int)c1.n, kp1, (int)c1.m, e1));
+    const IgemmEpi e2 = make_epi(l2, (float*)l2.out->data, (const int*)rs2, pw2.col_sums);
+    LELE_TRY(launch_igemm(ctx, (const int8_t*)aq2, pw2.wt, rows, (int)c2.n, kp2, (int)c1.m, e2));
+    return qprof_mark(ctx, 3);
+}
+
+/* Two quantised linears with a ReLU between them (the feed-forward block of a transformer layer):
+ *     out = fused_quantized_linear[_residual](fused_quantized_linear(input, W1.., relu = 1), W2.., relu2, res1, res2)
+ * bit for bit.  When the hidden layer is large the f32 hidden tensor is never stored: its product runs twice on the matrix cores
+ * (igemm_kernel EM 1: range only; EM 2: quantise with that range, i8 + row sums), then the second GEMM consumes the i8 rows. */
+int ffn_impl(LeleCtx* ctx, const LeleTensor* input, const QW& w1, const QW& w2, const QReq& rq, LeleBuf* out, int64_t* out_shape, int32_t* out_rank) {
+    LELE_REQUIRE(ctx && input && w1.w && w1.scale && w2.w && w2.scale && out, "fused_ffn_quantized: NULL argument");
+    LELE_REQUIRE(input->rank >= 2 && w1.w->rank >= 2 && w2.w->rank >= 2, "fused_ffn_quantized: rank >= 2 required");
+    LELE_REQUIRE(!rq.res2 || rq.res1, "fused_ffn_quantized: res2 without res1");
+    LELE_HIP_CHECK(hipSetDevice(ctx->device));
+    QLayer l1, l2;
+    l1.c = call_dims(input, w1);
+    const FfnRoute route = ffn_route(ctx, input, l1.c, w2.w->shape[w2.w->rank - 2], w2.w->shape[w2.w->rank - 1], rq.res1, rq.res2);
+    if (route == FfnRoute::Unfused) return ffn_unfused(ctx, input, w1, w2, rq, out, out_shape, out_rank);
+    // the second layer reads the hidden tensor [.., m, n1], which exists in i8 only
+    std::vector<int64_t> hshape(l1.c.shp);
+    const LeleTensor hidden{nullptr, hshape.data(), input->rank, LELE_F32, LELE_MEM_DEVICE};
+    LELE_TRY(describe_call("fused_ffn_quantized", &hidden, w2, &l2.c));
+    const QCall &c1 = l1.c, &c2 = l2.c;
+    LELE_TRY(out->reserve((size_t)c2.rows * c2.n * 4));
+    LELE_TRY(ctx->arena_reset());
+    const void *dx = nullptr, *dws1 = nullptr, *db1 = nullptr, *dws2 = nullptr, *db2 = nullptr, *dr1 = nullptr, *dr2 = nullptr;
+    LELE_TRY(ctx->dev_ptr(input, &dx));
+    LELE_TRY(ctx->dev_ptr(w1.scale, &dws1));
+    LELE_TRY(ctx->dev_ptr(w2.scale, &dws2));
+    if (c1.blen) LELE_TRY(ctx->dev_ptr(w1.bias, &db1));
+    if (c2.blen) LELE_TRY(ctx->dev_ptr(w2.bias, &db2));
+    if (rq.res1) LELE_TRY(ctx->dev_ptr(rq.res1, &dr1));
+    if (rq.res2) LELE_TRY(ctx->dev_ptr(rq.res2, &dr2));
+    LELE_TRY(first_scalar_of(ctx, w1.zero, &l1.wz));
+    LELE_TRY(first_scalar_of(ctx, w2.zero, &l2.wz));
+    find_partials(ctx, input, c1.batch, c1.m, c1.k, &l1.partial, &l1.nblk);
+    void *prm1 = nullptr, *prm2 = nullptr;
+    LELE_TRY(ctx->arena_alloc((size_t)c1.batch * sizeof(QParams), &prm1));
+    LELE_TRY(ctx->arena_alloc((size_t)c1.batch * sizeof(QParams), &prm2));
+    l1.weight = w1.w, l1.x = (const float*)dx, l1.ws = (const float*)dws1, l1.bias = (const float*)db1, l1.relu = 1, l1.prm = (QParams*)prm1;
+    l2.weight = w2.w, l2.ws = (const float*)dws2, l2.bias = (const float*)db2, l2.relu = rq.relu, l2.prm = (QParams*)prm2;
+    l2.res1 = (const float*)dr1, l2.res2 = (const float*)dr2, l2.out = out;
+    LELE_TRY(qprof_mark(ctx, 0));
+    if (!l1.partial) LELE_TRY(launch_range(ctx, l1.x, c1.batch, c1.m * c1.k, l1.prm, nullptr, nullptr, &l1.partial, &l1.nblk));
+    LELE_TRY(qprof_mark(ctx, 1));
+    if (route == FfnRoute::Rs) LELE_TRY(ffn_rs(ctx, l1, l2, rq.ln));
+    else LELE_TRY(ffn_tiled(ctx, l1, l2));
+    return set_shape_v(out_shape, out_rank, c2.shp);
+}
+
+}  // namespace
+
+extern "C" {
+
+int lele_hip_fused_quantized_linear(LeleCtx* ctx, const LeleTensor* input, const LeleTensor* weight_int8,
+                                    const LeleTensor* weight_scale, const LeleTensor* weight_zero,
+                                    const LeleTensor* bias, int apply_relu, LeleBuf* out, int64_t* out_shape,
+                                    int32_t* out_rank) {
+    return fql_impl(ctx, input, {weight_int8, weight_scale, weight_zero, bias}, QReq{apply_relu}, out, out_shape, out_rank);
 }
 
 /* Packed batch: every segment of input [R, K] is a batch slice of its own (quantization.rs:104-128).  Three things know about
@@ -1602,14 +1864,10 @@ int lele_hip_fused_quantized_linear_segments(LeleCtx* ctx, const LeleTensor* inp
     LELE_REQUIRE(ctx && input && weight_int8 && weight_scale && out, "fused_quantized_linear_segments: NULL argument");
     int64_t rows = 0, k = 0, tmax = 0;
     LELE_TRY(seg_offsets(input, row_offsets, count, &rows, &k, &tmax, "fused_quantized_linear_segments"));
-    LELE_REQUIRE(weight_int8->rank >= 2, "fused_quantized_linear: rank >= 2 required");
-    const int64_t kw = weight_int8->shape[weight_int8->rank - 2], n = weight_int8->shape[weight_int8->rank - 1];
-    LELE_REQUIRE(k == kw, "fused_quantized_linear: K mismatch (%lld vs %lld)", (long long)k, (long long)kw);
-    const int64_t ws_len = numel(weight_scale);
-    LELE_REQUIRE(ws_len >= 1, "fused_quantized_linear: empty weight_scale");
-    LELE_REQUIRE(ws_len <= 1 || ws_len >= n, "fused_quantized_linear: weight_scale has %lld entries for N=%lld", (long long)ws_len, (long long)n);
-    const int64_t blen = bias ? numel(bias) : 0;
-    LELE_REQUIRE(blen == 0 || blen >= n, "fused_quantized_linear: bias has %lld entries for N=%lld", (long long)blen, (long long)n);
+    QLayer l;  // input [R, K]: one "slice" of R rows, whose rows find their segment's parameters through row_seg
+    LELE_TRY(describe_call("fused_quantized_linear", input, {weight_int8, weight_scale, weight_zero, bias}, &l.c));
+    const QCall& c = l.c;
+    const int64_t n = c.n;
     LELE_REQUIRE(rows < (int64_t(1) << 31) && count < (int64_t(1) << 31), "fused_quantized_linear_segments: more than 2^31 rows or segments");
     LELE_HIP_CHECK(hipSetDevice(ctx->device));
     const void* tab = nullptr;
@@ -1619,7 +1877,7 @@ int lele_hip_fused_quantized_linear_segments(LeleCtx* ctx, const LeleTensor* inp
     }
     if (rows == 0 || n == 0 || k == 0) {
         LELE_TRY(out->reserve((size_t)rows * n * 4));
-        return set_shape(out_shape, out_rank, {rows, n});
+        return set_shape_v(out_shape, out_rank, c.shp);
     }
     const int64_t* doff = (const int64_t*)tab;
     const int* drowseg = (const int*)((const char*)tab + (size_t)(count + 1) * 8);
@@ -1627,9 +1885,8 @@ int lele_hip_fused_quantized_linear_segments(LeleCtx* ctx, const LeleTensor* inp
     const void *dx = nullptr, *dws = nullptr, *db = nullptr;
     LELE_TRY(ctx->dev_ptr(input, &dx));
     LELE_TRY(ctx->dev_ptr(weight_scale, &dws));
-    if (blen) LELE_TRY(ctx->dev_ptr(bias, &db));
-    float wz = 0.0f;
-    LELE_TRY(weight_zero_of(ctx, weight_zero, &wz));
+    if (c.blen) LELE_TRY(ctx->dev_ptr(bias, &db));
+    LELE_TRY(first_scalar_of(ctx, weight_zero, &l.wz));
     // 1. one range per segment: {min, max} partials only, which the row quantiser's waves reduce themselves (as in the dense chain: one
     // launch fewer).  Enough blocks for every thread of the LONGEST segment to stream ~4 float4, at most 128 pairs a segment (a row's
     // wave reads its segment's pairs in one trip); the surplus blocks of a shorter segment leave the neutral pair.
@@ -1637,10 +1894,11 @@ int lele_hip_fused_quantized_linear_segments(LeleCtx* ctx, const LeleTensor* inp
     void *prm = nullptr, *partial = nullptr;
     LELE_TRY(ctx->arena_alloc((size_t)count * sizeof(QParams), &prm));
     LELE_TRY(ctx->arena_alloc((size_t)count * nblk * 8, &partial));
+    l.x = (const float*)dx, l.ws = (const float*)dws, l.bias = (const float*)db, l.relu = apply_relu, l.prm = (QParams*)prm;
     LELE_TRY(qprof_mark(ctx, 0));
     for (int64_t c0 = 0; c0 < count; c0 += 65535) {  // grid.y limit
         const int64_t nc = std::min<int64_t>(65535, count - c0);
-        hipLaunchKernelGGL(qminmax_seg_kernel, dim3(nblk, (unsigned)nc), dim3(256), 0, ctx->stream, (const float*)dx, doff + c0, k,
+        hipLaunchKernelGGL(qminmax_seg_kernel, dim3(nblk, (unsigned)nc), dim3(256), 0, ctx->stream, l.x, doff + c0, k,
                            (float*)partial + c0 * nblk * 2);
     }
     LELE_TRY(qprof_mark(ctx, 1));
@@ -1654,22 +1912,15 @@ int lele_hip_fused_quantized_linear_segments(LeleCtx* ctx, const LeleTensor* inp
     // every fallible step is behind us: `out` is as it was until here (reserve clears any producer-side statistics of `out`;
     // those of `input` describe equal slices and are not read)
     LELE_TRY(out->reserve((size_t)rows * n * 4));
-    if (rows <= 2048 || kp <= 2048)  // as the dense chain chooses: the whole row in flight at once
-        hipLaunchKernelGGL((qrows_kernel<0, true>), dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, ctx->stream, (const float*)dx, rows, (int)k, kp,
-                           (int)rows, (QParams*)prm, (int8_t*)aq, (int*)rs, (const float*)partial, nblk, (unsigned*)nullptr, (int*)nullptr, drowseg);
-    else
-        hipLaunchKernelGGL((qrows_kernel<0, false>), dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, ctx->stream, (const float*)dx, rows, (int)k, kp,
-                           (int)rows, (QParams*)prm, (int8_t*)aq, (int*)rs, (const float*)partial, nblk, (unsigned*)nullptr, (int*)nullptr, drowseg);
+    LELE_TRY(launch_qrows(ctx, rows <= 2048 || kp <= 2048, l.x, rows, (int)k, kp, (int)rows, l.prm, (int8_t*)aq, (int*)rs, (const float*)partial,
+                          nblk, nullptr, nullptr, drowseg));
     LELE_TRY(qprof_mark(ctx, 2));
-    IgemmEpi epi{(float*)out->data, rows, n, (int)rows, (int)k, (const int*)rs, pw.col_sums, (const QParams*)prm, 0,
-                 (int)wz, (const float*)dws, (int)ws_len, blen ? (const float*)db : nullptr, apply_relu};
+    IgemmEpi epi = make_epi(l, (float*)out->data, (const int*)rs, pw.col_sums);
     epi.row_seg = drowseg;
-    LELE_TRY(launch_igemm(ctx, (const int8_t*)aq, pw.wt, rows, (int)n, kp, 0, (int)rows, epi));
+    LELE_TRY(launch_igemm(ctx, (const int8_t*)aq, pw.wt, rows, (int)n, kp, (int)rows, epi));
     LELE_TRY(qprof_mark(ctx, 3));
-    return set_shape(out_shape, out_rank, {rows, n});
+    return set_shape_v(out_shape, out_rank, c.shp);
 }
-
-int lele_hip_binary(LeleCtx* ctx, int op, const LeleTensor* a, const LeleTensor* b, LeleBuf* out, int64_t* out_shape, int32_t* out_rank);
 
 int lele_hip_fused_quantized_linear_residual(LeleCtx* ctx, const LeleTensor* input, const LeleTensor* weight_int8,
                                              const LeleTensor* weight_scale, const LeleTensor* weight_zero, const LeleTensor* bias,
@@ -1677,21 +1928,9 @@ int lele_hip_fused_quantized_linear_residual(LeleCtx* ctx, const LeleTensor* inp
                                              int64_t* out_shape, int32_t* out_rank) {
     LELE_REQUIRE(ctx && input && weight_int8 && res1 && out, "fused_quantized_linear_residual: NULL argument");
     LELE_REQUIRE(res1->dtype == LELE_F32 && (!res2 || res2->dtype == LELE_F32), "fused_quantized_linear_residual: f32 residuals required");
-    int64_t on = weight_int8->shape[weight_int8->rank - 1];
-    for (int i = 0; i + 1 < input->rank; ++i) on *= input->shape[i];
-    // same shape as the linear's result (leading unit dimensions aside): folded into the GEMM's store
-    auto same_shape = [&](const LeleTensor* t) {
-        if (numel(t) != on) return false;
-        const int r_lin = input->rank;
-        if (t->rank > r_lin) return false;  // a higher-rank residual changes the result's rank: the generic path
-        for (int d = 0; d < t->rank; ++d) {
-            const int64_t want = d == 0 ? weight_int8->shape[weight_int8->rank - 1] : input->shape[r_lin - 1 - d];
-            if (t->shape[t->rank - 1 - d] != want) return false;
-        }
-        return true;
-    };
-    if (same_shape(res1) && (!res2 || same_shape(res2)))
-        return fql_impl(ctx, input, weight_int8, weight_scale, weight_zero, bias, apply_relu, res1, res2, out, out_shape, out_rank);
+    const int64_t n = weight_int8->shape[weight_int8->rank - 1];
+    if (res_same_shape(input, n, res1) && (!res2 || res_same_shape(input, n, res2)))
+        return fql_impl(ctx, input, {weight_int8, weight_scale, weight_zero, bias}, QReq{apply_relu, res1, res2}, out, out_shape, out_rank);
     // broadcasting residuals: the node sequence this op stands for -- the plain linear, then one `add` per residual with full
     // numpy broadcasting (a residual may broadcast OUTWARD: intermediates go to library-owned temporaries, the last sum to `out`)
     int64_t sh[LELE_MAX_RANK];
@@ -1700,7 +1939,7 @@ int lele_hip_fused_quantized_linear_residual(LeleCtx* ctx, const LeleTensor* inp
     LeleBuf *t0 = nullptr, *t1 = nullptr;
     LELE_TRY(ctx->tmp_buf(0, &t0));
     LELE_TRY(ctx->tmp_buf(1, &t1));
-    LELE_TRY(fql_impl(ctx, input, weight_int8, weight_scale, weight_zero, bias, apply_relu, nullptr, nullptr, t0, sh, &r));
+    LELE_TRY(fql_impl(ctx, input, {weight_int8, weight_scale, weight_zero, bias}, QReq{apply_relu}, t0, sh, &r));
     LeleBuf* cur = t0;
     for (int i = 0; i < nres; ++i) {
         const LeleTensor* res = i == 0 ? res1 : res2;
@@ -1715,9 +1954,6 @@ int lele_hip_fused_quantized_linear_residual(LeleCtx* ctx, const LeleTensor* inp
     }
     return set_shape_v(out_shape, out_rank, std::vector<int64_t>(sh, sh + r));
 }
-
-int lele_hip_layer_norm(LeleCtx* ctx, const LeleTensor* x, const LeleTensor* scale, const LeleTensor* bias, int32_t axis, float epsilon,
-                        LeleBuf* out, int64_t* out_shape, int32_t* out_rank);
 
 /* x1 = fused_quantized_linear[_residual](input, W.., relu, res1, res2);  x1n = layer_norm(x1, ln_scale, ln_bias, axis = -1, epsilon)
  * -- a projection, the Adds behind it and the LayerNorm that reads their sum (norm.rs:226 -> avx/norm.rs:10-133), bit for bit the
@@ -1735,31 +1971,15 @@ int lele_hip_fused_quantized_linear_residual_ln(LeleCtx* ctx, const LeleTensor* 
     LnReq ln{ln_scale, ln_bias, epsilon, ln_out};
     int64_t sh[LELE_MAX_RANK];
     int32_t r = 0;
-    bool direct = true;   // same-shape residuals: the call that may normalise in its epilogue
-    if (res1) {
-        int64_t on = weight_int8->shape[weight_int8->rank - 1];
-        for (int i = 0; i + 1 < input->rank; ++i) on *= input->shape[i];
-        auto same_shape = [&](const LeleTensor* t) {
-            if (t->dtype != LELE_F32 || numel(t) != on || t->rank > input->rank) return false;
-            for (int d = 0; d < t->rank; ++d)
-                if (t->shape[t->rank - 1 - d] != (d == 0 ? weight_int8->shape[weight_int8->rank - 1] : input->shape[input->rank - 1 - d])) return false;
-            return true;
-        };
-        direct = same_shape(res1) && (!res2 || same_shape(res2));
-    }
-    if (direct) LELE_TRY(fql_impl(ctx, input, weight_int8, weight_scale, weight_zero, bias, apply_relu, res1, res2, out, sh, &r, &ln));
-    else LELE_TRY(lele_hip_fused_quantized_linear_residual(ctx, input, weight_int8, weight_scale, weight_zero, bias, apply_relu, res1, res2, out, sh, &r));
-    if (!ln.done) {
-        LeleTensor x1{out->data, sh, r, LELE_F32, LELE_MEM_DEVICE};
-        int64_t sh2[LELE_MAX_RANK];
-        int32_t r2 = 0;
-        LELE_TRY(lele_hip_layer_norm(ctx, &x1, ln_scale, ln_bias, -1, epsilon, ln_out, sh2, &r2));
-    }
+    const int64_t n = weight_int8->shape[weight_int8->rank - 1];
+    // same-shape residuals: the call that may normalise in its epilogue
+    if (!res1 || (res_same_shape(input, n, res1) && (!res2 || res_same_shape(input, n, res2))))
+        LELE_TRY(fql_impl(ctx, input, {weight_int8, weight_scale, weight_zero, bias}, QReq{apply_relu, res1, res2, &ln}, out, sh, &r));
+    else
+        LELE_TRY(lele_hip_fused_quantized_linear_residual(ctx, input, weight_int8, weight_scale, weight_zero, bias, apply_relu, res1, res2, out, sh, &r));
+    LELE_TRY(finish_ln(ctx, ln, out, sh, r));
     return set_shape_v(out_shape, out_rank, std::vector<int64_t>(sh, sh + r));
 }
-
-int lele_hip_depthwise_conv1d_tlc(LeleCtx* ctx, const LeleTensor* x, int64_t x_offset, const LeleTensor* w, const LeleTensor* bias,
-                                  int64_t pad_left, int64_t pad_right, int relu, int add_input, LeleBuf* out, int64_t* out_shape, int32_t* out_rank);
 
 /* The output half of a SAN-M attention block (SenseVoice's encoder layer) as ONE call:
  *   mem = depthwise_conv1d_tlc(v_src, fsmn_w, fsmn_bias, x_offset, pad_left, pad_right, relu = 0, add_input = 1)     (FSMN memory + v)
@@ -1775,40 +1995,19 @@ int lele_hip_sanm_out_block(LeleCtx* ctx, const LeleTensor* input, const LeleTen
     LELE_REQUIRE(ctx && input && weight_int8 && v_src && fsmn_w && ln_scale && ln_bias && out && ln_out, "sanm_out_block: NULL argument");
     LELE_REQUIRE(out != ln_out, "sanm_out_block: the sum and its normalised form need two buffers");
     LELE_REQUIRE(input->rank >= 2 && weight_int8->rank >= 2, "fused_quantized_linear: rank >= 2 required");
-    const int64_t m = input->shape[input->rank - 2], k = input->shape[input->rank - 1], n = weight_int8->shape[weight_int8->rank - 1];
-    int64_t batch = 1;
-    for (int i = 0; i + 2 < input->rank; ++i) batch *= input->shape[i];
-    const int64_t rows = batch * m;
-    // the one-launch form: the projection on igemm_as_kernel with whole rows, v_src [B, T, P] with B * T the projection's rows and T its
-    // slice length, 512 channels from a 16-byte aligned offset, k = 11 with the output as long as the input, res2 of the result's shape
-    auto aligned16 = [](const LeleTensor* t) { return t->mem != LELE_MEM_DEVICE || (((uintptr_t)t->data) & 15) == 0; };
-    bool fused = env_int("LELE_HIP_FSMN_FUSED", 1) != 0 && weight_int8->shape[weight_int8->rank - 2] == k && rows > 0 &&
-                 as_fits(ctx, rows, n, k, input->mem == LELE_MEM_DEVICE ? input->data : nullptr) && !rs_fits(ctx, rows, n, rs_kp(k)) &&
-                 as_ln_ok(ctx, rows, n, apply_relu, ln_scale, ln_bias) && v_src->rank == 3 && v_src->dtype == LELE_F32 && fsmn_w->rank == 3 &&
-                 fsmn_w->dtype == LELE_F32 && fsmn_w->shape[0] == 512 && fsmn_w->shape[1] == 1 && fsmn_w->shape[2] == 11 &&
-                 v_src->shape[0] * v_src->shape[1] == rows && v_src->shape[1] == m && m >= 32 && x_offset >= 0 && x_offset % 4 == 0 &&
-                 x_offset + 512 <= v_src->shape[2] && v_src->shape[2] % 4 == 0 && aligned16(v_src) && pad_left == 5 && pad_right == 5 && (!fsmn_bias || (fsmn_bias->dtype == LELE_F32 && numel(fsmn_bias) >= 512)) &&
-                 v_src->shape[2] * rows < (int64_t(1) << 30);
-    if (fused && res2) {
-        fused = res2->dtype == LELE_F32 && numel(res2) == rows * n && res2->rank <= input->rank && aligned16(res2);
-        for (int d = 0; fused && d < res2->rank; ++d)
-            fused = res2->shape[res2->rank - 1 - d] == (d == 0 ? n : input->shape[input->rank - 1 - d]);
-    }
-    int64_t sh[LELE_MAX_RANK];
-    int32_t r = 0;
+    const QCall c = call_dims(input, {weight_int8, weight_scale, weight_zero, bias});
+    // the one-launch form: the dense linear, asked for its LayerNorm and for the memory block as a first residual that the kernel computes
+    LnReq ln{ln_scale, ln_bias, epsilon, ln_out};
+    ln.fs_x = v_src, ln.fs_w = fsmn_w, ln.fs_b = fsmn_bias, ln.fs_pl = pad_left, ln.fs_off = x_offset;
+    const QReq rq{apply_relu, nullptr, res2, &ln};
+    auto one_launch = [&](const void* dout) { return fql_route(ctx, c, rq, staged_addr(input), dout) == QRoute::AsLnFsmn; };
+    bool fused = env_int("LELE_HIP_FSMN_FUSED", 1) != 0 && c.kw == c.k && c.rows > 0 && fsmn_fits(c, v_src, fsmn_w, fsmn_bias, x_offset, pad_left, pad_right) &&
+                 (!res2 || res_same_shape(input, c.n, res2)) && one_launch(nullptr);  // `out` is not touched unless all else holds
     if (fused) {
-        LELE_TRY(out->reserve((size_t)rows * n * 4));
-        fused = (((uintptr_t)out->data) & 15) == 0;
+        LELE_TRY(out->reserve((size_t)c.rows * c.n * 4));
+        fused = one_launch(out->data);
     }
-    if (fused) {
-        LnReq ln{ln_scale, ln_bias, epsilon, ln_out};
-        ln.fs_x = v_src, ln.fs_w = fsmn_w, ln.fs_b = fsmn_bias, ln.fs_pl = pad_left, ln.fs_off = x_offset;
-        // res1 of the kernel is the memory block it computes; the caller's res2 stays the second residual.  fql_impl's NRES counts
-        // operands: hand it `input` as a stand-in for res1 (never read in this form)
-        LELE_TRY(fql_impl(ctx, input, weight_int8, weight_scale, weight_zero, bias, apply_relu, input, res2, out, sh, &r, &ln));
-        LELE_REQUIRE(ln.done, "internal: sanm_out_block's one-launch form did not run");
-        return set_shape_v(out_shape, out_rank, std::vector<int64_t>(sh, sh + r));
-    }
+    if (fused) return fql_impl(ctx, input, {weight_int8, weight_scale, weight_zero, bias}, rq, out, out_shape, out_rank);
     LeleBuf* mem = nullptr;
     LELE_TRY(ctx->tmp_buf(2, &mem));
     int64_t msh[LELE_MAX_RANK];
@@ -1819,196 +2018,11 @@ int lele_hip_sanm_out_block(LeleCtx* ctx, const LeleTensor* input, const LeleTen
                                                        ln_bias, epsilon, out, ln_out, out_shape, out_rank);
 }
 
-/* Two quantised linears with a ReLU between them (the feed-forward block of a transformer layer):
- *     out = fused_quantized_linear[_residual](fused_quantized_linear(input, W1.., relu = 1), W2.., relu2, res1, res2)
- * bit for bit.  When the hidden layer is large the f32 hidden tensor is never stored: its product runs twice on the matrix cores
- * (igemm_kernel EM 1: range only; EM 2: quantise with that range, i8 + row sums), then the second GEMM consumes the i8 rows. */
-static int ffn_impl(LeleCtx* ctx, const LeleTensor* input, const LeleTensor* w1_int8, const LeleTensor* w1_scale,
-                    const LeleTensor* w1_zero, const LeleTensor* b1, const LeleTensor* w2_int8,
-                    const LeleTensor* w2_scale, const LeleTensor* w2_zero, const LeleTensor* b2, int apply_relu2,
-                    const LeleTensor* res1, const LeleTensor* res2, LeleBuf* out, int64_t* out_shape, int32_t* out_rank, LnReq* ln) {
-    LELE_REQUIRE(ctx && input && w1_int8 && w1_scale && w2_int8 && w2_scale && out, "fused_ffn_quantized: NULL argument");
-    LELE_REQUIRE(input->rank >= 2 && w1_int8->rank >= 2 && w2_int8->rank >= 2, "fused_ffn_quantized: rank >= 2 required");
-    LELE_REQUIRE(!res2 || res1, "fused_ffn_quantized: res2 without res1");
-    LELE_HIP_CHECK(hipSetDevice(ctx->device));
-    const int64_t m = input->shape[input->rank - 2], k1 = input->shape[input->rank - 1];
-    const int64_t n1 = w1_int8->shape[w1_int8->rank - 1], k2 = w2_int8->shape[w2_int8->rank - 2], n2 = w2_int8->shape[w2_int8->rank - 1];
-    int64_t batch = 1;
-    for (int i = 0; i + 2 < input->rank; ++i) batch *= input->shape[i];
-    const int64_t rows = batch * m;
-    const int64_t ws1_len = numel(w1_scale), b1_len = b1 ? numel(b1) : 0;
-    // the fused route: a hidden layer of whole 128-column tiles (= whole SIMD bodies of its quantiser), slices of at least one tile
-    // of rows, enough tiles to fill the chip, same-shape residuals; everything else runs the two calls it stands for
-    const bool args_ok = w1_int8->shape[w1_int8->rank - 2] == k1 && k2 == n1 && rows < (int64_t(1) << 31) && ws1_len >= 1 &&
-                         (ws1_len == 1 || ws1_len >= n1) && (b1_len == 0 || b1_len >= n1) && n2 >= 1;
-    // register-stationary route (igemm_rs.h): K = 512 into a hidden layer of exactly 2048 columns, whose i8 form is written in the
-    // fragment order of the second product and read once
-    // (the second product's threshold is ONE tile per CU: at one 30 s utterance -- 16 x 16 tiles -- the fused block replaces ffn1 with an f32
-    // hidden layer | row quantisation | small-problem GEMM: a configs[2] forward 5.33 -> 5.05 ms, round 6)
-    const bool rs_route = env_int("LELE_HIP_FFN_FUSED", 1) != 0 && args_ok && rs_kp(k1) == 512 && n1 == 2048 && rs_enabled(ctx, rows, n1) &&
-                          rs_enabled(ctx, rows, n2, 1) && rs_aligned(res1) && rs_aligned(res2);
-    bool fused = rs_route || (env_int("LELE_HIP_FFN_FUSED", 1) != 0 && args_ok && n1 % 128 == 0 && m >= 128 &&
-                              ((rows + 127) / 128) * (n1 / 128) >= 2 * (int64_t)ctx->num_cus);
-    if (fused && res1) {
-        int64_t on = n2 * rows;
-        auto same = [&](const LeleTensor* t) {
-            if (t->dtype != LELE_F32 || numel(t) != on || t->rank > input->rank) return false;
-            for (int d = 0; d < t->rank; ++d)
-                if (t->shape[t->rank - 1 - d] != (d == 0 ? n2 : input->shape[input->rank - 1 - d])) return false;
-            return true;
-        };
-        fused = same(res1) && (!res2 || same(res2));
-    }
-    if (!fused) {
-        LeleBuf* hid = nullptr;
-        LELE_TRY(ctx->tmp_buf(2, &hid));
-        int64_t sh[LELE_MAX_RANK];
-        int32_t r = 0;
-        LELE_TRY(fql_impl(ctx, input, w1_int8, w1_scale, w1_zero, b1, 1, nullptr, nullptr, hid, sh, &r));
-        LeleTensor h{hid->data, sh, r, LELE_F32, LELE_MEM_DEVICE};
-        if (res1) return lele_hip_fused_quantized_linear_residual(ctx, &h, w2_int8, w2_scale, w2_zero, b2, apply_relu2, res1, res2, out, out_shape, out_rank);
-        return fql_impl(ctx, &h, w2_int8, w2_scale, w2_zero, b2, apply_relu2, nullptr, nullptr, out, out_shape, out_rank);
-    }
-    const int64_t ws2_len = numel(w2_scale), b2_len = b2 ? numel(b2) : 0;
-    LELE_REQUIRE(ws2_len >= 1 && (ws2_len == 1 || ws2_len >= n2), "fused_ffn_quantized: weight_scale has %lld entries for N=%lld", (long long)ws2_len, (long long)n2);
-    LELE_REQUIRE(b2_len == 0 || b2_len >= n2, "fused_ffn_quantized: bias has %lld entries for N=%lld", (long long)b2_len, (long long)n2);
-    std::vector<int64_t> shp(input->shape, input->shape + input->rank - 1);
-    shp.push_back(n2);
-    LELE_TRY(out->reserve((size_t)rows * n2 * 4));
-    LELE_TRY(ctx->arena_reset());
-    const void *dx = nullptr, *dws1 = nullptr, *db1 = nullptr, *dws2 = nullptr, *db2 = nullptr, *dr1 = nullptr, *dr2 = nullptr;
-    LELE_TRY(ctx->dev_ptr(input, &dx));
-    LELE_TRY(ctx->dev_ptr(w1_scale, &dws1));
-    LELE_TRY(ctx->dev_ptr(w2_scale, &dws2));
-    if (b1_len) LELE_TRY(ctx->dev_ptr(b1, &db1));
-    if (b2_len) LELE_TRY(ctx->dev_ptr(b2, &db2));
-    if (res1) LELE_TRY(ctx->dev_ptr(res1, &dr1));
-    if (res2) LELE_TRY(ctx->dev_ptr(res2, &dr2));
-    float wz1 = 0.0f, wz2 = 0.0f;
-    LELE_TRY(weight_zero_of(ctx, w1_zero, &wz1));
-    LELE_TRY(weight_zero_of(ctx, w2_zero, &wz2));
-    const float* partial = nullptr;
-    int nblk = 0;
-    find_partials(ctx, input, batch, m, k1, &partial, &nblk);
-    void *prm1 = nullptr, *prm2 = nullptr, *aq1 = nullptr, *rs1 = nullptr, *aq2 = nullptr, *rs2 = nullptr, *hmax = nullptr;
-    LELE_TRY(ctx->arena_alloc((size_t)batch * sizeof(QParams), &prm1));
-    LELE_TRY(ctx->arena_alloc((size_t)batch * sizeof(QParams), &prm2));
-    LELE_TRY(qprof_mark(ctx, 0));
-    if (!partial) LELE_TRY(launch_range(ctx, (const float*)dx, batch, m * k1, (QParams*)prm1, nullptr, nullptr, &partial, &nblk));
-    LELE_TRY(qprof_mark(ctx, 1));
-    if (rs_route) {
-        FragW fw1, fw2;
-        LELE_TRY(frag_weights_of(ctx, w1_int8, (int)k1, (int)n1, 512, &fw1));
-        LELE_TRY(frag_weights_of(ctx, w2_int8, (int)k2, (int)n2, 2048, &fw2));
-        const int64_t nrt = (rows + 31) / 32;
-        void *af1 = nullptr, *hid = nullptr;
-        // both passes of the first product quantise the f32 rows in their loader waves, with parameters reduced inside the kernels; the
-        // range pass leaves four maxima a workgroup (plain stores: nothing to clear) which the quantise pass's loaders reduce
-        const bool fq = rs_fq(k1, dx) && rs_max_slices(ctx, rows, n1, m) <= 4;
-        LELE_TRY(ctx->arena_alloc((size_t)nrt * 2048 * 32, &hid));
-        LELE_TRY(ctx->arena_alloc((size_t)batch * 4, &hmax));
-        RsFq fqa;
-        if (fq) {
-            int ncb = 0, nrr = 0;
-            rs_grid(ctx, rows, n1, &ncb, &nrr);
-            void* hpart = nullptr;
-            LELE_TRY(ctx->arena_alloc((size_t)ncb * nrr * 16, &hpart));
-            fqa.x = (const float*)dx, fqa.partial = partial, fqa.nblk = nblk, fqa.hpart = (unsigned*)hpart;
-            fqa.sync = rs_sync_counters(ctx, rows, n1);
-        } else {
-            LELE_TRY(ctx->arena_alloc((size_t)nrt * 512 * 32, &af1));
-            LELE_TRY(ctx->arena_alloc((size_t)rows * 4, &rs1));
-            // rows -> i8 for the first product; the same launch clears the per-slice maxima the range pass adds into
-            LELE_TRY(launch_qrows_frag(ctx, (const float*)dx, rows, (int)k1, 512, (int)m, (QParams*)prm1, (int8_t*)af1, (int*)rs1, partial, nblk,
-                                       (unsigned*)hmax));
-        }
-        LELE_TRY(qprof_mark(ctx, 2));
-        // (tests) LELE_HIP_FFN_ONE_LAUNCH=2: fail instead of falling back to the two launches, so that a test of the one-launch form tests it
-        LELE_REQUIRE(env_int("LELE_HIP_FFN_ONE_LAUNCH", 1) != 2 || fqa.sync,
-                     "fused_ffn_quantized: LELE_HIP_FFN_ONE_LAUNCH=2, but this call cannot take the one-launch form (K = 512 exactly, 16-byte aligned "
-                     "rows, at most 4 slices and %d row tiles a workgroup, lane 0 of the only context of the device, counters made before a capture)",
-                     RS_NS_BOTH);
-        IgemmEpi e1{nullptr, rows, n1, (int)m, (int)k1, (const int*)rs1, fw1.col_sums, (const QParams*)prm1, 0, (int)wz1, (const float*)dws1,
-                    (int)ws1_len, b1_len ? (const float*)db1 : nullptr, 1};
-        e1.slice_max = (unsigned*)hmax;
-        if (fqa.sync) {  // both passes in one launch (igemm_rs.h, EM 3)
-            e1.q_prm = (QParams*)prm2;
-            LELE_TRY(launch_rs(ctx, 3, nullptr, fw1.wf, rows, (int)n1, (int8_t*)hid, e1, fqa));
-        } else {
-            LELE_TRY(launch_rs(ctx, 1, (const int8_t*)af1, fw1.wf, rows, (int)n1, nullptr, e1, fqa));   // range of the ReLU result per slice
-            e1.q_prm = (QParams*)prm2;
-            LELE_TRY(launch_rs(ctx, 2, (const int8_t*)af1, fw1.wf, rows, (int)n1, (int8_t*)hid, e1, fqa));  // the result again, as the next operand
-        }
-        IgemmEpi e2{(float*)out->data, rows, n2, (int)m, (int)k2, nullptr, fw2.col_sums, (const QParams*)prm2, 0, (int)wz2,
-                    (const float*)dws2, (int)ws2_len, b2_len ? (const float*)db2 : nullptr, apply_relu2, (const float*)dr1, (const float*)dr2};
-        // the second product: one column tile a workgroup over a range of row tiles (igemm_rs_ks4_kernel), or -- where the caller wants
-        // the LayerNorm of the result as well -- one row tile a workgroup with all 512 columns and the normalisation in the epilogue
-        const bool fuse_ln = ln && ask_fits(ctx, rows, n2, k2) && as_ln_ok(ctx, rows, n2, apply_relu2, ln->g, ln->b) && ln->out != out &&
-                             (((uintptr_t)out->data) & 15) == 0;
-        if (fuse_ln || (lab_int("LELE_HIP_IGEMM_ASK_ALWAYS", 0) != 0 && ask_fits(ctx, rows, n2, k2) && (((uintptr_t)out->data) & 15) == 0)) {
-            AsLn aln;
-            if (fuse_ln) {
-                const void *dg = nullptr, *dbeta = nullptr;
-                LELE_TRY(ctx->dev_ptr(ln->g, &dg));
-                LELE_TRY(ctx->dev_ptr(ln->b, &dbeta));
-                LELE_TRY(ln->out->reserve((size_t)rows * n2 * 4));
-                LELE_TRY(ln->out->reserve_rowstat(rows));
-                aln.g = (const float*)dg, aln.b = (const float*)dbeta, aln.eps = ln->eps, aln.out = (float*)ln->out->data;
-                aln.rowstat = (size_t)rows <= ln->out->rowstat_cap ? ln->out->rowstat : nullptr;
-            }
-            LELE_TRY(launch_ask(ctx, (const int8_t*)hid, fw2.wf, rows, e2, fuse_ln ? &aln : nullptr));
-            if (fuse_ln) {
-                ln->done = true;
-                if (aln.rowstat) {
-                    ln->out->rowstat_rows = rows;
-                    ln->out->rowstat_len = n2;
-                    ln->out->rowstat_kind = 0;
-                    ln->out->rowstat_valid = true;
-                }
-            }
-        } else {
-            LELE_TRY(launch_rs_ks4(ctx, (const int8_t*)hid, fw2.wf, rows, (int)n2, e2));
-        }
-        LELE_TRY(qprof_mark(ctx, 3));
-        return set_shape_v(out_shape, out_rank, shp);
-    }
-    const int kp1 = (int)((k1 + 15) & ~int64_t(15)), kp2 = (int)n1;
-    PackedW pw1, pw2;
-    LELE_TRY(packed_weights_of(ctx, w1_int8, nullptr, 1, (int)k1, (int)n1, kp1, &pw1));
-    LELE_TRY(packed_weights_of(ctx, w2_int8, nullptr, 1, (int)k2, (int)n2, kp2, &pw2));
-    LELE_TRY(ctx->arena_alloc((size_t)rows * kp1, &aq1));
-    LELE_TRY(ctx->arena_alloc((size_t)rows * 4, &rs1));
-    LELE_TRY(ctx->arena_alloc((size_t)rows * kp2, &aq2));
-    LELE_TRY(ctx->arena_alloc((size_t)rows * 4, &rs2));
-    LELE_TRY(ctx->arena_alloc((size_t)batch * 4, &hmax));
-    // rows -> i8 for the first GEMM; the same launch clears the accumulators of the two hidden-layer passes
-    if (kp1 <= 2048 && !lab_int("LELE_HIP_QROWS_STREAM", 0))
-        hipLaunchKernelGGL((qrows_kernel<0, true>), dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, ctx->stream, (const float*)dx, rows,
-                           (int)k1, kp1, (int)m, (QParams*)prm1, (int8_t*)aq1, (int*)rs1, partial, nblk, (unsigned*)hmax, (int*)rs2);
-    else
-        hipLaunchKernelGGL((qrows_kernel<0, false>), dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, ctx->stream, (const float*)dx, rows,
-                           (int)k1, kp1, (int)m, (QParams*)prm1, (int8_t*)aq1, (int*)rs1, partial, nblk, (unsigned*)hmax, (int*)rs2);
-    LELE_TRY(qprof_mark(ctx, 2));
-    IgemmEpi e1{nullptr, rows, n1, (int)m, (int)k1, (const int*)rs1, pw1.col_sums, (const QParams*)prm1, 0, (int)wz1, (const float*)dws1,
-                (int)ws1_len, b1_len ? (const float*)db1 : nullptr, 1};
-    e1.slice_max = (unsigned*)hmax;
-    LELE_TRY(launch_igemm_hidden(ctx, 1, (const int8_t*)aq1, pw1.wt, rows, (int)n1, kp1, (int)m, e1));
-    e1.q_out = (int8_t*)aq2;
-    e1.q_rowsum = (int*)rs2;
-    e1.q_prm = (QParams*)prm2;
-    LELE_TRY(launch_igemm_hidden(ctx, 2, (const int8_t*)aq1, pw1.wt, rows, (int)n1, kp1, (int)m, e1));
-    IgemmEpi e2{(float*)out->data, rows, n2, (int)m, (int)k2, (const int*)rs2, pw2.col_sums, (const QParams*)prm2, 0, (int)wz2,
-                (const float*)dws2, (int)ws2_len, b2_len ? (const float*)db2 : nullptr, apply_relu2, (const float*)dr1, (const float*)dr2};
-    LELE_TRY(launch_igemm(ctx, (const int8_t*)aq2, pw2.wt, rows, (int)n2, kp2, 0, (int)m, e2));
-    LELE_TRY(qprof_mark(ctx, 3));
-    return set_shape_v(out_shape, out_rank, shp);
-}
-
 int lele_hip_fused_ffn_quantized(LeleCtx* ctx, const LeleTensor* input, const LeleTensor* w1_int8, const LeleTensor* w1_scale,
                                  const LeleTensor* w1_zero, const LeleTensor* b1, const LeleTensor* w2_int8,
                                  const LeleTensor* w2_scale, const LeleTensor* w2_zero, const LeleTensor* b2, int apply_relu2,
                                  const LeleTensor* res1, const LeleTensor* res2, LeleBuf* out, int64_t* out_shape, int32_t* out_rank) {
-    return ffn_impl(ctx, input, w1_int8, w1_scale, w1_zero, b1, w2_int8, w2_scale, w2_zero, b2, apply_relu2, res1, res2, out, out_shape, out_rank, nullptr);
+    return ffn_impl(ctx, input, {w1_int8, w1_scale, w1_zero, b1}, {w2_int8, w2_scale, w2_zero, b2}, QReq{apply_relu2, res1, res2}, out, out_shape, out_rank);
 }
 
 /* out = fused_ffn_quantized(...);  ln_out = layer_norm(out, ln_scale, ln_bias, -1, epsilon) -- a transformer layer's feed-forward block,
@@ -2024,13 +2038,8 @@ int lele_hip_fused_ffn_quantized_ln(LeleCtx* ctx, const LeleTensor* input, const
     LnReq ln{ln_scale, ln_bias, epsilon, ln_out};
     int64_t sh[LELE_MAX_RANK];
     int32_t r = 0;
-    LELE_TRY(ffn_impl(ctx, input, w1_int8, w1_scale, w1_zero, b1, w2_int8, w2_scale, w2_zero, b2, apply_relu2, res1, res2, out, sh, &r, &ln));
-    if (!ln.done) {
-        LeleTensor y{out->data, sh, r, LELE_F32, LELE_MEM_DEVICE};
-        int64_t sh2[LELE_MAX_RANK];
-        int32_t r2 = 0;
-        LELE_TRY(lele_hip_layer_norm(ctx, &y, ln_scale, ln_bias, -1, epsilon, ln_out, sh2, &r2));
-    }
+    LELE_TRY(ffn_impl(ctx, input, {w1_int8, w1_scale, w1_zero, b1}, {w2_int8, w2_scale, w2_zero, b2}, QReq{apply_relu2, res1, res2, &ln}, out, sh, &r));
+    LELE_TRY(finish_ln(ctx, ln, out, sh, r));
     return set_shape_v(out_shape, out_rank, std::vector<int64_t>(sh, sh + r));
 }
 
@@ -2173,23 +2182,10 @@ int lele_hip_mat_mul_integer_with_scale_bias(LeleCtx* ctx, const LeleTensor* a, 
     shp.push_back(n);
     LELE_TRY(out->reserve((size_t)fb * m * n * 4));
     if (fb * m * n == 0) return set_shape_v(out_shape, out_rank, shp);
-    auto first_as_int = [&](const LeleTensor* t, int* v) -> int {  // `.data.first().map(|&v| v as i32).unwrap_or(0)`
-        *v = 0;
-        if (!t || numel(t) == 0) return 0;
-        float f = 0.0f;
-        if (t->mem == LELE_MEM_DEVICE) {
-            LELE_HIP_CHECK(hipMemcpyAsync(&f, t->data, 4, hipMemcpyDeviceToHost, ctx->stream));
-            LELE_REQUIRE(!ctx->capturing, "graph capture: this op must run once eagerly first (it allocates or synchronises)");
-            LELE_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-        } else {
-            f = *(const float*)t->data;
-        }
-        *v = (int)f;
-        return 0;
-    };
-    int zp_a = 0, zp_b = 0;
-    LELE_TRY(first_as_int(a_zero_point, &zp_a));
-    LELE_TRY(first_as_int(b_zero_point, &zp_b));
+    float za = 0.0f, zb = 0.0f;  // `.data.first().map(|&v| v as i32).unwrap_or(0)`
+    LELE_TRY(first_scalar_of(ctx, a_zero_point, &za));
+    LELE_TRY(first_scalar_of(ctx, b_zero_point, &zb));
+    const int zp_a = (int)za, zp_b = (int)zb;
     const int64_t slen = scale ? numel(scale) : 0, blen = bias ? numel(bias) : 0;
     LELE_REQUIRE(!scale || slen == 1 || slen >= n, "mat_mul_integer: scale has %lld entries for N=%lld",
                  (long long)slen, (long long)n);
@@ -2218,7 +2214,7 @@ int lele_hip_mat_mul_integer_with_scale_bias(LeleCtx* ctx, const LeleTensor* a, 
         IgemmEpi epi{(float*)out->data + (launches == 1 ? 0 : bi * m * n), rows, n, (int)m, (int)k, rsp,
                      pw.col_sums + (batch_b == 1 ? 0 : bi * n), nullptr, zp_a, zp_b, (const float*)ds, (int)slen,
                      (const float*)dbi, apply_relu};
-        LELE_TRY(launch_igemm(ctx, aptr, pw.wt + (batch_b == 1 ? 0 : bi * n * kp), rows, (int)n, kp, 0, (int)m, epi));
+        LELE_TRY(launch_igemm(ctx, aptr, pw.wt + (batch_b == 1 ? 0 : bi * n * kp), rows, (int)n, kp, (int)m, epi));
     }
     return set_shape_v(out_shape, out_rank, shp);
 }

@@ -366,7 +366,7 @@ def test_dynamic_quantize_linear_on_adversarial_slices(ctx, orc, length):
             assert _same(y.numpy(), ry), (kind, length, at_min, _diff(y.numpy(), ry))
 
 
-# (b, m, k, n) -> the route fql_impl (quant.hip) selects for it
+# (b, m, k, n) -> the route fql_route (quant.hip) selects for it
 ROUTES = [
     ((1, 93, 560, 1536), "tiled: K = 560 pads to 576 (rs_fits needs kp == 512) -> qrows_kernel + igemm_kernel"),
     ((2, 5, 37, 19), "tiled chain on a tiny product (launch_igemm's small-problem kernel); K = 37: a scalar tail of 5 per row"),
