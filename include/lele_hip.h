@@ -386,7 +386,11 @@ int lele_hip_conv_stats(LeleCtx* ctx, int64_t* calls, int64_t* macs);
  * add3 ("add3.vec4" / "add3.w1"), halves_pow_add_sqrt ("hpas.w1").  And the recurrent calls: lstm / gru ("rnn.lstm" / "rnn.gru", then
  * the GEMM kernel of W x: "gemm.thin_m", "gemm.small", a tile, "gemm.k0" for I = 0; nothing more for T = 0), lstm_segments / gru_segments
  * ("rnns.lstm" / "rnns.gru", then "rnns.reg16" / "reg32" / "reg64" for recurrent weights in registers or "rnns.stream1" / "stream2" /
- * "stream4" / "stream8" for the streamed form by the width of its members' register tile).  The route never names an earlier call.  Recorded on the
+ * "stream4" / "stream8" for the streamed form by the width of its members' register tile).  And the ConvInteger family on the i8 matrix
+ * cores: conv_integer ("ci8.codes") and conv_integer_from_f32 / _multi ("ci8.quant": the image is quantised as it is packed), then the
+ * kernel: "ci8.nj4" / "ci8.nj2" / "ci8.nj1" (a wave owns 4 / 2 / 1 strips of 32 positions) or "ci8.nj2_ksplit" / "ci8.nj1_ksplit" (the four
+ * waves of a workgroup share the strips and split K); the f32 form reports "ci.f32", then the convolution's own route.
+ * fused_scale_bias(_silu) reports "fsb.w1".  The route never names an earlier call.  Recorded on the
  * host when the call is issued (a call recorded into a graph reports the route it recorded).  NUL-terminated into buf; an error when cap is too small.
  * lele_hip_route_names: every level name a route can hold, one per line; host only, no GPU needed. */
 int lele_hip_last_route(LeleCtx* ctx, char* buf, size_t cap);

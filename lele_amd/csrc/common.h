@@ -200,7 +200,8 @@ struct LeleCtx {
     // at the launch site -- a wrapper that re-shaped the call first (route[0], "ci.f32"), the operator's own choice (route[1], e.g.
     // "conv.gemm_tap", "attn.rows32") and the GEMM core's (route[2], what gemm::launch returned; for attention the key-tile class,
     // "attn.nt6"; for the register-resident norm kernels of eltwise.hip the rows a block holds, "rows.rpb4"); unused levels are nullptr.
-    // The data-movement (manip.hip), element-wise / reduce / norm (eltwise.hip) and LSTM / GRU (rnn.hip) entry points record theirs the same way
+    // The data-movement (manip.hip), element-wise / reduce / norm (eltwise.hip) and LSTM / GRU (rnn.hip) entry points record theirs the same way,
+    // and so does the i8 ConvInteger of conv.hip: how the image was packed ("ci8.codes" / "ci8.quant"), then the kernel ("ci8.nj2_ksplit")
     const char* route[3] = {nullptr, nullptr, nullptr};
     void set_route(const char* op, const char* core = nullptr) {
         route[0] = nullptr;

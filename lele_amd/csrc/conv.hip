@@ -1832,7 +1832,8 @@ __global__ __launch_bounds__(256) void ci8_conv_kernel(const unsigned char* __re
                 for (int r = 0; r < 16; ++r) acc[j][r] += red[((w * NJ + j) * 16 + r) * 64 + lane];
     }
     const int zx = prm.dq ? prm.dq[0].zp_i : prm.zx_host, zw = prm.zw, K = g.c * taps;
-    const int konst = K * zx * zw - 16384 * K;
+    // every term is an exact i32 and so is their sum, but a partial sum may pass 2^31 at the largest K the guard admits: added modulo 2^32
+    const unsigned konst = (unsigned)(K * zx * zw - 16384 * K);
 #pragma unroll
     for (int j = 0; j < NJ; ++j) {
         int sx = 0;  // sum of the u8 codes over this position's window (zeros outside the image): taps of the per-pixel channel sums
@@ -1845,7 +1846,8 @@ __global__ __launch_bounds__(256) void ci8_conv_kernel(const unsigned char* __re
         for (int r = 0; r < 16; ++r) {
             const int o = tile * 32 + (r & 3) + 8 * (r >> 2) + 4 * hv;
             if (p < g.plane && o < g.oc)
-                out[((int64_t)n * g.oc + o) * g.plane + p] = (float)(acc[j][r] + (128 - zw) * sx + (128 - zx) * wsum[o] + konst);
+                out[((int64_t)n * g.oc + o) * g.plane + p] =
+                    (float)(int)((unsigned)acc[j][r] + (unsigned)((128 - zw) * sx) + (unsigned)((128 - zx) * wsum[o]) + konst);
         }
     }
 }
@@ -1966,6 +1968,7 @@ inline bool steps_lt8(int steps) { return steps < 8; }  // too few (tap, chunk) 
 // the parameters at dq), weights w (u8 codes as f32), zero points zx_host (ignored when dq) and w_zp.  See the section comment.
 int ci_run(LeleCtx* ctx, ConvGeom g, const LeleTensor* w, float w_zp, const float* const* srcs, const int64_t* src_c, int nsrc, const QParamsDev* dq,
            float zx_host, float* out) {
+    ctx->set_route(nullptr);
     if ((int64_t)g.n * g.oc * g.plane == 0) return 0;
     const int taps = g.kh * g.kw;
     const int64_t spatial = (int64_t)g.ih * g.iw, K = (int64_t)g.c * taps;
@@ -2015,14 +2018,18 @@ int ci_run(LeleCtx* ctx, ConvGeom g, const LeleTensor* w, float w_zp, const floa
         // the widest wave tile that still gives every CU two workgroups; below that the waves of a workgroup split K instead
         const int64_t units = (int64_t)g.n * tiles, want = 2 * (int64_t)ctx->num_cus;
         auto blocks = [&](int nj, bool ks) { return ((int64_t)g.plane + (ks ? 1 : 4) * 32 * nj - 1) / ((ks ? 1 : 4) * 32 * nj); };
-#define LELE_CI8(NJ_, KS_)                                                                                                          \
-    hipLaunchKernelGGL((ci8_conv_kernel<NJ_, KS_>), dim3((unsigned)blocks(NJ_, KS_), (unsigned)tiles, (unsigned)g.n), dim3(256), 0, ctx->stream, \
-                       (const unsigned char*)img, (const int*)ts, (const ci_v4i*)fw, (const int*)((char*)fw + fbytes), prm, g, cp, out)
-        if (units * blocks(4, false) >= want) LELE_CI8(4, false);
-        else if (units * blocks(2, false) >= want) LELE_CI8(2, false);
-        else if (units * blocks(1, false) >= want || steps_lt8(taps * chunks)) LELE_CI8(1, false);
-        else if (units * blocks(2, true) >= want) LELE_CI8(2, true);
-        else LELE_CI8(1, true);
+        // lele_hip_last_route: how the image was packed (codes taken as they are / quantised on the way), then the kernel
+#define LELE_CI8(NJ_, KS_, NAME_)                                                                                                   \
+    do {                                                                                                                            \
+        ctx->set_route(dq ? "ci8.quant" : "ci8.codes", NAME_);                                                                      \
+        hipLaunchKernelGGL((ci8_conv_kernel<NJ_, KS_>), dim3((unsigned)blocks(NJ_, KS_), (unsigned)tiles, (unsigned)g.n), dim3(256), 0, ctx->stream, \
+                           (const unsigned char*)img, (const int*)ts, (const ci_v4i*)fw, (const int*)((char*)fw + fbytes), prm, g, cp, out); \
+    } while (0)
+        if (units * blocks(4, false) >= want) LELE_CI8(4, false, "ci8.nj4");
+        else if (units * blocks(2, false) >= want) LELE_CI8(2, false, "ci8.nj2");
+        else if (units * blocks(1, false) >= want || steps_lt8(taps * chunks)) LELE_CI8(1, false, "ci8.nj1");
+        else if (units * blocks(2, true) >= want) LELE_CI8(2, true, "ci8.nj2_ksplit");
+        else LELE_CI8(1, true, "ci8.nj1_ksplit");
 #undef LELE_CI8
         LELE_HIP_CHECK(hipGetLastError());
         return 0;
@@ -2525,6 +2532,7 @@ int lele_hip_fused_scale_bias(LeleCtx* ctx, const LeleTensor* data, const LeleTe
     if (scale_dev_or_null) LELE_TRY(ctx->dev_ptr(scale_dev_or_null, &dsc));
     const int64_t total = numel(data);
     LELE_TRY(out->reserve((size_t)total * 4));
+    ctx->set_route(total ? "fsb.w1" : nullptr);
     if (total) {
         hipLaunchKernelGGL(ci_scale_bias_kernel, dim3(grid_for(total)), dim3(256), 0, ctx->stream, (const float*)dd, total,
                            data->shape[1], data->shape[2] * data->shape[3], (const float*)dsc, scale_mul, (const float*)db, silu,

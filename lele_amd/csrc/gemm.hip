@@ -85,6 +85,9 @@ const char* const kRouteNames[] = {
     "conv.gemm_pw", "conv.gemm_tap", "conv.gemm_generic",
     "convt.ks", "convt.phase", "convt.phase_fill",
     "ci.f32",
+    // the i8 matrix-core ConvInteger: how the image was packed (u8 codes as given / the from_f32 forms' dynamic quantisation), then the
+    // instantiation of ci8_conv_kernel<NJ, KSPLIT>; fused_scale_bias(_silu) has one kernel
+    "ci8.codes", "ci8.quant", "ci8.nj4", "ci8.nj2", "ci8.nj1", "ci8.nj2_ksplit", "ci8.nj1_ksplit", "fsb.w1",
     // lele_hip_attention_view: the kernel, then its key-tile class (softmax registers per lane = tpad / 32); the one-pass kernel has
     // no classes.  lele_hip_attention_segments: one name for the launches of a layout
     "attn.flash", "attn.rows16", "attn.rows32", "attn.rows64", "attn.rows16_exact", "attn.rows32_exact", "attn.rows64_exact",
