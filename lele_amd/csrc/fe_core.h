@@ -151,7 +151,17 @@ FE_HD void phase_a(cf* a, const TW& tw_re, const TW& tw_im) {
 //   * registers whose sample index 16*rev5(r)+p is >= 400 are the zero padding: stage-1 butterflies whose
 //     odd input is padding reduce to copies (e + 0, e - 0);
 //   * stage 2/k=1 and stage 3/k even have zero imaginary inputs: fma(w, 0, x) == x, w*0 == +-0.
-// REQUIRES tw_re[0]==1, tw_im[0]==+-0, tw_re[1]==1, tw_im[1]==+-0 (checked on the host when tables are built).
+//   * stage 4/k=0 and stage 5/k=0 use table[7] = table[15] = (1, -0) on complex inputs: t = (fma(1, or, -((-0)*oi)),
+//     fma(1, oi, (-0)*or)) is o itself, except that a zero component of o may come out with the other sign
+//     (-0 + +0 == +0).  So the butterfly is e + o, e - o: two packed instructions instead of four.  A zero's sign
+//     cannot reach the result.  Call two finite values "alike" when they are equal or both zero.  Every operation
+//     the network applies from here on (add, subtract, multiply, fma, negation) maps alike inputs to alike
+//     outputs: a sum or fma whose other terms are not all zero does not see the sign of a zero term, and one whose
+//     terms are all zero gives a zero of either sign; a product with a zero is a zero.  The network ends in the power
+//     re*re + im*im (bin 256: re256*re256 + 0*0), which is +0 for a zero of either sign and equal for equal
+//     values.  (Finite values: like the other folds here, this one does not reproduce the NaNs that 0 * inf makes
+//     of a frame that has already overflowed.)
+// REQUIRES tw_re[i]==1, tw_im[i]==+-0 for i = 0, 1, tw_off(4), tw_off(5) (checked on the host when tables are built).
 // Input: x[r] real (r = 0..31, zero where rev5(r) >= 25).  Output: a[r] complex.
 template <typename TW>
 FE_HD void phase_a_fast(const float* x, cf* a, const TW& tw_re, const TW& tw_im) {
@@ -202,8 +212,13 @@ FE_HD void phase_a_fast(const float* x, cf* a, const TW& tw_re, const TW& tw_im)
         const int half = 1 << (s - 1);
 #pragma unroll
         for (int b = 0; b < kRegs; b += 2 * half) {
+            {  // k = 0: w = (1, -0)
+                const cf e = a[b], o = a[b + half];
+                a[b] = cadd(e, o);
+                a[b + half] = csub(e, o);
+            }
 #pragma unroll
-            for (int k = 0; k < half; ++k)
+            for (int k = 1; k < half; ++k)
                 bfly_fma(make_tw(tw_re[tw_off(s) + k], tw_im[tw_off(s) + k]), a[b + k], a[b + half + k]);
         }
     }

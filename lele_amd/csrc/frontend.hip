@@ -353,13 +353,47 @@ __device__ __forceinline__ void fe_main_body(const float* __restrict__ pcm, int6
     }
     __syncthreads();  // tables (and, when FUSED, the means) are in LDS; the PCM tile may now be overwritten
 
+    // STDMEL: the first bins of this lane's five filters are the same in every pass: read here, once
+    int mstart[5] = {0, 0, 0, 0, 0};
+    if (STDMEL) {
+#pragma unroll
+        for (int rd = 0; rd < 5; ++rd) mstart[rd] = s_mstart[rd * 16 + p];
+    }
+
+    // LFR targets of a frame f (lfr.rs:36-52): rows i, blocks b with n*i + b - pad == f; the first is b = (f + pad) % n in row
+    // i = (f + pad) / n, the others follow at b + n in row i - 1, ...  A lane's frame advances by 4 a pass, so the division is done
+    // here, once, and (b, i) are carried: b += 4, then the carry into i (next_targets below).  lfr_o is the first target's BYTE
+    // offset inside the utterance's output, carried the same way, so that a store is the utterance's (wave-uniform) base plus a
+    // 32-bit lane offset; the host refuses an utterance whose output does not fit 4 GiB.  Offsets are formed modulo 2^32 and used
+    // only where (i, b) is a real target, where the true value fits.
+    const int f_first = (int)(bl.x() * FR) + wave * (4 * PASSES) + g;
+    const int nfr = (int)num_frames, tl = (int)t_lfr;
+    const int pad = (tb.lfr_m - 1) / 2;
+    const unsigned blk_bytes = 4u * (unsigned)tb.n_mels, row_bytes = 4u * (unsigned)d_out;
+    auto target_off = [&](int i, int b) { return (unsigned)i * row_bytes + (unsigned)b * blk_bytes + 4u * (unsigned)p; };
+    int lfr_b = (f_first + pad) % tb.lfr_n, lfr_i = (f_first + pad) / tb.lfr_n;
+    unsigned lfr_o = target_off(lfr_i, lfr_b);
+    auto next_targets = [&]() {
+        lfr_b += 4;
+        if (tb.lfr_n >= 4) {  // (wave-uniform) at most one row further: a compare and three selects
+            const bool carry = lfr_b >= tb.lfr_n;
+            lfr_b -= carry ? tb.lfr_n : 0;
+            lfr_i += carry ? 1 : 0;
+            lfr_o += carry ? 4u * blk_bytes + row_bytes - (unsigned)tb.lfr_n * blk_bytes : 4u * blk_bytes;
+        } else {  // up to four rows further
+            lfr_i += lfr_b / tb.lfr_n;
+            lfr_b = lfr_b % tb.lfr_n;
+            lfr_o = target_off(lfr_i, lfr_b);
+        }
+    };
+
     // One pass = 4 frames per wave.  The last pass is a second copy of the body WITHOUT the request for the next pass's samples: with
     // that request behind a branch the compiler sank half of the pre-emphasis below it -- the lane rotation and its multiply ended up
     // in different blocks (no DPP operand: 25 v_mov_dpp + 25 v_mov a pass) and the 25 samples were copied twice per pass.
     auto run_pass = [&](int pass, auto load_next_c) {
         constexpr bool load_next = decltype(load_next_c)::value;
-        const int64_t f = (int64_t)bl.x() * FR + wave * (4 * PASSES) + pass * 4 + g;
-        const bool valid = f < num_frames;
+        const int fi = f_first + pass * 4;
+        const bool valid = fi < nfr;
         const float mean = FUSED ? s_mean[wave * (4 * PASSES) + pass * 4 + g] : mean_next;
         if (LOWREG) {  // the compiler must not hoist these loads out of the pass loop (that is the register form again)
             int off = 0;
@@ -440,13 +474,6 @@ __device__ __forceinline__ void fe_main_body(const float* __restrict__ pcm, int6
         if (p == 0) prow[256] = fe::power(p256, 0.0f);
         __builtin_amdgcn_wave_barrier();
 
-        // LFR targets of this frame (lfr.rs:36-52): rows i, blocks b with n*i + b - pad == f.  Computed once per
-        // frame in 32-bit arithmetic; the clamped first/last frames are handled in the rare branches below.
-        const int fi = (int)f, nfr = (int)num_frames, tl = (int)t_lfr;
-        const int pad = (tb.lfr_m - 1) / 2;
-        const int fp = fi + pad;
-        const int b_first = fp % tb.lfr_n, i_first = fp / tb.lfr_n;
-
         // 7. sparse mel: lane pm = p owns filters m = 16*rd + p; sequential sum += w*P (mel.rs:92-104)
         // 8. ln(max(x, 1e-5)) (mel.rs:124-128) and LFR scatter (lfr.rs:18-54)
         float vals[STDMEL ? 5 : kMaxMelRounds];
@@ -455,18 +482,27 @@ __device__ __forceinline__ void fe_main_body(const float* __restrict__ pcm, int6
             vals[rd] = 0.0f;
             if (!STDMEL && rd >= tb.mel_rounds) continue;
             const int m = rd * 16 + p;
-            const int start = s_mstart[m];
+            const int start = STDMEL ? mstart[rd < 5 ? rd : 0] : s_mstart[m];
             const float* pp = prow + start;
             float acc = 0.0f;
             if (STDMEL) {
                 const float* wp = tb.melw + kStdMelOff[rd < 5 ? rd : 0] * 16 + p;  // L1-resident table, coalesced
-                float w[17];
+                // every weight and every power of the round is requested before the (sequential) sum starts
+                float w[17], pv[17];
 #pragma unroll
                 for (int t = 0; t < 17; ++t)
                     if (t < kStdMelLen[rd < 5 ? rd : 0]) w[t] = wp[t * 16];
 #pragma unroll
                 for (int t = 0; t < 17; ++t)
-                    if (t < kStdMelLen[rd < 5 ? rd : 0]) acc = fe::fadd(acc, fe::fmul(w[t], pp[t]));
+                    if (t < kStdMelLen[rd < 5 ? rd : 0]) pv[t] = pp[t];
+#pragma unroll
+                for (int t = 0; t < 17; ++t)
+                    if (t < kStdMelLen[rd < 5 ? rd : 0]) {
+                        // step 0: 0 + w*P is w*P itself -- a weight is +0 or positive and a power is a sum of squares, so the
+                        // product is never the -0 that the addition would turn into +0
+                        const float wp0 = fe::fmul(w[t], pv[t]);
+                        acc = t == 0 ? wp0 : fe::fadd(acc, wp0);
+                    }
             } else {
                 const int t0 = s_moff[rd], t1 = s_moff[rd + 1];
                 const float* wp = s_melw + t0 * 16 + p;
@@ -488,35 +524,40 @@ __device__ __forceinline__ void fe_main_body(const float* __restrict__ pcm, int6
                 vals[rd] = fe::fadd(r, fe::ffma(l2, lo, fe::ffma(l2, hi, -r)));
             }
         }
-        // store: log-mel row (test hook) and/or the LFR scatter; lane p writes mels p, p+16, ... of each target
+        // store: log-mel row (test hook) and/or the LFR scatter; lane p writes mels p, p+16, ... of each target (the targets of this
+        // pass's frame: lfr_b, lfr_i, lfr_o above); the clamped first/last frames are handled in the rare branches below
         if (valid) {
             constexpr int kR = STDMEL ? 5 : kMaxMelRounds;
-            auto put = [&](float* dst) {
+            auto put = [&](float* dst_u, unsigned off) {  // dst_u: wave-uniform; off: bytes, this lane's mel 0 .. 15 of the target
+                float* dst = reinterpret_cast<float*>(reinterpret_cast<char*>(dst_u) + off);
 #pragma unroll
                 for (int rd = 0; rd < kR; ++rd)
-                    if (rd * 16 + p < tb.n_mels) __builtin_nontemporal_store(vals[rd], &dst[rd * 16]);  // streamed: keep L2 for the PCM
+                    if (STDMEL || rd * 16 + p < tb.n_mels)  // (STDMEL: 80 mels = five full rounds, no lane to mask)
+                        __builtin_nontemporal_store(vals[rd], &dst[rd * 16]);  // streamed: keep L2 for the PCM
             };
-            if (lm_u) put(lm_u + (int64_t)fi * tb.n_mels + p);
+            if (lm_u) put(lm_u, (unsigned)fi * blk_bytes + 4u * (unsigned)p);
             if (out_u) {
-                int i = i_first;
-                for (int b = b_first; b < tb.lfr_m && i >= 0; b += tb.lfr_n, --i)
-                    if (i < tl) put(out_u + i * d_out + b * tb.n_mels + p);
+                int i = lfr_i;
+                unsigned o = lfr_o;
+                for (int b = lfr_b; b < tb.lfr_m && i >= 0; b += tb.lfr_n, --i, o += (unsigned)tb.lfr_n * blk_bytes - row_bytes)
+                    if (i < tl) put(out_u, o);
                 if (fi == 0) {  // left clamp: raw index < 0 reads frame 0
                     for (int i2 = 0; i2 * tb.lfr_n - pad < 0 && i2 < tl; ++i2)
-                        for (int b = 0; b < tb.lfr_m && i2 * tb.lfr_n + b - pad < 0; ++b)
-                            put(out_u + i2 * d_out + b * tb.n_mels + p);
+                        for (int b = 0; b < tb.lfr_m && i2 * tb.lfr_n + b - pad < 0; ++b) put(out_u, target_off(i2, b));
                 }
                 if (fi == nfr - 1) {  // right clamp: raw index > T-1 reads the last frame
                     for (int i2 = tl - 1; i2 >= 0 && i2 * tb.lfr_n + (tb.lfr_m - 1) - pad > fi; --i2)
-                        for (int b = tb.lfr_m - 1; b >= 0 && i2 * tb.lfr_n + b - pad > fi; --b)
-                            put(out_u + i2 * d_out + b * tb.n_mels + p);
+                        for (int b = tb.lfr_m - 1; b >= 0 && i2 * tb.lfr_n + b - pad > fi; --b) put(out_u, target_off(i2, b));
                 }
             }
         }
         __builtin_amdgcn_wave_barrier();
     };
 #pragma unroll 1
-    for (int pass = 0; pass + 1 < PASSES; ++pass) run_pass(pass, std::true_type{});
+    for (int pass = 0; pass + 1 < PASSES; ++pass) {
+        run_pass(pass, std::true_type{});
+        next_targets();
+    }
     run_pass(PASSES - 1, std::false_type{});
 }
 
@@ -923,9 +964,9 @@ int lele_hip_frontend_create(LeleCtx* ctx, const LeleFeatureConfig* cfg, LeleFro
     std::vector<float> win, twr, twi;
     host_hann(fe->frame_len, win);
     host_twiddles(fe->n_fft, twr, twi);
-    // phase_a_fast folds table[0], table[1] == (1, -0) away: make sure this libm agrees (it must: cos(-0)=1)
-    LELE_REQUIRE(twr[0] == 1.0f && twi[0] == 0.0f && twr[1] == 1.0f && twi[1] == 0.0f,
-                 "frontend_create: unexpected twiddle table head");
+    // phase_a_fast folds the k = 0 entries of stages 1, 2, 4 and 5 == (1, -0) away: make sure this libm agrees (it must: cos(-0)=1)
+    for (int i : {0, 1, fe::tw_off(4), fe::tw_off(5)})
+        LELE_REQUIRE(twr[i] == 1.0f && twi[i] == 0.0f, "frontend_create: unexpected twiddle table entry %d", i);
     std::vector<float2> tw(512, make_float2(0.f, 0.f));
     for (size_t i = 0; i < twr.size(); ++i) tw[i] = make_float2(twr[i], twi[i]);
     twr.resize(512, 0.0f);
@@ -1124,6 +1165,9 @@ static int fe_run(LeleFrontend* fe, const LeleTensor* pcm, int64_t batch, int64_
         }
         return 0;
     }
+    // the kernel addresses an utterance's output by 32-bit byte offsets from the utterance's base
+    LELE_REQUIRE((want_logmel ? nf * fe->cfg.n_mels : t_lfr * cols) < (int64_t(1) << 30),
+                 "frontend: the features of one utterance (%lld frames) exceed 4 GiB", (long long)nf);
     const int aligned16 = ((uintptr_t)dpcm % 16 == 0) && (pcm_len % 4 == 0);
     dim3 grid((unsigned)((nf + 63) / 64), (unsigned)batch);
     hipEvent_t* ev = nullptr;
@@ -1256,6 +1300,9 @@ int lele_hip_frontend_compute_segments(LeleFrontend* fe, const LeleTensor* pcm, 
         return 0;
     }
     LELE_REQUIRE(blocks < (int64_t(1) << 31), "frontend_compute_segments: %lld blocks exceed the grid", (long long)blocks);
+    // (fe_run's bound, per segment: 32-bit byte offsets inside a segment's rows)
+    LELE_REQUIRE(!fe->fast || (max_nf + fe->cfg.lfr_n - 1) / fe->cfg.lfr_n * cols < (int64_t(1) << 30),
+                 "frontend_compute_segments: the features of one segment (%lld frames) exceed 4 GiB", (long long)max_nf);
     LeleCtx* ctx = fe->ctx;
     LELE_HIP_CHECK(hipSetDevice(ctx->device));
     LELE_TRY(ctx->arena_reset());
