@@ -597,6 +597,32 @@ int lele_hip_fused_quantized_linear_segments(LeleCtx* ctx, const LeleTensor* inp
                                              const LeleTensor* weight_int8, const LeleTensor* weight_scale, const LeleTensor* weight_zero,
                                              const LeleTensor* bias_or_null, int apply_relu, LeleBuf* out, int64_t* out_shape,
                                              int32_t* out_rank);
+/* The greedy decode head (examples/sensevoice/src/tokenizer.rs:50-71 behind quantization.rs:77-169): out_ids = i32, the input's shape
+ * without its last axis, bit for bit lele_hip_argmax_last(lele_hip_fused_quantized_linear(input, .., apply_relu = 0)) -- one dynamic
+ * range per batch slice, the same result elements, of equal maxima the LAST index wins, +0.0 and -0.0 compare equal (partial_cmp).  The
+ * arg-max is taken inside the GEMM's epilogue: the logits [rows, N] are never stored and no buffer of rows x N elements is reserved.
+ * A row whose logits hold a NaN has an unspecified id (the reference panics there: tokenizer.rs:56, partial_cmp(..).unwrap()).
+ * rows == 0 gives an empty result of the right shape; K == 0 or N == 0 is an error.  Everything is checked before anything is launched
+ * or resized; graph-capturable after one eager run of the same shape. */
+int lele_hip_fused_quantized_linear_argmax(LeleCtx* ctx, const LeleTensor* input, const LeleTensor* weight_int8,
+                                           const LeleTensor* weight_scale, const LeleTensor* weight_zero, const LeleTensor* bias_or_null,
+                                           LeleBuf* out_ids, int64_t* out_shape, int32_t* out_rank);
+/* ... of a packed batch (tokenizer.rs:50-71, quantization.rs:77-169): input f32 [R, K] -> out_ids i32 [R]; every segment is a slice of
+ * its own exactly as in lele_hip_fused_quantized_linear_segments (the same offset checks, layout table and per-segment range pass), so
+ * segment i's ids are bit for bit lele_hip_fused_quantized_linear_argmax of input[off[i]:off[i+1]] alone.  0-row segments are skipped.
+ * NaN rows as above.  Graph-capturable after one eager run of the same layout. */
+int lele_hip_fused_quantized_linear_argmax_segments(LeleCtx* ctx, const LeleTensor* input, const int64_t* row_offsets, int64_t count,
+                                                    const LeleTensor* weight_int8, const LeleTensor* weight_scale,
+                                                    const LeleTensor* weight_zero, const LeleTensor* bias_or_null, LeleBuf* out_ids,
+                                                    int64_t* out_shape, int32_t* out_rank);
+/* lele_hip_token_filter per segment of packed ids (tokenizer.rs:50-71 after quantization.rs:77-169 produced them): ids i32 [R],
+ * row_offsets host [count + 1] from 0 to R, skip U8 [V] -> out_ids i32 [count, W], out_counts i32 [count].  Row i holds the kept ids of
+ * segment i in frame order, then -1: lele_hip_token_filter on that segment's ids alone, padded with -1 to W (ids outside [0, V) are
+ * dropped).  W = width; width == 0 means the longest segment's row count, at least 1.  A non-zero width smaller than a segment is an
+ * error that names the segment.  Everything is checked before anything is launched or resized; the [count, W] ids + counts are the
+ * form the ranks of a sharded batch exchange.  Graph-capturable after one eager run of the same layout. */
+int lele_hip_token_filter_segments(LeleCtx* ctx, const LeleTensor* ids, const int64_t* row_offsets, int64_t count, const LeleTensor* skip,
+                                   int64_t width, LeleBuf* out_ids, LeleBuf* out_counts, int64_t* out_shape, int32_t* out_rank);
 /* lele_hip_attention_view per segment: qkv f32 [R, P] holds Q, K, V of `heads` heads of width dh at columns q_offset, k_offset,
  * v_offset (head h at + h * dh); for every segment and head softmax(Q K^T * scale) V over THAT SEGMENT's rows only, queries and keys
  * alike (gemm.rs:112-222, norm.rs:8) -> out [R, heads * dh], heads merged.  Supported: dh == 128, every segment <= 512 rows, q_offset,

@@ -5,6 +5,7 @@
 //   lele_hip_argmax_last   <- /root/reference/examples/sensevoice/src/tokenizer.rs:50-61 (per-frame arg-max of the logits;
 //                             Iterator::max_by keeps the LAST of equal maxima)
 //   lele_hip_token_filter  <- tokenizer.rs:63-71  (drop blank / special ids, keep frame order; no CTC collapsing upstream)
+//   lele_hip_token_filter_segments <- the same per segment of a packed batch of ids -> [count, W] ids + counts
 //   lele_hip_image_preprocess   <- /root/reference/examples/yolo26n-seg/src/image.rs:62-111 (PIL-style nearest resize to
 //                             target x target, HWC u8 -> CHW f32 / 255)
 //   lele_hip_yolo_seg_postprocess <- image.rs:127-265 (score / box filter in query order, box rescale, per-detection mask =
@@ -100,6 +101,41 @@ __global__ __launch_bounds__(256) void token_filter_kernel(const int32_t* __rest
     }
     const int n = base;
     for (int64_t j = n + threadIdx.x; j < t; j += 256) o[j] = -1;
+    if (threadIdx.x == 0) counts[row] = n;
+}
+
+// token_filter_kernel's rule on a packed batch: workgroup b compacts ids[off[b], off[b + 1]) into row b of out [count, w] (w >= the
+// segment's rows: checked on the host), then -1 up to w
+__global__ __launch_bounds__(256) void token_filter_seg_kernel(const int32_t* __restrict__ ids, const int64_t* __restrict__ off,
+                                                               const uint8_t* __restrict__ skip, int64_t vocab, int64_t w,
+                                                               int32_t* __restrict__ out, int32_t* __restrict__ counts) {
+    const int64_t row = blockIdx.x;
+    const int64_t t = off[row + 1] - off[row];
+    const int32_t* p = ids + off[row];
+    int32_t* o = out + row * w;
+    __shared__ int wave_cnt[4];
+    __shared__ int base;
+    if (threadIdx.x == 0) base = 0;
+    __syncthreads();
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    for (int64_t c0 = 0; c0 < t; c0 += 256) {
+        const int64_t j = c0 + threadIdx.x;
+        const int32_t id = j < t ? p[j] : 0;
+        const bool keep = j < t && id >= 0 && id < vocab && skip[id] == 0;
+        const unsigned long long m = __ballot(keep);
+        const int before = __popcll(m & ((1ull << lane) - 1ull));
+        if (lane == 0) wave_cnt[wave] = __popcll(m);
+        __syncthreads();
+        int woff = 0;
+        for (int wv = 0; wv < wave; ++wv) woff += wave_cnt[wv];
+        const int b0 = base;
+        if (keep) o[b0 + woff + before] = id;
+        __syncthreads();
+        if (threadIdx.x == 0) base = b0 + wave_cnt[0] + wave_cnt[1] + wave_cnt[2] + wave_cnt[3];
+        __syncthreads();
+    }
+    const int n = base;
+    for (int64_t j = n + threadIdx.x; j < w; j += 256) o[j] = -1;
     if (threadIdx.x == 0) counts[row] = n;
 }
 
@@ -261,6 +297,43 @@ int lele_hip_token_filter(LeleCtx* ctx, const LeleTensor* ids, const LeleTensor*
         LELE_HIP_CHECK(hipGetLastError());
     }
     return set_shape_v(out_shape, out_rank, std::vector<int64_t>(ids->shape, ids->shape + ids->rank));
+}
+
+int lele_hip_token_filter_segments(LeleCtx* ctx, const LeleTensor* ids, const int64_t* row_offsets, int64_t count, const LeleTensor* skip,
+                                   int64_t width, LeleBuf* out_ids, LeleBuf* out_counts, int64_t* out_shape, int32_t* out_rank) {
+    LELE_REQUIRE(ctx && ids && skip && out_ids && out_counts, "token_filter_segments: NULL argument");
+    LELE_REQUIRE(ids->dtype == LELE_I32 && ids->rank == 1, "token_filter_segments: ids must be i32 [R]");
+    LELE_REQUIRE((skip->dtype == LELE_U8 || skip->dtype == LELE_I8) && skip->rank == 1, "token_filter_segments: skip must be a byte vector [V]");
+    LELE_REQUIRE(count >= 0 && row_offsets, "token_filter_segments: bad row_offsets (count %lld)", (long long)count);
+    const int64_t rows = ids->shape[0];
+    LELE_REQUIRE(row_offsets[0] == 0 && row_offsets[count] == rows, "token_filter_segments: row_offsets must run from 0 to R = %lld (got %lld .. %lld)",
+                 (long long)rows, (long long)row_offsets[0], (long long)row_offsets[count]);
+    LELE_REQUIRE(width >= 0, "token_filter_segments: negative width");
+    int64_t tmax = 0;
+    for (int64_t i = 0; i < count; ++i) {
+        const int64_t len = row_offsets[i + 1] - row_offsets[i];
+        LELE_REQUIRE(len >= 0, "token_filter_segments: row_offsets decrease at segment %lld", (long long)i);
+        LELE_REQUIRE(width == 0 || len <= width, "token_filter_segments: segment %lld has %lld rows, more than width = %lld", (long long)i,
+                     (long long)len, (long long)width);
+        tmax = std::max(tmax, len);
+    }
+    const int64_t w = width ? width : std::max<int64_t>(tmax, 1);
+    LELE_REQUIRE(count < (int64_t(1) << 31) && w < (int64_t(1) << 31), "token_filter_segments: more than 2^31 segments or columns");
+    LELE_HIP_CHECK(hipSetDevice(ctx->device));
+    const void* doff = nullptr;
+    if (count > 0) LELE_TRY(offsets_table(ctx, row_offsets, count, &doff));
+    LELE_TRY(ctx->arena_reset());
+    const void *di = nullptr, *ds = nullptr;
+    if (rows > 0) LELE_TRY(ctx->dev_ptr(ids, &di));
+    if (count > 0) LELE_TRY(ctx->dev_ptr(skip, &ds));
+    LELE_TRY(out_ids->reserve((size_t)std::max<int64_t>(count * w, 1) * 4));
+    LELE_TRY(out_counts->reserve((size_t)std::max<int64_t>(count, 1) * 4));
+    if (count > 0) {
+        hipLaunchKernelGGL(token_filter_seg_kernel, dim3((unsigned)count), dim3(256), 0, ctx->stream, (const int32_t*)di, (const int64_t*)doff,
+                           (const uint8_t*)ds, skip->shape[0], w, (int32_t*)out_ids->data, (int32_t*)out_counts->data);
+        LELE_HIP_CHECK(hipGetLastError());
+    }
+    return set_shape(out_shape, out_rank, {count, w});
 }
 
 int lele_hip_image_preprocess(LeleCtx* ctx, const LeleTensor* rgb, int32_t target, LeleBuf* out, int64_t* out_shape,

@@ -419,6 +419,7 @@ struct IgemmEpi {
     int* q_rowsum = nullptr;        // EM 2: sum over the row of (q - 128), accumulated over column blocks
     QParams* q_prm = nullptr;       // EM 2: the slices' parameters, published for the next GEMM's epilogue
     const int* row_seg = nullptr;   // packed batch (lele_hip_fused_quantized_linear_segments): row -> segment, the slice of prm[]
+    unsigned long long* arg_keys = nullptr;  // EM 3: [column tiles][rows], a tile's best argmax_key(value, column) per row (plain stores)
     // Everything that depends only on the row (slice parameters, row-sum term, output row pointer) or only on the
     // column (column sum, weight scale, bias) is computed once per row / column of a thread's tile, not per element.
     struct RowCtx {
@@ -481,12 +482,45 @@ struct IgemmEpi {
     }
 };
 
+// (value, column) as one unsigned key whose order is "greater value wins, equal values: greater column wins" (tokenizer.rs:50-61,
+// Iterator::max_by keeps the last of equal maxima).  The value's bits are made order-preserving (negative: all bits flipped, else the
+// sign bit set) after -0.0 is folded onto +0.0, which partial_cmp holds equal.  Every key of a real value is > 0, what a masked column carries.
+__device__ __forceinline__ unsigned long long argmax_key(float v, int col) {
+    unsigned b = __float_as_uint(v);
+    b = b == 0x80000000u ? 0u : b;
+    b ^= (unsigned)((int)b >> 31) | 0x80000000u;
+    return ((unsigned long long)b << 32) | (unsigned)col;
+}
+// the column tiles' keys [tiles][rows] -> ids: the greatest key's column.  Nothing depends on the order the tiles ran in.  A workgroup
+// takes 16 rows; 16 threads a row share its tiles (a row's whole list behind ONE thread is a chain of ~200 loads: 45 us at any size).
+__global__ __launch_bounds__(256) void argmax_finish_kernel(const unsigned long long* __restrict__ keys, int64_t rows, int tiles,
+                                                            int32_t* __restrict__ ids) {
+    __shared__ unsigned long long s_best[16][17];
+    const int rr = threadIdx.x & 15, g = threadIdx.x >> 4;
+    const int64_t r = (int64_t)blockIdx.x * 16 + rr;
+    unsigned long long best = 0ull;
+    if (r < rows) {
+#pragma unroll 8
+        for (int t = g; t < tiles; t += 16) best = max(best, keys[(int64_t)t * rows + r]);
+    }
+    s_best[g][rr] = best;
+    __syncthreads();
+    if (g == 0 && r < rows) {
+#pragma unroll
+        for (int o = 1; o < 16; ++o) best = max(best, s_best[o][rr]);
+        ids[r] = (int32_t)(unsigned)best;
+    }
+}
+
 // EM (epilogue mode) 0: the result as f32.  EM 1 / 2 are the two passes of the fused two-layer form, where the f32 result (the
 // hidden layer of a feed-forward block, 45 MB per configs[3] shard) never exists in HBM -- recomputing the product costs ~5 us of
 // matrix-core time against ~30 us of traffic for writing it and reading it twice:
 //   EM 1: only the per-slice maximum of the (ReLU) result, by atomic max into epi.slice_max;
 //   EM 2: the result again, quantised with the slice's now-known range exactly as qrows_kernel would quantise the stored f32
 //         (SIMD body: rint(fma(v, 1/scale, zp)), saturated), written as i8 with its row sums -- what the next GEMM consumes.
+// EM 3 is the greedy decode head (lele_hip_fused_quantized_linear_argmax): of the result only each row's arg-max leaves the chip, as
+//   one argmax_key per (row, column tile) in epi.arg_keys, which argmax_finish_kernel reduces.  Row context as EM 0 (any number of
+//   slices a tile).
 template <int BM, int BN, int WM, int WN, int BKB /* bytes of K per LDS tile: 64 or 128 */, int OCC = 1, int EM = 0>
 __global__ __launch_bounds__(WM* WN * 64) __attribute__((amdgpu_waves_per_eu(OCC))) void igemm_kernel(const int8_t* __restrict__ a, const int8_t* __restrict__ b,
                                                             int64_t rows, int n, int kp, int64_t b_batch_stride,
@@ -509,8 +543,8 @@ __global__ __launch_bounds__(WM* WN * 64) __attribute__((amdgpu_waves_per_eu(OCC
     gemm::tile_coords(tx, ty, tz);  // XCD-aware order (gemm_core.h)
     const int64_t m0 = (int64_t)ty * BM;
     // EM 1 / 2 (m >= BM): the tile's rows below `split` belong to slice s0, the rest to slice s0 + 1
-    const int s0 = EM ? (int)(m0 / epi.m) : 0;
-    const int split = EM ? (int)(((int64_t)s0 + 1) * epi.m - m0) : 0;
+    const int s0 = (EM == 1 || EM == 2) ? (int)(m0 / epi.m) : 0;
+    const int split = (EM == 1 || EM == 2) ? (int)(((int64_t)s0 + 1) * epi.m - m0) : 0;
     if (EM == 1 && tid < 2) s_mx[tid] = 0u;
     if (EM == 2 && tid < 2) {
         const int64_t nslices = epi.rows / epi.m;
@@ -688,6 +722,55 @@ __global__ __launch_bounds__(WM* WN * 64) __attribute__((amdgpu_waves_per_eu(OCC
             }
         }
         if (tx == 0 && tid < 2 && (tid == 0 || split < rows_here)) epi.q_prm[s0 + tid] = s_q[tid];
+        return;
+    }
+    if constexpr (EM == 3) {
+        static_assert(EM != 3 || TMT == 2, "the butterfly below folds 32 rows a lane onto the 32 lanes of a half-wave");
+        const int rows_here = (int)(rows - m0 < BM ? rows - m0 : BM);
+        // a lane holds 32 rows x TNT columns: its best key per row over its own valid columns (a padded column's context is the clamped
+        // column's, so it is masked to 0, below every real key)
+        unsigned long long key[TMT * 16];
+#pragma unroll
+        for (int i = 0; i < TMT; ++i)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int lr = wm * TMT * 32 + i * 32 + 4 * hv + (r & 3) + 8 * (r >> 2);
+                const IgemmEpi::RowCtx rc{s_ca[lr], s_rterm[lr], s_ds[lr], nullptr};
+                unsigned long long best = 0ull;
+#pragma unroll
+                for (int j = 0; j < TNT; ++j) {
+                    const unsigned long long kj = argmax_key(epi.value24(rc, cc[j], acc[i][j][r]), cols[j]);
+                    best = max(best, cols[j] < n ? kj : 0ull);
+                }
+                key[i * 16 + r] = best;
+            }
+        // across the 32 lanes of a half-wave (the columns): each step a lane hands half of its rows to its partner and folds the
+        // partner's other half into its own, so 16 + 8 + 4 + 2 + 1 exchanges leave lane l31 with row l31's maximum
+#pragma unroll
+        for (int s = 0; s < 5; ++s) {
+            const int half = 16 >> s;
+            const bool up = (lane & half) != 0;
+#pragma unroll
+            for (int t = 0; t < half; ++t) {
+                const unsigned long long send = up ? key[t] : key[t + half];
+                const unsigned long long keep = up ? key[t + half] : key[t];
+                key[t] = max(keep, (unsigned long long)__shfl_xor(send, half));
+            }
+        }
+        // across the WN waves in the K loop's LDS (its last barrier has passed), then one store per row of the tile
+        unsigned long long* const s_key = reinterpret_cast<unsigned long long*>(igemm_lds);  // [WN][BM]
+        {
+            const int rr = l31 & 15;
+            const int lr = wm * TMT * 32 + (l31 >> 4) * 32 + 4 * hv + (rr & 3) + 8 * (rr >> 2);
+            s_key[wn * BM + lr] = key[0];
+        }
+        __syncthreads();
+        for (int t = tid; t < rows_here; t += NT) {
+            unsigned long long best = s_key[t];
+#pragma unroll
+            for (int w = 1; w < WN; ++w) best = max(best, s_key[w * BM + t]);
+            epi.arg_keys[(int64_t)tx * rows + m0 + t] = best;
+        }
         return;
     }
     if (epi.flags & 2) {
@@ -1043,6 +1126,24 @@ int launch_igemm_hidden(LeleCtx* ctx, int em, const int8_t* aq, const int8_t* wt
     auto kern = em == 1 ? igemm_kernel<128, 128, 2, 4, 128, 1, 1> : igemm_kernel<128, 128, 2, 4, 128, 1, 2>;
     LELE_HIP_CHECK(ensure_dyn_lds(reinterpret_cast<const void*>(kern), (int)lds));
     hipLaunchKernelGGL(kern, grid, dim3(512), lds, ctx->stream, aq, wt, rows, n, kp, (int64_t)0, m, epi);
+    LELE_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
+// the greedy head (EM 3): the tiled kernel in its big-shape configuration, then the best key's low word per row as ids.
+// `keys`: argmax_key_bytes(rows, n)
+size_t argmax_key_bytes(int64_t rows, int64_t n) { return (size_t)rows * (size_t)((n + 127) / 128) * 8; }
+int launch_igemm_argmax(LeleCtx* ctx, const int8_t* aq, const int8_t* wt, int64_t rows, int n, int kp, int m, const IgemmEpi& epi_in,
+                        unsigned long long* keys, int32_t* ids) {
+    LELE_REQUIRE(rows < (int64_t(128) * 65535), "quantized GEMM: more than 128 x 65535 rows");
+    constexpr size_t lds = (size_t)2 * (128 + 128) * (128 + 16);
+    IgemmEpi epi = epi_in;
+    epi.arg_keys = keys;
+    const dim3 grid((n + 127) / 128, (unsigned)((rows + 127) / 128));
+    auto kern = igemm_kernel<128, 128, 2, 4, 128, 1, 3>;
+    LELE_HIP_CHECK(ensure_dyn_lds(reinterpret_cast<const void*>(kern), (int)lds));
+    hipLaunchKernelGGL(kern, grid, dim3(512), lds, ctx->stream, aq, wt, rows, n, kp, (int64_t)0, m, epi);
+    hipLaunchKernelGGL(argmax_finish_kernel, dim3((unsigned)((rows + 15) / 16)), dim3(256), 0, ctx->stream, (const unsigned long long*)keys, rows, (int)grid.x, ids);
     LELE_HIP_CHECK(hipGetLastError());
     return 0;
 }
@@ -1435,6 +1536,7 @@ struct QReq {  // what the caller wants around the product
     int relu = 0;
     const LeleTensor *res1 = nullptr, *res2 = nullptr;  // same-shape residuals (res_same_shape), added in this order
     LnReq* ln = nullptr;
+    int argmax = 0;  // the greedy head: `out` receives argmax_last of the result as i32 [rows], the result itself is never stored
 };
 // one layer, validated and staged: what a route's body reads
 struct QLayer {
@@ -1520,10 +1622,12 @@ enum class QRoute {
     AsLn,      // ... with the requested LayerNorm in its epilogue
     AsLnFsmn,  // ... and the FSMN memory block computed in the kernel as the first residual
     Tiled,     // rows -> i8 in HBM (qrows_kernel), then the tiled i8 GEMM (launch_igemm)
+    TiledArgmax,  // ... with the arg-max epilogue (igemm_kernel EM 3): the only route of a QReq::argmax request
 };
 // The one place that chooses.  dx: the staged input; dout: out->data after its reserve (the one-pass kernels move 16 bytes at a
 // time).  A LayerNorm that the chosen kernel cannot take is left to the caller (LnReq::done stays false).
 QRoute fql_route(LeleCtx* ctx, const QCall& c, const QReq& rq, const void* dx, const void* dout) {
+    if (rq.argmax) return QRoute::TiledArgmax;
     const bool aligned = rs_aligned(rq.res1) && rs_aligned(rq.res2) && aligned16(dout);
     if (aligned && rs_fits(ctx, c.rows, c.n, c.k))
         // K = 512 exactly, 16-byte aligned rows: the loaders reduce their parameters from the {min, max} partials, nothing runs in front
@@ -1584,8 +1688,8 @@ int run_as(LeleCtx* ctx, const QLayer& l, QRoute route, LnReq* ln) {
     return 0;
 }
 
-// three-kernel chain: rows -> i8 (+ row sums) in HBM, then the tiled i8 GEMM
-int run_tiled(LeleCtx* ctx, const QLayer& l) {
+// three-kernel chain: rows -> i8 (+ row sums) in HBM, then the tiled i8 GEMM (argmax: its EM 3 form, l.out receives the ids)
+int run_tiled(LeleCtx* ctx, const QLayer& l, bool argmax = false) {
     const QCall& c = l.c;
     const int kp = (int)((c.k + 15) & ~int64_t(15));
     PackedW pw;
@@ -1596,6 +1700,13 @@ int run_tiled(LeleCtx* ctx, const QLayer& l) {
     LELE_TRY(launch_qrows(ctx, c.rows <= 2048 || (kp <= 2048 && !lab_int("LELE_HIP_QROWS_STREAM", 0)), l.x, c.rows, (int)c.k, kp, (int)c.m, l.prm,
                           (int8_t*)aq, (int*)rs, l.partial, l.nblk, nullptr, nullptr, nullptr));
     LELE_TRY(qprof_mark(ctx, 2));
+    if (argmax) {
+        void* keys = nullptr;
+        LELE_TRY(ctx->arena_alloc(argmax_key_bytes(c.rows, c.n), &keys));
+        LELE_TRY(launch_igemm_argmax(ctx, (const int8_t*)aq, pw.wt, c.rows, (int)c.n, kp, (int)c.m, make_epi(l, nullptr, (const int*)rs, pw.col_sums),
+                                     (unsigned long long*)keys, (int32_t*)l.out->data));
+        return qprof_mark(ctx, 3);
+    }
     IgemmEpi epi = make_epi(l, (float*)l.out->data, (const int*)rs, pw.col_sums);
     // small-problem kernel: publish one {min, max} pair per workgroup next to the result (for the linear that may follow)
     if (((c.rows + 63) / 64) * ((c.n + 63) / 64) < 2 * (int64_t)ctx->num_cus) LELE_TRY(attach_blockstat(l.out, c, &epi));
@@ -1610,10 +1721,14 @@ int run_tiled(LeleCtx* ctx, const QLayer& l) {
 int fql_impl(LeleCtx* ctx, const LeleTensor* input, const QW& w, const QReq& rq, LeleBuf* out, int64_t* out_shape, int32_t* out_rank) {
     LELE_REQUIRE(ctx && input && w.w && w.scale && out, "fused_quantized_linear: NULL argument");
     QLayer l;
-    LELE_TRY(describe_call("fused_quantized_linear", input, w, &l.c));
-    const QCall& c = l.c;
+    LELE_TRY(describe_call(rq.argmax ? "fused_quantized_linear_argmax" : "fused_quantized_linear", input, w, &l.c));
+    QCall& c = l.c;
+    if (rq.argmax) {  // ids: the input's shape without its last axis, one i32 a row
+        LELE_REQUIRE(c.n >= 1 && c.k >= 1, "fused_quantized_linear_argmax: empty K or N (K = %lld, N = %lld)", (long long)c.k, (long long)c.n);
+        c.shp.pop_back();
+    }
     LELE_HIP_CHECK(hipSetDevice(ctx->device));
-    LELE_TRY(out->reserve((size_t)c.rows * c.n * 4));
+    LELE_TRY(out->reserve(rq.argmax ? (size_t)c.rows * 4 : (size_t)c.rows * c.n * 4));
     if (c.rows == 0 || c.n == 0) return set_shape_v(out_shape, out_rank, c.shp);
     LELE_TRY(ctx->arena_reset());
     const void *dx = nullptr, *dws = nullptr, *db = nullptr, *dr1 = nullptr, *dr2 = nullptr;
@@ -1639,6 +1754,7 @@ int fql_impl(LeleCtx* ctx, const LeleTensor* input, const QW& w, const QReq& rq,
         case QRoute::AsLn:
         case QRoute::AsLnFsmn: LELE_TRY(run_as(ctx, l, route, rq.ln)); break;
         case QRoute::Tiled: LELE_TRY(run_tiled(ctx, l)); break;
+        case QRoute::TiledArgmax: LELE_TRY(run_tiled(ctx, l, true)); break;
     }
     return set_shape_v(out_shape, out_rank, c.shp);
 }
@@ -1844,31 +1960,26 @@ int ffn_impl(LeleCtx* ctx, const LeleTensor* input, const QW& w1, const QW& w2, 
     return set_shape_v(out_shape, out_rank, c2.shp);
 }
 
-}  // namespace
-
-extern "C" {
-
-int lele_hip_fused_quantized_linear(LeleCtx* ctx, const LeleTensor* input, const LeleTensor* weight_int8,
-                                    const LeleTensor* weight_scale, const LeleTensor* weight_zero,
-                                    const LeleTensor* bias, int apply_relu, LeleBuf* out, int64_t* out_shape,
-                                    int32_t* out_rank) {
-    return fql_impl(ctx, input, {weight_int8, weight_scale, weight_zero, bias}, QReq{apply_relu}, out, out_shape, out_rank);
-}
-
 /* Packed batch: every segment of input [R, K] is a batch slice of its own (quantization.rs:104-128).  Three things know about
  * segments -- the range pass (one {min, max} per segment), the row quantiser's parameter lookup and the epilogue's row_ctx, the last
  * two through a row -> segment map -- and the integer sums are exact, so a segment's rows are the dense entry point's on it alone. */
-int lele_hip_fused_quantized_linear_segments(LeleCtx* ctx, const LeleTensor* input, const int64_t* row_offsets, int64_t count,
-                                             const LeleTensor* weight_int8, const LeleTensor* weight_scale, const LeleTensor* weight_zero,
-                                             const LeleTensor* bias, int apply_relu, LeleBuf* out, int64_t* out_shape, int32_t* out_rank) {
-    LELE_REQUIRE(ctx && input && weight_int8 && weight_scale && out, "fused_quantized_linear_segments: NULL argument");
+int fql_segments_impl(LeleCtx* ctx, const char* who, int argmax, const LeleTensor* input, const int64_t* row_offsets, int64_t count,
+                      const LeleTensor* weight_int8, const LeleTensor* weight_scale, const LeleTensor* weight_zero,
+                      const LeleTensor* bias, int apply_relu, LeleBuf* out, int64_t* out_shape, int32_t* out_rank) {
+    LELE_REQUIRE(ctx && input && weight_int8 && weight_scale && out, "%s: NULL argument", who);
     int64_t rows = 0, k = 0, tmax = 0;
-    LELE_TRY(seg_offsets(input, row_offsets, count, &rows, &k, &tmax, "fused_quantized_linear_segments"));
+    LELE_TRY(seg_offsets(input, row_offsets, count, &rows, &k, &tmax, who));
     QLayer l;  // input [R, K]: one "slice" of R rows, whose rows find their segment's parameters through row_seg
-    LELE_TRY(describe_call("fused_quantized_linear", input, {weight_int8, weight_scale, weight_zero, bias}, &l.c));
-    const QCall& c = l.c;
+    LELE_TRY(describe_call(argmax ? who : "fused_quantized_linear", input, {weight_int8, weight_scale, weight_zero, bias}, &l.c));
+    QCall& c = l.c;
     const int64_t n = c.n;
-    LELE_REQUIRE(rows < (int64_t(1) << 31) && count < (int64_t(1) << 31), "fused_quantized_linear_segments: more than 2^31 rows or segments");
+    LELE_REQUIRE(rows < (int64_t(1) << 31) && count < (int64_t(1) << 31), "%s: more than 2^31 rows or segments", who);
+    size_t out_bytes = (size_t)rows * n * 4;
+    if (argmax) {  // ids [R]: one i32 a row, the result itself is never stored
+        LELE_REQUIRE(n >= 1 && k >= 1, "%s: empty K or N (K = %lld, N = %lld)", who, (long long)k, (long long)n);
+        c.shp.pop_back();
+        out_bytes = (size_t)rows * 4;
+    }
     LELE_HIP_CHECK(hipSetDevice(ctx->device));
     const void* tab = nullptr;
     if (rows > 0 && n > 0 && k > 0) {
@@ -1876,7 +1987,7 @@ int lele_hip_fused_quantized_linear_segments(LeleCtx* ctx, const LeleTensor* inp
         LELE_TRY(layout_table(ctx, "qseg", 0, 0, row_offsets, count, build_rowseg, &arg, &tab));
     }
     if (rows == 0 || n == 0 || k == 0) {
-        LELE_TRY(out->reserve((size_t)rows * n * 4));
+        LELE_TRY(out->reserve(out_bytes));
         return set_shape_v(out_shape, out_rank, c.shp);
     }
     const int64_t* doff = (const int64_t*)tab;
@@ -1906,20 +2017,58 @@ int lele_hip_fused_quantized_linear_segments(LeleCtx* ctx, const LeleTensor* inp
     const int kp = (int)((k + 15) & ~int64_t(15));
     PackedW pw;
     LELE_TRY(packed_weights_of(ctx, weight_int8, nullptr, 1, (int)k, (int)n, kp, &pw));
-    void *aq = nullptr, *rs = nullptr;
+    void *aq = nullptr, *rs = nullptr, *keys = nullptr;
     LELE_TRY(ctx->arena_alloc((size_t)rows * kp, &aq));
     LELE_TRY(ctx->arena_alloc((size_t)rows * 4, &rs));
+    if (argmax) LELE_TRY(ctx->arena_alloc(argmax_key_bytes(rows, n), &keys));
     // every fallible step is behind us: `out` is as it was until here (reserve clears any producer-side statistics of `out`;
     // those of `input` describe equal slices and are not read)
-    LELE_TRY(out->reserve((size_t)rows * n * 4));
+    LELE_TRY(out->reserve(out_bytes));
     LELE_TRY(launch_qrows(ctx, rows <= 2048 || kp <= 2048, l.x, rows, (int)k, kp, (int)rows, l.prm, (int8_t*)aq, (int*)rs, (const float*)partial,
                           nblk, nullptr, nullptr, drowseg));
     LELE_TRY(qprof_mark(ctx, 2));
-    IgemmEpi epi = make_epi(l, (float*)out->data, (const int*)rs, pw.col_sums);
+    IgemmEpi epi = make_epi(l, argmax ? nullptr : (float*)out->data, (const int*)rs, pw.col_sums);
     epi.row_seg = drowseg;
-    LELE_TRY(launch_igemm(ctx, (const int8_t*)aq, pw.wt, rows, (int)n, kp, (int)rows, epi));
+    if (argmax) LELE_TRY(launch_igemm_argmax(ctx, (const int8_t*)aq, pw.wt, rows, (int)n, kp, (int)rows, epi, (unsigned long long*)keys, (int32_t*)out->data));
+    else LELE_TRY(launch_igemm(ctx, (const int8_t*)aq, pw.wt, rows, (int)n, kp, (int)rows, epi));
     LELE_TRY(qprof_mark(ctx, 3));
     return set_shape_v(out_shape, out_rank, c.shp);
+}
+
+}  // namespace
+
+extern "C" {
+
+int lele_hip_fused_quantized_linear(LeleCtx* ctx, const LeleTensor* input, const LeleTensor* weight_int8,
+                                    const LeleTensor* weight_scale, const LeleTensor* weight_zero,
+                                    const LeleTensor* bias, int apply_relu, LeleBuf* out, int64_t* out_shape,
+                                    int32_t* out_rank) {
+    return fql_impl(ctx, input, {weight_int8, weight_scale, weight_zero, bias}, QReq{apply_relu}, out, out_shape, out_rank);
+}
+
+int lele_hip_fused_quantized_linear_segments(LeleCtx* ctx, const LeleTensor* input, const int64_t* row_offsets, int64_t count,
+                                             const LeleTensor* weight_int8, const LeleTensor* weight_scale, const LeleTensor* weight_zero,
+                                             const LeleTensor* bias, int apply_relu, LeleBuf* out, int64_t* out_shape, int32_t* out_rank) {
+    return fql_segments_impl(ctx, "fused_quantized_linear_segments", 0, input, row_offsets, count, weight_int8, weight_scale, weight_zero, bias,
+                             apply_relu, out, out_shape, out_rank);
+}
+
+/* The greedy decode head (tokenizer.rs:50-61 behind quantization.rs:77-169): argmax_last(fused_quantized_linear(.., apply_relu = 0)) bit for
+ * bit, with the arg-max inside the GEMM's epilogue (igemm_kernel EM 3) -- the logits are never stored. */
+int lele_hip_fused_quantized_linear_argmax(LeleCtx* ctx, const LeleTensor* input, const LeleTensor* weight_int8, const LeleTensor* weight_scale,
+                                           const LeleTensor* weight_zero, const LeleTensor* bias, LeleBuf* out_ids, int64_t* out_shape,
+                                           int32_t* out_rank) {
+    QReq rq;
+    rq.argmax = 1;
+    return fql_impl(ctx, input, {weight_int8, weight_scale, weight_zero, bias}, rq, out_ids, out_shape, out_rank);
+}
+
+int lele_hip_fused_quantized_linear_argmax_segments(LeleCtx* ctx, const LeleTensor* input, const int64_t* row_offsets, int64_t count,
+                                                    const LeleTensor* weight_int8, const LeleTensor* weight_scale,
+                                                    const LeleTensor* weight_zero, const LeleTensor* bias, LeleBuf* out_ids,
+                                                    int64_t* out_shape, int32_t* out_rank) {
+    return fql_segments_impl(ctx, "fused_quantized_linear_argmax_segments", 1, input, row_offsets, count, weight_int8, weight_scale, weight_zero,
+                             bias, 0, out_ids, out_shape, out_rank);
 }
 
 int lele_hip_fused_quantized_linear_residual(LeleCtx* ctx, const LeleTensor* input, const LeleTensor* weight_int8,

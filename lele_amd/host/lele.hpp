@@ -987,6 +987,35 @@ inline TensorView fused_quantized_linear_segments(const TensorView& input, const
                                                    out.raw(), sh.dims, &sh.rank));
     LELE_RET(out, LELE_F32);
 }
+// the greedy decode head: argmax_last(fused_quantized_linear(.., apply_relu = false)) bit for bit, the logits never stored
+inline TensorView fused_quantized_linear_argmax(const TensorView& input, const TensorView& weight_int8, const TensorView& weight_scale,
+                                                const TensorView& weight_zero, const TensorView* bias, Buffer& out) {
+    Shape sh;
+    LeleTensor a = input.c(), b = weight_int8.c(), s = weight_scale.c(), z = weight_zero.c();
+    Opt ob(bias);
+    check(lele_hip_fused_quantized_linear_argmax(ctx(), &a, &b, &s, &z, ob.p, out.raw(), sh.dims, &sh.rank));
+    LELE_RET(out, LELE_I32);
+}
+inline TensorView fused_quantized_linear_argmax_segments(const TensorView& input, const std::vector<int64_t>& offsets,
+                                                         const TensorView& weight_int8, const TensorView& weight_scale,
+                                                         const TensorView& weight_zero, const TensorView* bias, Buffer& out) {
+    Shape sh;
+    LeleTensor a = input.c(), b = weight_int8.c(), s = weight_scale.c(), z = weight_zero.c();
+    Opt ob(bias);
+    check(lele_hip_fused_quantized_linear_argmax_segments(ctx(), &a, offsets.data(), (int64_t)offsets.size() - 1, &b, &s, &z, ob.p, out.raw(),
+                                                          sh.dims, &sh.rank));
+    LELE_RET(out, LELE_I32);
+}
+// token_filter per segment of packed ids [R] -> ([count, W] ids padded with -1, [count] counts); width 0 = the longest segment
+inline std::pair<TensorView, TensorView> token_filter_segments(const TensorView& ids, const std::vector<int64_t>& offsets,
+                                                               const TensorView& skip, int64_t width, Buffer& out_ids, Buffer& out_counts) {
+    Shape sh;
+    LeleTensor ti = ids.c(), ts = skip.c();
+    check(lele_hip_token_filter_segments(ctx(), &ti, offsets.data(), (int64_t)offsets.size() - 1, &ts, width, out_ids.raw(), out_counts.raw(),
+                                         sh.dims, &sh.rank));
+    std::vector<int64_t> s(sh.dims, sh.dims + sh.rank), r(sh.dims, sh.dims + (sh.rank > 0 ? sh.rank - 1 : 0));
+    return {TensorView::from_device(out_ids, s, LELE_I32), TensorView::from_device(out_counts, r, LELE_I32)};
+}
 inline TensorView attention_segments(const TensorView& qkv, const std::vector<int64_t>& offsets, int64_t q_offset, int64_t k_offset,
                                      int64_t v_offset, int64_t heads, int64_t dh, const TensorView* scale, Buffer& out) {
     Shape sh;

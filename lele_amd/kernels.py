@@ -1216,6 +1216,48 @@ def fused_quantized_linear_segments(input, offsets, weight_int8, weight_scale, w
     return TensorView(_lib.DevTensor(out, sh.get(), np.float32))
 
 
+def fused_quantized_linear_argmax(input, weight_int8, weight_scale, weight_zero, bias, out=None, ctx=None):
+    """the greedy decode head: argmax_last(fused_quantized_linear(input, .., apply_relu=False)) bit for bit -> int32, the input's shape
+    without its last axis.  The arg-max is taken in the GEMM's epilogue: the logits are never stored (tokenizer.rs:50-61)."""
+    ctx = _ctx(ctx)
+    keep = []
+    out = out or ctx.buf()
+    sh = _lib.OutShape()
+    _lib.check(_lib.lib().lele_hip_fused_quantized_linear_argmax(
+        ctx._h, _t(input, keep), _t(weight_int8, keep), _t(weight_scale, keep), _t(weight_zero, keep), _t(bias, keep), out._h, sh.shape,
+        C.byref(sh.rank)))
+    return TensorView(_lib.DevTensor(out, sh.get(), np.int32))
+
+
+def fused_quantized_linear_argmax_segments(input, offsets, weight_int8, weight_scale, weight_zero, bias, out=None, ctx=None):
+    """fused_quantized_linear_argmax with every segment of the packed input [R, K] as a batch slice of its own -> int32 [R]: rows
+    offsets[i] .. offsets[i + 1] are, bit for bit, the dense call on that range alone"""
+    ctx = _ctx(ctx)
+    keep = []
+    out = out or ctx.buf()
+    sh = _lib.OutShape()
+    off = _offsets(offsets)
+    _lib.check(_lib.lib().lele_hip_fused_quantized_linear_argmax_segments(
+        ctx._h, _t(input, keep), _lib.i64_ptr(off), C.c_int64(len(off) - 1), _t(weight_int8, keep), _t(weight_scale, keep),
+        _t(weight_zero, keep), _t(bias, keep), out._h, sh.shape, C.byref(sh.rank)))
+    return TensorView(_lib.DevTensor(out, sh.get(), np.int32))
+
+
+def token_filter_segments(ids, offsets, skip, width=0, out_ids=None, out_counts=None, ctx=None):
+    """token_filter per segment of packed ids int32 [R] -> (ids int32 [count, W] padded with -1, counts int32 [count]); W = width, or
+    the longest segment's rows (at least 1) when width == 0.  The form lele_amd.sharded gathers."""
+    ctx = _ctx(ctx)
+    keep = []
+    oi, oc = out_ids or ctx.buf(), out_counts or ctx.buf()
+    sh = _lib.OutShape()
+    off = _offsets(offsets)
+    _lib.check(_lib.lib().lele_hip_token_filter_segments(
+        ctx._h, _t(ids, keep), _lib.i64_ptr(off), C.c_int64(len(off) - 1), _t(skip, keep), C.c_int64(int(width)), oi._h, oc._h, sh.shape,
+        C.byref(sh.rank)))
+    shape = sh.get()
+    return TensorView(_lib.DevTensor(oi, shape, np.int32)), TensorView(_lib.DevTensor(oc, shape[:-1], np.int32))
+
+
 def attention_segments(qkv, offsets, heads, dh, scale=None, q_offset=0, k_offset=None, v_offset=None, out=None, ctx=None):
     """softmax(Q K^T * scale) V per segment and head over that segment's rows only: qkv [R, P] holds Q | K | V at the column offsets
     (default: the packed projection, 0, heads * dh, 2 * heads * dh) -> [R, heads * dh], heads merged.  dh == 128, segments of at most

@@ -100,6 +100,7 @@ class Encoder:
         self.scale = Weight(np.array([DH ** -0.5], np.float32))
         # one workspace slot per distinct live value, as lele's compile-time buffer plan would assign
         self.ws = [ctx.buf() for _ in range(16)]
+        self.dec = [ctx.buf() for _ in range(3)]   # the greedy head's results: frame ids, kept ids, counts
 
     def ql(self, x, p, relu, slot):
         return self.K.fused_quantized_linear(x, p.w, p.scale, p.zero, p.bias, relu, out=self.ws[slot], ctx=self.ctx)
@@ -163,12 +164,22 @@ class Encoder:
         xn = self.K.layer_norm(x, self.ln_out[0], self.ln_out[1], -1, 1e-5, out=self.ws[1], ctx=self.ctx)
         return self.ql(xn, self.ctc, False, 2)
 
-    def forward(self, feats, taps=None):
-        """feats: [B, T, 560] device tensor (LFR + CMVN output) -> logits [B, T+4, VOCAB].  taps: {layer index: dict} to fill"""
+    def trunk(self, feats, taps=None):
         x = self.embed(feats)
         for i in range(len(self.layers)):
             x = self.layer(x, i, None if taps is None else taps.get(i))
-        return self.head(x)
+        return x
+
+    def forward(self, feats, taps=None):
+        """feats: [B, T, 560] device tensor (LFR + CMVN output) -> logits [B, T+4, VOCAB].  taps: {layer index: dict} to fill"""
+        return self.head(self.trunk(feats, taps))
+
+    def greedy(self, feats):
+        """feats: [B, T, 560] -> greedy frame ids int32 [B, T+4] = argmax_last(forward(feats)) bit for bit, with the arg-max inside the
+        CTC projection: the [B, T+4, VOCAB] logits are never stored"""
+        p = self.ctc
+        xn = self.K.layer_norm(self.trunk(feats), self.ln_out[0], self.ln_out[1], -1, 1e-5, out=self.ws[1], ctx=self.ctx)
+        return self.K.fused_quantized_linear_argmax(xn, p.w, p.scale, p.zero, p.bias, out=self.dec[0], ctx=self.ctx)
 
     # ---- the packed batch: utterances of different lengths as x [R, D] + offsets, each computed exactly as if it ran alone
     def qls(self, x, off, p, relu, slot):
@@ -208,17 +219,30 @@ class Encoder:
         """feats: packed [R, 560] device tensor (compute_segments -> Cmvn.compute_segments), offsets [count + 1] -> (logits
         [R + 4 * count, VOCAB], offsets' with offsets'[i] = offsets[i] + 4 * i): every utterance gets the four prompt rows and runs
         through the encoder exactly as if it were alone.  taps: {layer index: dict} to fill, plus "embed" / "head" for the two ends"""
+        x, xn, off = self.trunk_segments(feats, offsets, taps)
+        logits = self.qls(xn, off, self.ctc, False, 2)
+        if taps is not None and "head" in taps:
+            taps["head"].update(x=x.numpy(), xn=xn.numpy(), logits=logits.numpy())
+        return logits, off
+
+    def trunk_segments(self, feats, offsets, taps=None):
+        """everything of forward_segments in front of the CTC projection -> (x, layer_norm(x), offsets')"""
         K, ctx, ws = self.K, self.ctx, self.ws
         x, off = K.segments_prepend(feats, offsets, self.prompt, out=ws[0], ctx=ctx)      # prompt [1, 4, 560]: four rows
         if taps is not None and "embed" in taps:
             taps["embed"].update(x=x.numpy())
         for i in range(len(self.layers)):
             x = self.layer_segments(x, off, i, None if taps is None else taps.get(i))
-        xn = K.layer_norm(x, self.ln_out[0], self.ln_out[1], -1, 1e-5, out=ws[1], ctx=ctx)
-        logits = self.qls(xn, off, self.ctc, False, 2)
-        if taps is not None and "head" in taps:
-            taps["head"].update(x=x.numpy(), xn=xn.numpy(), logits=logits.numpy())
-        return logits, off
+        return x, K.layer_norm(x, self.ln_out[0], self.ln_out[1], -1, 1e-5, out=ws[1], ctx=ctx), off
+
+    def greedy_segments(self, feats, offsets, skip, width=0):
+        """feats: packed [R, 560], offsets [count + 1], skip uint8 [VOCAB] -> (ids int32 [count, W], counts int32 [count]): per utterance
+        the kept greedy ids of forward_segments' logits (token_filter of their argmax_last), padded with -1 -- the form lele_amd.sharded
+        gathers.  W = width, or the longest utterance's rows + 4 when 0.  The logits are never stored."""
+        K, ctx, p = self.K, self.ctx, self.ctc
+        _, xn, off = self.trunk_segments(feats, offsets)
+        ids = K.fused_quantized_linear_argmax_segments(xn, off, p.w, p.scale, p.zero, p.bias, out=self.dec[0], ctx=ctx)
+        return K.token_filter_segments(ids, off, skip, width, out_ids=self.dec[1], out_counts=self.dec[2], ctx=ctx)
 
 
 def encoder_arrays(enc):
@@ -229,12 +253,14 @@ def encoder_arrays(enc):
                         "out": ql(L.out), "ffn1": ql(L.ffn1), "ffn2": ql(L.ffn2), "fsmn": L.fsmn.arr} for L in enc.layers]}
 
 
-def encoder_onnx(enc, batch):
+def encoder_onnx(enc, batch, head=True):
     """The same assumed topology as an ONNX model (bytes), built from the Encoder's weights: what a SenseVoice export
     with dynamically quantised linears looks like to lele's compiler.  `lele_amd.compiler` must turn it back into the
-    call sequence of Encoder.forward."""
+    call sequence of Encoder.forward.  head=False: the model ends in front of the CTC projection, its output `xf` [batch, t4, 512] is
+    what kernels.fused_quantized_linear_argmax takes with enc.ctc (the greedy head: ids without the logits)."""
     from lele_amd.compiler import onnx_pb as pb
-    g = pb.Graph([], [pb.ValueInfo("feats", pb.FLOAT, [batch, "t", 560])], [pb.ValueInfo("logits", pb.FLOAT, [batch, "t4", VOCAB])])
+    out = pb.ValueInfo("logits", pb.FLOAT, [batch, "t4", VOCAB]) if head else pb.ValueInfo("xf", pb.FLOAT, [batch, "t4", D])
+    g = pb.Graph([], [pb.ValueInfo("feats", pb.FLOAT, [batch, "t", 560])], [out])
     I = g.initializer
     I += [pb.Tensor("prompt", enc.prompt.arr), pb.Tensor("att_scale", enc.scale.arr), pb.Tensor("shape_heads", np.array([0, 0, HEADS, DH], np.int64)),
           pb.Tensor("shape_merge", np.array([0, 0, D], np.int64)), pb.Tensor("split_qkv", np.array([D, D, D], np.int64))]
@@ -270,7 +296,8 @@ def encoder_onnx(enc, batch):
         x = t("x2")
     I += [pb.Tensor("lnf_g", enc.ln_out[0].arr), pb.Tensor("lnf_b", enc.ln_out[1].arr)]
     g.node.append(pb.Node("LayerNormalization", [x, "lnf_g", "lnf_b"], ["xf"], axis=-1, epsilon=1e-5))
-    enc.ctc.onnx(g, "xf", "logits", False, "ctc")
+    if head:
+        enc.ctc.onnx(g, "xf", "logits", False, "ctc")
     return pb.Model(g, opset=17).serialize()
 
 
