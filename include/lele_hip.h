@@ -623,6 +623,37 @@ int lele_hip_fused_quantized_linear_argmax_segments(LeleCtx* ctx, const LeleTens
  * form the ranks of a sharded batch exchange.  Graph-capturable after one eager run of the same layout. */
 int lele_hip_token_filter_segments(LeleCtx* ctx, const LeleTensor* ids, const int64_t* row_offsets, int64_t count, const LeleTensor* skip,
                                    int64_t width, LeleBuf* out_ids, LeleBuf* out_counts, int64_t* out_shape, int32_t* out_rank);
+/* The greedy decode head with the winner's confidence (examples/sensevoice/src/tokenizer.rs:50-71 behind quantization.rs:77-169):
+ * out_ids as lele_hip_fused_quantized_linear_argmax, bit for bit; out_logprob = f32 of the same shape, the log of the winner's soft-max
+ * posterior, logprob = -ln sum_j exp(v_j - v_id) over the row's N logits v (the result elements of lele_hip_fused_quantized_linear,
+ * apply_relu = 0), in [-ln N, 0]; N == 1 gives exactly 0.0.  It is formed from differences to the maximum inside the GEMM's epilogue,
+ * never as v_id - (max + ln sum): within 1e-5 of the float64 value of that formula for any offset of the logits.  The logits are never
+ * stored.  A row holding a NaN or +-inf logit has an unspecified score, as its id.  The two buffers must be distinct.  rows == 0 gives
+ * empty results of the right shape; K == 0 or N == 0 is an error.  Everything is checked before anything is launched or resized;
+ * graph-capturable after one eager run of the same shape. */
+int lele_hip_fused_quantized_linear_argmax_logprob(LeleCtx* ctx, const LeleTensor* input, const LeleTensor* weight_int8,
+                                                   const LeleTensor* weight_scale, const LeleTensor* weight_zero,
+                                                   const LeleTensor* bias_or_null, LeleBuf* out_ids, LeleBuf* out_logprob, int64_t* out_shape,
+                                                   int32_t* out_rank);
+/* ... of a packed batch (tokenizer.rs:50-71, quantization.rs:77-169): input f32 [R, K] -> out_ids i32 [R], out_logprob f32 [R]; the
+ * checks, layout table and per-segment range pass of lele_hip_fused_quantized_linear_argmax_segments, so segment i's ids and scores are
+ * bit for bit lele_hip_fused_quantized_linear_argmax_logprob of input[off[i]:off[i+1]] alone.  0-row segments are skipped.  Graph-capturable
+ * after one eager run of the same layout. */
+int lele_hip_fused_quantized_linear_argmax_logprob_segments(LeleCtx* ctx, const LeleTensor* input, const int64_t* row_offsets, int64_t count,
+                                                            const LeleTensor* weight_int8, const LeleTensor* weight_scale,
+                                                            const LeleTensor* weight_zero, const LeleTensor* bias_or_null, LeleBuf* out_ids,
+                                                            LeleBuf* out_logprob, int64_t* out_shape, int32_t* out_rank);
+/* lele_hip_token_filter_segments with each kept token's frame and score (tokenizer.rs:50-71 after quantization.rs:77-169 produced the
+ * ids): ids i32 [R], logprob_or_null f32 [R], row_offsets host [count + 1] from 0 to R, skip U8 [V] -> out_ids i32 [count, W] and
+ * out_counts i32 [count], identical to lele_hip_token_filter_segments for the same arguments; out_frames i32 [count, W]: for each kept
+ * id its row index within its segment (row - off[i]), then -1; out_logprob f32 [count, W]: the input score at that frame, copied bit for
+ * bit, then 0.0 -- left untouched, and may be NULL, when logprob_or_null is NULL.  The width rule and its error (which names the
+ * segment) are lele_hip_token_filter_segments'.  A dense [B, T] batch is the packed layout with off[i] = i * T (ids flattened to
+ * [B * T]): there is no dense twin.  Everything is checked before anything is launched or resized; count == 0 and R == 0 give empty
+ * results of the right shape.  Graph-capturable after one eager run of the same layout. */
+int lele_hip_token_align_segments(LeleCtx* ctx, const LeleTensor* ids, const LeleTensor* logprob_or_null, const int64_t* row_offsets,
+                                  int64_t count, const LeleTensor* skip, int64_t width, LeleBuf* out_ids, LeleBuf* out_frames,
+                                  LeleBuf* out_logprob, LeleBuf* out_counts, int64_t* out_shape, int32_t* out_rank);
 /* lele_hip_attention_view per segment: qkv f32 [R, P] holds Q, K, V of `heads` heads of width dh at columns q_offset, k_offset,
  * v_offset (head h at + h * dh); for every segment and head softmax(Q K^T * scale) V over THAT SEGMENT's rows only, queries and keys
  * alike (gemm.rs:112-222, norm.rs:8) -> out [R, heads * dh], heads merged.  Supported: dh == 128, every segment <= 512 rows, q_offset,

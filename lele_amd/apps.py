@@ -6,6 +6,7 @@ The device halves are in csrc/app.hip (`kernels.wav_to_f32`, `argmax_last`, `tok
   * `special_token_mask`  -- the per-vocabulary skip flags of examples/sensevoice/src/tokenizer.rs:63-69
   * `detokenize`          -- tokenizer.rs:74-81 (join, sentencepiece underscore -> space, trim)
   * `vad_segments`        -- examples/silero/src/main.rs:151-228 (speech segments from per-chunk probabilities)
+  * `token_times`         -- encoder frames of kept tokens (kernels.token_align_segments) -> start times in seconds
 """
 import numpy as np
 
@@ -23,6 +24,16 @@ def detokenize(ids, id_to_token):
     """tokenizer.rs:74-81: kept ids (as produced by kernels.token_filter, -1 padding ignored) -> text"""
     text = "".join(id_to_token[int(i)] for i in ids if int(i) >= 0)
     return text.replace("▁", " ").strip()
+
+
+def token_times(frames, prompt_rows=4, lfr_n=6, frame_shift_ms=10.0):
+    """frames as kernels.token_align_segments gives them (row index within the utterance, -1 = padding) -> start times in seconds,
+    float64 of the same shape: an encoder row behind the `prompt_rows` prompt rows covers `lfr_n` feature frames of `frame_shift_ms`,
+    so row f starts at (f - prompt_rows) * lfr_n * frame_shift_ms / 1000.  A frame inside the prompt rows is reported as 0.0, padding
+    is passed through as -1."""
+    f = np.asarray(frames, np.int64)
+    t = np.maximum(f - int(prompt_rows), 0).astype(np.float64) * (int(lfr_n) * float(frame_shift_ms)) / 1000.0
+    return np.where(f < 0, -1.0, t)
 
 
 def _ms_to_samples(ms, sample_rate):

@@ -6,6 +6,7 @@
 //                             Iterator::max_by keeps the LAST of equal maxima)
 //   lele_hip_token_filter  <- tokenizer.rs:63-71  (drop blank / special ids, keep frame order; no CTC collapsing upstream)
 //   lele_hip_token_filter_segments <- the same per segment of a packed batch of ids -> [count, W] ids + counts
+//   lele_hip_token_align_segments  <- ... and with every kept id its frame within the segment and its score
 //   lele_hip_image_preprocess   <- /root/reference/examples/yolo26n-seg/src/image.rs:62-111 (PIL-style nearest resize to
 //                             target x target, HWC u8 -> CHW f32 / 255)
 //   lele_hip_yolo_seg_postprocess <- image.rs:127-265 (score / box filter in query order, box rescale, per-detection mask =
@@ -139,7 +140,56 @@ __global__ __launch_bounds__(256) void token_filter_seg_kernel(const int32_t* __
     if (threadIdx.x == 0) counts[row] = n;
 }
 
-// image.rs:84-105 + 69-79: dst(y, x) <- src(min(floor((y + 0.5) * H / T), H - 1), min(floor((x + 0.5) * W / T), W - 1)) / 255
+// token_filter_seg_kernel with the two things a served transcript needs beside the id: per kept token its frame (row index within the
+// segment) into frames [count, w], then -1, and, where out_lp != NULL, its score lp[off[b] + frame] into out_lp [count, w], then 0.0.
+// The same ballot / LDS prefix compaction; ids and counts are token_filter_seg_kernel's.
+__global__ __launch_bounds__(256) void token_align_seg_kernel(const int32_t* __restrict__ ids, const float* __restrict__ lp,
+                                                              const int64_t* __restrict__ off, const uint8_t* __restrict__ skip, int64_t vocab,
+                                                              int64_t w, int32_t* __restrict__ out, int32_t* __restrict__ frames,
+                                                              float* __restrict__ out_lp /* NULL: no scores */, int32_t* __restrict__ counts) {
+    const int64_t row = blockIdx.x;
+    const int64_t t = off[row + 1] - off[row];
+    const int32_t* p = ids + off[row];
+    const float* q = lp + off[row];  // read only where out_lp != NULL (and the segment has rows)
+    int32_t* o = out + row * w;
+    int32_t* f = frames + row * w;
+    float* s = out_lp ? out_lp + row * w : nullptr;
+    __shared__ int wave_cnt[4];
+    __shared__ int base;
+    if (threadIdx.x == 0) base = 0;
+    __syncthreads();
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    for (int64_t c0 = 0; c0 < t; c0 += 256) {
+        const int64_t j = c0 + threadIdx.x;
+        const int32_t id = j < t ? p[j] : 0;
+        const bool keep = j < t && id >= 0 && id < vocab && skip[id] == 0;
+        const unsigned long long m = __ballot(keep);
+        const int before = __popcll(m & ((1ull << lane) - 1ull));
+        if (lane == 0) wave_cnt[wave] = __popcll(m);
+        __syncthreads();
+        int woff = 0;
+        for (int wv = 0; wv < wave; ++wv) woff += wave_cnt[wv];
+        const int b0 = base;
+        if (keep) {
+            const int at = b0 + woff + before;
+            o[at] = id;
+            f[at] = (int32_t)j;
+            if (s) s[at] = q[j];
+        }
+        __syncthreads();
+        if (threadIdx.x == 0) base = b0 + wave_cnt[0] + wave_cnt[1] + wave_cnt[2] + wave_cnt[3];
+        __syncthreads();
+    }
+    const int n = base;
+    for (int64_t j = n + threadIdx.x; j < w; j += 256) {
+        o[j] = -1;
+        f[j] = -1;
+        if (s) s[j] = 0.0f;
+    }
+    if (threadIdx.x == 0) counts[row] = n;
+}
+
+// image.rs:84-105 + 69-79: dst(y, x) <-src(min(floor((y + 0.5) * H / T), H - 1), min(floor((x + 0.5) * W / T), W - 1)) / 255
 __global__ void image_preprocess_kernel(const uint8_t* __restrict__ rgb, int h, int w, int target, float* __restrict__ out) {
     const int total = target * target;
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += gridDim.x * blockDim.x) {
@@ -331,6 +381,55 @@ int lele_hip_token_filter_segments(LeleCtx* ctx, const LeleTensor* ids, const in
     if (count > 0) {
         hipLaunchKernelGGL(token_filter_seg_kernel, dim3((unsigned)count), dim3(256), 0, ctx->stream, (const int32_t*)di, (const int64_t*)doff,
                            (const uint8_t*)ds, skip->shape[0], w, (int32_t*)out_ids->data, (int32_t*)out_counts->data);
+        LELE_HIP_CHECK(hipGetLastError());
+    }
+    return set_shape(out_shape, out_rank, {count, w});
+}
+
+int lele_hip_token_align_segments(LeleCtx* ctx, const LeleTensor* ids, const LeleTensor* logprob, const int64_t* row_offsets, int64_t count,
+                                  const LeleTensor* skip, int64_t width, LeleBuf* out_ids, LeleBuf* out_frames, LeleBuf* out_logprob,
+                                  LeleBuf* out_counts, int64_t* out_shape, int32_t* out_rank) {
+    LELE_REQUIRE(ctx && ids && skip && out_ids && out_frames && out_counts, "token_align_segments: NULL argument");
+    LELE_REQUIRE(!logprob || out_logprob, "token_align_segments: scores given but no out_logprob");
+    const bool lp_apart = !logprob || (out_logprob != out_ids && out_logprob != out_frames && out_logprob != out_counts);
+    LELE_REQUIRE(out_ids != out_frames && out_ids != out_counts && out_frames != out_counts && lp_apart,
+                 "token_align_segments: the output buffers must be distinct");
+    LELE_REQUIRE(ids->dtype == LELE_I32 && ids->rank == 1, "token_align_segments: ids must be i32 [R]");
+    LELE_REQUIRE(!logprob || (logprob->dtype == LELE_F32 && logprob->rank == 1 && logprob->shape[0] == ids->shape[0]),
+                 "token_align_segments: logprob must be f32 [R], one score per id");
+    LELE_REQUIRE((skip->dtype == LELE_U8 || skip->dtype == LELE_I8) && skip->rank == 1, "token_align_segments: skip must be a byte vector [V]");
+    LELE_REQUIRE(count >= 0 && row_offsets, "token_align_segments: bad row_offsets (count %lld)", (long long)count);
+    const int64_t rows = ids->shape[0];
+    LELE_REQUIRE(row_offsets[0] == 0 && row_offsets[count] == rows, "token_align_segments: row_offsets must run from 0 to R = %lld (got %lld .. %lld)",
+                 (long long)rows, (long long)row_offsets[0], (long long)row_offsets[count]);
+    LELE_REQUIRE(width >= 0, "token_align_segments: negative width");
+    int64_t tmax = 0;
+    for (int64_t i = 0; i < count; ++i) {
+        const int64_t len = row_offsets[i + 1] - row_offsets[i];
+        LELE_REQUIRE(len >= 0, "token_align_segments: row_offsets decrease at segment %lld", (long long)i);
+        LELE_REQUIRE(width == 0 || len <= width, "token_align_segments: segment %lld has %lld rows, more than width = %lld", (long long)i,
+                     (long long)len, (long long)width);
+        tmax = std::max(tmax, len);
+    }
+    const int64_t w = width ? width : std::max<int64_t>(tmax, 1);
+    LELE_REQUIRE(count < (int64_t(1) << 31) && w < (int64_t(1) << 31), "token_align_segments: more than 2^31 segments or columns");
+    LELE_HIP_CHECK(hipSetDevice(ctx->device));
+    const void* doff = nullptr;
+    if (count > 0) LELE_TRY(offsets_table(ctx, row_offsets, count, &doff));
+    LELE_TRY(ctx->arena_reset());
+    const void *di = nullptr, *dl = nullptr, *ds = nullptr;
+    if (rows > 0) LELE_TRY(ctx->dev_ptr(ids, &di));
+    if (rows > 0 && logprob) LELE_TRY(ctx->dev_ptr(logprob, &dl));
+    if (count > 0) LELE_TRY(ctx->dev_ptr(skip, &ds));
+    const size_t cells = (size_t)std::max<int64_t>(count * w, 1) * 4;
+    LELE_TRY(out_ids->reserve(cells));
+    LELE_TRY(out_frames->reserve(cells));
+    if (logprob) LELE_TRY(out_logprob->reserve(cells));
+    LELE_TRY(out_counts->reserve((size_t)std::max<int64_t>(count, 1) * 4));
+    if (count > 0) {
+        hipLaunchKernelGGL(token_align_seg_kernel, dim3((unsigned)count), dim3(256), 0, ctx->stream, (const int32_t*)di, (const float*)dl,
+                           (const int64_t*)doff, (const uint8_t*)ds, skip->shape[0], w, (int32_t*)out_ids->data, (int32_t*)out_frames->data,
+                           logprob ? (float*)out_logprob->data : (float*)nullptr, (int32_t*)out_counts->data);
         LELE_HIP_CHECK(hipGetLastError());
     }
     return set_shape(out_shape, out_rank, {count, w});

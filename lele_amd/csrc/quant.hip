@@ -419,7 +419,8 @@ struct IgemmEpi {
     int* q_rowsum = nullptr;        // EM 2: sum over the row of (q - 128), accumulated over column blocks
     QParams* q_prm = nullptr;       // EM 2: the slices' parameters, published for the next GEMM's epilogue
     const int* row_seg = nullptr;   // packed batch (lele_hip_fused_quantized_linear_segments): row -> segment, the slice of prm[]
-    unsigned long long* arg_keys = nullptr;  // EM 3: [column tiles][rows], a tile's best argmax_key(value, column) per row (plain stores)
+    unsigned long long* arg_keys = nullptr;  // EM 3 / 4: [column tiles][rows], a tile's best argmax_key(value, column) per row (plain stores)
+    float* arg_sums = nullptr;  // EM 4: [column tiles][rows], sum over the tile's columns of exp(value - the tile's maximum) (plain stores)
     // Everything that depends only on the row (slice parameters, row-sum term, output row pointer) or only on the
     // column (column sum, weight scale, bias) is computed once per row / column of a thread's tile, not per element.
     struct RowCtx {
@@ -512,6 +513,50 @@ __global__ __launch_bounds__(256) void argmax_finish_kernel(const unsigned long 
     }
 }
 
+// the value a key's high word was made of (-0.0 comes back as +0.0)
+__device__ __forceinline__ float argmax_key_value(unsigned long long key) {
+    const unsigned b = (unsigned)(key >> 32);
+    return __uint_as_float((b & 0x80000000u) ? b ^ 0x80000000u : ~b);
+}
+// argmax_finish_kernel with the winner's log-probability (EM 4): with M the greatest key and m_t the maximum of tile t (its key's high
+// word), S = sum_t sums[t] * exp(m_t - M) and logprob = -ln S, never value - (max + ln S).  The same 16 rows x 16 threads; thread g
+// adds tiles g, g + 16, .. in that order and thread 0 joins the 16 partial sums in thread order: the order is a function of the tile
+// count alone, at most 15 + ceil(tiles / 16) additions deep.
+__global__ __launch_bounds__(256) void argmax_logprob_finish_kernel(const unsigned long long* __restrict__ keys, const float* __restrict__ sums,
+                                                                    int64_t rows, int tiles, int32_t* __restrict__ ids,
+                                                                    float* __restrict__ logprob) {
+    __shared__ unsigned long long s_best[16][17];
+    __shared__ float s_part[16][17];
+    const int rr = threadIdx.x & 15, g = threadIdx.x >> 4;
+    const int64_t r = (int64_t)blockIdx.x * 16 + rr;
+    unsigned long long best = 0ull;
+    if (r < rows) {
+#pragma unroll 8
+        for (int t = g; t < tiles; t += 16) best = max(best, keys[(int64_t)t * rows + r]);
+    }
+    s_best[g][rr] = best;
+    __syncthreads();
+#pragma unroll
+    for (int o = 0; o < 16; ++o) best = max(best, s_best[o][rr]);
+    const float mx = argmax_key_value(best);
+    float part = 0.0f;
+    if (r < rows) {
+#pragma unroll 8
+        for (int t = g; t < tiles; t += 16) {
+            const int64_t at = (int64_t)t * rows + r;
+            part += sums[at] * __expf(argmax_key_value(keys[at]) - mx);
+        }
+    }
+    s_part[g][rr] = part;
+    __syncthreads();
+    if (g == 0 && r < rows) {
+#pragma unroll
+        for (int o = 1; o < 16; ++o) part += s_part[o][rr];
+        ids[r] = (int32_t)(unsigned)best;
+        logprob[r] = 0.0f - logf(part);  // S == 1 gives +0.0
+    }
+}
+
 // EM (epilogue mode) 0: the result as f32.  EM 1 / 2 are the two passes of the fused two-layer form, where the f32 result (the
 // hidden layer of a feed-forward block, 45 MB per configs[3] shard) never exists in HBM -- recomputing the product costs ~5 us of
 // matrix-core time against ~30 us of traffic for writing it and reading it twice:
@@ -521,6 +566,11 @@ __global__ __launch_bounds__(256) void argmax_finish_kernel(const unsigned long 
 // EM 3 is the greedy decode head (lele_hip_fused_quantized_linear_argmax): of the result only each row's arg-max leaves the chip, as
 //   one argmax_key per (row, column tile) in epi.arg_keys, which argmax_finish_kernel reduces.  Row context as EM 0 (any number of
 //   slices a tile).
+// EM 4 is EM 3 with the winner's log-probability (lele_hip_fused_quantized_linear_argmax_logprob): besides the key, per (row, column
+//   tile) the sum over the tile's valid columns of exp(value - the tile's maximum) in epi.arg_sums; argmax_logprob_finish_kernel
+//   rescales and adds the tiles.  The maximum is the one the key butterfly found, so the sums are taken after it, by the same butterfly
+//   with plain f32 adds (commutative bit for bit, the pairing lane ^ 16, 8, 4, 2, 1 the same for every row) and joined over the waves in
+//   wave order: a row's sum depends on (n, column) only, not on where the row sits in its tile.
 template <int BM, int BN, int WM, int WN, int BKB /* bytes of K per LDS tile: 64 or 128 */, int OCC = 1, int EM = 0>
 __global__ __launch_bounds__(WM* WN * 64) __attribute__((amdgpu_waves_per_eu(OCC))) void igemm_kernel(const int8_t* __restrict__ a, const int8_t* __restrict__ b,
                                                             int64_t rows, int n, int kp, int64_t b_batch_stride,
@@ -724,8 +774,10 @@ __global__ __launch_bounds__(WM* WN * 64) __attribute__((amdgpu_waves_per_eu(OCC
         if (tx == 0 && tid < 2 && (tid == 0 || split < rows_here)) epi.q_prm[s0 + tid] = s_q[tid];
         return;
     }
-    if constexpr (EM == 3) {
-        static_assert(EM != 3 || TMT == 2, "the butterfly below folds 32 rows a lane onto the 32 lanes of a half-wave");
+    if constexpr (EM == 3 || EM == 4) {
+        static_assert(!(EM == 3 || EM == 4) || TMT == 2, "the butterfly below folds 32 rows a lane onto the 32 lanes of a half-wave");
+        static_assert(EM != 4 || (TNT == 1 && NT >= BM), "EM 4: one column a lane, one thread a row in the joins");
+        float val[EM == 4 ? TMT * 16 : 1];  // EM 4: the lane's 32 logits, kept for the sums
         const int rows_here = (int)(rows - m0 < BM ? rows - m0 : BM);
         // a lane holds 32 rows x TNT columns: its best key per row over its own valid columns (a padded column's context is the clamped
         // column's, so it is masked to 0, below every real key)
@@ -739,7 +791,9 @@ __global__ __launch_bounds__(WM* WN * 64) __attribute__((amdgpu_waves_per_eu(OCC
                 unsigned long long best = 0ull;
 #pragma unroll
                 for (int j = 0; j < TNT; ++j) {
-                    const unsigned long long kj = argmax_key(epi.value24(rc, cc[j], acc[i][j][r]), cols[j]);
+                    const float v = epi.value24(rc, cc[j], acc[i][j][r]);
+                    if constexpr (EM == 4) val[i * 16 + r] = v;
+                    const unsigned long long kj = argmax_key(v, cols[j]);
                     best = max(best, cols[j] < n ? kj : 0ull);
                 }
                 key[i * 16 + r] = best;
@@ -765,6 +819,52 @@ __global__ __launch_bounds__(WM* WN * 64) __attribute__((amdgpu_waves_per_eu(OCC
             s_key[wn * BM + lr] = key[0];
         }
         __syncthreads();
+        if constexpr (EM == 4) {
+            float* const s_max = reinterpret_cast<float*>(igemm_lds + WN * BM * 8);  // [BM], the tile's maximum per row
+            float* const s_sum = s_max + BM;                                         // [WN][BM]
+            if (tid < BM) {  // rows past the last are the last row again (clamped context): computed, never stored
+                unsigned long long best = s_key[tid];
+#pragma unroll
+                for (int w = 1; w < WN; ++w) best = max(best, s_key[w * BM + tid]);
+                if (tid < rows_here) epi.arg_keys[(int64_t)tx * rows + m0 + tid] = best;
+                s_max[tid] = argmax_key_value(best);
+            }
+            __syncthreads();
+            // exp(value - the tile's maximum) of the lane's column, nothing for a padded column (its value is the clamped column's)
+            const bool valid = cols[0] < n;
+#pragma unroll
+            for (int i = 0; i < TMT; ++i)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const int lr = wm * TMT * 32 + i * 32 + 4 * hv + (r & 3) + 8 * (r >> 2);
+                    const float e = __expf(val[i * 16 + r] - s_max[lr]);
+                    val[i * 16 + r] = valid ? e : 0.0f;
+                }
+#pragma unroll
+            for (int s = 0; s < 5; ++s) {
+                const int half = 16 >> s;
+                const bool up = (lane & half) != 0;
+#pragma unroll
+                for (int t = 0; t < half; ++t) {
+                    const float send = up ? val[t] : val[t + half];
+                    const float keep = up ? val[t + half] : val[t];
+                    val[t] = keep + __shfl_xor(send, half);
+                }
+            }
+            {
+                const int rr = l31 & 15;
+                const int lr = wm * TMT * 32 + (l31 >> 4) * 32 + 4 * hv + (rr & 3) + 8 * (rr >> 2);
+                s_sum[wn * BM + lr] = val[0];
+            }
+            __syncthreads();
+            if (tid < rows_here) {
+                float sum = s_sum[tid];
+#pragma unroll
+                for (int w = 1; w < WN; ++w) sum += s_sum[w * BM + tid];
+                epi.arg_sums[(int64_t)tx * rows + m0 + tid] = sum;
+            }
+            return;
+        }
         for (int t = tid; t < rows_here; t += NT) {
             unsigned long long best = s_key[t];
 #pragma unroll
@@ -1133,13 +1233,25 @@ int launch_igemm_hidden(LeleCtx* ctx, int em, const int8_t* aq, const int8_t* wt
 // the greedy head (EM 3): the tiled kernel in its big-shape configuration, then the best key's low word per row as ids.
 // `keys`: argmax_key_bytes(rows, n)
 size_t argmax_key_bytes(int64_t rows, int64_t n) { return (size_t)rows * (size_t)((n + 127) / 128) * 8; }
+// `sums` / `logprob`: both or neither; with them the EM 4 form, `sums` of argmax_sum_bytes(rows, n)
+size_t argmax_sum_bytes(int64_t rows, int64_t n) { return (size_t)rows * (size_t)((n + 127) / 128) * 4; }
 int launch_igemm_argmax(LeleCtx* ctx, const int8_t* aq, const int8_t* wt, int64_t rows, int n, int kp, int m, const IgemmEpi& epi_in,
-                        unsigned long long* keys, int32_t* ids) {
+                        unsigned long long* keys, int32_t* ids, float* sums = nullptr, float* logprob = nullptr) {
     LELE_REQUIRE(rows < (int64_t(128) * 65535), "quantized GEMM: more than 128 x 65535 rows");
     constexpr size_t lds = (size_t)2 * (128 + 128) * (128 + 16);
     IgemmEpi epi = epi_in;
     epi.arg_keys = keys;
     const dim3 grid((n + 127) / 128, (unsigned)((rows + 127) / 128));
+    if (logprob) {
+        epi.arg_sums = sums;
+        auto kern = igemm_kernel<128, 128, 2, 4, 128, 1, 4>;
+        LELE_HIP_CHECK(ensure_dyn_lds(reinterpret_cast<const void*>(kern), (int)lds));
+        hipLaunchKernelGGL(kern, grid, dim3(512), lds, ctx->stream, aq, wt, rows, n, kp, (int64_t)0, m, epi);
+        hipLaunchKernelGGL(argmax_logprob_finish_kernel, dim3((unsigned)((rows + 15) / 16)), dim3(256), 0, ctx->stream,
+                           (const unsigned long long*)keys, (const float*)sums, rows, (int)grid.x, ids, logprob);
+        LELE_HIP_CHECK(hipGetLastError());
+        return 0;
+    }
     auto kern = igemm_kernel<128, 128, 2, 4, 128, 1, 3>;
     LELE_HIP_CHECK(ensure_dyn_lds(reinterpret_cast<const void*>(kern), (int)lds));
     hipLaunchKernelGGL(kern, grid, dim3(512), lds, ctx->stream, aq, wt, rows, n, kp, (int64_t)0, m, epi);
@@ -1537,6 +1649,7 @@ struct QReq {  // what the caller wants around the product
     const LeleTensor *res1 = nullptr, *res2 = nullptr;  // same-shape residuals (res_same_shape), added in this order
     LnReq* ln = nullptr;
     int argmax = 0;  // the greedy head: `out` receives argmax_last of the result as i32 [rows], the result itself is never stored
+    LeleBuf* logprob = nullptr;  // ... with the winner's log-probability as f32 [rows] (needs argmax; igemm_kernel EM 4)
 };
 // one layer, validated and staged: what a route's body reads
 struct QLayer {
@@ -1550,6 +1663,7 @@ struct QLayer {
     const float* partial = nullptr;  // {min, max} pairs of x, nblk a slice
     int nblk = 0;
     LeleBuf* out = nullptr;
+    LeleBuf* logprob = nullptr;  // QReq::logprob
 };
 IgemmEpi make_epi(const QLayer& l, float* out, const int* row_sums, const int* col_sums) {
     return IgemmEpi{out, l.c.rows, l.c.n, (int)l.c.m, (int)l.c.k, row_sums, col_sums, l.prm, 0, (int)l.wz, l.ws, (int)l.c.ws_len, l.bias, l.relu,
@@ -1701,10 +1815,11 @@ int run_tiled(LeleCtx* ctx, const QLayer& l, bool argmax = false) {
                           (int8_t*)aq, (int*)rs, l.partial, l.nblk, nullptr, nullptr, nullptr));
     LELE_TRY(qprof_mark(ctx, 2));
     if (argmax) {
-        void* keys = nullptr;
+        void *keys = nullptr, *sums = nullptr;
         LELE_TRY(ctx->arena_alloc(argmax_key_bytes(c.rows, c.n), &keys));
+        if (l.logprob) LELE_TRY(ctx->arena_alloc(argmax_sum_bytes(c.rows, c.n), &sums));
         LELE_TRY(launch_igemm_argmax(ctx, (const int8_t*)aq, pw.wt, c.rows, (int)c.n, kp, (int)c.m, make_epi(l, nullptr, (const int*)rs, pw.col_sums),
-                                     (unsigned long long*)keys, (int32_t*)l.out->data));
+                                     (unsigned long long*)keys, (int32_t*)l.out->data, (float*)sums, l.logprob ? (float*)l.logprob->data : nullptr));
         return qprof_mark(ctx, 3);
     }
     IgemmEpi epi = make_epi(l, (float*)l.out->data, (const int*)rs, pw.col_sums);
@@ -1721,14 +1836,16 @@ int run_tiled(LeleCtx* ctx, const QLayer& l, bool argmax = false) {
 int fql_impl(LeleCtx* ctx, const LeleTensor* input, const QW& w, const QReq& rq, LeleBuf* out, int64_t* out_shape, int32_t* out_rank) {
     LELE_REQUIRE(ctx && input && w.w && w.scale && out, "fused_quantized_linear: NULL argument");
     QLayer l;
-    LELE_TRY(describe_call(rq.argmax ? "fused_quantized_linear_argmax" : "fused_quantized_linear", input, w, &l.c));
+    const char* const who = rq.logprob ? "fused_quantized_linear_argmax_logprob" : rq.argmax ? "fused_quantized_linear_argmax" : "fused_quantized_linear";
+    LELE_TRY(describe_call(who, input, w, &l.c));
     QCall& c = l.c;
     if (rq.argmax) {  // ids: the input's shape without its last axis, one i32 a row
-        LELE_REQUIRE(c.n >= 1 && c.k >= 1, "fused_quantized_linear_argmax: empty K or N (K = %lld, N = %lld)", (long long)c.k, (long long)c.n);
+        LELE_REQUIRE(c.n >= 1 && c.k >= 1, "%s: empty K or N (K = %lld, N = %lld)", who, (long long)c.k, (long long)c.n);
         c.shp.pop_back();
     }
     LELE_HIP_CHECK(hipSetDevice(ctx->device));
     LELE_TRY(out->reserve(rq.argmax ? (size_t)c.rows * 4 : (size_t)c.rows * c.n * 4));
+    if (rq.logprob) LELE_TRY(rq.logprob->reserve((size_t)c.rows * 4));
     if (c.rows == 0 || c.n == 0) return set_shape_v(out_shape, out_rank, c.shp);
     LELE_TRY(ctx->arena_reset());
     const void *dx = nullptr, *dws = nullptr, *db = nullptr, *dr1 = nullptr, *dr2 = nullptr;
@@ -1742,7 +1859,7 @@ int fql_impl(LeleCtx* ctx, const LeleTensor* input, const QW& w, const QReq& rq,
     void* prm = nullptr;
     LELE_TRY(ctx->arena_alloc((size_t)c.batch * sizeof(QParams), &prm));
     l.weight = w.w, l.x = (const float*)dx, l.ws = (const float*)dws, l.bias = (const float*)db, l.relu = rq.relu;
-    l.res1 = (const float*)dr1, l.res2 = (const float*)dr2, l.prm = (QParams*)prm, l.out = out;
+    l.res1 = (const float*)dr1, l.res2 = (const float*)dr2, l.prm = (QParams*)prm, l.out = out, l.logprob = rq.logprob;
     LELE_TRY(qprof_mark(ctx, 0));
     if (!l.partial) LELE_TRY(launch_range(ctx, l.x, c.batch, c.m * c.k, l.prm, nullptr, nullptr, &l.partial, &l.nblk));
     LELE_TRY(qprof_mark(ctx, 1));
@@ -1965,7 +2082,8 @@ int ffn_impl(LeleCtx* ctx, const LeleTensor* input, const QW& w1, const QW& w2, 
  * two through a row -> segment map -- and the integer sums are exact, so a segment's rows are the dense entry point's on it alone. */
 int fql_segments_impl(LeleCtx* ctx, const char* who, int argmax, const LeleTensor* input, const int64_t* row_offsets, int64_t count,
                       const LeleTensor* weight_int8, const LeleTensor* weight_scale, const LeleTensor* weight_zero,
-                      const LeleTensor* bias, int apply_relu, LeleBuf* out, int64_t* out_shape, int32_t* out_rank) {
+                      const LeleTensor* bias, int apply_relu, LeleBuf* out, int64_t* out_shape, int32_t* out_rank,
+                      LeleBuf* logprob = nullptr /* with argmax: the winners' log-probabilities f32 [R] (EM 4) */) {
     LELE_REQUIRE(ctx && input && weight_int8 && weight_scale && out, "%s: NULL argument", who);
     int64_t rows = 0, k = 0, tmax = 0;
     LELE_TRY(seg_offsets(input, row_offsets, count, &rows, &k, &tmax, who));
@@ -1988,6 +2106,7 @@ int fql_segments_impl(LeleCtx* ctx, const char* who, int argmax, const LeleTenso
     }
     if (rows == 0 || n == 0 || k == 0) {
         LELE_TRY(out->reserve(out_bytes));
+        if (logprob) LELE_TRY(logprob->reserve(out_bytes));
         return set_shape_v(out_shape, out_rank, c.shp);
     }
     const int64_t* doff = (const int64_t*)tab;
@@ -2017,19 +2136,23 @@ int fql_segments_impl(LeleCtx* ctx, const char* who, int argmax, const LeleTenso
     const int kp = (int)((k + 15) & ~int64_t(15));
     PackedW pw;
     LELE_TRY(packed_weights_of(ctx, weight_int8, nullptr, 1, (int)k, (int)n, kp, &pw));
-    void *aq = nullptr, *rs = nullptr, *keys = nullptr;
+    void *aq = nullptr, *rs = nullptr, *keys = nullptr, *sums = nullptr;
     LELE_TRY(ctx->arena_alloc((size_t)rows * kp, &aq));
     LELE_TRY(ctx->arena_alloc((size_t)rows * 4, &rs));
     if (argmax) LELE_TRY(ctx->arena_alloc(argmax_key_bytes(rows, n), &keys));
+    if (logprob) LELE_TRY(ctx->arena_alloc(argmax_sum_bytes(rows, n), &sums));
     // every fallible step is behind us: `out` is as it was until here (reserve clears any producer-side statistics of `out`;
     // those of `input` describe equal slices and are not read)
     LELE_TRY(out->reserve(out_bytes));
+    if (logprob) LELE_TRY(logprob->reserve(out_bytes));
     LELE_TRY(launch_qrows(ctx, rows <= 2048 || kp <= 2048, l.x, rows, (int)k, kp, (int)rows, l.prm, (int8_t*)aq, (int*)rs, (const float*)partial,
                           nblk, nullptr, nullptr, drowseg));
     LELE_TRY(qprof_mark(ctx, 2));
     IgemmEpi epi = make_epi(l, argmax ? nullptr : (float*)out->data, (const int*)rs, pw.col_sums);
     epi.row_seg = drowseg;
-    if (argmax) LELE_TRY(launch_igemm_argmax(ctx, (const int8_t*)aq, pw.wt, rows, (int)n, kp, (int)rows, epi, (unsigned long long*)keys, (int32_t*)out->data));
+    if (argmax)
+        LELE_TRY(launch_igemm_argmax(ctx, (const int8_t*)aq, pw.wt, rows, (int)n, kp, (int)rows, epi, (unsigned long long*)keys, (int32_t*)out->data,
+                                     (float*)sums, logprob ? (float*)logprob->data : nullptr));
     else LELE_TRY(launch_igemm(ctx, (const int8_t*)aq, pw.wt, rows, (int)n, kp, (int)rows, epi));
     LELE_TRY(qprof_mark(ctx, 3));
     return set_shape_v(out_shape, out_rank, c.shp);
@@ -2069,6 +2192,27 @@ int lele_hip_fused_quantized_linear_argmax_segments(LeleCtx* ctx, const LeleTens
                                                     int64_t* out_shape, int32_t* out_rank) {
     return fql_segments_impl(ctx, "fused_quantized_linear_argmax_segments", 1, input, row_offsets, count, weight_int8, weight_scale, weight_zero,
                              bias, 0, out_ids, out_shape, out_rank);
+}
+
+/* ... with the winner's log-probability (tokenizer.rs:50-71 behind quantization.rs:77-169): -ln sum_j exp(v_j - v_id) from the same epilogue
+ * (igemm_kernel EM 4), the ids bit for bit those of the call above. */
+int lele_hip_fused_quantized_linear_argmax_logprob(LeleCtx* ctx, const LeleTensor* input, const LeleTensor* weight_int8,
+                                                   const LeleTensor* weight_scale, const LeleTensor* weight_zero, const LeleTensor* bias,
+                                                   LeleBuf* out_ids, LeleBuf* out_logprob, int64_t* out_shape, int32_t* out_rank) {
+    LELE_REQUIRE(out_ids && out_logprob && out_ids != out_logprob, "fused_quantized_linear_argmax_logprob: two distinct output buffers required");
+    QReq rq;
+    rq.argmax = 1;
+    rq.logprob = out_logprob;
+    return fql_impl(ctx, input, {weight_int8, weight_scale, weight_zero, bias}, rq, out_ids, out_shape, out_rank);
+}
+
+int lele_hip_fused_quantized_linear_argmax_logprob_segments(LeleCtx* ctx, const LeleTensor* input, const int64_t* row_offsets, int64_t count,
+                                                            const LeleTensor* weight_int8, const LeleTensor* weight_scale,
+                                                            const LeleTensor* weight_zero, const LeleTensor* bias, LeleBuf* out_ids,
+                                                            LeleBuf* out_logprob, int64_t* out_shape, int32_t* out_rank) {
+    LELE_REQUIRE(out_ids && out_logprob && out_ids != out_logprob, "fused_quantized_linear_argmax_logprob_segments: two distinct output buffers required");
+    return fql_segments_impl(ctx, "fused_quantized_linear_argmax_logprob_segments", 1, input, row_offsets, count, weight_int8, weight_scale,
+                             weight_zero, bias, 0, out_ids, out_shape, out_rank, out_logprob);
 }
 
 int lele_hip_fused_quantized_linear_residual(LeleCtx* ctx, const LeleTensor* input, const LeleTensor* weight_int8,

@@ -1016,6 +1016,45 @@ inline std::pair<TensorView, TensorView> token_filter_segments(const TensorView&
     std::vector<int64_t> s(sh.dims, sh.dims + sh.rank), r(sh.dims, sh.dims + (sh.rank > 0 ? sh.rank - 1 : 0));
     return {TensorView::from_device(out_ids, s, LELE_I32), TensorView::from_device(out_counts, r, LELE_I32)};
 }
+// the greedy decode head with the winner's confidence -> (ids i32, logprob f32 = -ln sum_j exp(v_j - v_id)), the logits never stored
+inline std::pair<TensorView, TensorView> fused_quantized_linear_argmax_logprob(const TensorView& input, const TensorView& weight_int8,
+                                                                               const TensorView& weight_scale, const TensorView& weight_zero,
+                                                                               const TensorView* bias, Buffer& out_ids, Buffer& out_logprob) {
+    Shape sh;
+    LeleTensor a = input.c(), b = weight_int8.c(), s = weight_scale.c(), z = weight_zero.c();
+    Opt ob(bias);
+    check(lele_hip_fused_quantized_linear_argmax_logprob(ctx(), &a, &b, &s, &z, ob.p, out_ids.raw(), out_logprob.raw(), sh.dims, &sh.rank));
+    std::vector<int64_t> shp(sh.dims, sh.dims + sh.rank);
+    return {TensorView::from_device(out_ids, shp, LELE_I32), TensorView::from_device(out_logprob, shp, LELE_F32)};
+}
+inline std::pair<TensorView, TensorView> fused_quantized_linear_argmax_logprob_segments(const TensorView& input, const std::vector<int64_t>& offsets,
+                                                                                        const TensorView& weight_int8, const TensorView& weight_scale,
+                                                                                        const TensorView& weight_zero, const TensorView* bias,
+                                                                                        Buffer& out_ids, Buffer& out_logprob) {
+    Shape sh;
+    LeleTensor a = input.c(), b = weight_int8.c(), s = weight_scale.c(), z = weight_zero.c();
+    Opt ob(bias);
+    check(lele_hip_fused_quantized_linear_argmax_logprob_segments(ctx(), &a, offsets.data(), (int64_t)offsets.size() - 1, &b, &s, &z, ob.p,
+                                                                  out_ids.raw(), out_logprob.raw(), sh.dims, &sh.rank));
+    std::vector<int64_t> shp(sh.dims, sh.dims + sh.rank);
+    return {TensorView::from_device(out_ids, shp, LELE_I32), TensorView::from_device(out_logprob, shp, LELE_F32)};
+}
+// token_filter_segments with each kept token's frame (row within its segment, then -1) and, where `logprob` is given, its score (then 0.0)
+struct AlignedTokens {
+    TensorView ids, frames, logprob, counts;  // logprob: an empty view when no scores were given
+};
+inline AlignedTokens token_align_segments(const TensorView& ids, const TensorView* logprob, const std::vector<int64_t>& offsets,
+                                          const TensorView& skip, int64_t width, Buffer& out_ids, Buffer& out_frames, Buffer& out_logprob,
+                                          Buffer& out_counts) {
+    Shape sh;
+    LeleTensor ti = ids.c(), ts = skip.c();
+    Opt ol(logprob);
+    check(lele_hip_token_align_segments(ctx(), &ti, ol.p, offsets.data(), (int64_t)offsets.size() - 1, &ts, width, out_ids.raw(), out_frames.raw(),
+                                        out_logprob.raw(), out_counts.raw(), sh.dims, &sh.rank));
+    std::vector<int64_t> s(sh.dims, sh.dims + sh.rank), r(sh.dims, sh.dims + (sh.rank > 0 ? sh.rank - 1 : 0));
+    return {TensorView::from_device(out_ids, s, LELE_I32), TensorView::from_device(out_frames, s, LELE_I32),
+            logprob ? TensorView::from_device(out_logprob, s, LELE_F32) : TensorView(), TensorView::from_device(out_counts, r, LELE_I32)};
+}
 inline TensorView attention_segments(const TensorView& qkv, const std::vector<int64_t>& offsets, int64_t q_offset, int64_t k_offset,
                                      int64_t v_offset, int64_t heads, int64_t dh, const TensorView* scale, Buffer& out) {
     Shape sh;

@@ -1258,6 +1258,56 @@ def token_filter_segments(ids, offsets, skip, width=0, out_ids=None, out_counts=
     return TensorView(_lib.DevTensor(oi, shape, np.int32)), TensorView(_lib.DevTensor(oc, shape[:-1], np.int32))
 
 
+def fused_quantized_linear_argmax_logprob(input, weight_int8, weight_scale, weight_zero, bias, out_ids=None, out_logprob=None, ctx=None):
+    """the greedy decode head with the winner's confidence -> (ids int32, logprob float32), both the input's shape without its last axis:
+    ids are fused_quantized_linear_argmax's bit for bit, logprob = -ln sum_j exp(v_j - v_id) over the row's logits, from the same GEMM
+    epilogue; the logits are never stored (tokenizer.rs:50-71)."""
+    ctx = _ctx(ctx)
+    keep = []
+    oi, ol = out_ids or ctx.buf(), out_logprob or ctx.buf()
+    sh = _lib.OutShape()
+    _lib.check(_lib.lib().lele_hip_fused_quantized_linear_argmax_logprob(
+        ctx._h, _t(input, keep), _t(weight_int8, keep), _t(weight_scale, keep), _t(weight_zero, keep), _t(bias, keep), oi._h, ol._h, sh.shape,
+        C.byref(sh.rank)))
+    shape = sh.get()
+    return TensorView(_lib.DevTensor(oi, shape, np.int32)), TensorView(_lib.DevTensor(ol, shape, np.float32))
+
+
+def fused_quantized_linear_argmax_logprob_segments(input, offsets, weight_int8, weight_scale, weight_zero, bias, out_ids=None,
+                                                   out_logprob=None, ctx=None):
+    """fused_quantized_linear_argmax_logprob with every segment of the packed input [R, K] as a batch slice of its own -> (int32 [R],
+    float32 [R]): rows offsets[i] .. offsets[i + 1] are, bit for bit, the dense call on that range alone"""
+    ctx = _ctx(ctx)
+    keep = []
+    oi, ol = out_ids or ctx.buf(), out_logprob or ctx.buf()
+    sh = _lib.OutShape()
+    off = _offsets(offsets)
+    _lib.check(_lib.lib().lele_hip_fused_quantized_linear_argmax_logprob_segments(
+        ctx._h, _t(input, keep), _lib.i64_ptr(off), C.c_int64(len(off) - 1), _t(weight_int8, keep), _t(weight_scale, keep),
+        _t(weight_zero, keep), _t(bias, keep), oi._h, ol._h, sh.shape, C.byref(sh.rank)))
+    shape = sh.get()
+    return TensorView(_lib.DevTensor(oi, shape, np.int32)), TensorView(_lib.DevTensor(ol, shape, np.float32))
+
+
+def token_align_segments(ids, logprob, offsets, skip, width=0, out_ids=None, out_frames=None, out_logprob=None, out_counts=None, ctx=None):
+    """token_filter_segments with each kept token's frame and score: packed ids int32 [R], logprob float32 [R] or None -> (ids int32
+    [count, W] padded with -1, frames int32 [count, W]: the kept ids' row indices within their segment, then -1, logprob float32
+    [count, W]: the scores at those frames, then 0.0 (None when `logprob` is None), counts int32 [count]).  A dense [B, T] batch is the
+    packed layout with offsets[i] = i * T."""
+    ctx = _ctx(ctx)
+    keep = []
+    oi, of, oc = out_ids or ctx.buf(), out_frames or ctx.buf(), out_counts or ctx.buf()
+    ol = None if logprob is None else (out_logprob or ctx.buf())
+    sh = _lib.OutShape()
+    off = _offsets(offsets)
+    _lib.check(_lib.lib().lele_hip_token_align_segments(
+        ctx._h, _t(ids, keep), _t(logprob, keep), _lib.i64_ptr(off), C.c_int64(len(off) - 1), _t(skip, keep), C.c_int64(int(width)), oi._h,
+        of._h, ol._h if ol is not None else None, oc._h, sh.shape, C.byref(sh.rank)))
+    shape = sh.get()
+    return (TensorView(_lib.DevTensor(oi, shape, np.int32)), TensorView(_lib.DevTensor(of, shape, np.int32)),
+            None if ol is None else TensorView(_lib.DevTensor(ol, shape, np.float32)), TensorView(_lib.DevTensor(oc, shape[:-1], np.int32)))
+
+
 def attention_segments(qkv, offsets, heads, dh, scale=None, q_offset=0, k_offset=None, v_offset=None, out=None, ctx=None):
     """softmax(Q K^T * scale) V per segment and head over that segment's rows only: qkv [R, P] holds Q | K | V at the column offsets
     (default: the packed projection, 0, heads * dh, 2 * heads * dh) -> [R, heads * dh], heads merged.  dh == 128, segments of at most

@@ -101,6 +101,7 @@ class Encoder:
         # one workspace slot per distinct live value, as lele's compile-time buffer plan would assign
         self.ws = [ctx.buf() for _ in range(16)]
         self.dec = [ctx.buf() for _ in range(3)]   # the greedy head's results: frame ids, kept ids, counts
+        self.sco = [ctx.buf() for _ in range(3)]   # the scored head's: frame scores, kept frames, kept scores
 
     def ql(self, x, p, relu, slot):
         return self.K.fused_quantized_linear(x, p.w, p.scale, p.zero, p.bias, relu, out=self.ws[slot], ctx=self.ctx)
@@ -181,6 +182,14 @@ class Encoder:
         xn = self.K.layer_norm(self.trunk(feats), self.ln_out[0], self.ln_out[1], -1, 1e-5, out=self.ws[1], ctx=self.ctx)
         return self.K.fused_quantized_linear_argmax(xn, p.w, p.scale, p.zero, p.bias, out=self.dec[0], ctx=self.ctx)
 
+    def greedy_scored(self, feats):
+        """feats: [B, T, 560] -> (ids int32 [B, T+4], logprob float32 [B, T+4]): greedy's ids bit for bit and the log of each winner's
+        soft-max posterior, both out of the CTC projection's epilogue; the logits are never stored"""
+        p = self.ctc
+        xn = self.K.layer_norm(self.trunk(feats), self.ln_out[0], self.ln_out[1], -1, 1e-5, out=self.ws[1], ctx=self.ctx)
+        return self.K.fused_quantized_linear_argmax_logprob(xn, p.w, p.scale, p.zero, p.bias, out_ids=self.dec[0], out_logprob=self.sco[0],
+                                                            ctx=self.ctx)
+
     # ---- the packed batch: utterances of different lengths as x [R, D] + offsets, each computed exactly as if it ran alone
     def qls(self, x, off, p, relu, slot):
         return self.K.fused_quantized_linear_segments(x, off, p.w, p.scale, p.zero, p.bias, relu, out=self.ws[slot], ctx=self.ctx)
@@ -243,6 +252,17 @@ class Encoder:
         _, xn, off = self.trunk_segments(feats, offsets)
         ids = K.fused_quantized_linear_argmax_segments(xn, off, p.w, p.scale, p.zero, p.bias, out=self.dec[0], ctx=ctx)
         return K.token_filter_segments(ids, off, skip, width, out_ids=self.dec[1], out_counts=self.dec[2], ctx=ctx)
+
+    def greedy_segments_scored(self, feats, offsets, skip, width=0):
+        """greedy_segments with what a served transcript needs beside the ids -> (ids int32 [count, W], frames int32 [count, W], logprob
+        float32 [count, W], counts int32 [count]): ids and counts are greedy_segments', frames the kept tokens' rows within their utterance
+        (prompt rows included: lele_amd.apps.token_times turns them into seconds), then -1, logprob their log-posteriors, then 0.0"""
+        K, ctx, p = self.K, self.ctx, self.ctc
+        _, xn, off = self.trunk_segments(feats, offsets)
+        ids, lp = K.fused_quantized_linear_argmax_logprob_segments(xn, off, p.w, p.scale, p.zero, p.bias, out_ids=self.dec[0],
+                                                                   out_logprob=self.sco[0], ctx=ctx)
+        return K.token_align_segments(ids, lp, off, skip, width, out_ids=self.dec[1], out_frames=self.sco[1], out_logprob=self.sco[2],
+                                      out_counts=self.dec[2], ctx=ctx)
 
 
 def encoder_arrays(enc):

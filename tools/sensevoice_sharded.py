@@ -10,7 +10,8 @@ weights replicated (same seed on every rank).  A step is: batched front-end (PCM
 plan of the encoder (up to the CTC projection) replayed as one hipGraph -> the greedy head (the projection with the arg-max in its
 epilogue: the logits are never stored) and the blank / special-token filter on the device -> one
 all-gather of the token ids (`lele_amd.sharded.all_gather_ids`; 22 KB per GPU) so that every rank holds the transcripts of
-the whole batch.  No other traffic crosses a link.  Timed region: barrier + device sync on both sides, MAX over ranks.
+the whole batch.  --scores: the head also gives each winner's log-probability and the filter each kept token's frame; they stay on
+their rank, which prints its utterances' mean log-probability and token times.  No other traffic crosses a link.  Timed region: barrier + device sync on both sides, MAX over ranks.
 The topology is assumed and the weights synthetic (SURVEY.md 8a note); what is measured is the path, not accuracy."""
 import argparse
 import json
@@ -33,6 +34,8 @@ def main():
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--dist", action="store_true", help="initialise torch.distributed (nccl = RCCL) even for one rank")
+    ap.add_argument("--scores", action="store_true", help="the scored head on each rank: per utterance the mean log-probability of its "
+                    "kept tokens and their start times are printed by the rank that owns it (the gather of the ids is unchanged)")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     rank, world, local = int(os.environ.get("RANK", 0)), int(os.environ.get("WORLD_SIZE", 1)), int(os.environ.get("LOCAL_RANK", 0))
@@ -84,10 +87,24 @@ def main():
     def greedy(out=None):
         return K.fused_quantized_linear_argmax(xf, ctc.w, ctc.scale, ctc.zero, ctc.bias, out=out, ctx=ctx)
 
+    # --scores: ids + the winners' log-probabilities out of the same epilogue, then the filter that keeps each token's frame and score;
+    # a dense [B, T] batch is the packed layout with offsets i * T, and width T makes its ids the [B, T] block token_filter gives
+    lbuf, frbuf, slbuf = (ctx.buf() for _ in range(3))
+    t4 = int(xf.shape[1])
+    dense_off = np.arange(hi - lo + 1, dtype=np.int64) * t4
+    scored = {}
+
+    def greedy_scored():
+        ids, lp = K.fused_quantized_linear_argmax_logprob(xf, ctc.w, ctc.scale, ctc.zero, ctc.bias, out_ids=abuf, out_logprob=lbuf, ctx=ctx)
+        ids, frames, kept_lp, counts = K.token_align_segments(K.reshape(ids, [-1]), K.reshape(lp, [-1]), dense_off, skip, t4, out_ids=ibuf,
+                                                              out_frames=frbuf, out_logprob=slbuf, out_counts=nbuf, ctx=ctx)
+        scored.update(frames=frames, logprob=kept_lp)          # stay on this rank
+        return ids, counts
+
     def step():
         features()                                                  # same buffers every step: the graph reads cbuf
         graph.launch()
-        ids, counts = K.token_filter(greedy(abuf), skip, out_ids=ibuf, out_counts=nbuf, ctx=ctx)
+        ids, counts = greedy_scored() if args.scores else K.token_filter(greedy(abuf), skip, out_ids=ibuf, out_counts=nbuf, ctx=ctx)
         return all_gather_ids(ids.numpy(), counts.numpy(), total, dist, device)   # .numpy() waits for the stream
 
     def fence():
@@ -128,6 +145,14 @@ def main():
         if args.out:
             os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
             json.dump(rec, open(args.out, "w"), indent=1)
+    if args.scores:      # every rank reports its own utterances: scores and times are not gathered
+        from lele_amd.apps import token_times
+        times, lp = token_times(scored["frames"].numpy()), scored["logprob"].numpy()
+        for i, kept in enumerate(mine):
+            c = len(kept)
+            print(json.dumps({"utterance": lo + i, "rank": rank, "tokens": c,
+                              "mean_logprob": round(float(lp[i, :c].mean()), 5) if c else None,
+                              "token_times_s": [round(float(t), 3) for t in times[i, :c]]}), flush=True)
     if dist is not None:
         dist.barrier()
         dist.destroy_process_group()
