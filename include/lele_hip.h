@@ -643,6 +643,27 @@ int lele_hip_fused_quantized_linear_argmax_logprob_segments(LeleCtx* ctx, const 
                                                             const LeleTensor* weight_int8, const LeleTensor* weight_scale,
                                                             const LeleTensor* weight_zero, const LeleTensor* bias_or_null, LeleBuf* out_ids,
                                                             LeleBuf* out_logprob, int64_t* out_shape, int32_t* out_rank);
+/* The decode head with the k best tokens a frame (tokenizer.rs:50-61 continued past the winner, behind quantization.rs:77-169), for CTC
+ * prefix beam search, n-best lists and rescoring: 1 <= k <= 8, out_ids i32 of the input's shape without its last axis plus a trailing
+ * axis of k, out_logprob f32 of the same shape.  Slot j of a row holds the column of its (j + 1)-th greatest logit v (the result elements
+ * of lele_hip_fused_quantized_linear, apply_relu = 0): the greater value first, of equal values the GREATER COLUMN FIRST, +0.0 and -0.0
+ * equal -- the order the arg-max head breaks ties in, NOT the stable lowest-index-first order of lele_hip_topk (conv2d.rs:1385-1435).
+ * Slot 0 is lele_hip_fused_quantized_linear_argmax_logprob bit for bit, id and score; out_logprob[.., j] = (v_j - v_0) + logprob_0 in
+ * f32; slots j >= N hold id -1 and -inf.  The logits are never stored and no buffer of rows x N elements is reserved: the workspace is
+ * rows * ceil(N / 128) * (8 k + 4) bytes, k keys and one sum per (row, 128-column tile).  No atomics, nothing depends on workgroup
+ * order.  A row holding a NaN or +-inf logit is unspecified.  The two buffers must be distinct.  rows == 0 gives empty results of the
+ * right shape; K == 0, N == 0 or k outside [1, 8] is an error.  Everything is checked before anything is launched or resized;
+ * graph-capturable after one eager run of the same shape. */
+int lele_hip_fused_quantized_linear_topk(LeleCtx* ctx, const LeleTensor* input, const LeleTensor* weight_int8, const LeleTensor* weight_scale,
+                                         const LeleTensor* weight_zero, const LeleTensor* bias_or_null, int32_t k, LeleBuf* out_ids,
+                                         LeleBuf* out_logprob, int64_t* out_shape, int32_t* out_rank);
+/* ... of a packed batch: input f32 [R, K] -> out_ids i32 [R, k], out_logprob f32 [R, k]; the checks, layout table and per-segment range
+ * pass of lele_hip_fused_quantized_linear_argmax_segments, so segment i's rows are bit for bit lele_hip_fused_quantized_linear_topk of
+ * input[off[i]:off[i+1]] alone.  0-row segments are skipped.  Graph-capturable after one eager run of the same layout. */
+int lele_hip_fused_quantized_linear_topk_segments(LeleCtx* ctx, const LeleTensor* input, const int64_t* row_offsets, int64_t count,
+                                                  const LeleTensor* weight_int8, const LeleTensor* weight_scale,
+                                                  const LeleTensor* weight_zero, const LeleTensor* bias_or_null, int32_t k, LeleBuf* out_ids,
+                                                  LeleBuf* out_logprob, int64_t* out_shape, int32_t* out_rank);
 /* lele_hip_token_filter_segments with each kept token's frame and score (tokenizer.rs:50-71 after quantization.rs:77-169 produced the
  * ids): ids i32 [R], logprob_or_null f32 [R], row_offsets host [count + 1] from 0 to R, skip U8 [V] -> out_ids i32 [count, W] and
  * out_counts i32 [count], identical to lele_hip_token_filter_segments for the same arguments; out_frames i32 [count, W]: for each kept

@@ -36,6 +36,45 @@ def token_times(frames, prompt_rows=4, lfr_n=6, frame_shift_ms=10.0):
     return np.where(f < 0, -1.0, t)
 
 
+def ctc_prefix_beam_search(ids, logprob, blank=0, beam=4, nbest=1):
+    """CTC prefix beam search over the k best candidates of every frame, as kernels.fused_quantized_linear_topk gives them for ONE
+    utterance (the caller slices the prompt rows off, as with token_times): ids int [T, k], logprob [T, k] -> the `nbest` best label
+    sequences as [(tuple of ids, log score)], best first, equal scores in the order of the tuples.  The score of a sequence is the log
+    of the sum, over the alignments that collapse to it (repeats merged, then blanks removed) and use only the given candidates, of the
+    product of their frame probabilities.  float64 log space, one blank-ended and one label-ended score per prefix; at most `beam`
+    prefixes survive a frame; a candidate with id -1 (fewer than k columns) is skipped.  Pure host code."""
+    ids, logprob = np.asarray(ids, np.int64), np.asarray(logprob, np.float64)
+    if ids.ndim != 2 or ids.shape != logprob.shape:
+        raise ValueError("ctc_prefix_beam_search: ids and logprob must both be [T, k]")
+    if beam < 1 or nbest < 1:
+        raise ValueError("ctc_prefix_beam_search: beam and nbest must be at least 1")
+    ninf = -np.inf
+    beams = {(): (0.0, ninf)}                   # prefix -> (log p ending in blank, log p ending in its last label)
+    total = lambda s: np.logaddexp(s[0], s[1])  # noqa: E731
+    for t in range(ids.shape[0]):
+        nxt = {}
+
+        def add(prefix, which, lp):
+            s = nxt.setdefault(prefix, [ninf, ninf])
+            s[which] = np.logaddexp(s[which], lp)
+
+        for prefix, (pb, pnb) in beams.items():
+            for c, lp in zip(ids[t].tolist(), logprob[t].tolist()):
+                if c < 0:
+                    continue
+                if c == blank:
+                    add(prefix, 0, np.logaddexp(pb, pnb) + lp)
+                elif prefix and prefix[-1] == c:
+                    add(prefix, 1, pnb + lp)             # the repeat merges
+                    add(prefix + (c,), 1, pb + lp)       # ... unless a blank separates the two
+                else:
+                    add(prefix + (c,), 1, np.logaddexp(pb, pnb) + lp)
+        ranked = sorted(nxt.items(), key=lambda kv: (-total(kv[1]), kv[0]))
+        beams = {p: (s[0], s[1]) for p, s in ranked[:beam]}
+    ranked = sorted(beams.items(), key=lambda kv: (-total(kv[1]), kv[0]))
+    return [(p, float(total(s))) for p, s in ranked[:nbest]]
+
+
 def _ms_to_samples(ms, sample_rate):
     # ((sr as f32) * (ms / 1000.0)).round() as usize -- f32 arithmetic, round half away from zero
     v = np.float32(sample_rate) * (np.float32(ms) / np.float32(1000.0))

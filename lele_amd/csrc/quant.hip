@@ -421,6 +421,7 @@ struct IgemmEpi {
     const int* row_seg = nullptr;   // packed batch (lele_hip_fused_quantized_linear_segments): row -> segment, the slice of prm[]
     unsigned long long* arg_keys = nullptr;  // EM 3 / 4: [column tiles][rows], a tile's best argmax_key(value, column) per row (plain stores)
     float* arg_sums = nullptr;  // EM 4: [column tiles][rows], sum over the tile's columns of exp(value - the tile's maximum) (plain stores)
+    int topk = 0;               // EM 5: keys kept per (row, column tile), 1 .. 8; arg_keys is [column tiles][topk][rows] then
     // Everything that depends only on the row (slice parameters, row-sum term, output row pointer) or only on the
     // column (column sum, weight scale, bias) is computed once per row / column of a thread's tile, not per element.
     struct RowCtx {
@@ -557,6 +558,76 @@ __global__ __launch_bounds__(256) void argmax_logprob_finish_kernel(const unsign
     }
 }
 
+// x into a list sorted greatest first; the least of the nine falls out.  Keys of real candidates are distinct (they carry their column),
+// so the list a set of keys leaves does not depend on the order they came in.
+__device__ __forceinline__ void topk_insert(unsigned long long (&list)[8], unsigned long long x) {
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        const unsigned long long hi = max(list[i], x);
+        x = min(list[i], x);
+        list[i] = hi;
+    }
+}
+// argmax_logprob_finish_kernel for EM 5: keys [tiles][k][rows] -> a row's k greatest keys as ids [rows][k] and log-probabilities.
+// The same 16 rows x 16 threads: thread g keeps the 8 greatest keys of tiles g, g + 16, .., thread 0 merges the 16 lists from LDS.
+// Slot 0's log-probability is argmax_logprob_finish_kernel's, from the tiles' round-0 keys and sums in its addition order; slot j's is
+// (v_j - v_0) + logprob_0 with the values the keys carry.  Key 0 is "no candidate" (fewer than k columns): id -1, -inf.
+__global__ __launch_bounds__(256) void topk_logprob_finish_kernel(const unsigned long long* __restrict__ keys, const float* __restrict__ sums,
+                                                                  int64_t rows, int tiles, int k, int32_t* __restrict__ ids,
+                                                                  float* __restrict__ logprob) {
+    __shared__ unsigned long long s_list[16][8][17];
+    __shared__ float s_part[16][17];
+    const int rr = threadIdx.x & 15, g = threadIdx.x >> 4;
+    const int64_t r = (int64_t)blockIdx.x * 16 + rr;
+    unsigned long long list[8] = {0ull, 0ull, 0ull, 0ull, 0ull, 0ull, 0ull, 0ull};
+    if (r < rows) {
+#pragma unroll 2
+        for (int t = g; t < tiles; t += 16) {  // a tile's keys are requested together (a load behind every insertion is a chain of ~50 round trips)
+            unsigned long long x[8];
+#pragma unroll
+            for (int j = 0; j < 8; ++j) x[j] = j < k ? keys[((int64_t)t * k + j) * rows + r] : 0ull;
+#pragma unroll
+            for (int j = 0; j < 8; ++j)
+                if (x[j] > list[7]) topk_insert(list, x[j]);
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < 8; ++i) s_list[g][i][rr] = list[i];
+    __syncthreads();
+    unsigned long long best = list[0];
+#pragma unroll
+    for (int o = 0; o < 16; ++o) best = max(best, s_list[o][0][rr]);
+    const float mx = argmax_key_value(best);
+    float part = 0.0f;
+    if (r < rows) {
+#pragma unroll 8
+        for (int t = g; t < tiles; t += 16) {
+            const int64_t at = (int64_t)t * rows + r;
+            part += sums[at] * __expf(argmax_key_value(keys[(int64_t)t * k * rows + r]) - mx);
+        }
+    }
+    s_part[g][rr] = part;
+    __syncthreads();
+    if (g == 0 && r < rows) {
+#pragma unroll
+        for (int o = 1; o < 16; ++o) part += s_part[o][rr];
+        for (int o = 1; o < 16; ++o)
+#pragma unroll
+            for (int i = 0; i < 8; ++i) {
+                const unsigned long long x = s_list[o][i][rr];
+                if (x > list[7]) topk_insert(list, x);
+            }
+        const float lp0 = 0.0f - logf(part);  // S == 1 gives +0.0
+#pragma unroll
+        for (int j = 0; j < 8; ++j)
+            if (j < k) {
+                const bool none = list[j] == 0ull;
+                ids[r * k + j] = none ? -1 : (int32_t)(unsigned)list[j];
+                logprob[r * k + j] = j == 0 ? lp0 : none ? -INFINITY : (argmax_key_value(list[j]) - mx) + lp0;
+            }
+    }
+}
+
 // EM (epilogue mode) 0: the result as f32.  EM 1 / 2 are the two passes of the fused two-layer form, where the f32 result (the
 // hidden layer of a feed-forward block, 45 MB per configs[3] shard) never exists in HBM -- recomputing the product costs ~5 us of
 // matrix-core time against ~30 us of traffic for writing it and reading it twice:
@@ -571,6 +642,11 @@ __global__ __launch_bounds__(256) void argmax_logprob_finish_kernel(const unsign
 //   rescales and adds the tiles.  The maximum is the one the key butterfly found, so the sums are taken after it, by the same butterfly
 //   with plain f32 adds (commutative bit for bit, the pairing lane ^ 16, 8, 4, 2, 1 the same for every row) and joined over the waves in
 //   wave order: a row's sum depends on (n, column) only, not on where the row sits in its tile.
+// EM 5 is EM 4 with the tile's epi.topk best keys per row instead of one (lele_hip_fused_quantized_linear_topk): epi.topk rounds of EM 3's
+//   butterfly and join over the lane's 32 kept logits.  Round j stores the tile's j-th key per row in epi.arg_keys[tile][j][row]; a
+//   column that has won a row takes no part in that row from then on (masked by COLUMN -- the lane clears its own key word of that row:
+//   equal values in other columns stay candidates), and a round that finds nothing left stores key 0.  Round 0 is EM 3's key, the sums
+//   are EM 4's, taken behind round 0.  topk_logprob_finish_kernel merges the tiles.
 template <int BM, int BN, int WM, int WN, int BKB /* bytes of K per LDS tile: 64 or 128 */, int OCC = 1, int EM = 0>
 __global__ __launch_bounds__(WM* WN * 64) __attribute__((amdgpu_waves_per_eu(OCC))) void igemm_kernel(const int8_t* __restrict__ a, const int8_t* __restrict__ b,
                                                             int64_t rows, int n, int kp, int64_t b_batch_stride,
@@ -870,6 +946,107 @@ __global__ __launch_bounds__(WM* WN * 64) __attribute__((amdgpu_waves_per_eu(OCC
 #pragma unroll
             for (int w = 1; w < WN; ++w) best = max(best, s_key[w * BM + t]);
             epi.arg_keys[(int64_t)tx * rows + m0 + t] = best;
+        }
+        return;
+    }
+    if constexpr (EM == 5) {
+        static_assert(EM != 5 || (TMT == 2 && TNT == 1 && NT >= BM), "EM 5: EM 4's tile, one column a lane, one thread a row in the joins");
+        const int rows_here = (int)(rows - m0 < BM ? rows - m0 : BM);
+        const int kk = epi.topk;
+        // the lane's 32 logits as the high words of their keys: a key is the register pair {column, word}, made by no instruction.  (The
+        // sums take the values back out, -0.0 as +0.0, which no difference to a maximum and no exponential tells apart; kept as values the
+        // rounds' loop would hold both forms, 32 registers more than two workgroups a CU leave.)  Word 0 is "no candidate": a padded
+        // column from the start, a column that has won the row from then on -- masked by COLUMN, equal values elsewhere stay.  Every
+        // real value's word is > 0.
+        const bool valid = cols[0] < n;
+        unsigned kb[TMT * 16];
+#pragma unroll
+        for (int i = 0; i < TMT; ++i)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int lr = wm * TMT * 32 + i * 32 + 4 * hv + (r & 3) + 8 * (r >> 2);
+                const IgemmEpi::RowCtx rc{s_ca[lr], s_rterm[lr], s_ds[lr], nullptr};
+                kb[i * 16 + r] = valid ? (unsigned)(argmax_key(epi.value24(rc, cc[0], acc[i][0][r]), 0) >> 32) : 0u;
+            }
+        unsigned long long* const s_key = reinterpret_cast<unsigned long long*>(igemm_lds);  // [WN][BM], as EM 4
+        float* const s_max = reinterpret_cast<float*>(igemm_lds + WN * BM * 8);              // [BM], round 0's maximum per row
+        float* const s_sum = s_max + BM;                                                     // [WN][BM]
+        unsigned* const s_win = reinterpret_cast<unsigned*>(s_sum + WN * BM);                // [BM], the round's winning column per row
+        const int mine = wm * TMT * 32 + (l31 >> 4) * 32 + 4 * hv + ((l31 & 15) & 3) + 8 * ((l31 & 15) >> 2);  // the row lane l31 ends up with
+        // EM 4's sums, relative to round 0's maximum: the same operations in the same order, taken once, behind round 0
+        auto tile_sums = [&]() {
+            float val[TMT * 16];
+#pragma unroll
+            for (int i = 0; i < TMT; ++i)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const int lr = wm * TMT * 32 + i * 32 + 4 * hv + (r & 3) + 8 * (r >> 2);
+                    const float e = __expf(argmax_key_value((unsigned long long)kb[i * 16 + r] << 32) - s_max[lr]);
+                    val[i * 16 + r] = valid ? e : 0.0f;
+                }
+#pragma unroll
+            for (int s = 0; s < 5; ++s) {
+                const int half = 16 >> s;
+                const bool up = (lane & half) != 0;
+#pragma unroll
+                for (int t = 0; t < half; ++t) {
+                    const float send = up ? val[t] : val[t + half];
+                    const float keep = up ? val[t + half] : val[t];
+                    val[t] = keep + __shfl_xor(send, half);
+                }
+            }
+            s_sum[wn * BM + mine] = val[0];
+            __syncthreads();
+            if (tid < rows_here) {
+                float sum = s_sum[tid];
+#pragma unroll
+                for (int w = 1; w < WN; ++w) sum += s_sum[w * BM + tid];
+                epi.arg_sums[(int64_t)tx * rows + m0 + tid] = sum;
+            }
+        };
+        for (int j = 0; j < kk; ++j) {
+            // EM 3's butterfly; the keys are made inside its first step, so that 16 of them are live and not 32 (registers: two workgroups
+            // a CU need <= 128)
+            unsigned long long key[16];
+#pragma unroll
+            for (int t = 0; t < 16; ++t) {
+                const bool up = (lane & 16) != 0;
+                const unsigned long long lo = ((unsigned long long)kb[t] << 32) | (unsigned)cols[0];
+                const unsigned long long hi = ((unsigned long long)kb[t + 16] << 32) | (unsigned)cols[0];
+                key[t] = max(up ? hi : lo, (unsigned long long)__shfl_xor(up ? lo : hi, 16));
+            }
+#pragma unroll
+            for (int s = 1; s < 5; ++s) {
+                const int half = 16 >> s;
+                const bool up = (lane & half) != 0;
+#pragma unroll
+                for (int t = 0; t < half; ++t) {
+                    const unsigned long long send = up ? key[t] : key[t + half];
+                    const unsigned long long keep = up ? key[t + half] : key[t];
+                    key[t] = max(keep, (unsigned long long)__shfl_xor(send, half));
+                }
+            }
+            s_key[wn * BM + mine] = key[0];
+            __syncthreads();
+            if (tid < BM) {  // rows past the last are the last row again (clamped context): computed, never stored
+                unsigned long long best = s_key[tid];
+#pragma unroll
+                for (int w = 1; w < WN; ++w) best = max(best, s_key[w * BM + tid]);
+                const bool any = (best >> 32) != 0ull;  // nothing left in this tile: key 0, and no column matches
+                if (tid < rows_here) epi.arg_keys[((int64_t)tx * kk + j) * rows + m0 + tid] = any ? best : 0ull;
+                if (j == 0) s_max[tid] = argmax_key_value(best);
+                s_win[tid] = any ? (unsigned)best : ~0u;
+            }
+            __syncthreads();  // (the next round's s_key stores come after every read of this round's; its s_win stores after its first barrier)
+            if (j == 0) tile_sums();
+            if (j + 1 == kk) break;  // nothing follows the last round's winners
+#pragma unroll
+            for (int i = 0; i < TMT; ++i)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const int lr = wm * TMT * 32 + i * 32 + 4 * hv + (r & 3) + 8 * (r >> 2);
+                    kb[i * 16 + r] = s_win[lr] == (unsigned)cols[0] ? 0u : kb[i * 16 + r];
+                }
         }
         return;
     }
@@ -1256,6 +1433,34 @@ int launch_igemm_argmax(LeleCtx* ctx, const int8_t* aq, const int8_t* wt, int64_
     LELE_HIP_CHECK(ensure_dyn_lds(reinterpret_cast<const void*>(kern), (int)lds));
     hipLaunchKernelGGL(kern, grid, dim3(512), lds, ctx->stream, aq, wt, rows, n, kp, (int64_t)0, m, epi);
     hipLaunchKernelGGL(argmax_finish_kernel, dim3((unsigned)((rows + 15) / 16)), dim3(256), 0, ctx->stream, (const unsigned long long*)keys, rows, (int)grid.x, ids);
+    LELE_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
+// The k-best head's two tables, rows * ceil(n / 128) * (8 topk + 4) bytes together.  They live in the context's scratch block, not in
+// the staging arena: at 64 x 171 rows and k = 4 they are 77 MB, more than the arena holds, and an arena that overflows cannot be
+// captured; the scratch block grows in the eager run that a capture needs anyway.
+int topk_workspace(LeleCtx* ctx, int64_t rows, int64_t n, int topk, void** keys, void** sums) {
+    const size_t key_bytes = (size_t)topk * argmax_key_bytes(rows, n);
+    void* base = nullptr;
+    LELE_TRY(ctx->get_scratch(key_bytes + argmax_sum_bytes(rows, n), &base));
+    *keys = base, *sums = (char*)base + key_bytes;
+    return 0;
+}
+// the k-best head (EM 5): `keys` of topk * argmax_key_bytes(rows, n), `sums` of argmax_sum_bytes(rows, n) -- rows * ceil(n / 128) *
+// (8 topk + 4) bytes together; ids / logprob [rows][topk]
+int launch_igemm_topk(LeleCtx* ctx, const int8_t* aq, const int8_t* wt, int64_t rows, int n, int kp, int m, const IgemmEpi& epi_in, int topk,
+                      unsigned long long* keys, float* sums, int32_t* ids, float* logprob) {
+    LELE_REQUIRE(rows < (int64_t(128) * 65535), "quantized GEMM: more than 128 x 65535 rows");
+    constexpr size_t lds = (size_t)2 * (128 + 128) * (128 + 16);
+    IgemmEpi epi = epi_in;
+    epi.arg_keys = keys, epi.arg_sums = sums, epi.topk = topk;
+    const dim3 grid((n + 127) / 128, (unsigned)((rows + 127) / 128));
+    auto kern = igemm_kernel<128, 128, 2, 4, 128, 4, 5>;  // <= 128 registers: two workgroups a CU, as EM 3 / EM 4 get by themselves
+    LELE_HIP_CHECK(ensure_dyn_lds(reinterpret_cast<const void*>(kern), (int)lds));
+    hipLaunchKernelGGL(kern, grid, dim3(512), lds, ctx->stream, aq, wt, rows, n, kp, (int64_t)0, m, epi);
+    hipLaunchKernelGGL(topk_logprob_finish_kernel, dim3((unsigned)((rows + 15) / 16)), dim3(256), 0, ctx->stream, (const unsigned long long*)keys,
+                       (const float*)sums, rows, (int)grid.x, topk, ids, logprob);
     LELE_HIP_CHECK(hipGetLastError());
     return 0;
 }
@@ -1650,6 +1855,7 @@ struct QReq {  // what the caller wants around the product
     LnReq* ln = nullptr;
     int argmax = 0;  // the greedy head: `out` receives argmax_last of the result as i32 [rows], the result itself is never stored
     LeleBuf* logprob = nullptr;  // ... with the winner's log-probability as f32 [rows] (needs argmax; igemm_kernel EM 4)
+    int topk = 0;  // ... the k best a row, 1 .. 8: `out` i32 [rows][topk], logprob f32 [rows][topk] (needs both; igemm_kernel EM 5)
 };
 // one layer, validated and staged: what a route's body reads
 struct QLayer {
@@ -1664,6 +1870,7 @@ struct QLayer {
     int nblk = 0;
     LeleBuf* out = nullptr;
     LeleBuf* logprob = nullptr;  // QReq::logprob
+    int topk = 0;                // QReq::topk
 };
 IgemmEpi make_epi(const QLayer& l, float* out, const int* row_sums, const int* col_sums) {
     return IgemmEpi{out, l.c.rows, l.c.n, (int)l.c.m, (int)l.c.k, row_sums, col_sums, l.prm, 0, (int)l.wz, l.ws, (int)l.c.ws_len, l.bias, l.relu,
@@ -1816,6 +2023,12 @@ int run_tiled(LeleCtx* ctx, const QLayer& l, bool argmax = false) {
     LELE_TRY(qprof_mark(ctx, 2));
     if (argmax) {
         void *keys = nullptr, *sums = nullptr;
+        if (l.topk) {
+            LELE_TRY(topk_workspace(ctx, c.rows, c.n, l.topk, &keys, &sums));
+            LELE_TRY(launch_igemm_topk(ctx, (const int8_t*)aq, pw.wt, c.rows, (int)c.n, kp, (int)c.m, make_epi(l, nullptr, (const int*)rs, pw.col_sums),
+                                       l.topk, (unsigned long long*)keys, (float*)sums, (int32_t*)l.out->data, (float*)l.logprob->data));
+            return qprof_mark(ctx, 3);
+        }
         LELE_TRY(ctx->arena_alloc(argmax_key_bytes(c.rows, c.n), &keys));
         if (l.logprob) LELE_TRY(ctx->arena_alloc(argmax_sum_bytes(c.rows, c.n), &sums));
         LELE_TRY(launch_igemm_argmax(ctx, (const int8_t*)aq, pw.wt, c.rows, (int)c.n, kp, (int)c.m, make_epi(l, nullptr, (const int*)rs, pw.col_sums),
@@ -1836,16 +2049,21 @@ int run_tiled(LeleCtx* ctx, const QLayer& l, bool argmax = false) {
 int fql_impl(LeleCtx* ctx, const LeleTensor* input, const QW& w, const QReq& rq, LeleBuf* out, int64_t* out_shape, int32_t* out_rank) {
     LELE_REQUIRE(ctx && input && w.w && w.scale && out, "fused_quantized_linear: NULL argument");
     QLayer l;
-    const char* const who = rq.logprob ? "fused_quantized_linear_argmax_logprob" : rq.argmax ? "fused_quantized_linear_argmax" : "fused_quantized_linear";
+    const char* const who = rq.topk      ? "fused_quantized_linear_topk"
+                            : rq.logprob ? "fused_quantized_linear_argmax_logprob"
+                            : rq.argmax  ? "fused_quantized_linear_argmax"
+                                         : "fused_quantized_linear";
     LELE_TRY(describe_call(who, input, w, &l.c));
     QCall& c = l.c;
     if (rq.argmax) {  // ids: the input's shape without its last axis, one i32 a row
         LELE_REQUIRE(c.n >= 1 && c.k >= 1, "%s: empty K or N (K = %lld, N = %lld)", who, (long long)c.k, (long long)c.n);
         c.shp.pop_back();
+        if (rq.topk) c.shp.push_back(rq.topk);  // ... or topk a row
     }
+    const size_t per_row = rq.topk ? (size_t)rq.topk : 1;
     LELE_HIP_CHECK(hipSetDevice(ctx->device));
-    LELE_TRY(out->reserve(rq.argmax ? (size_t)c.rows * 4 : (size_t)c.rows * c.n * 4));
-    if (rq.logprob) LELE_TRY(rq.logprob->reserve((size_t)c.rows * 4));
+    LELE_TRY(out->reserve(rq.argmax ? (size_t)c.rows * per_row * 4 : (size_t)c.rows * c.n * 4));
+    if (rq.logprob) LELE_TRY(rq.logprob->reserve((size_t)c.rows * per_row * 4));
     if (c.rows == 0 || c.n == 0) return set_shape_v(out_shape, out_rank, c.shp);
     LELE_TRY(ctx->arena_reset());
     const void *dx = nullptr, *dws = nullptr, *db = nullptr, *dr1 = nullptr, *dr2 = nullptr;
@@ -1859,7 +2077,7 @@ int fql_impl(LeleCtx* ctx, const LeleTensor* input, const QW& w, const QReq& rq,
     void* prm = nullptr;
     LELE_TRY(ctx->arena_alloc((size_t)c.batch * sizeof(QParams), &prm));
     l.weight = w.w, l.x = (const float*)dx, l.ws = (const float*)dws, l.bias = (const float*)db, l.relu = rq.relu;
-    l.res1 = (const float*)dr1, l.res2 = (const float*)dr2, l.prm = (QParams*)prm, l.out = out, l.logprob = rq.logprob;
+    l.res1 = (const float*)dr1, l.res2 = (const float*)dr2, l.prm = (QParams*)prm, l.out = out, l.logprob = rq.logprob, l.topk = rq.topk;
     LELE_TRY(qprof_mark(ctx, 0));
     if (!l.partial) LELE_TRY(launch_range(ctx, l.x, c.batch, c.m * c.k, l.prm, nullptr, nullptr, &l.partial, &l.nblk));
     LELE_TRY(qprof_mark(ctx, 1));
@@ -2083,7 +2301,8 @@ int ffn_impl(LeleCtx* ctx, const LeleTensor* input, const QW& w1, const QW& w2, 
 int fql_segments_impl(LeleCtx* ctx, const char* who, int argmax, const LeleTensor* input, const int64_t* row_offsets, int64_t count,
                       const LeleTensor* weight_int8, const LeleTensor* weight_scale, const LeleTensor* weight_zero,
                       const LeleTensor* bias, int apply_relu, LeleBuf* out, int64_t* out_shape, int32_t* out_rank,
-                      LeleBuf* logprob = nullptr /* with argmax: the winners' log-probabilities f32 [R] (EM 4) */) {
+                      LeleBuf* logprob = nullptr /* with argmax: the winners' log-probabilities f32 [R] (EM 4) */,
+                      int topk = 0 /* with logprob: the k best a row, ids and log-probabilities [R, topk] (EM 5) */) {
     LELE_REQUIRE(ctx && input && weight_int8 && weight_scale && out, "%s: NULL argument", who);
     int64_t rows = 0, k = 0, tmax = 0;
     LELE_TRY(seg_offsets(input, row_offsets, count, &rows, &k, &tmax, who));
@@ -2096,7 +2315,8 @@ int fql_segments_impl(LeleCtx* ctx, const char* who, int argmax, const LeleTenso
     if (argmax) {  // ids [R]: one i32 a row, the result itself is never stored
         LELE_REQUIRE(n >= 1 && k >= 1, "%s: empty K or N (K = %lld, N = %lld)", who, (long long)k, (long long)n);
         c.shp.pop_back();
-        out_bytes = (size_t)rows * 4;
+        if (topk) c.shp.push_back(topk);
+        out_bytes = (size_t)rows * (topk ? topk : 1) * 4;
     }
     LELE_HIP_CHECK(hipSetDevice(ctx->device));
     const void* tab = nullptr;
@@ -2139,8 +2359,9 @@ int fql_segments_impl(LeleCtx* ctx, const char* who, int argmax, const LeleTenso
     void *aq = nullptr, *rs = nullptr, *keys = nullptr, *sums = nullptr;
     LELE_TRY(ctx->arena_alloc((size_t)rows * kp, &aq));
     LELE_TRY(ctx->arena_alloc((size_t)rows * 4, &rs));
-    if (argmax) LELE_TRY(ctx->arena_alloc(argmax_key_bytes(rows, n), &keys));
-    if (logprob) LELE_TRY(ctx->arena_alloc(argmax_sum_bytes(rows, n), &sums));
+    if (topk) LELE_TRY(topk_workspace(ctx, rows, n, topk, &keys, &sums));
+    else if (argmax) LELE_TRY(ctx->arena_alloc(argmax_key_bytes(rows, n), &keys));
+    if (logprob && !topk) LELE_TRY(ctx->arena_alloc(argmax_sum_bytes(rows, n), &sums));
     // every fallible step is behind us: `out` is as it was until here (reserve clears any producer-side statistics of `out`;
     // those of `input` describe equal slices and are not read)
     LELE_TRY(out->reserve(out_bytes));
@@ -2150,7 +2371,10 @@ int fql_segments_impl(LeleCtx* ctx, const char* who, int argmax, const LeleTenso
     LELE_TRY(qprof_mark(ctx, 2));
     IgemmEpi epi = make_epi(l, argmax ? nullptr : (float*)out->data, (const int*)rs, pw.col_sums);
     epi.row_seg = drowseg;
-    if (argmax)
+    if (topk)
+        LELE_TRY(launch_igemm_topk(ctx, (const int8_t*)aq, pw.wt, rows, (int)n, kp, (int)rows, epi, topk, (unsigned long long*)keys, (float*)sums,
+                                   (int32_t*)out->data, (float*)logprob->data));
+    else if (argmax)
         LELE_TRY(launch_igemm_argmax(ctx, (const int8_t*)aq, pw.wt, rows, (int)n, kp, (int)rows, epi, (unsigned long long*)keys, (int32_t*)out->data,
                                      (float*)sums, logprob ? (float*)logprob->data : nullptr));
     else LELE_TRY(launch_igemm(ctx, (const int8_t*)aq, pw.wt, rows, (int)n, kp, (int)rows, epi));
@@ -2213,6 +2437,30 @@ int lele_hip_fused_quantized_linear_argmax_logprob_segments(LeleCtx* ctx, const 
     LELE_REQUIRE(out_ids && out_logprob && out_ids != out_logprob, "fused_quantized_linear_argmax_logprob_segments: two distinct output buffers required");
     return fql_segments_impl(ctx, "fused_quantized_linear_argmax_logprob_segments", 1, input, row_offsets, count, weight_int8, weight_scale,
                              weight_zero, bias, 0, out_ids, out_shape, out_rank, out_logprob);
+}
+
+/* ... and the k best tokens a frame (1 <= k <= 8) in argmax_key's order -- greater value first, of equal values the greater column first --
+ * with their log-probabilities, from k rounds of the same epilogue (igemm_kernel EM 5).  Slot 0 is the call above bit for bit. */
+int lele_hip_fused_quantized_linear_topk(LeleCtx* ctx, const LeleTensor* input, const LeleTensor* weight_int8, const LeleTensor* weight_scale,
+                                         const LeleTensor* weight_zero, const LeleTensor* bias, int32_t k, LeleBuf* out_ids,
+                                         LeleBuf* out_logprob, int64_t* out_shape, int32_t* out_rank) {
+    LELE_REQUIRE(out_ids && out_logprob && out_ids != out_logprob, "fused_quantized_linear_topk: two distinct output buffers required");
+    LELE_REQUIRE(k >= 1 && k <= 8, "fused_quantized_linear_topk: k = %d outside [1, 8]", (int)k);
+    QReq rq;
+    rq.argmax = 1;
+    rq.logprob = out_logprob;
+    rq.topk = k;
+    return fql_impl(ctx, input, {weight_int8, weight_scale, weight_zero, bias}, rq, out_ids, out_shape, out_rank);
+}
+
+int lele_hip_fused_quantized_linear_topk_segments(LeleCtx* ctx, const LeleTensor* input, const int64_t* row_offsets, int64_t count,
+                                                  const LeleTensor* weight_int8, const LeleTensor* weight_scale, const LeleTensor* weight_zero,
+                                                  const LeleTensor* bias, int32_t k, LeleBuf* out_ids, LeleBuf* out_logprob,
+                                                  int64_t* out_shape, int32_t* out_rank) {
+    LELE_REQUIRE(out_ids && out_logprob && out_ids != out_logprob, "fused_quantized_linear_topk_segments: two distinct output buffers required");
+    LELE_REQUIRE(k >= 1 && k <= 8, "fused_quantized_linear_topk_segments: k = %d outside [1, 8]", (int)k);
+    return fql_segments_impl(ctx, "fused_quantized_linear_topk_segments", 1, input, row_offsets, count, weight_int8, weight_scale, weight_zero,
+                             bias, 0, out_ids, out_shape, out_rank, out_logprob, k);
 }
 
 int lele_hip_fused_quantized_linear_residual(LeleCtx* ctx, const LeleTensor* input, const LeleTensor* weight_int8,

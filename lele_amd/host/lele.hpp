@@ -1039,6 +1039,30 @@ inline std::pair<TensorView, TensorView> fused_quantized_linear_argmax_logprob_s
     std::vector<int64_t> shp(sh.dims, sh.dims + sh.rank);
     return {TensorView::from_device(out_ids, shp, LELE_I32), TensorView::from_device(out_logprob, shp, LELE_F32)};
 }
+// the decode head with the k best tokens a frame (1 <= k <= 8) -> (ids i32 [.., k], logprob f32 [.., k]): greater value first, of equal
+// values the greater column first; slot 0 is fused_quantized_linear_argmax_logprob bit for bit, missing candidates are -1 / -inf
+inline std::pair<TensorView, TensorView> fused_quantized_linear_topk(const TensorView& input, const TensorView& weight_int8,
+                                                                     const TensorView& weight_scale, const TensorView& weight_zero,
+                                                                     const TensorView* bias, int32_t k, Buffer& out_ids, Buffer& out_logprob) {
+    Shape sh;
+    LeleTensor a = input.c(), b = weight_int8.c(), s = weight_scale.c(), z = weight_zero.c();
+    Opt ob(bias);
+    check(lele_hip_fused_quantized_linear_topk(ctx(), &a, &b, &s, &z, ob.p, k, out_ids.raw(), out_logprob.raw(), sh.dims, &sh.rank));
+    std::vector<int64_t> shp(sh.dims, sh.dims + sh.rank);
+    return {TensorView::from_device(out_ids, shp, LELE_I32), TensorView::from_device(out_logprob, shp, LELE_F32)};
+}
+inline std::pair<TensorView, TensorView> fused_quantized_linear_topk_segments(const TensorView& input, const std::vector<int64_t>& offsets,
+                                                                              const TensorView& weight_int8, const TensorView& weight_scale,
+                                                                              const TensorView& weight_zero, const TensorView* bias, int32_t k,
+                                                                              Buffer& out_ids, Buffer& out_logprob) {
+    Shape sh;
+    LeleTensor a = input.c(), b = weight_int8.c(), s = weight_scale.c(), z = weight_zero.c();
+    Opt ob(bias);
+    check(lele_hip_fused_quantized_linear_topk_segments(ctx(), &a, offsets.data(), (int64_t)offsets.size() - 1, &b, &s, &z, ob.p, k,
+                                                        out_ids.raw(), out_logprob.raw(), sh.dims, &sh.rank));
+    std::vector<int64_t> shp(sh.dims, sh.dims + sh.rank);
+    return {TensorView::from_device(out_ids, shp, LELE_I32), TensorView::from_device(out_logprob, shp, LELE_F32)};
+}
 // token_filter_segments with each kept token's frame (row within its segment, then -1) and, where `logprob` is given, its score (then 0.0)
 struct AlignedTokens {
     TensorView ids, frames, logprob, counts;  // logprob: an empty view when no scores were given

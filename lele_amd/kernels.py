@@ -1289,6 +1289,38 @@ def fused_quantized_linear_argmax_logprob_segments(input, offsets, weight_int8, 
     return TensorView(_lib.DevTensor(oi, shape, np.int32)), TensorView(_lib.DevTensor(ol, shape, np.float32))
 
 
+def fused_quantized_linear_topk(input, weight_int8, weight_scale, weight_zero, bias, k, out_ids=None, out_logprob=None, ctx=None):
+    """the decode head with the k best tokens a frame, 1 <= k <= 8 -> (ids int32, logprob float32), both the input's shape without its last
+    axis plus a trailing axis of k: slot j holds the column of the row's (j + 1)-th greatest logit -- greater value first, of equal values
+    the greater column first (not topk's stable order) -- and its log-probability; slot 0 is fused_quantized_linear_argmax_logprob bit for
+    bit, slots past the row's length hold -1 / -inf.  The logits are never stored."""
+    ctx = _ctx(ctx)
+    keep = []
+    oi, ol = out_ids or ctx.buf(), out_logprob or ctx.buf()
+    sh = _lib.OutShape()
+    _lib.check(_lib.lib().lele_hip_fused_quantized_linear_topk(
+        ctx._h, _t(input, keep), _t(weight_int8, keep), _t(weight_scale, keep), _t(weight_zero, keep), _t(bias, keep), C.c_int32(int(k)),
+        oi._h, ol._h, sh.shape, C.byref(sh.rank)))
+    shape = sh.get()
+    return TensorView(_lib.DevTensor(oi, shape, np.int32)), TensorView(_lib.DevTensor(ol, shape, np.float32))
+
+
+def fused_quantized_linear_topk_segments(input, offsets, weight_int8, weight_scale, weight_zero, bias, k, out_ids=None, out_logprob=None,
+                                         ctx=None):
+    """fused_quantized_linear_topk with every segment of the packed input [R, K] as a batch slice of its own -> (int32 [R, k], float32
+    [R, k]): rows offsets[i] .. offsets[i + 1] are, bit for bit, the dense call on that range alone"""
+    ctx = _ctx(ctx)
+    keep = []
+    oi, ol = out_ids or ctx.buf(), out_logprob or ctx.buf()
+    sh = _lib.OutShape()
+    off = _offsets(offsets)
+    _lib.check(_lib.lib().lele_hip_fused_quantized_linear_topk_segments(
+        ctx._h, _t(input, keep), _lib.i64_ptr(off), C.c_int64(len(off) - 1), _t(weight_int8, keep), _t(weight_scale, keep),
+        _t(weight_zero, keep), _t(bias, keep), C.c_int32(int(k)), oi._h, ol._h, sh.shape, C.byref(sh.rank)))
+    shape = sh.get()
+    return TensorView(_lib.DevTensor(oi, shape, np.int32)), TensorView(_lib.DevTensor(ol, shape, np.float32))
+
+
 def token_align_segments(ids, logprob, offsets, skip, width=0, out_ids=None, out_frames=None, out_logprob=None, out_counts=None, ctx=None):
     """token_filter_segments with each kept token's frame and score: packed ids int32 [R], logprob float32 [R] or None -> (ids int32
     [count, W] padded with -1, frames int32 [count, W]: the kept ids' row indices within their segment, then -1, logprob float32

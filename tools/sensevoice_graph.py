@@ -190,6 +190,15 @@ class Encoder:
         return self.K.fused_quantized_linear_argmax_logprob(xn, p.w, p.scale, p.zero, p.bias, out_ids=self.dec[0], out_logprob=self.sco[0],
                                                             ctx=self.ctx)
 
+    def topk(self, feats, k):
+        """feats: [B, T, 560] -> (ids int32 [B, T+4, k], logprob float32 [B, T+4, k]): every frame's k best tokens (1 <= k <= 8) and their
+        log-posteriors out of the CTC projection's epilogue, slot 0 greedy_scored's bit for bit -- what lele_amd.apps.ctc_prefix_beam_search
+        consumes per utterance; the logits are never stored"""
+        p = self.ctc
+        xn = self.K.layer_norm(self.trunk(feats), self.ln_out[0], self.ln_out[1], -1, 1e-5, out=self.ws[1], ctx=self.ctx)
+        return self.K.fused_quantized_linear_topk(xn, p.w, p.scale, p.zero, p.bias, k, out_ids=self.dec[0], out_logprob=self.sco[0],
+                                                  ctx=self.ctx)
+
     # ---- the packed batch: utterances of different lengths as x [R, D] + offsets, each computed exactly as if it ran alone
     def qls(self, x, off, p, relu, slot):
         return self.K.fused_quantized_linear_segments(x, off, p.w, p.scale, p.zero, p.bias, relu, out=self.ws[slot], ctx=self.ctx)
@@ -263,6 +272,15 @@ class Encoder:
                                                                    out_logprob=self.sco[0], ctx=ctx)
         return K.token_align_segments(ids, lp, off, skip, width, out_ids=self.dec[1], out_frames=self.sco[1], out_logprob=self.sco[2],
                                       out_counts=self.dec[2], ctx=ctx)
+
+    def topk_segments(self, feats, offsets, k):
+        """feats: packed [R, 560], offsets [count + 1] -> (ids int32 [R', k], logprob float32 [R', k], offsets' [count + 1]): topk per
+        utterance of the packed batch, R' = R + 4 count rows (every utterance behind its prompt rows), offsets' their layout"""
+        K, ctx, p = self.K, self.ctx, self.ctc
+        _, xn, off = self.trunk_segments(feats, offsets)
+        ids, lp = K.fused_quantized_linear_topk_segments(xn, off, p.w, p.scale, p.zero, p.bias, k, out_ids=self.dec[0], out_logprob=self.sco[0],
+                                                         ctx=ctx)
+        return ids, lp, off
 
 
 def encoder_arrays(enc):
