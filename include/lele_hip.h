@@ -675,6 +675,26 @@ int lele_hip_fused_quantized_linear_topk_segments(LeleCtx* ctx, const LeleTensor
 int lele_hip_token_align_segments(LeleCtx* ctx, const LeleTensor* ids, const LeleTensor* logprob_or_null, const int64_t* row_offsets,
                                   int64_t count, const LeleTensor* skip, int64_t width, LeleBuf* out_ids, LeleBuf* out_frames,
                                   LeleBuf* out_logprob, LeleBuf* out_counts, int64_t* out_shape, int32_t* out_rank);
+/* CTC prefix beam search over the k best candidates of every frame, per segment of a packed batch (the consumer of
+ * lele_hip_fused_quantized_linear_topk_segments): ids i32 [R, k], logprob f32 [R, k], 1 <= k <= 8, row_offsets host [count + 1] from 0 to
+ * R.  Segment i's frames are rows off[i] + skip_rows .. off[i + 1] (none when it has at most skip_rows rows; SenseVoice: 4 prompt rows).
+ * 1 <= beam <= 8 prefixes survive a frame, 1 <= nbest <= beam are reported, best first: out_tokens i32 [count, nbest, W] (the reported
+ * shape): the label sequence, then -1; out_lengths i32 [count, nbest]; out_scores f32 [count, nbest]: the log of the summed probability
+ * of the alignments that collapse to the sequence, accumulated and ordered in float64 and rounded once; out_counts i32 [count]: the
+ * hypotheses the segment has (<= nbest; a segment without frames has one, empty, score +0.0; slots past it hold -1 / 0 / -inf).  A
+ * candidate with id < 0 is skipped; equal totals are ordered as tuples of labels compare (element by element, of a sequence and its
+ * extension the shorter first); ids are labels only, nothing is indexed by one.  The ids of a frame must be distinct; with duplicates, or with
+ * NaN / +inf scores, the result is unspecified but the call terminates and stays inside its buffers (entries are ordered strictly,
+ * by total, tuple and entry index; a NaN total ranks as -inf).  W = width, or with width == 0 the most frames of any segment (at least 1); a segment
+ * with more frames than a given width is an error that names it.  The four buffers must be distinct.  Workspace: the prefix trie, 8 * (1 +
+ * beam * most frames) bytes a segment -- in LDS while that is at most 56 KiB (895 frames at beam 8), beyond it count times as much of the
+ * context's scratch block.  A dense [B, T, k] batch is the packed layout with off[i] = i * T: there is
+ * no dense twin.  Everything is checked before anything is launched or resized; count == 0 and R == 0 give empty results of the right
+ * shape.  Graph-capturable after one eager run of the same layout. */
+int lele_hip_ctc_beam_search_segments(LeleCtx* ctx, const LeleTensor* ids, const LeleTensor* logprob, const int64_t* row_offsets,
+                                      int64_t count, int64_t skip_rows, int32_t blank, int32_t beam, int32_t nbest, int64_t width,
+                                      LeleBuf* out_tokens, LeleBuf* out_lengths, LeleBuf* out_scores, LeleBuf* out_counts,
+                                      int64_t* out_shape, int32_t* out_rank);
 /* lele_hip_attention_view per segment: qkv f32 [R, P] holds Q, K, V of `heads` heads of width dh at columns q_offset, k_offset,
  * v_offset (head h at + h * dh); for every segment and head softmax(Q K^T * scale) V over THAT SEGMENT's rows only, queries and keys
  * alike (gemm.rs:112-222, norm.rs:8) -> out [R, heads * dh], heads merged.  Supported: dh == 128, every segment <= 512 rows, q_offset,

@@ -7,6 +7,8 @@ The device halves are in csrc/app.hip (`kernels.wav_to_f32`, `argmax_last`, `tok
   * `detokenize`          -- tokenizer.rs:74-81 (join, sentencepiece underscore -> space, trim)
   * `vad_segments`        -- examples/silero/src/main.rs:151-228 (speech segments from per-chunk probabilities)
   * `token_times`         -- encoder frames of kept tokens (kernels.token_align_segments) -> start times in seconds
+  * `ctc_prefix_beam_search` -- the reference of kernels.ctc_beam_search_segments, one utterance on the host
+  * `beam_results`        -- that kernel's four arrays -> the reference's list format
 """
 import numpy as np
 
@@ -73,6 +75,17 @@ def ctc_prefix_beam_search(ids, logprob, blank=0, beam=4, nbest=1):
         beams = {p: (s[0], s[1]) for p, s in ranked[:beam]}
     ranked = sorted(beams.items(), key=lambda kv: (-total(kv[1]), kv[0]))
     return [(p, float(total(s))) for p, s in ranked[:nbest]]
+
+
+def beam_results(tokens, lengths, scores, counts):
+    """the four host arrays of kernels.ctc_beam_search_segments (tokens [count, nbest, W], lengths and scores [count, nbest], counts
+    [count]) -> per utterance the list ctc_prefix_beam_search returns: [(tuple of ids, score)], best first"""
+    tokens, lengths = np.asarray(tokens), np.asarray(lengths)
+    scores, counts = np.asarray(scores), np.asarray(counts)
+    if tokens.ndim != 3 or lengths.shape != tokens.shape[:2] or scores.shape != tokens.shape[:2] or counts.shape != tokens.shape[:1]:
+        raise ValueError("beam_results: tokens [count, nbest, W], lengths / scores [count, nbest] and counts [count] required")
+    return [[(tuple(int(v) for v in tokens[i, n, :int(lengths[i, n])]), float(scores[i, n])) for n in range(int(counts[i]))]
+            for i in range(tokens.shape[0])]
 
 
 def _ms_to_samples(ms, sample_rate):

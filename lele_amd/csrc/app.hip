@@ -7,7 +7,9 @@
 //   lele_hip_token_filter  <- tokenizer.rs:63-71  (drop blank / special ids, keep frame order; no CTC collapsing upstream)
 //   lele_hip_token_filter_segments <- the same per segment of a packed batch of ids -> [count, W] ids + counts
 //   lele_hip_token_align_segments  <- ... and with every kept id its frame within the segment and its score
-//   lele_hip_image_preprocess   <- /root/reference/examples/yolo26n-seg/src/image.rs:62-111 (PIL-style nearest resize to
+//   lele_hip_ctc_beam_search_segments <- apps.ctc_prefix_beam_search per segment of a packed batch of k-best candidates (no upstream
+//                             counterpart: the reference decodes greedily); float64, one wavefront a segment
+//   lele_hip_image_preprocess   <-/root/reference/examples/yolo26n-seg/src/image.rs:62-111 (PIL-style nearest resize to
 //                             target x target, HWC u8 -> CHW f32 / 255)
 //   lele_hip_yolo_seg_postprocess <- image.rs:127-265 (score / box filter in query order, box rescale, per-detection mask =
 //                             sigmoid(coeffs . mask_features), nearest upscale, box crop, thresholds)
@@ -187,6 +189,289 @@ __global__ __launch_bounds__(256) void token_align_seg_kernel(const int32_t* __r
         if (s) s[j] = 0.0f;
     }
     if (threadIdx.x == 0) counts[row] = n;
+}
+
+// ---- CTC prefix beam search over the k best candidates of every frame (apps.ctc_prefix_beam_search on the device) ----------------
+// A prefix is a node of a trie: {parent node, label}, node 0 the empty prefix.  A beam slot keeps its node, the node's parent and
+// label, its depth and the two float64 scores.  Wherever two prefixes are compared they are compared BY CONTENT: equal nodes are equal
+// prefixes, different nodes are walked upwards, so a prefix that left the beam and came back under a second node (its descendants
+// still hanging from the first) is still recognised.
+
+struct BeamSlots {
+    double pb[8], pnb[8], tot[8];
+    int node[8], parent[8], last[8], depth[8];
+};
+
+// the trie lives in LDS while a segment's nodes fit these bytes, else in the context's scratch block
+constexpr int64_t kBeamLdsTrieBytes = 56 * 1024;
+
+__device__ inline double logaddexp64(double a, double b) {
+    if (a == -INFINITY) return b;
+    if (b == -INFINITY) return a;
+    const double mx = a > b ? a : b, mn = a > b ? b : a;
+    if (mx == mn) return mx + 0.693147180559945309417;  // numpy's rule for equal arguments; inf - inf is never formed
+    return mx + log1p(exp(mn - mx));
+}
+
+// v of lane l, l uniform over the wave: two v_readlane_b32, no LDS round trip
+__device__ inline double beam_lane_f64(double v, int l) {
+    const long long b = __double_as_longlong(v);
+    const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)b, l), hi = (unsigned)__builtin_amdgcn_readlane((int)(b >> 32), l);
+    return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
+}
+
+// The wave's LDS writes before, its LDS reads behind.  With the trie in LDS nothing of the search passes through global memory between
+// the frames, so the wait covers LDS only: a __syncthreads() would also wait for the next frame's candidates (requested early on
+// purpose) and for the trie stores.  With the trie in global memory it is the full barrier.
+template <bool LDS_TRIE>
+__device__ inline void beam_sync() {
+    if (LDS_TRIE) {
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
+        __builtin_amdgcn_s_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
+    } else {
+        __syncthreads();
+    }
+}
+
+// the prefixes of nodes a and b, both of depth d: equal?  At most d steps.
+__device__ inline bool beam_same_prefix(const int2* trie, int a, int b, int d) {
+    for (int i = 0; i < d && a != b; ++i) {
+        const int2 x = trie[a], y = trie[b];
+        if (x.y != y.y) return false;
+        a = x.x;
+        b = y.x;
+    }
+    return a == b;
+}
+
+// Python's tuple order of two prefixes, each given as (node of all but the last label, last label, length): is A before B?
+// The longer is lifted to the other's length, then both climb until their nodes meet; the labels that differed nearest the root decide,
+// and of a sequence and its extension the shorter is first.  At most `lim` steps in all (lim >= both lengths).  Entries of a frame
+// whose ids are distinct are different prefixes; should two be EQUAL all the same (duplicate ids: the result is unspecified), the
+// entry indices ia / ib decide, so that the order stays strict and total and every rank is taken exactly once.
+__device__ inline bool beam_prefix_less(const int2* trie, int ra, int la, int na, int rb, int lb, int nb, int lim, int ia, int ib) {
+    if (na == 0 || nb == 0) return na != nb ? na < nb : ia < ib;
+    const bool a_shorter = na < nb, same_length = na == nb;
+    for (int i = 0; i < lim && na > nb; ++i, --na) {
+        const int2 x = trie[ra];
+        ra = x.x;
+        la = x.y;
+    }
+    for (int i = 0; i < lim && nb > na; ++i, --nb) {
+        const int2 y = trie[rb];
+        rb = y.x;
+        lb = y.y;
+    }
+    int res = 0;
+    for (int i = 0; i < lim; ++i) {
+        if (la != lb) res = la < lb ? -1 : 1;
+        if (ra == rb) break;
+        const int2 x = trie[ra], y = trie[rb];
+        ra = x.x;
+        la = x.y;
+        rb = y.x;
+        lb = y.y;
+    }
+    return res ? res < 0 : same_length ? ia < ib : a_shorter;
+}
+
+extern __shared__ int2 beam_trie_lds[];
+
+// One wavefront per segment.  Lane (s, j) = (lane >> 3, lane & 7) takes beam slot s and candidate j of the frame: it extends s by the
+// candidate's label (a NEW entry, or a contribution to the slot that already holds that prefix) and feeds s's own repeat; lane q < 8
+// then finishes the STAY entry of slot q (the slot's own prefix) in its registers.  Every entry is ranked by counting the entries that
+// beat it -- greater total first, equal totals in tuple order -- and rank r < beam becomes slot r of the other slot set, so the beam is
+// always sorted.  The totals are compared lane against lane (v_readlane over the ballot of live entries); only an exact tie, which is
+// rare, walks the trie.  Per segment node_stride = 1 + beam * (most frames of a segment) nodes; frame t's new prefixes are nodes
+// 1 + t * beam + rank.
+template <bool LDS_TRIE>
+__global__ __launch_bounds__(64) void ctc_beam_seg_kernel(const int32_t* __restrict__ ids, const float* __restrict__ lp,
+                                                          const int64_t* __restrict__ off, int k, int64_t skip_rows, int blank, int beam,
+                                                          int nbest, int64_t w, int64_t node_stride, int2* trie_all,
+                                                          int32_t* __restrict__ out_tok, int32_t* __restrict__ out_len,
+                                                          float* __restrict__ out_score, int32_t* __restrict__ out_cnt) {
+    const int64_t seg = blockIdx.x;
+    const int lane = threadIdx.x, s = lane >> 3, j = lane & 7;
+    const int64_t r0 = off[seg] + skip_rows, r1 = off[seg + 1];
+    const int frames = r1 > r0 ? (int)(r1 - r0) : 0;
+    int2* trie = LDS_TRIE ? beam_trie_lds : trie_all + seg * node_stride;
+    __shared__ BeamSlots slots[2];
+    __shared__ double ext_v[8], rep_v[8];
+    __shared__ int ext_has[8], rep_has[8], cand[8];
+    if (lane < 16) {  // every slot of both sets starts as the empty prefix: whatever is read later is a node of this segment
+        BeamSlots& b = slots[lane >> 3];
+        b.pb[lane & 7] = 0.0;
+        b.pnb[lane & 7] = -INFINITY;
+        b.tot[lane & 7] = 0.0;
+        b.node[lane & 7] = 0;
+        b.parent[lane & 7] = 0;
+        b.last[lane & 7] = -1;
+        b.depth[lane & 7] = 0;
+    }
+    if (lane == 0) trie[0] = make_int2(0, -1);
+    if (lane < 8) {
+        ext_has[lane] = 0;
+        rep_has[lane] = 0;
+    }
+    int cur = 0, nb = 1;
+    int c_next = -1;
+    float lp_next = -INFINITY;
+    if (frames > 0 && j < k) {
+        c_next = ids[r0 * k + j];
+        lp_next = lp[r0 * k + j];
+    }
+    beam_sync<LDS_TRIE>();
+    for (int t = 0; t < frames; ++t) {
+        const int c = c_next;
+        const double l = (double)lp_next;
+        if (t + 1 < frames && j < k) {  // the next frame's candidates, asked for before this frame's arithmetic
+            c_next = ids[(r0 + t + 1) * k + j];
+            lp_next = lp[(r0 + t + 1) * k + j];
+        }
+        const BeamSlots& B = slots[cur];
+        BeamSlots& N = slots[cur ^ 1];
+        const bool cv = j < k && c >= 0;
+        const unsigned long long bm = __ballot(cv && c == blank) & 0xffull;
+        const bool has_blank = bm != 0;
+        const double lp_blank = beam_lane_f64(l, has_blank ? __ffsll((long long)bm) - 1 : 0);
+        if (lane < 8) cand[lane] = c;
+        const bool live = s < nb;
+        const int my_node = B.node[s], my_last = B.last[s], my_depth = B.depth[s];
+        const int q_depth = B.depth[j], q_last = B.last[j], q_parent = B.parent[j];  // slot j's, for the others to read lane j
+        const bool ext = live && cv && c != blank;
+        const bool rep = ext && c == my_last;
+        double e = (rep ? B.pb[s] : B.tot[s]) + l;  // a repeat extends only what ended in a blank
+        if (e != e) e = -INFINITY;  // a NaN (a NaN or +inf score came in) would compare false with everything: ranks must stay distinct
+        bool fresh = ext;
+        for (int q = 0; q < nb; ++q) {
+            const int qd = __builtin_amdgcn_readlane(q_depth, q), ql = __builtin_amdgcn_readlane(q_last, q),
+                      qp = __builtin_amdgcn_readlane(q_parent, q);
+            if (ext && qd == my_depth + 1 && ql == c && beam_same_prefix(trie, qp, my_node, my_depth)) {
+                ext_v[q] = e;  // the extension IS slot q's prefix
+                ext_has[q] = 1;
+                fresh = false;
+            }
+        }
+        if (rep) {
+            rep_v[s] = B.pnb[s] + l;
+            rep_has[s] = 1;
+        }
+        beam_sync<LDS_TRIE>();
+        // lane q < nb: the stay entry of slot q
+        bool stay = false;
+        double st_pb = -INFINITY, st_pnb = -INFINITY, st_tot = -INFINITY;
+        if (lane < 8) {
+            const bool hr = rep_has[lane] != 0, he = ext_has[lane] != 0;
+            stay = lane < nb && (has_blank || hr || he);
+            st_pb = has_blank ? B.tot[lane] + lp_blank : -INFINITY;
+            st_pnb = logaddexp64(hr ? rep_v[lane] : -INFINITY, he ? ext_v[lane] : -INFINITY);
+            if (st_pb != st_pb) st_pb = -INFINITY;
+            if (st_pnb != st_pnb) st_pnb = -INFINITY;
+            st_tot = logaddexp64(st_pb, st_pnb);
+            if (st_tot != st_tot) st_tot = -INFINITY;
+            ext_has[lane] = 0;  // for the next frame, whose writes come behind this frame's last barrier
+            rep_has[lane] = 0;
+        }
+        // Both of this lane's entries, the new one (e) and, in lanes 0..7, the stay one (st_tot), against every live entry
+        const unsigned long long fresh_m = __ballot(fresh);
+        const unsigned stay_m = (unsigned)__ballot(stay) & 0xffu;
+        int rank = 0, srank = 0;
+        unsigned long long tie_nn = 0, tie_sn = 0;  // new entries that tie with my new / my stay entry
+        unsigned tie_ns = 0, tie_ss = 0;            // stay entries that tie with my new / my stay entry
+        for (unsigned long long m = fresh_m; m; m &= m - 1) {
+            const int i = __ffsll((long long)m) - 1;
+            const double tm = beam_lane_f64(e, i);
+            rank += tm > e;
+            srank += tm > st_tot;
+            if (tm == e) tie_nn |= 1ull << i;
+            if (tm == st_tot) tie_sn |= 1ull << i;
+        }
+        for (unsigned m = stay_m; m; m &= m - 1) {
+            const int q = __ffs((int)m) - 1;
+            const double tq = beam_lane_f64(st_tot, q);
+            rank += tq > e;
+            srank += tq > st_tot;
+            if (tq == e) tie_ns |= 1u << q;
+            if (tq == st_tot) tie_ss |= 1u << q;
+        }
+        const int lim = t + 2;
+        tie_nn &= ~(1ull << lane);
+        if (lane < 8) tie_ss &= ~(1u << lane);
+        if (fresh && (tie_nn | tie_ns)) {  // exact ties: the tuple order decides
+            for (unsigned long long m = tie_nn; m; m &= m - 1) {
+                const int i = __ffsll((long long)m) - 1;
+                rank += beam_prefix_less(trie, B.node[i >> 3], cand[i & 7], B.depth[i >> 3] + 1, my_node, c, my_depth + 1, lim, i, lane);
+            }
+            for (unsigned m = tie_ns; m; m &= m - 1) {
+                const int q = __ffs((int)m) - 1;
+                rank += beam_prefix_less(trie, B.parent[q], B.last[q], B.depth[q], my_node, c, my_depth + 1, lim, 64 + q, lane);
+            }
+        }
+        if (stay && (tie_sn | tie_ss)) {
+            for (unsigned long long m = tie_sn; m; m &= m - 1) {
+                const int i = __ffsll((long long)m) - 1;
+                srank += beam_prefix_less(trie, B.node[i >> 3], cand[i & 7], B.depth[i >> 3] + 1, B.parent[lane], B.last[lane], B.depth[lane], lim, i,
+                                          64 + lane);
+            }
+            for (unsigned m = tie_ss; m; m &= m - 1) {
+                const int q = __ffs((int)m) - 1;
+                srank += beam_prefix_less(trie, B.parent[q], B.last[q], B.depth[q], B.parent[lane], B.last[lane], B.depth[lane], lim, 64 + q,
+                                          64 + lane);
+            }
+        }
+        if (fresh && rank < beam) {
+            const int node = 1 + t * beam + rank;
+            trie[node] = make_int2(my_node, c);
+            N.node[rank] = node;
+            N.parent[rank] = my_node;
+            N.last[rank] = c;
+            N.depth[rank] = my_depth + 1;
+            N.pb[rank] = -INFINITY;
+            N.pnb[rank] = e;
+            N.tot[rank] = e;
+        }
+        if (stay && srank < beam) {
+            N.node[srank] = B.node[lane];
+            N.parent[srank] = B.parent[lane];
+            N.last[srank] = B.last[lane];
+            N.depth[srank] = B.depth[lane];
+            N.pb[srank] = st_pb;
+            N.pnb[srank] = st_pnb;
+            N.tot[srank] = st_tot;
+        }
+        const int entries = __popcll(fresh_m) + __popc(stay_m);
+        nb = entries < beam ? entries : beam;
+        cur ^= 1;
+        beam_sync<LDS_TRIE>();  // the new slots and the trie nodes written above, before anyone reads them
+    }
+    const BeamSlots& F = slots[cur];
+    const int cnt = nb < nbest ? nb : nbest;
+    if (lane < nbest) {
+        const int64_t h = seg * nbest + lane;
+        int32_t* o = out_tok + h * w;
+        if (lane < cnt) {
+            const int d = F.depth[lane] < frames ? F.depth[lane] : frames;  // a depth never exceeds the frames; the store range is held to it
+            int rest = F.parent[lane], lab = F.last[lane];
+            for (int i = d - 1; i >= 0; --i) {  // from the back; d <= frames <= w
+                o[i] = lab;
+                const int2 x = trie[rest];
+                rest = x.x;
+                lab = x.y;
+            }
+            out_len[h] = d;
+            out_score[h] = (float)F.tot[lane];
+        } else {
+            out_len[h] = 0;
+            out_score[h] = -INFINITY;
+        }
+    }
+    if (lane == 0) out_cnt[seg] = cnt;
+    for (int n = 0; n < nbest; ++n) {
+        int32_t* o = out_tok + (seg * nbest + n) * w;
+        const int d = n < cnt ? (F.depth[n] < frames ? F.depth[n] : frames) : 0;
+        for (int64_t col = (int64_t)d + lane; col < w; col += 64) o[col] = -1;
+    }
 }
 
 // image.rs:84-105 + 69-79: dst(y, x) <-src(min(floor((y + 0.5) * H / T), H - 1), min(floor((x + 0.5) * W / T), W - 1)) / 255
@@ -433,6 +718,66 @@ int lele_hip_token_align_segments(LeleCtx* ctx, const LeleTensor* ids, const Lel
         LELE_HIP_CHECK(hipGetLastError());
     }
     return set_shape(out_shape, out_rank, {count, w});
+}
+
+int lele_hip_ctc_beam_search_segments(LeleCtx* ctx, const LeleTensor* ids, const LeleTensor* logprob, const int64_t* row_offsets, int64_t count,
+                                      int64_t skip_rows, int32_t blank, int32_t beam, int32_t nbest, int64_t width, LeleBuf* out_tokens,
+                                      LeleBuf* out_lengths, LeleBuf* out_scores, LeleBuf* out_counts, int64_t* out_shape, int32_t* out_rank) {
+    LELE_REQUIRE(ctx && ids && logprob && out_tokens && out_lengths && out_scores && out_counts, "ctc_beam_search_segments: NULL argument");
+    LELE_REQUIRE(out_tokens != out_lengths && out_tokens != out_scores && out_tokens != out_counts && out_lengths != out_scores &&
+                     out_lengths != out_counts && out_scores != out_counts,
+                 "ctc_beam_search_segments: the output buffers must be distinct");
+    LELE_REQUIRE(ids->dtype == LELE_I32 && ids->rank == 2, "ctc_beam_search_segments: ids must be i32 [R, k]");
+    LELE_REQUIRE(logprob->dtype == LELE_F32 && logprob->rank == 2 && logprob->shape[0] == ids->shape[0] && logprob->shape[1] == ids->shape[1],
+                 "ctc_beam_search_segments: logprob must be f32 [R, k], one score per id");
+    const int64_t rows = ids->shape[0], k = ids->shape[1];
+    LELE_REQUIRE(k >= 1 && k <= 8, "ctc_beam_search_segments: k = %lld outside [1, 8]", (long long)k);
+    LELE_REQUIRE(beam >= 1 && beam <= 8, "ctc_beam_search_segments: beam = %d outside [1, 8]", (int)beam);
+    LELE_REQUIRE(nbest >= 1 && nbest <= beam, "ctc_beam_search_segments: nbest = %d outside [1, beam = %d]", (int)nbest, (int)beam);
+    LELE_REQUIRE(skip_rows >= 0 && blank >= 0, "ctc_beam_search_segments: negative skip_rows or blank");
+    LELE_REQUIRE(count >= 0 && row_offsets, "ctc_beam_search_segments: bad row_offsets (count %lld)", (long long)count);
+    LELE_REQUIRE(row_offsets[0] == 0 && row_offsets[count] == rows, "ctc_beam_search_segments: row_offsets must run from 0 to R = %lld (got %lld .. %lld)",
+                 (long long)rows, (long long)row_offsets[0], (long long)row_offsets[count]);
+    LELE_REQUIRE(width >= 0, "ctc_beam_search_segments: negative width");
+    int64_t tmax = 0;
+    for (int64_t i = 0; i < count; ++i) {
+        const int64_t len = row_offsets[i + 1] - row_offsets[i];
+        LELE_REQUIRE(len >= 0, "ctc_beam_search_segments: row_offsets decrease at segment %lld", (long long)i);
+        const int64_t frames = std::max<int64_t>(len - skip_rows, 0);
+        LELE_REQUIRE(width == 0 || frames <= width, "ctc_beam_search_segments: segment %lld has %lld frames, more than width = %lld", (long long)i,
+                     (long long)frames, (long long)width);
+        tmax = std::max(tmax, frames);
+    }
+    const int64_t w = width ? width : std::max<int64_t>(tmax, 1);
+    LELE_REQUIRE(count < (int64_t(1) << 31) && w < (int64_t(1) << 31) && tmax < (int64_t(1) << 27),
+                 "ctc_beam_search_segments: more than 2^31 segments or columns, or a segment of 2^27 frames");
+    LELE_HIP_CHECK(hipSetDevice(ctx->device));
+    const void* doff = nullptr;
+    if (count > 0) LELE_TRY(offsets_table(ctx, row_offsets, count, &doff));
+    LELE_TRY(ctx->arena_reset());
+    const void *di = nullptr, *dl = nullptr;
+    if (rows > 0) LELE_TRY(ctx->dev_ptr(ids, &di));
+    if (rows > 0) LELE_TRY(ctx->dev_ptr(logprob, &dl));
+    // the prefix trie: per segment the root and at most `beam` new prefixes a frame, 8 bytes a node; in LDS while it fits, else in the
+    // context's scratch block
+    const int64_t node_stride = 1 + tmax * beam;
+    const bool lds_trie = node_stride * (int64_t)sizeof(int2) <= kBeamLdsTrieBytes;
+    void* trie = nullptr;
+    if (count > 0 && !lds_trie) LELE_TRY(ctx->get_scratch((size_t)(count * node_stride) * sizeof(int2), &trie));
+    const size_t hyps = (size_t)std::max<int64_t>(count * nbest, 1) * 4;
+    LELE_TRY(out_tokens->reserve((size_t)std::max<int64_t>(count * nbest * w, 1) * 4));
+    LELE_TRY(out_lengths->reserve(hyps));
+    LELE_TRY(out_scores->reserve(hyps));
+    LELE_TRY(out_counts->reserve((size_t)std::max<int64_t>(count, 1) * 4));
+    if (count > 0) {
+        auto kernel = lds_trie ? ctc_beam_seg_kernel<true> : ctc_beam_seg_kernel<false>;
+        hipLaunchKernelGGL(kernel, dim3((unsigned)count), dim3(64), lds_trie ? (size_t)node_stride * sizeof(int2) : 0, ctx->stream,
+                           (const int32_t*)di, (const float*)dl, (const int64_t*)doff, (int)k, skip_rows, (int)blank, (int)beam, (int)nbest, w,
+                           node_stride, (int2*)trie, (int32_t*)out_tokens->data, (int32_t*)out_lengths->data, (float*)out_scores->data,
+                           (int32_t*)out_counts->data);
+        LELE_HIP_CHECK(hipGetLastError());
+    }
+    return set_shape(out_shape, out_rank, {count, (int64_t)nbest, w});
 }
 
 int lele_hip_image_preprocess(LeleCtx* ctx, const LeleTensor* rgb, int32_t target, LeleBuf* out, int64_t* out_shape,

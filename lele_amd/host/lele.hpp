@@ -1079,6 +1079,22 @@ inline AlignedTokens token_align_segments(const TensorView& ids, const TensorVie
     return {TensorView::from_device(out_ids, s, LELE_I32), TensorView::from_device(out_frames, s, LELE_I32),
             logprob ? TensorView::from_device(out_logprob, s, LELE_F32) : TensorView(), TensorView::from_device(out_counts, r, LELE_I32)};
 }
+// CTC prefix beam search over the k-best head's candidates (ids i32 [R, k], logprob f32 [R, k]), a segment's frames being its rows behind
+// the first skip_rows: tokens i32 [count, nbest, W] then -1, lengths / scores [count, nbest], counts [count], best first
+struct BeamHypotheses {
+    TensorView tokens, lengths, scores, counts;
+};
+inline BeamHypotheses ctc_beam_search_segments(const TensorView& ids, const TensorView& logprob, const std::vector<int64_t>& offsets,
+                                               int64_t skip_rows, int32_t blank, int32_t beam, int32_t nbest, int64_t width, Buffer& out_tokens,
+                                               Buffer& out_lengths, Buffer& out_scores, Buffer& out_counts) {
+    Shape sh;
+    LeleTensor ti = ids.c(), tl = logprob.c();
+    check(lele_hip_ctc_beam_search_segments(ctx(), &ti, &tl, offsets.data(), (int64_t)offsets.size() - 1, skip_rows, blank, beam, nbest, width,
+                                            out_tokens.raw(), out_lengths.raw(), out_scores.raw(), out_counts.raw(), sh.dims, &sh.rank));
+    std::vector<int64_t> s(sh.dims, sh.dims + sh.rank), h(sh.dims, sh.dims + (sh.rank > 1 ? 2 : 0)), c(sh.dims, sh.dims + (sh.rank > 0 ? 1 : 0));
+    return {TensorView::from_device(out_tokens, s, LELE_I32), TensorView::from_device(out_lengths, h, LELE_I32),
+            TensorView::from_device(out_scores, h, LELE_F32), TensorView::from_device(out_counts, c, LELE_I32)};
+}
 inline TensorView attention_segments(const TensorView& qkv, const std::vector<int64_t>& offsets, int64_t q_offset, int64_t k_offset,
                                      int64_t v_offset, int64_t heads, int64_t dh, const TensorView* scale, Buffer& out) {
     Shape sh;

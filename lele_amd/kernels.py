@@ -1340,6 +1340,27 @@ def token_align_segments(ids, logprob, offsets, skip, width=0, out_ids=None, out
             None if ol is None else TensorView(_lib.DevTensor(ol, shape, np.float32)), TensorView(_lib.DevTensor(oc, shape[:-1], np.int32)))
 
 
+def ctc_beam_search_segments(ids, logprob, offsets, blank=0, beam=4, nbest=1, skip_rows=0, width=0, out_tokens=None, out_lengths=None,
+                             out_scores=None, out_counts=None, ctx=None):
+    """CTC prefix beam search on the device, one segment of the packed candidates a workgroup: ids int32 [R, k], logprob float32 [R, k]
+    as fused_quantized_linear_topk_segments gives them (1 <= k <= 8), frames of segment i = rows offsets[i] + skip_rows .. offsets[i + 1]
+    -> (tokens int32 [count, nbest, W] padded with -1, lengths int32 [count, nbest], scores float32 [count, nbest], counts int32
+    [count]), best first: apps.ctc_prefix_beam_search of every segment's frames (1 <= nbest <= beam <= 8), float64 inside, the scores
+    rounded once.  apps.beam_results turns the four into that function's format.  A dense [B, T, k] batch is the packed layout with
+    offsets[i] = i * T."""
+    ctx = _ctx(ctx)
+    keep = []
+    ot, ol, os_, oc = out_tokens or ctx.buf(), out_lengths or ctx.buf(), out_scores or ctx.buf(), out_counts or ctx.buf()
+    sh = _lib.OutShape()
+    off = _offsets(offsets)
+    _lib.check(_lib.lib().lele_hip_ctc_beam_search_segments(
+        ctx._h, _t(ids, keep), _t(logprob, keep), _lib.i64_ptr(off), C.c_int64(len(off) - 1), C.c_int64(int(skip_rows)), C.c_int32(int(blank)),
+        C.c_int32(int(beam)), C.c_int32(int(nbest)), C.c_int64(int(width)), ot._h, ol._h, os_._h, oc._h, sh.shape, C.byref(sh.rank)))
+    shape = sh.get()
+    return (TensorView(_lib.DevTensor(ot, shape, np.int32)), TensorView(_lib.DevTensor(ol, shape[:2], np.int32)),
+            TensorView(_lib.DevTensor(os_, shape[:2], np.float32)), TensorView(_lib.DevTensor(oc, shape[:1], np.int32)))
+
+
 def attention_segments(qkv, offsets, heads, dh, scale=None, q_offset=0, k_offset=None, v_offset=None, out=None, ctx=None):
     """softmax(Q K^T * scale) V per segment and head over that segment's rows only: qkv [R, P] holds Q | K | V at the column offsets
     (default: the packed projection, 0, heads * dh, 2 * heads * dh) -> [R, heads * dh], heads merged.  dh == 128, segments of at most

@@ -102,6 +102,7 @@ class Encoder:
         self.ws = [ctx.buf() for _ in range(16)]
         self.dec = [ctx.buf() for _ in range(3)]   # the greedy head's results: frame ids, kept ids, counts
         self.sco = [ctx.buf() for _ in range(3)]   # the scored head's: frame scores, kept frames, kept scores
+        self.hyp = [ctx.buf() for _ in range(4)]   # the beam search's: tokens, lengths, scores, counts
 
     def ql(self, x, p, relu, slot):
         return self.K.fused_quantized_linear(x, p.w, p.scale, p.zero, p.bias, relu, out=self.ws[slot], ctx=self.ctx)
@@ -281,6 +282,24 @@ class Encoder:
         ids, lp = K.fused_quantized_linear_topk_segments(xn, off, p.w, p.scale, p.zero, p.bias, k, out_ids=self.dec[0], out_logprob=self.sco[0],
                                                          ctx=ctx)
         return ids, lp, off
+
+    def beam_segments(self, feats, offsets, k, beam, nbest, width=0):
+        """topk_segments, then CTC prefix beam search on the device over every utterance's frames behind its four prompt rows -> (tokens
+        int32 [count, nbest, W], lengths int32 [count, nbest], scores float32 [count, nbest], counts int32 [count]), best first:
+        lele_amd.apps.beam_results turns them into ctc_prefix_beam_search's lists.  W = width, or the longest utterance's rows when 0."""
+        ids, lp, off = self.topk_segments(feats, offsets, k)
+        h = self.hyp
+        return self.K.ctc_beam_search_segments(ids, lp, off, 0, beam, nbest, 4, width, out_tokens=h[0], out_lengths=h[1], out_scores=h[2],
+                                               out_counts=h[3], ctx=self.ctx)
+
+    def beam(self, feats, k, beam, nbest):
+        """feats: [B, T, 560] -> beam_segments' four results for the dense batch: topk, read as the packed layout off[i] = i * (T + 4)"""
+        ids, lp = self.topk(feats, k)
+        b, t4 = ids.shape[0], ids.shape[1]
+        h = self.hyp
+        return self.K.ctc_beam_search_segments(self.K.reshape(ids, [b * t4, k]), self.K.reshape(lp, [b * t4, k]),
+                                               np.arange(b + 1, dtype=np.int64) * t4, 0, beam, nbest, 4, 0, out_tokens=h[0], out_lengths=h[1],
+                                               out_scores=h[2], out_counts=h[3], ctx=self.ctx)
 
 
 def encoder_arrays(enc):
