@@ -484,149 +484,9 @@ struct IgemmEpi {
     }
 };
 
-// (value, column) as one unsigned key whose order is "greater value wins, equal values: greater column wins" (tokenizer.rs:50-61,
-// Iterator::max_by keeps the last of equal maxima).  The value's bits are made order-preserving (negative: all bits flipped, else the
-// sign bit set) after -0.0 is folded onto +0.0, which partial_cmp holds equal.  Every key of a real value is > 0, what a masked column carries.
-__device__ __forceinline__ unsigned long long argmax_key(float v, int col) {
-    unsigned b = __float_as_uint(v);
-    b = b == 0x80000000u ? 0u : b;
-    b ^= (unsigned)((int)b >> 31) | 0x80000000u;
-    return ((unsigned long long)b << 32) | (unsigned)col;
-}
-// the column tiles' keys [tiles][rows] -> ids: the greatest key's column.  Nothing depends on the order the tiles ran in.  A workgroup
-// takes 16 rows; 16 threads a row share its tiles (a row's whole list behind ONE thread is a chain of ~200 loads: 45 us at any size).
-__global__ __launch_bounds__(256) void argmax_finish_kernel(const unsigned long long* __restrict__ keys, int64_t rows, int tiles,
-                                                            int32_t* __restrict__ ids) {
-    __shared__ unsigned long long s_best[16][17];
-    const int rr = threadIdx.x & 15, g = threadIdx.x >> 4;
-    const int64_t r = (int64_t)blockIdx.x * 16 + rr;
-    unsigned long long best = 0ull;
-    if (r < rows) {
-#pragma unroll 8
-        for (int t = g; t < tiles; t += 16) best = max(best, keys[(int64_t)t * rows + r]);
-    }
-    s_best[g][rr] = best;
-    __syncthreads();
-    if (g == 0 && r < rows) {
-#pragma unroll
-        for (int o = 1; o < 16; ++o) best = max(best, s_best[o][rr]);
-        ids[r] = (int32_t)(unsigned)best;
-    }
-}
-
-// the value a key's high word was made of (-0.0 comes back as +0.0)
-__device__ __forceinline__ float argmax_key_value(unsigned long long key) {
-    const unsigned b = (unsigned)(key >> 32);
-    return __uint_as_float((b & 0x80000000u) ? b ^ 0x80000000u : ~b);
-}
-// argmax_finish_kernel with the winner's log-probability (EM 4): with M the greatest key and m_t the maximum of tile t (its key's high
-// word), S = sum_t sums[t] * exp(m_t - M) and logprob = -ln S, never value - (max + ln S).  The same 16 rows x 16 threads; thread g
-// adds tiles g, g + 16, .. in that order and thread 0 joins the 16 partial sums in thread order: the order is a function of the tile
-// count alone, at most 15 + ceil(tiles / 16) additions deep.
-__global__ __launch_bounds__(256) void argmax_logprob_finish_kernel(const unsigned long long* __restrict__ keys, const float* __restrict__ sums,
-                                                                    int64_t rows, int tiles, int32_t* __restrict__ ids,
-                                                                    float* __restrict__ logprob) {
-    __shared__ unsigned long long s_best[16][17];
-    __shared__ float s_part[16][17];
-    const int rr = threadIdx.x & 15, g = threadIdx.x >> 4;
-    const int64_t r = (int64_t)blockIdx.x * 16 + rr;
-    unsigned long long best = 0ull;
-    if (r < rows) {
-#pragma unroll 8
-        for (int t = g; t < tiles; t += 16) best = max(best, keys[(int64_t)t * rows + r]);
-    }
-    s_best[g][rr] = best;
-    __syncthreads();
-#pragma unroll
-    for (int o = 0; o < 16; ++o) best = max(best, s_best[o][rr]);
-    const float mx = argmax_key_value(best);
-    float part = 0.0f;
-    if (r < rows) {
-#pragma unroll 8
-        for (int t = g; t < tiles; t += 16) {
-            const int64_t at = (int64_t)t * rows + r;
-            part += sums[at] * __expf(argmax_key_value(keys[at]) - mx);
-        }
-    }
-    s_part[g][rr] = part;
-    __syncthreads();
-    if (g == 0 && r < rows) {
-#pragma unroll
-        for (int o = 1; o < 16; ++o) part += s_part[o][rr];
-        ids[r] = (int32_t)(unsigned)best;
-        logprob[r] = 0.0f - logf(part);  // S == 1 gives +0.0
-    }
-}
-
-// x into a list sorted greatest first; the least of the nine falls out.  Keys of real candidates are distinct (they carry their column),
-// so the list a set of keys leaves does not depend on the order they came in.
-__device__ __forceinline__ void topk_insert(unsigned long long (&list)[8], unsigned long long x) {
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-        const unsigned long long hi = max(list[i], x);
-        x = min(list[i], x);
-        list[i] = hi;
-    }
-}
-// argmax_logprob_finish_kernel for EM 5: keys [tiles][k][rows] -> a row's k greatest keys as ids [rows][k] and log-probabilities.
-// The same 16 rows x 16 threads: thread g keeps the 8 greatest keys of tiles g, g + 16, .., thread 0 merges the 16 lists from LDS.
-// Slot 0's log-probability is argmax_logprob_finish_kernel's, from the tiles' round-0 keys and sums in its addition order; slot j's is
-// (v_j - v_0) + logprob_0 with the values the keys carry.  Key 0 is "no candidate" (fewer than k columns): id -1, -inf.
-__global__ __launch_bounds__(256) void topk_logprob_finish_kernel(const unsigned long long* __restrict__ keys, const float* __restrict__ sums,
-                                                                  int64_t rows, int tiles, int k, int32_t* __restrict__ ids,
-                                                                  float* __restrict__ logprob) {
-    __shared__ unsigned long long s_list[16][8][17];
-    __shared__ float s_part[16][17];
-    const int rr = threadIdx.x & 15, g = threadIdx.x >> 4;
-    const int64_t r = (int64_t)blockIdx.x * 16 + rr;
-    unsigned long long list[8] = {0ull, 0ull, 0ull, 0ull, 0ull, 0ull, 0ull, 0ull};
-    if (r < rows) {
-#pragma unroll 2
-        for (int t = g; t < tiles; t += 16) {  // a tile's keys are requested together (a load behind every insertion is a chain of ~50 round trips)
-            unsigned long long x[8];
-#pragma unroll
-            for (int j = 0; j < 8; ++j) x[j] = j < k ? keys[((int64_t)t * k + j) * rows + r] : 0ull;
-#pragma unroll
-            for (int j = 0; j < 8; ++j)
-                if (x[j] > list[7]) topk_insert(list, x[j]);
-        }
-    }
-#pragma unroll
-    for (int i = 0; i < 8; ++i) s_list[g][i][rr] = list[i];
-    __syncthreads();
-    unsigned long long best = list[0];
-#pragma unroll
-    for (int o = 0; o < 16; ++o) best = max(best, s_list[o][0][rr]);
-    const float mx = argmax_key_value(best);
-    float part = 0.0f;
-    if (r < rows) {
-#pragma unroll 8
-        for (int t = g; t < tiles; t += 16) {
-            const int64_t at = (int64_t)t * rows + r;
-            part += sums[at] * __expf(argmax_key_value(keys[(int64_t)t * k * rows + r]) - mx);
-        }
-    }
-    s_part[g][rr] = part;
-    __syncthreads();
-    if (g == 0 && r < rows) {
-#pragma unroll
-        for (int o = 1; o < 16; ++o) part += s_part[o][rr];
-        for (int o = 1; o < 16; ++o)
-#pragma unroll
-            for (int i = 0; i < 8; ++i) {
-                const unsigned long long x = s_list[o][i][rr];
-                if (x > list[7]) topk_insert(list, x);
-            }
-        const float lp0 = 0.0f - logf(part);  // S == 1 gives +0.0
-#pragma unroll
-        for (int j = 0; j < 8; ++j)
-            if (j < k) {
-                const bool none = list[j] == 0ull;
-                ids[r * k + j] = none ? -1 : (int32_t)(unsigned)list[j];
-                logprob[r * k + j] = j == 0 ? lp0 : none ? -INFINITY : (argmax_key_value(list[j]) - mx) + lp0;
-            }
-    }
-}
+}  // namespace
+#include "igemm_head.h"
+namespace {
 
 // EM (epilogue mode) 0: the result as f32.  EM 1 / 2 are the two passes of the fused two-layer form, where the f32 result (the
 // hidden layer of a feed-forward block, 45 MB per configs[3] shard) never exists in HBM -- recomputing the product costs ~5 us of
@@ -634,20 +494,9 @@ __global__ __launch_bounds__(256) void topk_logprob_finish_kernel(const unsigned
 //   EM 1: only the per-slice maximum of the (ReLU) result, by atomic max into epi.slice_max;
 //   EM 2: the result again, quantised with the slice's now-known range exactly as qrows_kernel would quantise the stored f32
 //         (SIMD body: rint(fma(v, 1/scale, zp)), saturated), written as i8 with its row sums -- what the next GEMM consumes.
-// EM 3 is the greedy decode head (lele_hip_fused_quantized_linear_argmax): of the result only each row's arg-max leaves the chip, as
-//   one argmax_key per (row, column tile) in epi.arg_keys, which argmax_finish_kernel reduces.  Row context as EM 0 (any number of
-//   slices a tile).
-// EM 4 is EM 3 with the winner's log-probability (lele_hip_fused_quantized_linear_argmax_logprob): besides the key, per (row, column
-//   tile) the sum over the tile's valid columns of exp(value - the tile's maximum) in epi.arg_sums; argmax_logprob_finish_kernel
-//   rescales and adds the tiles.  The maximum is the one the key butterfly found, so the sums are taken after it, by the same butterfly
-//   with plain f32 adds (commutative bit for bit, the pairing lane ^ 16, 8, 4, 2, 1 the same for every row) and joined over the waves in
-//   wave order: a row's sum depends on (n, column) only, not on where the row sits in its tile.
-// EM 5 is EM 4 with the tile's epi.topk best keys per row instead of one (lele_hip_fused_quantized_linear_topk): epi.topk rounds of EM 3's
-//   butterfly and join over the lane's 32 kept logits.  Round j stores the tile's j-th key per row in epi.arg_keys[tile][j][row]; a
-//   column that has won a row takes no part in that row from then on (masked by COLUMN -- the lane clears its own key word of that row:
-//   equal values in other columns stay candidates), and a round that finds nothing left stores key 0.  Round 0 is EM 3's key, the sums
-//   are EM 4's, taken behind round 0.  topk_logprob_finish_kernel merges the tiles.
-template <int BM, int BN, int WM, int WN, int BKB /* bytes of K per LDS tile: 64 or 128 */, int OCC = 1, int EM = 0>
+// EM 3 / 4 / 5 are the decode heads (ids, ids with log-probabilities, the k best): head_epilogue, igemm_head.h, where the kernel is
+// declared with its default arguments (OCC = 1, EM = 0).
+template <int BM, int BN, int WM, int WN, int BKB /* bytes of K per LDS tile: 64 or 128 */, int OCC, int EM>
 __global__ __launch_bounds__(WM* WN * 64) __attribute__((amdgpu_waves_per_eu(OCC))) void igemm_kernel(const int8_t* __restrict__ a, const int8_t* __restrict__ b,
                                                             int64_t rows, int n, int kp, int64_t b_batch_stride,
                                                             int m_per_batch, IgemmEpi epi) {
@@ -850,204 +699,8 @@ __global__ __launch_bounds__(WM* WN * 64) __attribute__((amdgpu_waves_per_eu(OCC
         if (tx == 0 && tid < 2 && (tid == 0 || split < rows_here)) epi.q_prm[s0 + tid] = s_q[tid];
         return;
     }
-    if constexpr (EM == 3 || EM == 4) {
-        static_assert(!(EM == 3 || EM == 4) || TMT == 2, "the butterfly below folds 32 rows a lane onto the 32 lanes of a half-wave");
-        static_assert(EM != 4 || (TNT == 1 && NT >= BM), "EM 4: one column a lane, one thread a row in the joins");
-        float val[EM == 4 ? TMT * 16 : 1];  // EM 4: the lane's 32 logits, kept for the sums
-        const int rows_here = (int)(rows - m0 < BM ? rows - m0 : BM);
-        // a lane holds 32 rows x TNT columns: its best key per row over its own valid columns (a padded column's context is the clamped
-        // column's, so it is masked to 0, below every real key)
-        unsigned long long key[TMT * 16];
-#pragma unroll
-        for (int i = 0; i < TMT; ++i)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int lr = wm * TMT * 32 + i * 32 + 4 * hv + (r & 3) + 8 * (r >> 2);
-                const IgemmEpi::RowCtx rc{s_ca[lr], s_rterm[lr], s_ds[lr], nullptr};
-                unsigned long long best = 0ull;
-#pragma unroll
-                for (int j = 0; j < TNT; ++j) {
-                    const float v = epi.value24(rc, cc[j], acc[i][j][r]);
-                    if constexpr (EM == 4) val[i * 16 + r] = v;
-                    const unsigned long long kj = argmax_key(v, cols[j]);
-                    best = max(best, cols[j] < n ? kj : 0ull);
-                }
-                key[i * 16 + r] = best;
-            }
-        // across the 32 lanes of a half-wave (the columns): each step a lane hands half of its rows to its partner and folds the
-        // partner's other half into its own, so 16 + 8 + 4 + 2 + 1 exchanges leave lane l31 with row l31's maximum
-#pragma unroll
-        for (int s = 0; s < 5; ++s) {
-            const int half = 16 >> s;
-            const bool up = (lane & half) != 0;
-#pragma unroll
-            for (int t = 0; t < half; ++t) {
-                const unsigned long long send = up ? key[t] : key[t + half];
-                const unsigned long long keep = up ? key[t + half] : key[t];
-                key[t] = max(keep, (unsigned long long)__shfl_xor(send, half));
-            }
-        }
-        // across the WN waves in the K loop's LDS (its last barrier has passed), then one store per row of the tile
-        unsigned long long* const s_key = reinterpret_cast<unsigned long long*>(igemm_lds);  // [WN][BM]
-        {
-            const int rr = l31 & 15;
-            const int lr = wm * TMT * 32 + (l31 >> 4) * 32 + 4 * hv + (rr & 3) + 8 * (rr >> 2);
-            s_key[wn * BM + lr] = key[0];
-        }
-        __syncthreads();
-        if constexpr (EM == 4) {
-            float* const s_max = reinterpret_cast<float*>(igemm_lds + WN * BM * 8);  // [BM], the tile's maximum per row
-            float* const s_sum = s_max + BM;                                         // [WN][BM]
-            if (tid < BM) {  // rows past the last are the last row again (clamped context): computed, never stored
-                unsigned long long best = s_key[tid];
-#pragma unroll
-                for (int w = 1; w < WN; ++w) best = max(best, s_key[w * BM + tid]);
-                if (tid < rows_here) epi.arg_keys[(int64_t)tx * rows + m0 + tid] = best;
-                s_max[tid] = argmax_key_value(best);
-            }
-            __syncthreads();
-            // exp(value - the tile's maximum) of the lane's column, nothing for a padded column (its value is the clamped column's)
-            const bool valid = cols[0] < n;
-#pragma unroll
-            for (int i = 0; i < TMT; ++i)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int lr = wm * TMT * 32 + i * 32 + 4 * hv + (r & 3) + 8 * (r >> 2);
-                    const float e = __expf(val[i * 16 + r] - s_max[lr]);
-                    val[i * 16 + r] = valid ? e : 0.0f;
-                }
-#pragma unroll
-            for (int s = 0; s < 5; ++s) {
-                const int half = 16 >> s;
-                const bool up = (lane & half) != 0;
-#pragma unroll
-                for (int t = 0; t < half; ++t) {
-                    const float send = up ? val[t] : val[t + half];
-                    const float keep = up ? val[t + half] : val[t];
-                    val[t] = keep + __shfl_xor(send, half);
-                }
-            }
-            {
-                const int rr = l31 & 15;
-                const int lr = wm * TMT * 32 + (l31 >> 4) * 32 + 4 * hv + (rr & 3) + 8 * (rr >> 2);
-                s_sum[wn * BM + lr] = val[0];
-            }
-            __syncthreads();
-            if (tid < rows_here) {
-                float sum = s_sum[tid];
-#pragma unroll
-                for (int w = 1; w < WN; ++w) sum += s_sum[w * BM + tid];
-                epi.arg_sums[(int64_t)tx * rows + m0 + tid] = sum;
-            }
-            return;
-        }
-        for (int t = tid; t < rows_here; t += NT) {
-            unsigned long long best = s_key[t];
-#pragma unroll
-            for (int w = 1; w < WN; ++w) best = max(best, s_key[w * BM + t]);
-            epi.arg_keys[(int64_t)tx * rows + m0 + t] = best;
-        }
-        return;
-    }
-    if constexpr (EM == 5) {
-        static_assert(EM != 5 || (TMT == 2 && TNT == 1 && NT >= BM), "EM 5: EM 4's tile, one column a lane, one thread a row in the joins");
-        const int rows_here = (int)(rows - m0 < BM ? rows - m0 : BM);
-        const int kk = epi.topk;
-        // the lane's 32 logits as the high words of their keys: a key is the register pair {column, word}, made by no instruction.  (The
-        // sums take the values back out, -0.0 as +0.0, which no difference to a maximum and no exponential tells apart; kept as values the
-        // rounds' loop would hold both forms, 32 registers more than two workgroups a CU leave.)  Word 0 is "no candidate": a padded
-        // column from the start, a column that has won the row from then on -- masked by COLUMN, equal values elsewhere stay.  Every
-        // real value's word is > 0.
-        const bool valid = cols[0] < n;
-        unsigned kb[TMT * 16];
-#pragma unroll
-        for (int i = 0; i < TMT; ++i)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int lr = wm * TMT * 32 + i * 32 + 4 * hv + (r & 3) + 8 * (r >> 2);
-                const IgemmEpi::RowCtx rc{s_ca[lr], s_rterm[lr], s_ds[lr], nullptr};
-                kb[i * 16 + r] = valid ? (unsigned)(argmax_key(epi.value24(rc, cc[0], acc[i][0][r]), 0) >> 32) : 0u;
-            }
-        unsigned long long* const s_key = reinterpret_cast<unsigned long long*>(igemm_lds);  // [WN][BM], as EM 4
-        float* const s_max = reinterpret_cast<float*>(igemm_lds + WN * BM * 8);              // [BM], round 0's maximum per row
-        float* const s_sum = s_max + BM;                                                     // [WN][BM]
-        unsigned* const s_win = reinterpret_cast<unsigned*>(s_sum + WN * BM);                // [BM], the round's winning column per row
-        const int mine = wm * TMT * 32 + (l31 >> 4) * 32 + 4 * hv + ((l31 & 15) & 3) + 8 * ((l31 & 15) >> 2);  // the row lane l31 ends up with
-        // EM 4's sums, relative to round 0's maximum: the same operations in the same order, taken once, behind round 0
-        auto tile_sums = [&]() {
-            float val[TMT * 16];
-#pragma unroll
-            for (int i = 0; i < TMT; ++i)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int lr = wm * TMT * 32 + i * 32 + 4 * hv + (r & 3) + 8 * (r >> 2);
-                    const float e = __expf(argmax_key_value((unsigned long long)kb[i * 16 + r] << 32) - s_max[lr]);
-                    val[i * 16 + r] = valid ? e : 0.0f;
-                }
-#pragma unroll
-            for (int s = 0; s < 5; ++s) {
-                const int half = 16 >> s;
-                const bool up = (lane & half) != 0;
-#pragma unroll
-                for (int t = 0; t < half; ++t) {
-                    const float send = up ? val[t] : val[t + half];
-                    const float keep = up ? val[t + half] : val[t];
-                    val[t] = keep + __shfl_xor(send, half);
-                }
-            }
-            s_sum[wn * BM + mine] = val[0];
-            __syncthreads();
-            if (tid < rows_here) {
-                float sum = s_sum[tid];
-#pragma unroll
-                for (int w = 1; w < WN; ++w) sum += s_sum[w * BM + tid];
-                epi.arg_sums[(int64_t)tx * rows + m0 + tid] = sum;
-            }
-        };
-        for (int j = 0; j < kk; ++j) {
-            // EM 3's butterfly; the keys are made inside its first step, so that 16 of them are live and not 32 (registers: two workgroups
-            // a CU need <= 128)
-            unsigned long long key[16];
-#pragma unroll
-            for (int t = 0; t < 16; ++t) {
-                const bool up = (lane & 16) != 0;
-                const unsigned long long lo = ((unsigned long long)kb[t] << 32) | (unsigned)cols[0];
-                const unsigned long long hi = ((unsigned long long)kb[t + 16] << 32) | (unsigned)cols[0];
-                key[t] = max(up ? hi : lo, (unsigned long long)__shfl_xor(up ? lo : hi, 16));
-            }
-#pragma unroll
-            for (int s = 1; s < 5; ++s) {
-                const int half = 16 >> s;
-                const bool up = (lane & half) != 0;
-#pragma unroll
-                for (int t = 0; t < half; ++t) {
-                    const unsigned long long send = up ? key[t] : key[t + half];
-                    const unsigned long long keep = up ? key[t + half] : key[t];
-                    key[t] = max(keep, (unsigned long long)__shfl_xor(send, half));
-                }
-            }
-            s_key[wn * BM + mine] = key[0];
-            __syncthreads();
-            if (tid < BM) {  // rows past the last are the last row again (clamped context): computed, never stored
-                unsigned long long best = s_key[tid];
-#pragma unroll
-                for (int w = 1; w < WN; ++w) best = max(best, s_key[w * BM + tid]);
-                const bool any = (best >> 32) != 0ull;  // nothing left in this tile: key 0, and no column matches
-                if (tid < rows_here) epi.arg_keys[((int64_t)tx * kk + j) * rows + m0 + tid] = any ? best : 0ull;
-                if (j == 0) s_max[tid] = argmax_key_value(best);
-                s_win[tid] = any ? (unsigned)best : ~0u;
-            }
-            __syncthreads();  // (the next round's s_key stores come after every read of this round's; its s_win stores after its first barrier)
-            if (j == 0) tile_sums();
-            if (j + 1 == kk) break;  // nothing follows the last round's winners
-#pragma unroll
-            for (int i = 0; i < TMT; ++i)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int lr = wm * TMT * 32 + i * 32 + 4 * hv + (r & 3) + 8 * (r >> 2);
-                    kb[i * 16 + r] = s_win[lr] == (unsigned)cols[0] ? 0u : kb[i * 16 + r];
-                }
-        }
+    if constexpr (EM >= 3) {
+        head_epilogue<EM, BM, WM, WN, TMT, TNT>(epi, acc, cc, cols, s_ca, s_rterm, s_ds, igemm_lds, tid, wm, wn, tx, m0, rows, n);
         return;
     }
     if (epi.flags & 2) {
@@ -1403,64 +1056,6 @@ int launch_igemm_hidden(LeleCtx* ctx, int em, const int8_t* aq, const int8_t* wt
     auto kern = em == 1 ? igemm_kernel<128, 128, 2, 4, 128, 1, 1> : igemm_kernel<128, 128, 2, 4, 128, 1, 2>;
     LELE_HIP_CHECK(ensure_dyn_lds(reinterpret_cast<const void*>(kern), (int)lds));
     hipLaunchKernelGGL(kern, grid, dim3(512), lds, ctx->stream, aq, wt, rows, n, kp, (int64_t)0, m, epi);
-    LELE_HIP_CHECK(hipGetLastError());
-    return 0;
-}
-
-// the greedy head (EM 3): the tiled kernel in its big-shape configuration, then the best key's low word per row as ids.
-// `keys`: argmax_key_bytes(rows, n)
-size_t argmax_key_bytes(int64_t rows, int64_t n) { return (size_t)rows * (size_t)((n + 127) / 128) * 8; }
-// `sums` / `logprob`: both or neither; with them the EM 4 form, `sums` of argmax_sum_bytes(rows, n)
-size_t argmax_sum_bytes(int64_t rows, int64_t n) { return (size_t)rows * (size_t)((n + 127) / 128) * 4; }
-int launch_igemm_argmax(LeleCtx* ctx, const int8_t* aq, const int8_t* wt, int64_t rows, int n, int kp, int m, const IgemmEpi& epi_in,
-                        unsigned long long* keys, int32_t* ids, float* sums = nullptr, float* logprob = nullptr) {
-    LELE_REQUIRE(rows < (int64_t(128) * 65535), "quantized GEMM: more than 128 x 65535 rows");
-    constexpr size_t lds = (size_t)2 * (128 + 128) * (128 + 16);
-    IgemmEpi epi = epi_in;
-    epi.arg_keys = keys;
-    const dim3 grid((n + 127) / 128, (unsigned)((rows + 127) / 128));
-    if (logprob) {
-        epi.arg_sums = sums;
-        auto kern = igemm_kernel<128, 128, 2, 4, 128, 1, 4>;
-        LELE_HIP_CHECK(ensure_dyn_lds(reinterpret_cast<const void*>(kern), (int)lds));
-        hipLaunchKernelGGL(kern, grid, dim3(512), lds, ctx->stream, aq, wt, rows, n, kp, (int64_t)0, m, epi);
-        hipLaunchKernelGGL(argmax_logprob_finish_kernel, dim3((unsigned)((rows + 15) / 16)), dim3(256), 0, ctx->stream,
-                           (const unsigned long long*)keys, (const float*)sums, rows, (int)grid.x, ids, logprob);
-        LELE_HIP_CHECK(hipGetLastError());
-        return 0;
-    }
-    auto kern = igemm_kernel<128, 128, 2, 4, 128, 1, 3>;
-    LELE_HIP_CHECK(ensure_dyn_lds(reinterpret_cast<const void*>(kern), (int)lds));
-    hipLaunchKernelGGL(kern, grid, dim3(512), lds, ctx->stream, aq, wt, rows, n, kp, (int64_t)0, m, epi);
-    hipLaunchKernelGGL(argmax_finish_kernel, dim3((unsigned)((rows + 15) / 16)), dim3(256), 0, ctx->stream, (const unsigned long long*)keys, rows, (int)grid.x, ids);
-    LELE_HIP_CHECK(hipGetLastError());
-    return 0;
-}
-
-// The k-best head's two tables, rows * ceil(n / 128) * (8 topk + 4) bytes together.  They live in the context's scratch block, not in
-// the staging arena: at 64 x 171 rows and k = 4 they are 77 MB, more than the arena holds, and an arena that overflows cannot be
-// captured; the scratch block grows in the eager run that a capture needs anyway.
-int topk_workspace(LeleCtx* ctx, int64_t rows, int64_t n, int topk, void** keys, void** sums) {
-    const size_t key_bytes = (size_t)topk * argmax_key_bytes(rows, n);
-    void* base = nullptr;
-    LELE_TRY(ctx->get_scratch(key_bytes + argmax_sum_bytes(rows, n), &base));
-    *keys = base, *sums = (char*)base + key_bytes;
-    return 0;
-}
-// the k-best head (EM 5): `keys` of topk * argmax_key_bytes(rows, n), `sums` of argmax_sum_bytes(rows, n) -- rows * ceil(n / 128) *
-// (8 topk + 4) bytes together; ids / logprob [rows][topk]
-int launch_igemm_topk(LeleCtx* ctx, const int8_t* aq, const int8_t* wt, int64_t rows, int n, int kp, int m, const IgemmEpi& epi_in, int topk,
-                      unsigned long long* keys, float* sums, int32_t* ids, float* logprob) {
-    LELE_REQUIRE(rows < (int64_t(128) * 65535), "quantized GEMM: more than 128 x 65535 rows");
-    constexpr size_t lds = (size_t)2 * (128 + 128) * (128 + 16);
-    IgemmEpi epi = epi_in;
-    epi.arg_keys = keys, epi.arg_sums = sums, epi.topk = topk;
-    const dim3 grid((n + 127) / 128, (unsigned)((rows + 127) / 128));
-    auto kern = igemm_kernel<128, 128, 2, 4, 128, 4, 5>;  // <= 128 registers: two workgroups a CU, as EM 3 / EM 4 get by themselves
-    LELE_HIP_CHECK(ensure_dyn_lds(reinterpret_cast<const void*>(kern), (int)lds));
-    hipLaunchKernelGGL(kern, grid, dim3(512), lds, ctx->stream, aq, wt, rows, n, kp, (int64_t)0, m, epi);
-    hipLaunchKernelGGL(topk_logprob_finish_kernel, dim3((unsigned)((rows + 15) / 16)), dim3(256), 0, ctx->stream, (const unsigned long long*)keys,
-                       (const float*)sums, rows, (int)grid.x, topk, ids, logprob);
     LELE_HIP_CHECK(hipGetLastError());
     return 0;
 }
@@ -1853,10 +1448,26 @@ struct QReq {  // what the caller wants around the product
     int relu = 0;
     const LeleTensor *res1 = nullptr, *res2 = nullptr;  // same-shape residuals (res_same_shape), added in this order
     LnReq* ln = nullptr;
-    int argmax = 0;  // the greedy head: `out` receives argmax_last of the result as i32 [rows], the result itself is never stored
-    LeleBuf* logprob = nullptr;  // ... with the winner's log-probability as f32 [rows] (needs argmax; igemm_kernel EM 4)
-    int topk = 0;  // ... the k best a row, 1 .. 8: `out` i32 [rows][topk], logprob f32 [rows][topk] (needs both; igemm_kernel EM 5)
+    HeadReq head;  // a decode head in place of the product (igemm_head.h)
 };
+// the entry point a request came through, as its messages name it
+const char* fql_who(const HeadReq& head, bool packed) {
+    switch (head.mode) {
+        case Head::Ids: return packed ? "fused_quantized_linear_argmax_segments" : "fused_quantized_linear_argmax";
+        case Head::Scored: return packed ? "fused_quantized_linear_argmax_logprob_segments" : "fused_quantized_linear_argmax_logprob";
+        case Head::TopK: return packed ? "fused_quantized_linear_topk_segments" : "fused_quantized_linear_topk";
+        case Head::None: break;
+    }
+    return packed ? "fused_quantized_linear_segments" : "fused_quantized_linear";
+}
+// a head's result: the input's shape without its last axis, one i32 a row -- or k a row
+int head_shape(const char* who, const HeadReq& head, QCall* c) {
+    if (!head) return 0;
+    LELE_REQUIRE(c->n >= 1 && c->k >= 1, "%s: empty K or N (K = %lld, N = %lld)", who, (long long)c->k, (long long)c->n);
+    c->shp.pop_back();
+    if (head.topk()) c->shp.push_back(head.k);
+    return 0;
+}
 // one layer, validated and staged: what a route's body reads
 struct QLayer {
     QCall c;
@@ -1869,8 +1480,7 @@ struct QLayer {
     const float* partial = nullptr;  // {min, max} pairs of x, nblk a slice
     int nblk = 0;
     LeleBuf* out = nullptr;
-    LeleBuf* logprob = nullptr;  // QReq::logprob
-    int topk = 0;                // QReq::topk
+    HeadReq head;  // QReq::head
 };
 IgemmEpi make_epi(const QLayer& l, float* out, const int* row_sums, const int* col_sums) {
     return IgemmEpi{out, l.c.rows, l.c.n, (int)l.c.m, (int)l.c.k, row_sums, col_sums, l.prm, 0, (int)l.wz, l.ws, (int)l.c.ws_len, l.bias, l.relu,
@@ -1943,12 +1553,12 @@ enum class QRoute {
     AsLn,      // ... with the requested LayerNorm in its epilogue
     AsLnFsmn,  // ... and the FSMN memory block computed in the kernel as the first residual
     Tiled,     // rows -> i8 in HBM (qrows_kernel), then the tiled i8 GEMM (launch_igemm)
-    TiledArgmax,  // ... with the arg-max epilogue (igemm_kernel EM 3): the only route of a QReq::argmax request
+    TiledHead,  // ... with a head's epilogue (igemm_kernel EM 3 / 4 / 5): the only route of a QReq::head request
 };
 // The one place that chooses.  dx: the staged input; dout: out->data after its reserve (the one-pass kernels move 16 bytes at a
 // time).  A LayerNorm that the chosen kernel cannot take is left to the caller (LnReq::done stays false).
 QRoute fql_route(LeleCtx* ctx, const QCall& c, const QReq& rq, const void* dx, const void* dout) {
-    if (rq.argmax) return QRoute::TiledArgmax;
+    if (rq.head) return QRoute::TiledHead;
     const bool aligned = rs_aligned(rq.res1) && rs_aligned(rq.res2) && aligned16(dout);
     if (aligned && rs_fits(ctx, c.rows, c.n, c.k))
         // K = 512 exactly, 16-byte aligned rows: the loaders reduce their parameters from the {min, max} partials, nothing runs in front
@@ -2009,8 +1619,8 @@ int run_as(LeleCtx* ctx, const QLayer& l, QRoute route, LnReq* ln) {
     return 0;
 }
 
-// three-kernel chain: rows -> i8 (+ row sums) in HBM, then the tiled i8 GEMM (argmax: its EM 3 form, l.out receives the ids)
-int run_tiled(LeleCtx* ctx, const QLayer& l, bool argmax = false) {
+// three-kernel chain: rows -> i8 (+ row sums) in HBM, then the tiled i8 GEMM (a head: l.out receives the ids)
+int run_tiled(LeleCtx* ctx, const QLayer& l) {
     const QCall& c = l.c;
     const int kp = (int)((c.k + 15) & ~int64_t(15));
     PackedW pw;
@@ -2021,18 +1631,11 @@ int run_tiled(LeleCtx* ctx, const QLayer& l, bool argmax = false) {
     LELE_TRY(launch_qrows(ctx, c.rows <= 2048 || (kp <= 2048 && !lab_int("LELE_HIP_QROWS_STREAM", 0)), l.x, c.rows, (int)c.k, kp, (int)c.m, l.prm,
                           (int8_t*)aq, (int*)rs, l.partial, l.nblk, nullptr, nullptr, nullptr));
     LELE_TRY(qprof_mark(ctx, 2));
-    if (argmax) {
-        void *keys = nullptr, *sums = nullptr;
-        if (l.topk) {
-            LELE_TRY(topk_workspace(ctx, c.rows, c.n, l.topk, &keys, &sums));
-            LELE_TRY(launch_igemm_topk(ctx, (const int8_t*)aq, pw.wt, c.rows, (int)c.n, kp, (int)c.m, make_epi(l, nullptr, (const int*)rs, pw.col_sums),
-                                       l.topk, (unsigned long long*)keys, (float*)sums, (int32_t*)l.out->data, (float*)l.logprob->data));
-            return qprof_mark(ctx, 3);
-        }
-        LELE_TRY(ctx->arena_alloc(argmax_key_bytes(c.rows, c.n), &keys));
-        if (l.logprob) LELE_TRY(ctx->arena_alloc(argmax_sum_bytes(c.rows, c.n), &sums));
-        LELE_TRY(launch_igemm_argmax(ctx, (const int8_t*)aq, pw.wt, c.rows, (int)c.n, kp, (int)c.m, make_epi(l, nullptr, (const int*)rs, pw.col_sums),
-                                     (unsigned long long*)keys, (int32_t*)l.out->data, (float*)sums, l.logprob ? (float*)l.logprob->data : nullptr));
+    if (l.head) {
+        HeadOut o;
+        LELE_TRY(head_workspace(ctx, l.head, c.rows, c.n, &o));
+        o.results(l.out, l.head);
+        LELE_TRY(launch_igemm_head(ctx, (const int8_t*)aq, pw.wt, c.rows, (int)c.n, kp, (int)c.m, make_epi(l, nullptr, (const int*)rs, pw.col_sums), l.head, o));
         return qprof_mark(ctx, 3);
     }
     IgemmEpi epi = make_epi(l, (float*)l.out->data, (const int*)rs, pw.col_sums);
@@ -2049,21 +1652,14 @@ int run_tiled(LeleCtx* ctx, const QLayer& l, bool argmax = false) {
 int fql_impl(LeleCtx* ctx, const LeleTensor* input, const QW& w, const QReq& rq, LeleBuf* out, int64_t* out_shape, int32_t* out_rank) {
     LELE_REQUIRE(ctx && input && w.w && w.scale && out, "fused_quantized_linear: NULL argument");
     QLayer l;
-    const char* const who = rq.topk      ? "fused_quantized_linear_topk"
-                            : rq.logprob ? "fused_quantized_linear_argmax_logprob"
-                            : rq.argmax  ? "fused_quantized_linear_argmax"
-                                         : "fused_quantized_linear";
+    const char* const who = fql_who(rq.head, false);
     LELE_TRY(describe_call(who, input, w, &l.c));
     QCall& c = l.c;
-    if (rq.argmax) {  // ids: the input's shape without its last axis, one i32 a row
-        LELE_REQUIRE(c.n >= 1 && c.k >= 1, "%s: empty K or N (K = %lld, N = %lld)", who, (long long)c.k, (long long)c.n);
-        c.shp.pop_back();
-        if (rq.topk) c.shp.push_back(rq.topk);  // ... or topk a row
-    }
-    const size_t per_row = rq.topk ? (size_t)rq.topk : 1;
+    LELE_TRY(head_shape(who, rq.head, &c));
+    const size_t out_bytes = (size_t)c.rows * (rq.head ? rq.head.k : c.n) * 4;
     LELE_HIP_CHECK(hipSetDevice(ctx->device));
-    LELE_TRY(out->reserve(rq.argmax ? (size_t)c.rows * per_row * 4 : (size_t)c.rows * c.n * 4));
-    if (rq.logprob) LELE_TRY(rq.logprob->reserve((size_t)c.rows * per_row * 4));
+    LELE_TRY(out->reserve(out_bytes));
+    if (rq.head.scored()) LELE_TRY(rq.head.logprob->reserve(out_bytes));
     if (c.rows == 0 || c.n == 0) return set_shape_v(out_shape, out_rank, c.shp);
     LELE_TRY(ctx->arena_reset());
     const void *dx = nullptr, *dws = nullptr, *db = nullptr, *dr1 = nullptr, *dr2 = nullptr;
@@ -2077,7 +1673,7 @@ int fql_impl(LeleCtx* ctx, const LeleTensor* input, const QW& w, const QReq& rq,
     void* prm = nullptr;
     LELE_TRY(ctx->arena_alloc((size_t)c.batch * sizeof(QParams), &prm));
     l.weight = w.w, l.x = (const float*)dx, l.ws = (const float*)dws, l.bias = (const float*)db, l.relu = rq.relu;
-    l.res1 = (const float*)dr1, l.res2 = (const float*)dr2, l.prm = (QParams*)prm, l.out = out, l.logprob = rq.logprob, l.topk = rq.topk;
+    l.res1 = (const float*)dr1, l.res2 = (const float*)dr2, l.prm = (QParams*)prm, l.out = out, l.head = rq.head;
     LELE_TRY(qprof_mark(ctx, 0));
     if (!l.partial) LELE_TRY(launch_range(ctx, l.x, c.batch, c.m * c.k, l.prm, nullptr, nullptr, &l.partial, &l.nblk));
     LELE_TRY(qprof_mark(ctx, 1));
@@ -2088,8 +1684,8 @@ int fql_impl(LeleCtx* ctx, const LeleTensor* input, const QW& w, const QReq& rq,
         case QRoute::As:
         case QRoute::AsLn:
         case QRoute::AsLnFsmn: LELE_TRY(run_as(ctx, l, route, rq.ln)); break;
-        case QRoute::Tiled: LELE_TRY(run_tiled(ctx, l)); break;
-        case QRoute::TiledArgmax: LELE_TRY(run_tiled(ctx, l, true)); break;
+        case QRoute::Tiled:
+        case QRoute::TiledHead: LELE_TRY(run_tiled(ctx, l)); break;
     }
     return set_shape_v(out_shape, out_rank, c.shp);
 }
@@ -2298,26 +1894,20 @@ int ffn_impl(LeleCtx* ctx, const LeleTensor* input, const QW& w1, const QW& w2, 
 /* Packed batch: every segment of input [R, K] is a batch slice of its own (quantization.rs:104-128).  Three things know about
  * segments -- the range pass (one {min, max} per segment), the row quantiser's parameter lookup and the epilogue's row_ctx, the last
  * two through a row -> segment map -- and the integer sums are exact, so a segment's rows are the dense entry point's on it alone. */
-int fql_segments_impl(LeleCtx* ctx, const char* who, int argmax, const LeleTensor* input, const int64_t* row_offsets, int64_t count,
-                      const LeleTensor* weight_int8, const LeleTensor* weight_scale, const LeleTensor* weight_zero,
-                      const LeleTensor* bias, int apply_relu, LeleBuf* out, int64_t* out_shape, int32_t* out_rank,
-                      LeleBuf* logprob = nullptr /* with argmax: the winners' log-probabilities f32 [R] (EM 4) */,
-                      int topk = 0 /* with logprob: the k best a row, ids and log-probabilities [R, topk] (EM 5) */) {
-    LELE_REQUIRE(ctx && input && weight_int8 && weight_scale && out, "%s: NULL argument", who);
+int fql_segments_impl(LeleCtx* ctx, const LeleTensor* input, const int64_t* row_offsets, int64_t count, const QW& w, const QReq& rq, LeleBuf* out,
+                      int64_t* out_shape, int32_t* out_rank) {
+    const char* const who = fql_who(rq.head, true);
+    LeleBuf* const logprob = rq.head.scored() ? rq.head.logprob : nullptr;
+    LELE_REQUIRE(ctx && input && w.w && w.scale && out, "%s: NULL argument", who);
     int64_t rows = 0, k = 0, tmax = 0;
     LELE_TRY(seg_offsets(input, row_offsets, count, &rows, &k, &tmax, who));
     QLayer l;  // input [R, K]: one "slice" of R rows, whose rows find their segment's parameters through row_seg
-    LELE_TRY(describe_call(argmax ? who : "fused_quantized_linear", input, {weight_int8, weight_scale, weight_zero, bias}, &l.c));
+    LELE_TRY(describe_call(rq.head ? who : fql_who(rq.head, false), input, w, &l.c));  // (without a head it names the dense call)
     QCall& c = l.c;
     const int64_t n = c.n;
     LELE_REQUIRE(rows < (int64_t(1) << 31) && count < (int64_t(1) << 31), "%s: more than 2^31 rows or segments", who);
-    size_t out_bytes = (size_t)rows * n * 4;
-    if (argmax) {  // ids [R]: one i32 a row, the result itself is never stored
-        LELE_REQUIRE(n >= 1 && k >= 1, "%s: empty K or N (K = %lld, N = %lld)", who, (long long)k, (long long)n);
-        c.shp.pop_back();
-        if (topk) c.shp.push_back(topk);
-        out_bytes = (size_t)rows * (topk ? topk : 1) * 4;
-    }
+    LELE_TRY(head_shape(who, rq.head, &c));
+    const size_t out_bytes = (size_t)rows * (rq.head ? rq.head.k : n) * 4;
     LELE_HIP_CHECK(hipSetDevice(ctx->device));
     const void* tab = nullptr;
     if (rows > 0 && n > 0 && k > 0) {
@@ -2334,9 +1924,9 @@ int fql_segments_impl(LeleCtx* ctx, const char* who, int argmax, const LeleTenso
     LELE_TRY(ctx->arena_reset());
     const void *dx = nullptr, *dws = nullptr, *db = nullptr;
     LELE_TRY(ctx->dev_ptr(input, &dx));
-    LELE_TRY(ctx->dev_ptr(weight_scale, &dws));
-    if (c.blen) LELE_TRY(ctx->dev_ptr(bias, &db));
-    LELE_TRY(first_scalar_of(ctx, weight_zero, &l.wz));
+    LELE_TRY(ctx->dev_ptr(w.scale, &dws));
+    if (c.blen) LELE_TRY(ctx->dev_ptr(w.bias, &db));
+    LELE_TRY(first_scalar_of(ctx, w.zero, &l.wz));
     // 1. one range per segment: {min, max} partials only, which the row quantiser's waves reduce themselves (as in the dense chain: one
     // launch fewer).  Enough blocks for every thread of the LONGEST segment to stream ~4 float4, at most 128 pairs a segment (a row's
     // wave reads its segment's pairs in one trip); the surplus blocks of a shorter segment leave the neutral pair.
@@ -2344,7 +1934,7 @@ int fql_segments_impl(LeleCtx* ctx, const char* who, int argmax, const LeleTenso
     void *prm = nullptr, *partial = nullptr;
     LELE_TRY(ctx->arena_alloc((size_t)count * sizeof(QParams), &prm));
     LELE_TRY(ctx->arena_alloc((size_t)count * nblk * 8, &partial));
-    l.x = (const float*)dx, l.ws = (const float*)dws, l.bias = (const float*)db, l.relu = apply_relu, l.prm = (QParams*)prm;
+    l.x = (const float*)dx, l.ws = (const float*)dws, l.bias = (const float*)db, l.relu = rq.relu, l.prm = (QParams*)prm;
     LELE_TRY(qprof_mark(ctx, 0));
     for (int64_t c0 = 0; c0 < count; c0 += 65535) {  // grid.y limit
         const int64_t nc = std::min<int64_t>(65535, count - c0);
@@ -2355,13 +1945,12 @@ int fql_segments_impl(LeleCtx* ctx, const char* who, int argmax, const LeleTenso
     // 2. rows -> i8 with their segment's parameters, 3. the tiled i8 GEMM whose epilogue looks the segment up per row
     const int kp = (int)((k + 15) & ~int64_t(15));
     PackedW pw;
-    LELE_TRY(packed_weights_of(ctx, weight_int8, nullptr, 1, (int)k, (int)n, kp, &pw));
-    void *aq = nullptr, *rs = nullptr, *keys = nullptr, *sums = nullptr;
+    LELE_TRY(packed_weights_of(ctx, w.w, nullptr, 1, (int)k, (int)n, kp, &pw));
+    void *aq = nullptr, *rs = nullptr;
     LELE_TRY(ctx->arena_alloc((size_t)rows * kp, &aq));
     LELE_TRY(ctx->arena_alloc((size_t)rows * 4, &rs));
-    if (topk) LELE_TRY(topk_workspace(ctx, rows, n, topk, &keys, &sums));
-    else if (argmax) LELE_TRY(ctx->arena_alloc(argmax_key_bytes(rows, n), &keys));
-    if (logprob && !topk) LELE_TRY(ctx->arena_alloc(argmax_sum_bytes(rows, n), &sums));
+    HeadOut ho;
+    if (rq.head) LELE_TRY(head_workspace(ctx, rq.head, rows, n, &ho));
     // every fallible step is behind us: `out` is as it was until here (reserve clears any producer-side statistics of `out`;
     // those of `input` describe equal slices and are not read)
     LELE_TRY(out->reserve(out_bytes));
@@ -2369,17 +1958,28 @@ int fql_segments_impl(LeleCtx* ctx, const char* who, int argmax, const LeleTenso
     LELE_TRY(launch_qrows(ctx, rows <= 2048 || kp <= 2048, l.x, rows, (int)k, kp, (int)rows, l.prm, (int8_t*)aq, (int*)rs, (const float*)partial,
                           nblk, nullptr, nullptr, drowseg));
     LELE_TRY(qprof_mark(ctx, 2));
-    IgemmEpi epi = make_epi(l, argmax ? nullptr : (float*)out->data, (const int*)rs, pw.col_sums);
+    IgemmEpi epi = make_epi(l, rq.head ? nullptr : (float*)out->data, (const int*)rs, pw.col_sums);
     epi.row_seg = drowseg;
-    if (topk)
-        LELE_TRY(launch_igemm_topk(ctx, (const int8_t*)aq, pw.wt, rows, (int)n, kp, (int)rows, epi, topk, (unsigned long long*)keys, (float*)sums,
-                                   (int32_t*)out->data, (float*)logprob->data));
-    else if (argmax)
-        LELE_TRY(launch_igemm_argmax(ctx, (const int8_t*)aq, pw.wt, rows, (int)n, kp, (int)rows, epi, (unsigned long long*)keys, (int32_t*)out->data,
-                                     (float*)sums, logprob ? (float*)logprob->data : nullptr));
-    else LELE_TRY(launch_igemm(ctx, (const int8_t*)aq, pw.wt, rows, (int)n, kp, (int)rows, epi));
+    if (rq.head) {
+        ho.results(out, rq.head);
+        LELE_TRY(launch_igemm_head(ctx, (const int8_t*)aq, pw.wt, rows, (int)n, kp, (int)rows, epi, rq.head, ho));
+    } else {
+        LELE_TRY(launch_igemm(ctx, (const int8_t*)aq, pw.wt, rows, (int)n, kp, (int)rows, epi));
+    }
     LELE_TRY(qprof_mark(ctx, 3));
     return set_shape_v(out_shape, out_rank, c.shp);
+}
+
+// the six head entry points: what they require of k and of their outputs, then the dense or the packed linear (row_offsets / count)
+int fql_head(LeleCtx* ctx, Head mode, int32_t k, bool packed, const LeleTensor* input, const int64_t* row_offsets, int64_t count, const QW& w,
+             LeleBuf* out_ids, LeleBuf* out_logprob, int64_t* out_shape, int32_t* out_rank) {
+    QReq rq;
+    rq.head = HeadReq{mode, mode == Head::TopK ? (int)k : 1, out_logprob};
+    const char* const who = fql_who(rq.head, packed);
+    if (rq.head.scored()) LELE_REQUIRE(out_ids && out_logprob && out_ids != out_logprob, "%s: two distinct output buffers required", who);
+    if (rq.head.topk()) LELE_REQUIRE(k >= 1 && k <= 8, "%s: k = %d outside [1, 8]", who, (int)k);
+    return packed ? fql_segments_impl(ctx, input, row_offsets, count, w, rq, out_ids, out_shape, out_rank)
+                  : fql_impl(ctx, input, w, rq, out_ids, out_shape, out_rank);
 }
 
 }  // namespace
@@ -2396,8 +1996,7 @@ int lele_hip_fused_quantized_linear(LeleCtx* ctx, const LeleTensor* input, const
 int lele_hip_fused_quantized_linear_segments(LeleCtx* ctx, const LeleTensor* input, const int64_t* row_offsets, int64_t count,
                                              const LeleTensor* weight_int8, const LeleTensor* weight_scale, const LeleTensor* weight_zero,
                                              const LeleTensor* bias, int apply_relu, LeleBuf* out, int64_t* out_shape, int32_t* out_rank) {
-    return fql_segments_impl(ctx, "fused_quantized_linear_segments", 0, input, row_offsets, count, weight_int8, weight_scale, weight_zero, bias,
-                             apply_relu, out, out_shape, out_rank);
+    return fql_segments_impl(ctx, input, row_offsets, count, {weight_int8, weight_scale, weight_zero, bias}, QReq{apply_relu}, out, out_shape, out_rank);
 }
 
 /* The greedy decode head (tokenizer.rs:50-61 behind quantization.rs:77-169): argmax_last(fused_quantized_linear(.., apply_relu = 0)) bit for
@@ -2405,17 +2004,14 @@ int lele_hip_fused_quantized_linear_segments(LeleCtx* ctx, const LeleTensor* inp
 int lele_hip_fused_quantized_linear_argmax(LeleCtx* ctx, const LeleTensor* input, const LeleTensor* weight_int8, const LeleTensor* weight_scale,
                                            const LeleTensor* weight_zero, const LeleTensor* bias, LeleBuf* out_ids, int64_t* out_shape,
                                            int32_t* out_rank) {
-    QReq rq;
-    rq.argmax = 1;
-    return fql_impl(ctx, input, {weight_int8, weight_scale, weight_zero, bias}, rq, out_ids, out_shape, out_rank);
+    return fql_head(ctx, Head::Ids, 1, false, input, nullptr, 0, {weight_int8, weight_scale, weight_zero, bias}, out_ids, nullptr, out_shape, out_rank);
 }
 
 int lele_hip_fused_quantized_linear_argmax_segments(LeleCtx* ctx, const LeleTensor* input, const int64_t* row_offsets, int64_t count,
                                                     const LeleTensor* weight_int8, const LeleTensor* weight_scale,
                                                     const LeleTensor* weight_zero, const LeleTensor* bias, LeleBuf* out_ids,
                                                     int64_t* out_shape, int32_t* out_rank) {
-    return fql_segments_impl(ctx, "fused_quantized_linear_argmax_segments", 1, input, row_offsets, count, weight_int8, weight_scale, weight_zero,
-                             bias, 0, out_ids, out_shape, out_rank);
+    return fql_head(ctx, Head::Ids, 1, true, input, row_offsets, count, {weight_int8, weight_scale, weight_zero, bias}, out_ids, nullptr, out_shape, out_rank);
 }
 
 /* ... with the winner's log-probability (tokenizer.rs:50-71 behind quantization.rs:77-169): -ln sum_j exp(v_j - v_id) from the same epilogue
@@ -2423,20 +2019,15 @@ int lele_hip_fused_quantized_linear_argmax_segments(LeleCtx* ctx, const LeleTens
 int lele_hip_fused_quantized_linear_argmax_logprob(LeleCtx* ctx, const LeleTensor* input, const LeleTensor* weight_int8,
                                                    const LeleTensor* weight_scale, const LeleTensor* weight_zero, const LeleTensor* bias,
                                                    LeleBuf* out_ids, LeleBuf* out_logprob, int64_t* out_shape, int32_t* out_rank) {
-    LELE_REQUIRE(out_ids && out_logprob && out_ids != out_logprob, "fused_quantized_linear_argmax_logprob: two distinct output buffers required");
-    QReq rq;
-    rq.argmax = 1;
-    rq.logprob = out_logprob;
-    return fql_impl(ctx, input, {weight_int8, weight_scale, weight_zero, bias}, rq, out_ids, out_shape, out_rank);
+    return fql_head(ctx, Head::Scored, 1, false, input, nullptr, 0, {weight_int8, weight_scale, weight_zero, bias}, out_ids, out_logprob, out_shape, out_rank);
 }
 
 int lele_hip_fused_quantized_linear_argmax_logprob_segments(LeleCtx* ctx, const LeleTensor* input, const int64_t* row_offsets, int64_t count,
                                                             const LeleTensor* weight_int8, const LeleTensor* weight_scale,
                                                             const LeleTensor* weight_zero, const LeleTensor* bias, LeleBuf* out_ids,
                                                             LeleBuf* out_logprob, int64_t* out_shape, int32_t* out_rank) {
-    LELE_REQUIRE(out_ids && out_logprob && out_ids != out_logprob, "fused_quantized_linear_argmax_logprob_segments: two distinct output buffers required");
-    return fql_segments_impl(ctx, "fused_quantized_linear_argmax_logprob_segments", 1, input, row_offsets, count, weight_int8, weight_scale,
-                             weight_zero, bias, 0, out_ids, out_shape, out_rank, out_logprob);
+    return fql_head(ctx, Head::Scored, 1, true, input, row_offsets, count, {weight_int8, weight_scale, weight_zero, bias}, out_ids, out_logprob, out_shape,
+                    out_rank);
 }
 
 /* ... and the k best tokens a frame (1 <= k <= 8) in argmax_key's order -- greater value first, of equal values the greater column first --
@@ -2444,23 +2035,15 @@ int lele_hip_fused_quantized_linear_argmax_logprob_segments(LeleCtx* ctx, const 
 int lele_hip_fused_quantized_linear_topk(LeleCtx* ctx, const LeleTensor* input, const LeleTensor* weight_int8, const LeleTensor* weight_scale,
                                          const LeleTensor* weight_zero, const LeleTensor* bias, int32_t k, LeleBuf* out_ids,
                                          LeleBuf* out_logprob, int64_t* out_shape, int32_t* out_rank) {
-    LELE_REQUIRE(out_ids && out_logprob && out_ids != out_logprob, "fused_quantized_linear_topk: two distinct output buffers required");
-    LELE_REQUIRE(k >= 1 && k <= 8, "fused_quantized_linear_topk: k = %d outside [1, 8]", (int)k);
-    QReq rq;
-    rq.argmax = 1;
-    rq.logprob = out_logprob;
-    rq.topk = k;
-    return fql_impl(ctx, input, {weight_int8, weight_scale, weight_zero, bias}, rq, out_ids, out_shape, out_rank);
+    return fql_head(ctx, Head::TopK, k, false, input, nullptr, 0, {weight_int8, weight_scale, weight_zero, bias}, out_ids, out_logprob, out_shape, out_rank);
 }
 
 int lele_hip_fused_quantized_linear_topk_segments(LeleCtx* ctx, const LeleTensor* input, const int64_t* row_offsets, int64_t count,
                                                   const LeleTensor* weight_int8, const LeleTensor* weight_scale, const LeleTensor* weight_zero,
                                                   const LeleTensor* bias, int32_t k, LeleBuf* out_ids, LeleBuf* out_logprob,
                                                   int64_t* out_shape, int32_t* out_rank) {
-    LELE_REQUIRE(out_ids && out_logprob && out_ids != out_logprob, "fused_quantized_linear_topk_segments: two distinct output buffers required");
-    LELE_REQUIRE(k >= 1 && k <= 8, "fused_quantized_linear_topk_segments: k = %d outside [1, 8]", (int)k);
-    return fql_segments_impl(ctx, "fused_quantized_linear_topk_segments", 1, input, row_offsets, count, weight_int8, weight_scale, weight_zero,
-                             bias, 0, out_ids, out_shape, out_rank, out_logprob, k);
+    return fql_head(ctx, Head::TopK, k, true, input, row_offsets, count, {weight_int8, weight_scale, weight_zero, bias}, out_ids, out_logprob, out_shape,
+                    out_rank);
 }
 
 int lele_hip_fused_quantized_linear_residual(LeleCtx* ctx, const LeleTensor* input, const LeleTensor* weight_int8,

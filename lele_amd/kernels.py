@@ -1216,31 +1216,45 @@ def fused_quantized_linear_segments(input, offsets, weight_int8, weight_scale, w
     return TensorView(_lib.DevTensor(out, sh.get(), np.float32))
 
 
+def _decode_head(input, offsets, weights, k, outs, ctx):
+    """the six decode heads' calls differ in the entry point, the packed forms' `offsets`, the k-best forms' `k` (None where there is
+    none) and one or two outputs -> (args, result): the entry point's arguments and, called behind it, what the wrapper returns --
+    the ids for outs = (out,), (ids, logprob) for outs = (out_ids, out_logprob)"""
+    ctx = _ctx(ctx)
+    keep = []
+    bufs = [o or ctx.buf() for o in outs]
+    sh = _lib.OutShape()
+    args = [ctx._h, _t(input, keep)]
+    if offsets is not None:
+        off = _offsets(offsets)
+        keep.append(off)
+        args += [_lib.i64_ptr(off), C.c_int64(len(off) - 1)]
+    args += [_t(w, keep) for w in weights]
+    if k is not None:
+        args.append(C.c_int32(int(k)))
+    args += [b._h for b in bufs] + [sh.shape, C.byref(sh.rank)]
+
+    def result():
+        del keep[:]  # (held until the call was made)
+        views = [TensorView(_lib.DevTensor(b, sh.get(), dt)) for b, dt in zip(bufs, (np.int32, np.float32))]
+        return views[0] if len(views) == 1 else tuple(views)
+    return args, result
+
+
 def fused_quantized_linear_argmax(input, weight_int8, weight_scale, weight_zero, bias, out=None, ctx=None):
     """the greedy decode head: argmax_last(fused_quantized_linear(input, .., apply_relu=False)) bit for bit -> int32, the input's shape
     without its last axis.  The arg-max is taken in the GEMM's epilogue: the logits are never stored (tokenizer.rs:50-61)."""
-    ctx = _ctx(ctx)
-    keep = []
-    out = out or ctx.buf()
-    sh = _lib.OutShape()
-    _lib.check(_lib.lib().lele_hip_fused_quantized_linear_argmax(
-        ctx._h, _t(input, keep), _t(weight_int8, keep), _t(weight_scale, keep), _t(weight_zero, keep), _t(bias, keep), out._h, sh.shape,
-        C.byref(sh.rank)))
-    return TensorView(_lib.DevTensor(out, sh.get(), np.int32))
+    args, result = _decode_head(input, None, (weight_int8, weight_scale, weight_zero, bias), None, (out,), ctx)
+    _lib.check(_lib.lib().lele_hip_fused_quantized_linear_argmax(*args))
+    return result()
 
 
 def fused_quantized_linear_argmax_segments(input, offsets, weight_int8, weight_scale, weight_zero, bias, out=None, ctx=None):
     """fused_quantized_linear_argmax with every segment of the packed input [R, K] as a batch slice of its own -> int32 [R]: rows
     offsets[i] .. offsets[i + 1] are, bit for bit, the dense call on that range alone"""
-    ctx = _ctx(ctx)
-    keep = []
-    out = out or ctx.buf()
-    sh = _lib.OutShape()
-    off = _offsets(offsets)
-    _lib.check(_lib.lib().lele_hip_fused_quantized_linear_argmax_segments(
-        ctx._h, _t(input, keep), _lib.i64_ptr(off), C.c_int64(len(off) - 1), _t(weight_int8, keep), _t(weight_scale, keep),
-        _t(weight_zero, keep), _t(bias, keep), out._h, sh.shape, C.byref(sh.rank)))
-    return TensorView(_lib.DevTensor(out, sh.get(), np.int32))
+    args, result = _decode_head(input, offsets, (weight_int8, weight_scale, weight_zero, bias), None, (out,), ctx)
+    _lib.check(_lib.lib().lele_hip_fused_quantized_linear_argmax_segments(*args))
+    return result()
 
 
 def token_filter_segments(ids, offsets, skip, width=0, out_ids=None, out_counts=None, ctx=None):
@@ -1262,31 +1276,18 @@ def fused_quantized_linear_argmax_logprob(input, weight_int8, weight_scale, weig
     """the greedy decode head with the winner's confidence -> (ids int32, logprob float32), both the input's shape without its last axis:
     ids are fused_quantized_linear_argmax's bit for bit, logprob = -ln sum_j exp(v_j - v_id) over the row's logits, from the same GEMM
     epilogue; the logits are never stored (tokenizer.rs:50-71)."""
-    ctx = _ctx(ctx)
-    keep = []
-    oi, ol = out_ids or ctx.buf(), out_logprob or ctx.buf()
-    sh = _lib.OutShape()
-    _lib.check(_lib.lib().lele_hip_fused_quantized_linear_argmax_logprob(
-        ctx._h, _t(input, keep), _t(weight_int8, keep), _t(weight_scale, keep), _t(weight_zero, keep), _t(bias, keep), oi._h, ol._h, sh.shape,
-        C.byref(sh.rank)))
-    shape = sh.get()
-    return TensorView(_lib.DevTensor(oi, shape, np.int32)), TensorView(_lib.DevTensor(ol, shape, np.float32))
+    args, result = _decode_head(input, None, (weight_int8, weight_scale, weight_zero, bias), None, (out_ids, out_logprob), ctx)
+    _lib.check(_lib.lib().lele_hip_fused_quantized_linear_argmax_logprob(*args))
+    return result()
 
 
 def fused_quantized_linear_argmax_logprob_segments(input, offsets, weight_int8, weight_scale, weight_zero, bias, out_ids=None,
                                                    out_logprob=None, ctx=None):
     """fused_quantized_linear_argmax_logprob with every segment of the packed input [R, K] as a batch slice of its own -> (int32 [R],
     float32 [R]): rows offsets[i] .. offsets[i + 1] are, bit for bit, the dense call on that range alone"""
-    ctx = _ctx(ctx)
-    keep = []
-    oi, ol = out_ids or ctx.buf(), out_logprob or ctx.buf()
-    sh = _lib.OutShape()
-    off = _offsets(offsets)
-    _lib.check(_lib.lib().lele_hip_fused_quantized_linear_argmax_logprob_segments(
-        ctx._h, _t(input, keep), _lib.i64_ptr(off), C.c_int64(len(off) - 1), _t(weight_int8, keep), _t(weight_scale, keep),
-        _t(weight_zero, keep), _t(bias, keep), oi._h, ol._h, sh.shape, C.byref(sh.rank)))
-    shape = sh.get()
-    return TensorView(_lib.DevTensor(oi, shape, np.int32)), TensorView(_lib.DevTensor(ol, shape, np.float32))
+    args, result = _decode_head(input, offsets, (weight_int8, weight_scale, weight_zero, bias), None, (out_ids, out_logprob), ctx)
+    _lib.check(_lib.lib().lele_hip_fused_quantized_linear_argmax_logprob_segments(*args))
+    return result()
 
 
 def fused_quantized_linear_topk(input, weight_int8, weight_scale, weight_zero, bias, k, out_ids=None, out_logprob=None, ctx=None):
@@ -1294,31 +1295,18 @@ def fused_quantized_linear_topk(input, weight_int8, weight_scale, weight_zero, b
     axis plus a trailing axis of k: slot j holds the column of the row's (j + 1)-th greatest logit -- greater value first, of equal values
     the greater column first (not topk's stable order) -- and its log-probability; slot 0 is fused_quantized_linear_argmax_logprob bit for
     bit, slots past the row's length hold -1 / -inf.  The logits are never stored."""
-    ctx = _ctx(ctx)
-    keep = []
-    oi, ol = out_ids or ctx.buf(), out_logprob or ctx.buf()
-    sh = _lib.OutShape()
-    _lib.check(_lib.lib().lele_hip_fused_quantized_linear_topk(
-        ctx._h, _t(input, keep), _t(weight_int8, keep), _t(weight_scale, keep), _t(weight_zero, keep), _t(bias, keep), C.c_int32(int(k)),
-        oi._h, ol._h, sh.shape, C.byref(sh.rank)))
-    shape = sh.get()
-    return TensorView(_lib.DevTensor(oi, shape, np.int32)), TensorView(_lib.DevTensor(ol, shape, np.float32))
+    args, result = _decode_head(input, None, (weight_int8, weight_scale, weight_zero, bias), k, (out_ids, out_logprob), ctx)
+    _lib.check(_lib.lib().lele_hip_fused_quantized_linear_topk(*args))
+    return result()
 
 
 def fused_quantized_linear_topk_segments(input, offsets, weight_int8, weight_scale, weight_zero, bias, k, out_ids=None, out_logprob=None,
                                          ctx=None):
     """fused_quantized_linear_topk with every segment of the packed input [R, K] as a batch slice of its own -> (int32 [R, k], float32
     [R, k]): rows offsets[i] .. offsets[i + 1] are, bit for bit, the dense call on that range alone"""
-    ctx = _ctx(ctx)
-    keep = []
-    oi, ol = out_ids or ctx.buf(), out_logprob or ctx.buf()
-    sh = _lib.OutShape()
-    off = _offsets(offsets)
-    _lib.check(_lib.lib().lele_hip_fused_quantized_linear_topk_segments(
-        ctx._h, _t(input, keep), _lib.i64_ptr(off), C.c_int64(len(off) - 1), _t(weight_int8, keep), _t(weight_scale, keep),
-        _t(weight_zero, keep), _t(bias, keep), C.c_int32(int(k)), oi._h, ol._h, sh.shape, C.byref(sh.rank)))
-    shape = sh.get()
-    return TensorView(_lib.DevTensor(oi, shape, np.int32)), TensorView(_lib.DevTensor(ol, shape, np.float32))
+    args, result = _decode_head(input, offsets, (weight_int8, weight_scale, weight_zero, bias), k, (out_ids, out_logprob), ctx)
+    _lib.check(_lib.lib().lele_hip_fused_quantized_linear_topk_segments(*args))
+    return result()
 
 
 def token_align_segments(ids, logprob, offsets, skip, width=0, out_ids=None, out_frames=None, out_logprob=None, out_counts=None, ctx=None):

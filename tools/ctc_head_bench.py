@@ -51,7 +51,8 @@ def main():
     ap.add_argument("--parents", nargs=3, default=None, metavar=("BEFORE", "BETWEEN", "AFTER"), help="with --merge: the records of three "
                     "--scored runs in turn, the parent build (LELE_HIP_LIBRARY), this build, the parent build -- the same legs in the same "
                     "order, which a --topk run's longer alternation is not: per shape, `fused` and `scored` of this build are set against "
-                    "the spread of the two parent runs (their interquartile ranges taken together)")
+                    "the spread of the two parent runs (their interquartile ranges taken together); three --topk runs of the same K "
+                    "add their `topkK` legs")
     ap.add_argument("--resources", default=None, help="with --merge: a JSON file of the compiler's resource-usage remarks, embedded as build_resources")
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
@@ -71,10 +72,12 @@ def main():
             runs = [json.load(open(p)) for p in (args.parents[0], args.parents[2])]
             mine = json.load(open(args.parents[1]))
             res["parent_build"] = {"library": runs[0].get("library"), "this_build": mine.get("library"),
-                                   "order": "parent, this build, parent: three --scored processes of one session, behind the --topk run",
+                                   "order": "parent, this build, parent: three processes of one session with the same legs",
                                    "spread": "from the least first quartile to the greatest third quartile of the two parent runs' timings"}
             for name, rec in res["shapes"].items():
-                for leg in ("fused", "scored"):
+                # ... and the `topkK` legs, where all three runs were --topk runs of the same K (the same alternation again)
+                ks = [k for k in range(1, 9) if all("topk%d_us_q1" % k in r["shapes"][name] for r in runs + [mine])]
+                for leg in ["fused", "scored"] + ["topk%d" % k for k in ks]:
                     a, b = (r["shapes"][name] for r in runs)
                     lo, hi = min(a[leg + "_us_q1"], b[leg + "_us_q1"]), max(a[leg + "_us_q3"], b[leg + "_us_q3"])
                     med = mine["shapes"][name][leg + "_us_median"]
