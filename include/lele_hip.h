@@ -390,7 +390,13 @@ int lele_hip_conv_stats(LeleCtx* ctx, int64_t* calls, int64_t* macs);
  * cores: conv_integer ("ci8.codes") and conv_integer_from_f32 / _multi ("ci8.quant": the image is quantised as it is packed), then the
  * kernel: "ci8.nj4" / "ci8.nj2" / "ci8.nj1" (a wave owns 4 / 2 / 1 strips of 32 positions) or "ci8.nj2_ksplit" / "ci8.nj1_ksplit" (the four
  * waves of a workgroup share the strips and split K); the f32 form reports "ci.f32", then the convolution's own route.
- * fused_scale_bias(_silu) reports "fsb.w1".  The route never names an earlier call.  Recorded on the
+ * fused_scale_bias(_silu) reports "fsb.w1".  And the audio front-end (frontend_compute / _compute_batch / _logmel / _compute_segments): the
+ * kernel -- "fe.main_std" / "fe.main_table" (400 / 160 / 512 framing: the unrolled 80-mel bank, or the table-driven mel loop of every other
+ * n_mels), "fe.seg_std" / "fe.seg_table" (the same two for compute_segments), "fe.generic_fused" (every other framing, one kernel) or
+ * "fe.generic_four" (its four-kernel form: batches beyond 65535 utterances) -- then for the main / seg kernels how the PCM tile was staged:
+ * "fe.tile_dma" (direct-to-LDS: 16-byte aligned runs), "fe.tile_regs" (through registers), "fe.tile_mixed" (a segment launch that holds
+ * both); "fe.two_kernel" instead for the lab form with the separate frame-sum kernel.  compute_segments on another framing reports its
+ * last segment's route.  The route never names an earlier call.  Recorded on the
  * host when the call is issued (a call recorded into a graph reports the route it recorded).  NUL-terminated into buf; an error when cap is too small.
  * lele_hip_route_names: every level name a route can hold, one per line; host only, no GPU needed. */
 int lele_hip_last_route(LeleCtx* ctx, char* buf, size_t cap);

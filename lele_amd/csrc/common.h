@@ -202,6 +202,7 @@ struct LeleCtx {
     // "attn.nt6"; for the register-resident norm kernels of eltwise.hip the rows a block holds, "rows.rpb4"); unused levels are nullptr.
     // The data-movement (manip.hip), element-wise / reduce / norm (eltwise.hip) and LSTM / GRU (rnn.hip) entry points record theirs the same way,
     // and so does the i8 ConvInteger of conv.hip: how the image was packed ("ci8.codes" / "ci8.quant"), then the kernel ("ci8.nj2_ksplit")
+    // and the audio front-end of frontend.hip: the kernel ("fe.main_std"), then how its PCM tile was staged ("fe.tile_dma")
     const char* route[3] = {nullptr, nullptr, nullptr};
     void set_route(const char* op, const char* core = nullptr) {
         route[0] = nullptr;

@@ -418,11 +418,16 @@ int lele_hip_cmvn(LeleCtx* ctx, const LeleTensor* x, float eps, LeleBuf* out, in
         void *dm = nullptr, *ds = nullptr;
         LELE_TRY(ctx->arena_alloc((size_t)nb * d * 4, &dm));
         LELE_TRY(ctx->arena_alloc((size_t)nb * d * 4, &ds));
-        hipLaunchKernelGGL(cmvn_moments_kernel, dim3((unsigned)((d + 63) / 64), (unsigned)nb), dim3(64), 0, ctx->stream,
-                           (const float*)dx, t, d, eps, (float*)dm, (float*)ds);
         const int blocks = (int)std::max<int64_t>(1, std::min<int64_t>((t * d + 255) / 256, 1024));
-        hipLaunchKernelGGL(cmvn_apply_kernel, dim3(blocks, (unsigned)nb), dim3(256), 0, ctx->stream, (const float*)dx, t, d,
-                           (const float*)dm, (const float*)ds, (float*)out->data);
+        for (int64_t c0 = 0; c0 < nb; c0 += 65535) {  // grid.y limit: utterance c0 + y of every chunk lands where the one launch would put it
+            const int64_t nc = std::min<int64_t>(65535, nb - c0);
+            const float* cx = (const float*)dx + c0 * t * d;
+            float *cm = (float*)dm + c0 * d, *cs = (float*)ds + c0 * d;
+            hipLaunchKernelGGL(cmvn_moments_kernel, dim3((unsigned)((d + 63) / 64), (unsigned)nc), dim3(64), 0, ctx->stream, cx, t, d, eps,
+                               cm, cs);
+            hipLaunchKernelGGL(cmvn_apply_kernel, dim3(blocks, (unsigned)nc), dim3(256), 0, ctx->stream, cx, t, d, (const float*)cm,
+                               (const float*)cs, (float*)out->data + c0 * t * d);
+        }
         LELE_HIP_CHECK(hipGetLastError());
     }
     std::vector<int64_t> shp(x->shape, x->shape + x->rank);

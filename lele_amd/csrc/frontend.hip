@@ -1082,6 +1082,7 @@ static int fe_generic(LeleFrontend* fe, const float* dpcm, int64_t batch, int64_
         const size_t padded = (size_t)fpb * n + (((size_t)fpb * n) >> 5) + 1;
         const size_t lds = (2 * padded + (size_t)fpb * bins + (size_t)(fpb - 1) * fe->hop_len + fe->frame_len + fpb) * 4;
         if (lds <= 96 * 1024) {
+            ctx->set_route("fe.generic_fused");
             const float *twr = nullptr, *twi = nullptr;
             LELE_TRY(fft_twiddles(ctx, n, &twr, &twi));
             LELE_HIP_CHECK(ensure_dyn_lds(reinterpret_cast<const void*>(fe_generic_fused_kernel), (int)lds));
@@ -1108,6 +1109,7 @@ static int fe_generic(LeleFrontend* fe, const float* dpcm, int64_t batch, int64_
             return 0;
         }
     }
+    ctx->set_route("fe.generic_four");
     const int64_t per_utt = nf * (4 + fe->n_fft * 4 + bins * 4 + nm * 4);
     const int64_t ub = std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(batch, 65535), (int64_t(1) << 28) / std::max<int64_t>(per_utt, 1)));
     void *gm = nullptr, *gf = nullptr, *gp = nullptr, *gl = nullptr;
@@ -1145,6 +1147,7 @@ static int fe_run(LeleFrontend* fe, const LeleTensor* pcm, int64_t batch, int64_
     LELE_REQUIRE(pcm->dtype == LELE_F32, "frontend: pcm must be f32");
     int64_t t_lfr = 0, cols = 0, nf = 0;
     lele_hip_frontend_out_rows(fe, pcm_len, &t_lfr, &cols, &nf);
+    ctx->set_route(nullptr);  // lele_hip_last_route: "" for a call that launches nothing
     if (nf == 0 || batch == 0) {  // TensorView::empty()
         out->bytes = 0;
         if (out_rank) *out_rank = 0;
@@ -1169,7 +1172,11 @@ static int fe_run(LeleFrontend* fe, const LeleTensor* pcm, int64_t batch, int64_
     LELE_REQUIRE((want_logmel ? nf * fe->cfg.n_mels : t_lfr * cols) < (int64_t(1) << 30),
                  "frontend: the features of one utterance (%lld frames) exceed 4 GiB", (long long)nf);
     const int aligned16 = ((uintptr_t)dpcm % 16 == 0) && (pcm_len % 4 == 0);
-    dim3 grid((unsigned)((nf + 63) / 64), (unsigned)batch);
+    // lele_hip_last_route: the kernel, then how it stages its PCM tile -- the condition fe_main_body evaluates (`tile_dma` there) on the
+    // same two values; the two-kernel lab form has no tile
+    ctx->set_route(fe->std_mel ? "fe.main_std" : "fe.main_table",
+                   !fe->fused ? "fe.two_kernel" : (aligned16 && fe->dev.tile_dma) ? "fe.tile_dma" : "fe.tile_regs");
+    constexpr int64_t kMaxGridY = 65535;  // utterances a launch: a longer batch runs in chunks (pcm_len % 4 == 0 where aligned16, so it holds for every chunk)
     hipEvent_t* ev = nullptr;
     if (fe->profiling) {
         if (fe->events_used + 3 > fe->events.size()) {
@@ -1183,16 +1190,16 @@ static int fe_run(LeleFrontend* fe, const LeleTensor* pcm, int64_t batch, int64_
         fe->events_used += 3;
         LELE_HIP_CHECK(hipEventRecord(ev[0], ctx->stream));
     }
-    if (!fe->fused)
-        hipLaunchKernelGGL(fe_frame_sum_kernel, grid, dim3(64), 0, ctx->stream, (const float*)dpcm, pcm_len, pcm_len, nf,
-                           (float*)dmean, aligned16);
+    for (int64_t c0 = 0; !fe->fused && c0 < batch; c0 += kMaxGridY) {
+        const dim3 grid((unsigned)((nf + 63) / 64), (unsigned)std::min<int64_t>(kMaxGridY, batch - c0));
+        hipLaunchKernelGGL(fe_frame_sum_kernel, grid, dim3(64), 0, ctx->stream, (const float*)dpcm + c0 * pcm_len, pcm_len, pcm_len, nf,
+                           (float*)dmean + c0 * nf, aligned16);
+    }
     if (ev) LELE_HIP_CHECK(hipEventRecord(ev[1], ctx->stream));
     const size_t mel_lds = (size_t)fe->dev.mel_steps * 16 * sizeof(float);
-    float* o = want_logmel ? nullptr : (float*)out->data;
-    float* lm = want_logmel ? (float*)out->data : nullptr;
-#define FE_LAUNCH(MODE, STD, FUS)                                                                                     \
-    hipLaunchKernelGGL((fe_main_kernel<MODE, STD, FUS>), grid, dim3(256), mel_lds, ctx->stream, (const float*)dpcm, \
-                       pcm_len, nf, t_lfr, (const float*)dmean, fe->dev, o, lm, aligned16)
+#define FE_LAUNCH(MODE, STD, FUS)                                                                                                    \
+    hipLaunchKernelGGL((fe_main_kernel<MODE, STD, FUS>), grid, dim3(256), mel_lds, ctx->stream, cpcm, pcm_len, nf, t_lfr, cmean, fe->dev, \
+                       o, lm, aligned16)
 #define FE_LAUNCH2(MODE, STD) \
     do {                      \
         if (fe->fused)        \
@@ -1200,10 +1207,17 @@ static int fe_run(LeleFrontend* fe, const LeleTensor* pcm, int64_t batch, int64_
         else                  \
             FE_LAUNCH(MODE, STD, false); \
     } while (0)
-    if (fe->dpp_mode == 1) {
-        if (fe->std_mel) FE_LAUNCH2(1, true); else FE_LAUNCH2(1, false);
-    } else {
-        if (fe->std_mel) FE_LAUNCH2(0, true); else FE_LAUNCH2(0, false);
+    for (int64_t c0 = 0; c0 < batch; c0 += kMaxGridY) {  // every chunk's utterances land where the one launch would put them
+        const dim3 grid((unsigned)((nf + 63) / 64), (unsigned)std::min<int64_t>(kMaxGridY, batch - c0));
+        const float* cpcm = (const float*)dpcm + c0 * pcm_len;
+        const float* cmean = (const float*)dmean + c0 * nf;
+        float* o = want_logmel ? nullptr : (float*)out->data + c0 * t_lfr * cols;
+        float* lm = want_logmel ? (float*)out->data + c0 * nf * fe->cfg.n_mels : nullptr;
+        if (fe->dpp_mode == 1) {
+            if (fe->std_mel) FE_LAUNCH2(1, true); else FE_LAUNCH2(1, false);
+        } else {
+            if (fe->std_mel) FE_LAUNCH2(0, true); else FE_LAUNCH2(0, false);
+        }
     }
 #undef FE_LAUNCH2
 #undef FE_LAUNCH
@@ -1294,6 +1308,7 @@ int lele_hip_frontend_compute_segments(LeleFrontend* fe, const LeleTensor* pcm, 
         max_nf = std::max(max_nf, nf);
     }
     const int64_t rows = row_offsets[count];
+    fe->ctx->set_route(nullptr);  // lele_hip_last_route: "" for a call that launches nothing
     if (rows == 0) {  // no segment holds a frame: TensorView::empty()
         out->bytes = 0;
         if (out_rank) *out_rank = 0;
@@ -1337,6 +1352,13 @@ int lele_hip_frontend_compute_segments(LeleFrontend* fe, const LeleTensor* pcm, 
     const FeSeg* dsegs = (const FeSeg*)table;
     const int* dblk = (const int*)(dsegs + nseg);
     const size_t mel_lds = (size_t)fe->dev.mel_steps * 16 * sizeof(float);
+    // lele_hip_last_route: the kernel, then the tile staging of its blocks -- fe_seg_main_kernel's own per-segment condition, evaluated
+    // here on the same values; one name for a launch that holds both kinds
+    int64_t n_dma = 0;
+    for (int64_t i = 0; i < count; ++i)
+        if (lengths[i] >= fe->frame_len)
+            n_dma += (((uintptr_t)((const float*)dpcm + starts[i]) & 15) == 0) && (lengths[i] % 4 == 0) && fe->dev.tile_dma;
+    ctx->set_route(fe->std_mel ? "fe.seg_std" : "fe.seg_table", n_dma == nseg ? "fe.tile_dma" : n_dma == 0 ? "fe.tile_regs" : "fe.tile_mixed");
 #define FE_SEG_LAUNCH(MODE, STD)                                                                                                 \
     hipLaunchKernelGGL((fe_seg_main_kernel<MODE, STD>), dim3((unsigned)blocks), dim3(256), mel_lds, ctx->stream, (const float*)dpcm, \
                        dsegs, dblk, fe->dev, o)

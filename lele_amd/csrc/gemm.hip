@@ -111,6 +111,11 @@ const char* const kRouteNames[] = {
     // rnn_seg_kernel: recurrent weights in registers in slices of 16 / 32 / 64, or streamed with 1 / 2 / 4 / 8 members a register tile
     "rnn.lstm", "rnn.gru", "rnns.lstm", "rnns.gru",
     "rnns.reg16", "rnns.reg32", "rnns.reg64", "rnns.stream1", "rnns.stream2", "rnns.stream4", "rnns.stream8",
+    // frontend.hip: the kernel (main / seg: the 400 / 160 / 512 framing, with the unrolled 80-mel bank or the table-driven mel loop;
+    // generic: every other framing, one fused kernel or the four-kernel form), then for the fast kernels how the PCM tile was staged
+    // (direct-to-LDS, through registers, or -- a segment launch -- both); fe.two_kernel: the lab form with the separate frame-sum kernel
+    "fe.main_std", "fe.main_table", "fe.seg_std", "fe.seg_table", "fe.generic_fused", "fe.generic_four",
+    "fe.tile_dma", "fe.tile_regs", "fe.tile_mixed", "fe.two_kernel",
 };
 
 }  // namespace

@@ -300,6 +300,10 @@ extern "C" void orc_sparse_mel_apply(float sr, int64_t n_fft, int64_t n_mels, fl
     SparseMelBank(sr, n_fft, n_mels, f_min, f_max).apply(power, out);
 }
 
+extern "C" void orc_log_compress(const float* in, int64_t n, float* out) {  // mel.rs:124-128: ln(max(x, 1e-5)), the libm logf of step 8 below
+    for (int64_t j = 0; j < n; ++j) out[j] = logf(in[j] > 1e-5f ? in[j] : 1e-5f);
+}
+
 extern "C" void orc_lfr(const float* in, int64_t t, int64_t d, int64_t m, int64_t n, float* out) {  // lfr.rs:18-54
     if (t == 0) return;
     int64_t t_lfr = (t + n - 1) / n, d_out = d * m, pad = (m - 1) / 2;
@@ -326,9 +330,10 @@ extern "C" int64_t orc_frontend_shape(int64_t pcm_len, int64_t sample_rate, floa
     return (nf + lfr_n - 1) / lfr_n;
 }
 
-extern "C" int64_t orc_frontend_compute(const float* pcm, int64_t pcm_len, int64_t sample_rate, int64_t n_mels,
-                                        float frame_length_ms, float frame_shift_ms, int64_t lfr_m, int64_t lfr_n,
-                                        float* mel_out, float* out) {
+// `energy_out` (may be NULL) receives the f32 mel sums [num_frames, n_mels]: the values step 8 passes to logf
+static int64_t frontend_compute(const float* pcm, int64_t pcm_len, int64_t sample_rate, int64_t n_mels,
+                                float frame_length_ms, float frame_shift_ms, int64_t lfr_m, int64_t lfr_n,
+                                float* mel_out, float* out, float* energy_out) {
     int64_t frame_len = (int64_t)((float)sample_rate * frame_length_ms / 1000.0f);
     int64_t n_fft = frame_len > 400 ? 1024 : 512;  // pipeline.rs:40
     int64_t hop_len = (int64_t)((float)sample_rate * frame_shift_ms / 1000.0f);
@@ -362,10 +367,23 @@ extern "C" int64_t orc_frontend_compute(const float* pcm, int64_t pcm_len, int64
         for (int64_t j = 0; j < n_fft / 2 + 1; ++j) power[j] = fre[j] * fre[j] + fim[j] * fim[j];  // 6.
         float* mel = mel_out + i * n_mels;
         bank.apply(power.data(), mel);                                                // 7.
+        if (energy_out) memcpy(energy_out + i * n_mels, mel, sizeof(float) * n_mels);
         for (int64_t j = 0; j < n_mels; ++j) mel[j] = logf(mel[j] > 1e-5f ? mel[j] : 1e-5f);  // 8. ln(max(x,eps))
     }
     orc_lfr(mel_out, num_frames, n_mels, lfr_m, lfr_n, out);
     return (num_frames + lfr_n - 1) / lfr_n;
+}
+
+extern "C" int64_t orc_frontend_compute(const float* pcm, int64_t pcm_len, int64_t sample_rate, int64_t n_mels,
+                                        float frame_length_ms, float frame_shift_ms, int64_t lfr_m, int64_t lfr_n,
+                                        float* mel_out, float* out) {
+    return frontend_compute(pcm, pcm_len, sample_rate, n_mels, frame_length_ms, frame_shift_ms, lfr_m, lfr_n, mel_out, out, nullptr);
+}
+
+extern "C" int64_t orc_frontend_compute_energy(const float* pcm, int64_t pcm_len, int64_t sample_rate, int64_t n_mels,
+                                               float frame_length_ms, float frame_shift_ms, int64_t lfr_m, int64_t lfr_n,
+                                               float* mel_out, float* out, float* energy_out) {
+    return frontend_compute(pcm, pcm_len, sample_rate, n_mels, frame_length_ms, frame_shift_ms, lfr_m, lfr_n, mel_out, out, energy_out);
 }
 
 extern "C" void orc_cmvn(const float* in, int64_t t, int64_t d, float eps, float* out) {  // cmvn.rs:14-66

@@ -63,6 +63,12 @@ int64_t orc_frontend_shape(int64_t pcm_len, int64_t sample_rate, float frame_len
 int64_t orc_frontend_compute(const float* pcm, int64_t pcm_len, int64_t sample_rate, int64_t n_mels,
                              float frame_length_ms, float frame_shift_ms, int64_t lfr_m, int64_t lfr_n,
                              float* mel_out, float* out);
+/* the same, and `energy_out` receives the f32 mel sums [num_frames, n_mels] BEFORE the log: exactly the values that
+ * orc_frontend_compute passes to logf(max(x, 1e-5f)) */
+int64_t orc_frontend_compute_energy(const float* pcm, int64_t pcm_len, int64_t sample_rate, int64_t n_mels,
+                                    float frame_length_ms, float frame_shift_ms, int64_t lfr_m, int64_t lfr_n,
+                                    float* mel_out, float* out, float* energy_out);
+void orc_log_compress(const float* in, int64_t n, float* out); /* mel.rs:124-128 */
 void orc_lfr(const float* in, int64_t t, int64_t d, int64_t m, int64_t n, float* out); /* lfr.rs:18-54 */
 void orc_cmvn(const float* in, int64_t t, int64_t d, float eps, float* out);          /* cmvn.rs:14-66 */
 void orc_cmvn_apply_with_stats(const float* in, int64_t t, int64_t d, float eps, const float* mean,

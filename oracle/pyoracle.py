@@ -37,7 +37,7 @@ def lib():
         _LIB.orc_hz_to_mel_htk.argtypes = [C.c_float]
         _LIB.orc_mel_to_hz_htk.restype = C.c_float
         _LIB.orc_mel_to_hz_htk.argtypes = [C.c_float]
-        for name in ("orc_frontend_shape", "orc_frontend_compute", "orc_stft", "orc_stft_power"):
+        for name in ("orc_frontend_shape", "orc_frontend_compute", "orc_frontend_compute_energy", "orc_stft", "orc_stft_power"):
             getattr(_LIB, name).restype = C.c_int64
     return _LIB
 
@@ -130,19 +130,35 @@ def frontend_shape(pcm_len, sample_rate=16000, frame_length_ms=25.0, frame_shift
 
 
 def frontend_compute(pcm, sample_rate=16000, n_mels=80, frame_length_ms=25.0, frame_shift_ms=10.0, lfr_m=7, lfr_n=6,
-                     return_mel=False):
-    """SenseVoiceFrontend::compute.  Returns LFR features [T, n_mels*lfr_m] (shape (0,) if too short)."""
+                     return_mel=False, return_energy=False):
+    """SenseVoiceFrontend::compute.  Returns LFR features [T, n_mels*lfr_m] (shape (0,) if too short).
+    return_mel: (features, log-mel [frames, n_mels]).  return_energy: (features, log-mel, energy) -- energy [frames, n_mels] holds the
+    f32 mel sums before the log, exactly the values the log-mel is logf(max(., 1e-5f)) of."""
     pcm = _f32(pcm)
     t, nf = frontend_shape(pcm.shape[0], sample_rate, frame_length_ms, frame_shift_ms, lfr_n)
     if t == 0:
         e = np.zeros((0,), np.float32)
-        return (e, e) if return_mel else e
+        return (e, e, e) if return_energy else (e, e) if return_mel else e
     mel = np.empty((nf, n_mels), np.float32)
     out = np.empty((t, n_mels * lfr_m), np.float32)
+    if return_energy:
+        energy = np.empty((nf, n_mels), np.float32)
+        r = lib().orc_frontend_compute_energy(_p(pcm), i64(pcm.shape[0]), i64(sample_rate), i64(n_mels), f(frame_length_ms),
+                                              f(frame_shift_ms), i64(lfr_m), i64(lfr_n), _p(mel), _p(out), _p(energy))
+        assert r == t
+        return out, mel, energy
     r = lib().orc_frontend_compute(_p(pcm), i64(pcm.shape[0]), i64(sample_rate), i64(n_mels), f(frame_length_ms),
                                    f(frame_shift_ms), i64(lfr_m), i64(lfr_n), _p(mel), _p(out))
     assert r == t
     return (out, mel) if return_mel else out
+
+
+def log_compress(x):
+    """ln(max(x, 1e-5)) element-wise with the libm logf the front-end restatement uses (mel.rs:124-128)"""
+    x = _f32(x)
+    out = np.empty_like(x)
+    lib().orc_log_compress(_p(x), i64(x.size), _p(out))
+    return out
 
 
 def lfr(x, m=7, n=6):
