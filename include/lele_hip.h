@@ -170,6 +170,42 @@ int lele_hip_frontend_logmel(LeleFrontend* fe, const LeleTensor* pcm, LeleBuf* o
 int lele_hip_frontend_set_profiling(LeleFrontend* fe, int on);
 int lele_hip_frontend_profile_read(LeleFrontend* fe, float* sum_kernel_ms, float* main_kernel_ms, int64_t* runs);
 
+/* ---- chunked streaming: N live streams (open microphones) fed a chunk a tick.  One push takes this tick's chunk of EVERY stream and
+ * returns every feature row that has become final; concatenated per stream, the rows are bit for bit what lele_hip_frontend_compute
+ * gives on the whole utterance, for any cut of the audio into chunks.  Per stream, after L samples in total (frame_len, hop, m, n of
+ * the FeatureConfig, pad = (m - 1) / 2):
+ *   frames        T(L) = L < frame_len ? 0 : (L - frame_len) / hop + 1
+ *   rows emitted  E(L) = number of i >= 0 with i*n + (m-1-pad) <= T-1   (row i is final once its right-most frame exists; it is written
+ *                 in the push that delivers that frame's last sample, no earlier and no later)
+ * A push flagged final also emits rows E .. ceil(T/n)-1 with the right clamp to frame T-1 (lfr.rs:43-44), drops the samples that
+ * complete no frame (as compute does) and resets the stream; a stream that never reaches one frame yields 0 rows.  The left clamp (raw
+ * index < 0 reads frame 0) applies at the start of a stream only.  Between pushes the device keeps, per stream, fewer than frame_len
+ * samples (the last L - T*hop, or all L while L < frame_len) and at most m-1 log-mel rows (frames max(0, E*n - pad) .. T-1); the
+ * counters L, T, E live on the host and are functions of the chunk lengths alone. */
+typedef struct LeleFrontendStream LeleFrontendStream;
+/* The closed forms above for one push of chunk_len samples onto a stream that has seen samples_before: rows the push emits, frames it
+ * completes, and the samples / log-mel rows carried AFTER it (0 and 0 after a final push).  Host arithmetic, no ctx, no GPU. */
+int lele_hip_frontend_stream_rows(const LeleFeatureConfig* cfg, int64_t samples_before, int64_t chunk_len, int32_t final, int64_t* rows,
+                                  int64_t* new_frames, int64_t* pcm_carry, int64_t* mel_carry);
+/* State of `streams` streams that take at most max_chunk samples a push, all of it allocated here: per stream a PCM region of
+ * frame_len - 1 + max_chunk samples (16-byte aligned base, pitch a multiple of 4 floats) and a log-mel region of m - 1 + (the most frames
+ * one push completes) rows.  Destroy it before its LeleFrontend.  Refused: a frame shift longer than the frame. */
+int lele_hip_frontend_stream_create(LeleFrontend* fe, int64_t streams, int64_t max_chunk, LeleFrontendStream** out);
+int lele_hip_frontend_stream_destroy(LeleFrontendStream* st);
+/* A new utterance in streams ids[0 .. count) (ids == NULL: in every stream).  Host counters only, nothing is launched. */
+int lele_hip_frontend_stream_reset(LeleFrontendStream* st, const int64_t* ids, int64_t count);
+/* samples seen (L), frames completed (T) and rows emitted (E) by stream `id` since its last reset or final push */
+int lele_hip_frontend_stream_counters(const LeleFrontendStream* st, int64_t id, int64_t* samples, int64_t* frames, int64_t* rows);
+/* One tick.  pcm: f32 [N], host or device; stream i's chunk is pcm[starts[i], starts[i] + lengths[i]) -- exactly one entry per stream,
+ * length 0 = no audio this tick (legal together with final).  final_or_null: one flag a stream, NULL = none.  out [R, n_mels*lfr_m]
+ * packed, row_offsets (streams + 1, written): the layout of lele_hip_frontend_compute_segments, so cmvn_apply_with_stats, the encoder's
+ * forward_segments and the decode heads take it as it is.  R == 0 gives rank 0.  Everything is checked before anything is launched: a
+ * range outside pcm, a length above max_chunk, a NULL argument or a call while the ctx records a graph (the counters advance on the
+ * host, so a push cannot be replayed) fail and leave `out` AND the streams as they were.  Three or four launches a push over all
+ * streams on the default framing (append, log-mel, emit, compact); other framings run the generic kernels once per stream. */
+int lele_hip_frontend_stream_push(LeleFrontendStream* st, const LeleTensor* pcm, const int64_t* starts, const int64_t* lengths,
+                                  const uint8_t* final_or_null, LeleBuf* out, int64_t* row_offsets, int64_t* out_shape, int32_t* out_rank);
+
 /* Lfr::compute, src/features/lfr.rs:18-54: [T, D] (or [1,T,D]) -> [ceil(T/n), D*m] */
 int lele_hip_lfr(LeleCtx* ctx, const LeleTensor* x, int64_t m, int64_t n, LeleBuf* out, int64_t* out_shape,
                  int32_t* out_rank);
@@ -396,7 +432,10 @@ int lele_hip_conv_stats(LeleCtx* ctx, int64_t* calls, int64_t* macs);
  * "fe.generic_four" (its four-kernel form: batches beyond 65535 utterances) -- then for the main / seg kernels how the PCM tile was staged:
  * "fe.tile_dma" (direct-to-LDS: 16-byte aligned runs), "fe.tile_regs" (through registers), "fe.tile_mixed" (a segment launch that holds
  * both); "fe.two_kernel" instead for the lab form with the separate frame-sum kernel.  compute_segments on another framing reports its
- * last segment's route.  The route never names an earlier call.  Recorded on the
+ * last segment's route.  frontend_stream_push adds no name: its log-mel launch is the segment kernel's body over the streams' regions and
+ * reports "fe.seg_std" / "fe.seg_table", then "fe.tile_dma" / "fe.tile_regs" / "fe.tile_mixed" by the same per-record condition (a region's carry +
+ * chunk is a multiple of 4 samples); the generic names on another framing (the last stream's); "" when no stream gained a frame.
+ * The route never names an earlier call.  Recorded on the
  * host when the call is issued (a call recorded into a graph reports the route it recorded).  NUL-terminated into buf; an error when cap is too small.
  * lele_hip_route_names: every level name a route can hold, one per line; host only, no GPU needed. */
 int lele_hip_last_route(LeleCtx* ctx, char* buf, size_t cap);

@@ -62,6 +62,8 @@ def lib():
         _i64p, _i32p = C.POINTER(C.c_int64), C.POINTER(C.c_int32)
         for name, at in (  # (a saved older build -- LELE_HIP_LIBRARY -- may lack them)
                 ("lele_hip_frontend_compute_segments", [C.c_void_p, C.c_void_p, _i64p, _i64p, C.c_int64, C.c_void_p, _i64p, _i64p, _i32p]),
+                ("lele_hip_frontend_stream_push", [C.c_void_p, C.c_void_p, _i64p, _i64p, C.POINTER(C.c_uint8), C.c_void_p, _i64p, _i64p, _i32p]),
+                ("lele_hip_frontend_stream_reset", [C.c_void_p, _i64p, C.c_int64]),
                 ("lele_hip_cmvn_segments", [C.c_void_p, C.c_void_p, _i64p, C.c_int64, C.c_float, C.c_void_p, _i64p, _i32p]),
                 ("lele_hip_segments_to_padded", [C.c_void_p, C.c_void_p, _i64p, C.c_int64, C.c_int64, C.c_float, C.c_void_p, _i64p, _i32p])):
             fn = getattr(_lib, name, None)

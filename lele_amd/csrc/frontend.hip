@@ -786,6 +786,144 @@ __global__ void fe_generic_lfr_kernel(const float* __restrict__ x, int64_t t, in
     }
 }
 
+// ------------------------------------------------------------------------------------------------------
+// stream_push: N live streams fed chunk by chunk (lele_hip.h).  Each stream owns a PCM region (its carried samples, then this tick's
+// chunk) and a log-mel region (its carried rows, then this tick's new frames); the counters live on the host and one record per
+// stream, rebuilt every push, tells the four kernels below what to do.  A push is append -> log-mel -> emit -> compact in stream
+// order, each one launch over ALL streams; no kernel reads a state range that another workgroup of the SAME launch writes.
+// ------------------------------------------------------------------------------------------------------
+struct FeStreamRec {
+    int64_t src;           // first sample of this tick's chunk in the pcm buffer
+    int64_t mel_base;      // global index of the frame in row 0 of the log-mel region
+    int64_t row_lo;        // index (inside the utterance) of the first LFR row this push emits
+    int64_t last_frame;    // T - 1 after this push (the right clamp of a final push)
+    int64_t out_row0;      // first row of the packed result
+    int32_t chunk, carry;  // samples of the chunk / carried in front of it
+    int32_t nf;            // frames this push completes: frame j of them starts at sample j * hop of the region
+    int32_t block0;        // first 64-frame block of the log-mel grid
+    int32_t mel_carry;     // rows carried in the log-mel region (the new frames go behind them)
+    int32_t rows;          // LFR rows this push emits
+    int32_t emit_block0;   // first block of the emit grid
+    int32_t final;         // the right clamp applies
+    int32_t pcm_keep, pcm_from;  // compact: samples [pcm_from, pcm_from + pcm_keep) of the region move to its front
+    int32_t mel_keep, mel_from;  // compact: rows [mel_from, mel_from + mel_keep) of the log-mel region move to its front
+};
+
+typedef float fe_f4 __attribute__((ext_vector_type(4)));
+constexpr int kAppendPiece = 256;  // floats a workgroup of 64 copies: 1 KB
+constexpr int kEmitRows = 4;       // LFR rows a workgroup of 256 gathers: one wave a row
+constexpr int kCompactRegs = 8;    // floats a thread of the compact kernel holds across its barrier
+
+// 1. append: the chunk goes behind the carried samples.  grid = streams x pieces of the longest chunk; an exact copy.
+__global__ __launch_bounds__(64) void fe_stream_append_kernel(const float* __restrict__ pcm, const FeStreamRec* __restrict__ recs, int pieces,
+                                                              float* __restrict__ pcm_state, int64_t pcm_pitch) {
+    const int s = blockIdx.x / pieces, piece = blockIdx.x - s * pieces;
+    const FeStreamRec r = recs[s];
+    const int o = piece * kAppendPiece;
+    if (o >= r.chunk) return;
+    const float* src = pcm + r.src + o;
+    float* dst = pcm_state + (int64_t)s * pcm_pitch + r.carry + o;
+    const int n = min(kAppendPiece, r.chunk - o);
+    LELE_DEV_ASSERT(r.carry + o + n <= pcm_pitch);
+    const int t = threadIdx.x;
+    if ((((uintptr_t)src | (uintptr_t)dst) & 15) == 0 && 4 * t + 4 <= n) {
+        *reinterpret_cast<float4*>(dst + 4 * t) = *reinterpret_cast<const float4*>(src + 4 * t);
+    } else if ((((uintptr_t)src | (uintptr_t)dst) & 15) == 0) {
+        for (int j = 4 * t; j < n; ++j) dst[j] = src[j];  // the piece's last, partial vector
+    } else {
+#pragma unroll
+        for (int u = 0; u < kAppendPiece / 64; ++u)
+            if (t + 64 * u < n) dst[t + 64 * u] = src[t + 64 * u];
+    }
+}
+
+// 2. log-mel: fe_main_body over every stream's new frames, as fe_seg_main_kernel runs it over segments -- the "utterance" is the
+// stream's PCM region (carry + chunk samples, frame j at j * hop), the LFR output is off and the log-mel rows go behind the carried ones.
+// (SegBlock's twin rather than SegBlock itself: the body's LDS arrays are statics of the fe_main_body instantiation, and sharing one
+// instantiation with fe_seg_main_kernel reordered operands in THAT kernel's code; a block type of its own leaves it as it was.)
+struct StreamBlock {
+    unsigned bx;
+    __device__ __forceinline__ unsigned x() const { return bx; }
+    __device__ __forceinline__ unsigned y() const { return 0u; }
+};
+template <int MODE, bool STDMEL>
+__global__ __launch_bounds__(256) void fe_stream_main_kernel(const float* __restrict__ pcm_state, int64_t pcm_pitch,
+                                                             const FeStreamRec* __restrict__ recs, const int* __restrict__ blk_stream, FeDev tb,
+                                                             float* __restrict__ mel_state, int64_t mel_pitch) {
+    extern __shared__ float s_melw[];
+    const int s = blk_stream[blockIdx.x];
+    const FeStreamRec r = recs[s];
+    const float* base = pcm_state + (int64_t)s * pcm_pitch;  // 16-byte aligned: the region's base is, and the pitch is a multiple of 4
+    const int64_t len = (int64_t)r.carry + r.chunk;
+    const int aligned16 = len % 4 == 0;
+    fe_main_body<MODE, STDMEL, true, 4, false>(base, len, r.nf, 0, nullptr, tb, nullptr,
+                                               mel_state + (int64_t)s * mel_pitch + (int64_t)r.mel_carry * tb.n_mels, aligned16, s_melw,
+                                               StreamBlock{(unsigned)(blockIdx.x - r.block0)});
+}
+
+// 3. emit: LFR row i of a stream is blocks b = 0 .. m-1 = frames i*n + b - pad; frame g sits in row g - mel_base of the stream's
+// log-mel region.  The left clamp goes to the utterance's frame 0 (still carried while any row needs it), the right clamp to frame T-1
+// exists only on a final push: every other row's right-most frame is in the region by the closed form that selected it.
+template <bool VEC>
+__global__ __launch_bounds__(256) void fe_stream_emit_kernel(const float* __restrict__ mel_state, int64_t mel_pitch,
+                                                             const FeStreamRec* __restrict__ recs, const int* __restrict__ blk_stream, int n_mels,
+                                                             int lfr_m, int lfr_n, float* __restrict__ out) {
+    const int s = blk_stream[blockIdx.x];
+    const FeStreamRec r = recs[s];
+    const int lane = threadIdx.x & 63;
+    const int k = (int)(blockIdx.x - r.emit_block0) * kEmitRows + (int)(threadIdx.x >> 6);  // row of this push, one wave each
+    if (k >= r.rows) return;
+    const int64_t i = r.row_lo + k;
+    const int pad = (lfr_m - 1) / 2;
+    const float* mel = mel_state + (int64_t)s * mel_pitch;
+    const int d_out = n_mels * lfr_m;
+    float* dst = out + (r.out_row0 + k) * d_out;
+    constexpr int W = VEC ? 4 : 1;
+    const int per = n_mels / W;  // VEC: n_mels % 4 == 0, so every block of every row starts 16-byte aligned on both sides
+    for (int v = lane; v < per * lfr_m; v += 64) {
+        const int b = v / per, c = v - b * per;
+        int64_t g = i * lfr_n + b - pad;
+        g = g < 0 ? 0 : g;
+        if (r.final) g = g > r.last_frame ? r.last_frame : g;
+        LELE_DEV_ASSERT(g >= r.mel_base && g - r.mel_base < r.mel_carry + r.nf);
+        const float* src = mel + (g - r.mel_base) * n_mels + W * c;
+        float* d = dst + b * n_mels + W * c;
+        if (VEC)
+            __builtin_nontemporal_store(*reinterpret_cast<const fe_f4*>(src), reinterpret_cast<fe_f4*>(d));
+        else
+            __builtin_nontemporal_store(*src, d);
+    }
+}
+
+// 4. compact: what the next push needs moves to the front of both regions.  Source and destination overlap when little was added, so
+// ONE workgroup a stream takes the whole move through registers: everything is read, one barrier, everything is written (a move past
+// 256 * kCompactRegs floats -- an LFR window far beyond the default's 399 + 6 * 80 -- goes in rounds of that size: a round's
+// destination ends below every later round's source, since the move is towards the front).
+__device__ __forceinline__ void fe_stream_move(float* region, int from, int count) {
+    if (from == 0) return;
+    for (int r0 = 0; r0 < count; r0 += 256 * kCompactRegs) {
+        float v[kCompactRegs];
+#pragma unroll
+        for (int u = 0; u < kCompactRegs; ++u) {
+            const int j = r0 + u * 256 + (int)threadIdx.x;
+            v[u] = j < count ? region[from + j] : 0.0f;
+        }
+        __syncthreads();
+#pragma unroll
+        for (int u = 0; u < kCompactRegs; ++u) {
+            const int j = r0 + u * 256 + (int)threadIdx.x;
+            if (j < count) region[j] = v[u];
+        }
+    }
+}
+__global__ __launch_bounds__(256) void fe_stream_compact_kernel(const FeStreamRec* __restrict__ recs, float* pcm_state, int64_t pcm_pitch,
+                                                                float* mel_state, int64_t mel_pitch, int n_mels) {
+    const FeStreamRec r = recs[blockIdx.x];  // (block-uniform: every thread takes the same barriers)
+    LELE_DEV_ASSERT(r.pcm_from + r.pcm_keep <= pcm_pitch && (int64_t)(r.mel_from + r.mel_keep) * n_mels <= mel_pitch);
+    fe_stream_move(pcm_state + (int64_t)blockIdx.x * pcm_pitch, r.pcm_from, r.pcm_keep);
+    fe_stream_move(mel_state + (int64_t)blockIdx.x * mel_pitch, r.mel_from * n_mels, r.mel_keep * n_mels);
+}
+
 }  // namespace
 
 // ------------------------------------------------------------------------------------------------------
@@ -1370,6 +1508,275 @@ int lele_hip_frontend_compute_segments(LeleFrontend* fe, const LeleTensor* pcm, 
 #undef FE_SEG_LAUNCH
     LELE_HIP_CHECK(hipGetLastError());
     return set_shape(out_shape, out_rank, {rows, cols});
+}
+
+/* ---- chunked streaming (see lele_hip.h): the closed forms, the per-stream state and one push ---- */
+}  // extern "C"
+
+namespace {
+struct FeStreamDims {
+    int64_t frame_len, hop, m, n, pad;
+    int64_t frames(int64_t len) const { return len < frame_len ? 0 : (len - frame_len) / hop + 1; }  // pipeline.rs:70-73
+    // rows whose right-most frame i*n + m-1-pad exists among t frames
+    int64_t rows(int64_t t) const { return t - 1 >= m - 1 - pad ? (t - 1 - (m - 1 - pad)) / n + 1 : 0; }
+    int64_t rows_final(int64_t t) const { return (t + n - 1) / n; }  // lfr.rs:33
+    // samples that a later frame still needs: from the first sample of frame t on (everything while there is no frame)
+    int64_t pcm_carry(int64_t len, int64_t t) const { return t == 0 ? len : std::max<int64_t>(0, len - t * hop); }
+    // frames that a later row still needs: from the left-most frame of row e on
+    int64_t mel_carry(int64_t t, int64_t e) const { return std::max<int64_t>(0, t - std::max<int64_t>(0, e * n - pad)); }
+};
+int fe_stream_dims(const LeleFeatureConfig* cfg, FeStreamDims* d) {
+    LELE_REQUIRE(cfg->sample_rate > 0 && cfg->n_mels > 0 && cfg->lfr_m > 0 && cfg->lfr_n > 0, "frontend_stream: invalid FeatureConfig");
+    d->frame_len = (int64_t)((float)cfg->sample_rate * cfg->frame_length_ms / 1000.0f);  // pipeline.rs:39
+    d->hop = (int64_t)((float)cfg->sample_rate * cfg->frame_shift_ms / 1000.0f);         // pipeline.rs:42
+    d->m = cfg->lfr_m;
+    d->n = cfg->lfr_n;
+    d->pad = (cfg->lfr_m - 1) / 2;
+    LELE_REQUIRE(d->frame_len >= 1 && d->hop >= 1, "frontend_stream: frame_len=%lld hop_len=%lld", (long long)d->frame_len, (long long)d->hop);
+    return 0;
+}
+}  // namespace
+
+struct LeleFrontendStream {
+    LeleFrontend* fe = nullptr;
+    hipStream_t stream = nullptr;  // the ctx stream the pushes are issued on (drained before the state is freed)
+    FeStreamDims dims{};
+    int64_t streams = 0, max_chunk = 0;
+    int64_t max_new_frames = 0;  // the most frames one push can complete
+    float* pcm_state = nullptr;  // [streams][pcm_pitch]: carried samples, then the chunk
+    float* mel_state = nullptr;  // [streams][mel_pitch]: carried log-mel rows, then the new frames'
+    int64_t pcm_pitch = 0, mel_pitch = 0;  // floats
+    std::vector<int64_t> samples, frames, rows;  // L, T, E of every stream: functions of the chunk lengths alone
+};
+
+extern "C" {
+
+int lele_hip_frontend_stream_rows(const LeleFeatureConfig* cfg, int64_t samples_before, int64_t chunk_len, int32_t final, int64_t* rows,
+                                  int64_t* new_frames, int64_t* pcm_carry, int64_t* mel_carry) {
+    LELE_REQUIRE(cfg, "frontend_stream_rows: cfg is NULL");
+    LELE_REQUIRE(samples_before >= 0 && chunk_len >= 0, "frontend_stream_rows: negative sample count");
+    FeStreamDims d;
+    LELE_TRY(fe_stream_dims(cfg, &d));
+    const int64_t t0 = d.frames(samples_before), len = samples_before + chunk_len, t1 = d.frames(len);
+    const int64_t e0 = d.rows(t0), e1 = final ? d.rows_final(t1) : d.rows(t1);
+    if (rows) *rows = e1 - e0;
+    if (new_frames) *new_frames = t1 - t0;
+    if (pcm_carry) *pcm_carry = final ? 0 : d.pcm_carry(len, t1);  // (a final push resets the stream)
+    if (mel_carry) *mel_carry = final ? 0 : d.mel_carry(t1, e1);
+    return 0;
+}
+
+int lele_hip_frontend_stream_create(LeleFrontend* fe, int64_t streams, int64_t max_chunk, LeleFrontendStream** out) {
+    LELE_REQUIRE(fe && out, "frontend_stream_create: NULL argument");
+    LELE_REQUIRE(streams >= 1 && max_chunk >= 1, "frontend_stream_create: streams %lld and max_chunk %lld must be at least 1", (long long)streams,
+                 (long long)max_chunk);
+    FeStreamDims d;
+    LELE_TRY(fe_stream_dims(&fe->cfg, &d));
+    // (a shift longer than the frame would have to DROP samples between two frames; no model this library serves is framed that way)
+    LELE_REQUIRE(d.hop <= d.frame_len, "frontend_stream_create: the frame shift (%lld samples) is longer than the frame (%lld)", (long long)d.hop,
+                 (long long)d.frame_len);
+    LeleCtx* ctx = fe->ctx;
+    LELE_REQUIRE(!ctx->capturing, "graph capture: frontend_stream_create allocates; create the stream before capturing");
+    const int64_t max_new = (max_chunk - 1) / d.hop + 1;
+    const int64_t pcm_pitch = (d.frame_len - 1 + max_chunk + 3) & ~int64_t(3);
+    const int64_t mel_pitch = ((d.m - 1 + max_new) * fe->cfg.n_mels + 3) & ~int64_t(3);
+    // the kernels index a region with 32-bit offsets, the grids count blocks in 32 bits
+    LELE_REQUIRE(pcm_pitch < (int64_t(1) << 30) && mel_pitch < (int64_t(1) << 30) && streams < (int64_t(1) << 24),
+                 "frontend_stream_create: %lld streams of %lld samples a push are beyond the kernels' 32-bit offsets", (long long)streams,
+                 (long long)max_chunk);
+    LELE_HIP_CHECK(hipSetDevice(ctx->device));
+    LeleFrontendStream* st = new LeleFrontendStream();
+    st->fe = fe;
+    st->stream = ctx->stream;
+    st->dims = d;
+    st->streams = streams;
+    st->max_chunk = max_chunk;
+    st->max_new_frames = max_new;
+    st->pcm_pitch = pcm_pitch;
+    st->mel_pitch = mel_pitch;
+    st->samples.assign((size_t)streams, 0);
+    st->frames.assign((size_t)streams, 0);
+    st->rows.assign((size_t)streams, 0);
+    hipError_t e = hipMalloc((void**)&st->pcm_state, (size_t)streams * pcm_pitch * sizeof(float));
+    if (e == hipSuccess) e = hipMalloc((void**)&st->mel_state, (size_t)streams * mel_pitch * sizeof(float));
+    if (e != hipSuccess) {
+        if (st->pcm_state) (void)hipFree(st->pcm_state);
+        delete st;
+        LELE_HIP_CHECK(e);
+    }
+    *out = st;
+    return 0;
+}
+
+int lele_hip_frontend_stream_destroy(LeleFrontendStream* st) {
+    if (!st) return 0;
+    (void)hipStreamSynchronize(st->stream);
+    (void)hipFree(st->pcm_state);
+    (void)hipFree(st->mel_state);
+    delete st;
+    return 0;
+}
+
+int lele_hip_frontend_stream_reset(LeleFrontendStream* st, const int64_t* ids, int64_t count) {
+    LELE_REQUIRE(st, "frontend_stream_reset: st is NULL");
+    if (!ids) {
+        std::fill(st->samples.begin(), st->samples.end(), 0);
+        std::fill(st->frames.begin(), st->frames.end(), 0);
+        std::fill(st->rows.begin(), st->rows.end(), 0);
+        return 0;
+    }
+    for (int64_t i = 0; i < count; ++i)
+        LELE_REQUIRE(ids[i] >= 0 && ids[i] < st->streams, "frontend_stream_reset: id %lld is not one of the %lld streams", (long long)ids[i],
+                     (long long)st->streams);
+    for (int64_t i = 0; i < count; ++i) st->samples[ids[i]] = st->frames[ids[i]] = st->rows[ids[i]] = 0;
+    return 0;
+}
+
+int lele_hip_frontend_stream_counters(const LeleFrontendStream* st, int64_t id, int64_t* samples, int64_t* frames, int64_t* rows) {
+    LELE_REQUIRE(st, "frontend_stream_counters: st is NULL");
+    LELE_REQUIRE(id >= 0 && id < st->streams, "frontend_stream_counters: id %lld is not one of the %lld streams", (long long)id, (long long)st->streams);
+    if (samples) *samples = st->samples[id];
+    if (frames) *frames = st->frames[id];
+    if (rows) *rows = st->rows[id];
+    return 0;
+}
+
+int lele_hip_frontend_stream_push(LeleFrontendStream* st, const LeleTensor* pcm, const int64_t* starts, const int64_t* lengths,
+                                  const uint8_t* final_or_null, LeleBuf* out, int64_t* row_offsets, int64_t* out_shape, int32_t* out_rank) {
+    LELE_REQUIRE(st && pcm && starts && lengths && out && row_offsets, "frontend_stream_push: NULL argument");
+    LeleFrontend* fe = st->fe;
+    LeleCtx* ctx = fe->ctx;
+    LELE_REQUIRE(!ctx->capturing, "frontend_stream_push: a push cannot be recorded into a graph (the stream counters advance on the host at "
+                                  "every call); push eagerly and capture what consumes the rows");
+    LELE_REQUIRE(pcm->dtype == LELE_F32 && pcm->rank == 1, "frontend_stream_push: pcm must be f32 [N]");
+    const int64_t n = pcm->shape[0], count = st->streams;
+    for (int64_t i = 0; i < count; ++i) {
+        LELE_REQUIRE(starts[i] >= 0 && lengths[i] >= 0 && starts[i] <= n - lengths[i],
+                     "frontend_stream_push: the chunk of stream %lld (start %lld, length %lld) lies outside the %lld samples of pcm", (long long)i,
+                     (long long)starts[i], (long long)lengths[i], (long long)n);
+        LELE_REQUIRE(lengths[i] <= st->max_chunk, "frontend_stream_push: the chunk of stream %lld has %lld samples, the stream was created for %lld",
+                     (long long)i, (long long)lengths[i], (long long)st->max_chunk);
+    }
+    // the plan of this push: one record a stream, one stream index a block of the log-mel and the emit grids.  Host arithmetic only;
+    // the counters are committed after the last launch has been issued.
+    const FeStreamDims& d = st->dims;
+    const int64_t nm = fe->cfg.n_mels, cols = nm * d.m;
+    std::vector<FeStreamRec> recs((size_t)count);
+    std::vector<int> blk, eblk;
+    std::vector<int64_t> nl((size_t)count), nt((size_t)count), ne((size_t)count);
+    int64_t max_chunk = 0, max_nf = 0, n_live = 0, n_dma = 0;
+    bool moves = false;
+    row_offsets[0] = 0;
+    for (int64_t i = 0; i < count; ++i) {
+        const bool fin = final_or_null && final_or_null[i];
+        const int64_t L = st->samples[i], T = st->frames[i], E = st->rows[i];
+        const int64_t c = d.pcm_carry(L, T), mc = d.mel_carry(T, E), len = c + lengths[i];
+        const int64_t L2 = L + lengths[i], T2 = d.frames(L2), E2 = fin ? d.rows_final(T2) : d.rows(T2);
+        FeStreamRec& r = recs[(size_t)i];
+        r = FeStreamRec{};
+        r.src = starts[i];
+        r.chunk = (int32_t)lengths[i];
+        r.carry = (int32_t)c;
+        r.nf = (int32_t)(T2 - T);
+        r.block0 = (int32_t)blk.size();
+        r.mel_carry = (int32_t)mc;
+        r.mel_base = T - mc;
+        r.row_lo = E;
+        r.rows = (int32_t)(E2 - E);
+        r.emit_block0 = (int32_t)eblk.size();
+        r.final = fin;
+        r.last_frame = T2 - 1;
+        r.out_row0 = row_offsets[i];
+        if (!fin) {
+            r.pcm_keep = (int32_t)d.pcm_carry(L2, T2);
+            r.pcm_from = (int32_t)(len - r.pcm_keep);
+            r.mel_keep = (int32_t)d.mel_carry(T2, E2);
+            r.mel_from = (int32_t)(mc + r.nf - r.mel_keep);
+            moves = moves || (r.pcm_keep && r.pcm_from) || (r.mel_keep && r.mel_from);
+        }
+        blk.insert(blk.end(), (size_t)((r.nf + 63) / 64), (int)i);
+        eblk.insert(eblk.end(), (size_t)((r.rows + kEmitRows - 1) / kEmitRows), (int)i);
+        row_offsets[i + 1] = row_offsets[i] + r.rows;
+        max_chunk = std::max<int64_t>(max_chunk, lengths[i]);
+        max_nf = std::max<int64_t>(max_nf, r.nf);
+        n_live += r.nf > 0;
+        n_dma += r.nf > 0 && len % 4 == 0 && fe->dev.tile_dma;  // fe_stream_main_kernel's own condition: the regions start 16-byte aligned
+        nl[(size_t)i] = fin ? 0 : L2;   // a final push leaves the stream reset
+        nt[(size_t)i] = fin ? 0 : T2;
+        ne[(size_t)i] = fin ? 0 : E2;
+    }
+    const int64_t total_rows = row_offsets[count];
+    const int64_t pieces = (max_chunk + kAppendPiece - 1) / kAppendPiece;
+    LELE_REQUIRE(count * pieces < (int64_t(1) << 31) && blk.size() < (size_t(1) << 31) && eblk.size() < (size_t(1) << 31),
+                 "frontend_stream_push: %lld streams of up to %lld samples exceed the grid", (long long)count, (long long)max_chunk);
+    LELE_HIP_CHECK(hipSetDevice(ctx->device));
+    ctx->set_route(nullptr);  // lele_hip_last_route: "" when no stream gained a frame
+    LELE_TRY(ctx->arena_reset());
+    const void* dpcm = nullptr;
+    LELE_TRY(ctx->dev_ptr(pcm, &dpcm));
+    // the table changes every push: through the staging arena, not through the exact-keyed seg_tables
+    const size_t rec_bytes = recs.size() * sizeof(FeStreamRec), blk_bytes = blk.size() * sizeof(int), eblk_bytes = eblk.size() * sizeof(int);
+    std::vector<char> blob(rec_bytes + blk_bytes + eblk_bytes);
+    memcpy(blob.data(), recs.data(), rec_bytes);
+    if (blk_bytes) memcpy(blob.data() + rec_bytes, blk.data(), blk_bytes);
+    if (eblk_bytes) memcpy(blob.data() + rec_bytes + blk_bytes, eblk.data(), eblk_bytes);
+    void* dtab = nullptr;
+    LELE_TRY(ctx->arena_alloc(blob.size(), &dtab));
+    void* dmean = nullptr;
+    if (!fe->fast && max_nf) LELE_TRY(ctx->get_scratch((size_t)max_nf * sizeof(float), &dmean));
+    if (total_rows) LELE_TRY(out->reserve((size_t)total_rows * cols * sizeof(float)));
+    LELE_HIP_CHECK(hipMemcpyAsync(dtab, blob.data(), blob.size(), hipMemcpyHostToDevice, ctx->stream));  // (pageable: staged before it returns)
+    const FeStreamRec* drecs = (const FeStreamRec*)dtab;
+    const int* dblk = (const int*)((const char*)dtab + rec_bytes);
+    const int* deblk = (const int*)((const char*)dtab + rec_bytes + blk_bytes);
+    if (pieces)
+        hipLaunchKernelGGL(fe_stream_append_kernel, dim3((unsigned)(count * pieces)), dim3(64), 0, ctx->stream, (const float*)dpcm, drecs, (int)pieces,
+                           st->pcm_state, st->pcm_pitch);
+    if (n_live && !fe->fast) {
+        // generic path: correct, not fast -- the generic kernels once per stream on the same regions (compute_segments does the same)
+        const size_t mark = ctx->arena_used;
+        for (int64_t i = 0; i < count; ++i) {
+            const FeStreamRec& r = recs[(size_t)i];
+            if (r.nf == 0) continue;
+            LELE_TRY(fe_generic(fe, st->pcm_state + i * st->pcm_pitch, 1, (int64_t)r.carry + r.chunk, r.nf, 0, cols,
+                                st->mel_state + i * st->mel_pitch + (int64_t)r.mel_carry * nm, true, dmean));
+            ctx->arena_used = mark;
+        }
+    } else if (n_live) {
+        // lele_hip_last_route: this is the segment kernel's body over the streams' regions, so it reports the segment names
+        ctx->set_route(fe->std_mel ? "fe.seg_std" : "fe.seg_table", n_dma == n_live ? "fe.tile_dma" : n_dma == 0 ? "fe.tile_regs" : "fe.tile_mixed");
+        const size_t mel_lds = (size_t)fe->dev.mel_steps * 16 * sizeof(float);
+#define FE_STREAM_LAUNCH(MODE, STD)                                                                                                \
+    hipLaunchKernelGGL((fe_stream_main_kernel<MODE, STD>), dim3((unsigned)blk.size()), dim3(256), mel_lds, ctx->stream,              \
+                       (const float*)st->pcm_state, st->pcm_pitch, drecs, dblk, fe->dev, st->mel_state, st->mel_pitch)
+        if (fe->dpp_mode == 1) {
+            if (fe->std_mel) FE_STREAM_LAUNCH(1, true); else FE_STREAM_LAUNCH(1, false);
+        } else {
+            if (fe->std_mel) FE_STREAM_LAUNCH(0, true); else FE_STREAM_LAUNCH(0, false);
+        }
+#undef FE_STREAM_LAUNCH
+    }
+    if (total_rows) {
+        if (nm % 4 == 0)
+            hipLaunchKernelGGL(fe_stream_emit_kernel<true>, dim3((unsigned)eblk.size()), dim3(256), 0, ctx->stream, (const float*)st->mel_state,
+                               st->mel_pitch, drecs, deblk, (int)nm, (int)d.m, (int)d.n, (float*)out->data);
+        else
+            hipLaunchKernelGGL(fe_stream_emit_kernel<false>, dim3((unsigned)eblk.size()), dim3(256), 0, ctx->stream, (const float*)st->mel_state,
+                               st->mel_pitch, drecs, deblk, (int)nm, (int)d.m, (int)d.n, (float*)out->data);
+    }
+    if (moves)
+        hipLaunchKernelGGL(fe_stream_compact_kernel, dim3((unsigned)count), dim3(256), 0, ctx->stream, drecs, st->pcm_state, st->pcm_pitch,
+                           st->mel_state, st->mel_pitch, (int)nm);
+    LELE_HIP_CHECK(hipGetLastError());
+    st->samples.swap(nl);
+    st->frames.swap(nt);
+    st->rows.swap(ne);
+    if (total_rows == 0) {  // nothing became final this tick: TensorView::empty()
+        out->bytes = 0;
+        if (out_rank) *out_rank = 0;
+        return 0;
+    }
+    return set_shape(out_shape, out_rank, {total_rows, cols});
 }
 
 int lele_hip_frontend_set_profiling(LeleFrontend* fe, int on) {

@@ -98,6 +98,101 @@ class SenseVoiceFrontend:
         return self._call(_lib.lib().lele_hip_frontend_logmel, pcm, out)
 
 
+def stream_rows(config, samples_before, chunk_len, final=False):
+    """The closed forms of chunked streaming (lele_hip_frontend_stream_rows; host arithmetic, no GPU): pushing chunk_len samples onto a
+    stream that has seen samples_before -> (rows emitted, frames completed, samples carried, log-mel rows carried after the push)."""
+    c = config or FeatureConfig()
+    cfg = _lib.LeleFeatureConfig(c.sample_rate, c.n_mels, c.frame_length_ms, c.frame_shift_ms, c.lfr_m, c.lfr_n)
+    r = [C.c_int64() for _ in range(4)]
+    _lib.check(_lib.lib().lele_hip_frontend_stream_rows(C.byref(cfg), C.c_int64(int(samples_before)), C.c_int64(int(chunk_len)),
+                                                        C.c_int32(1 if final else 0), *[C.byref(v) for v in r]))
+    return tuple(v.value for v in r)
+
+
+class FrontendStream:
+    """`streams` live audio streams fed chunk by chunk through one SenseVoiceFrontend (at most max_chunk samples a stream and push).
+    push() returns every feature row that has become final; concatenated per stream the rows are fe.compute(whole utterance), bit for
+    bit, for any cut of the audio into chunks (include/lele_hip.h, "chunked streaming")."""
+
+    def __init__(self, fe, streams, max_chunk):
+        self.fe, self.streams, self.max_chunk = fe, int(streams), int(max_chunk)
+        self._h = C.c_void_p()
+        _lib.check(_lib.lib().lele_hip_frontend_stream_create(fe._h, C.c_int64(self.streams), C.c_int64(self.max_chunk), C.byref(self._h)))
+        self._out = fe.ctx.buf()
+
+    def close(self):
+        if self._h:
+            _lib.lib().lele_hip_frontend_stream_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def push(self, chunks, final=None, out=None):
+        """chunks: a list of `streams` 1-D arrays (an empty one: no audio this tick), or (pcm, starts, lengths) with pcm f32 [N] on the
+        host or the device and stream i's chunk at pcm[starts[i]:starts[i] + lengths[i]].  final: None or one flag a stream -- the
+        utterance of that stream ends with this chunk: its last rows follow (right clamp) and the stream is reset.
+        -> (TensorView [R, n_mels*lfr_m], row_offsets np.int64 [streams + 1]): the packed layout of compute_segments."""
+        if isinstance(chunks, tuple) and len(chunks) == 3:
+            pcm, starts, lengths = chunks
+            starts = np.ascontiguousarray(starts, np.int64).reshape(-1)
+            lengths = np.ascontiguousarray(lengths, np.int64).reshape(-1)
+        else:
+            pcm, segs = pack(chunks)
+            starts = np.asarray([s for s, _ in segs], np.int64)
+            lengths = np.asarray([e - s for s, e in segs], np.int64)
+        if len(starts) != self.streams or len(lengths) != self.streams:
+            raise _lib.LeleError("FrontendStream.push: %d chunks for %d streams (one entry per stream; an empty chunk for a silent one)"
+                                 % (len(starts), self.streams))
+        fin = None
+        if final is not None:
+            fin = np.ascontiguousarray(np.asarray(final).astype(bool), np.uint8).reshape(-1)
+            if len(fin) != self.streams:
+                raise _lib.LeleError("FrontendStream.push: %d final flags for %d streams" % (len(fin), self.streams))
+        offsets = np.zeros(self.streams + 1, np.int64)
+        keep = []
+        t = _lib.as_tensor(unwrap(pcm), keep)
+        sh = _lib.OutShape()
+        out = out or self._out
+        _lib.check(_lib.lib().lele_hip_frontend_stream_push(
+            self._h, t, _lib.i64_ptr(starts), _lib.i64_ptr(lengths), fin.ctypes.data_as(C.POINTER(C.c_uint8)) if fin is not None else None,
+            out._h, _lib.i64_ptr(offsets), sh.shape, C.byref(sh.rank)))
+        if sh.rank.value == 0:
+            return TensorView.empty(), offsets
+        return TensorView(_lib.DevTensor(out, sh.get(), np.float32)), offsets
+
+    def reset(self, ids=None):
+        """a new utterance in the streams `ids` (None: in all of them); host counters only"""
+        if ids is None:
+            _lib.check(_lib.lib().lele_hip_frontend_stream_reset(self._h, None, C.c_int64(0)))
+        else:
+            a = np.ascontiguousarray(ids, np.int64).reshape(-1)
+            _lib.check(_lib.lib().lele_hip_frontend_stream_reset(self._h, _lib.i64_ptr(a), C.c_int64(len(a))))
+
+    def _counters(self, k):
+        out = np.zeros(self.streams, np.int64)
+        v = [C.c_int64(), C.c_int64(), C.c_int64()]
+        for i in range(self.streams):
+            _lib.check(_lib.lib().lele_hip_frontend_stream_counters(self._h, C.c_int64(i), *[C.byref(x) for x in v]))
+            out[i] = v[k].value
+        return out
+
+    @property
+    def samples_seen(self):
+        return self._counters(0)
+
+    @property
+    def frames_seen(self):
+        return self._counters(1)
+
+    @property
+    def rows_emitted(self):
+        return self._counters(2)
+
+
 def pack(arrays):
     """list of 1-D PCM arrays -> (pcm f32 [sum of lengths], [(start, end)]): one buffer for compute_segments"""
     arrays = [np.asarray(a, np.float32).reshape(-1) for a in arrays]

@@ -1295,9 +1295,69 @@ class SenseVoiceFrontend {  // pipeline.rs:29-193
         return TensorView::from_device(out, sh.vec());
     }
 
+    LeleFrontend* raw() const { return h_; }
+
    private:
     LeleFrontend* h_ = nullptr;
 };
+
+// `streams` live audio streams fed chunk by chunk (lele_hip.h, "chunked streaming"): push() returns every feature row that has become
+// final; per stream the rows concatenate to SenseVoiceFrontend::compute of the whole utterance, bit for bit.  Outlived by its frontend.
+class FrontendStream {
+   public:
+    FrontendStream(const SenseVoiceFrontend& fe, int64_t streams, int64_t max_chunk) : streams_(streams) {
+        check(lele_hip_frontend_stream_create(fe.raw(), streams, max_chunk, &h_));
+    }
+    ~FrontendStream() {
+        if (h_) lele_hip_frontend_stream_destroy(h_);
+    }
+    FrontendStream(const FrontendStream&) = delete;
+    FrontendStream& operator=(const FrontendStream&) = delete;
+    // pcm: f32 [N]; chunks: one (start, end) sample range of it per stream (start == end: no audio this tick); final: empty, or one flag
+    // per stream (the utterance ends with this chunk).  -> the packed [R, n_mels*lfr_m] with offsets (streams + 1, written), the layout
+    // of compute_segments; an empty TensorView when no row became final.
+    TensorView push(const TensorView& pcm, const std::vector<std::pair<int64_t, int64_t>>& chunks, const std::vector<uint8_t>& final, Buffer& out,
+                    std::vector<int64_t>& offsets) {
+        if ((int64_t)chunks.size() != streams_ || (!final.empty() && (int64_t)final.size() != streams_))
+            throw Error("FrontendStream::push: one chunk (and one final flag) per stream");
+        std::vector<int64_t> starts, lengths;
+        for (const auto& s : chunks) {
+            starts.push_back(s.first);
+            lengths.push_back(s.second - s.first);
+        }
+        offsets.assign(chunks.size() + 1, 0);
+        Shape sh;
+        LeleTensor t = pcm.c();
+        check(lele_hip_frontend_stream_push(h_, &t, starts.data(), lengths.data(), final.empty() ? nullptr : final.data(), out.raw(),
+                                            offsets.data(), sh.dims, &sh.rank));
+        if (sh.rank == 0) return TensorView();
+        return TensorView::from_device(out, sh.vec());
+    }
+    void reset() { check(lele_hip_frontend_stream_reset(h_, nullptr, 0)); }
+    void reset(const std::vector<int64_t>& ids) { check(lele_hip_frontend_stream_reset(h_, ids.data(), (int64_t)ids.size())); }
+    struct Counters {
+        int64_t samples, frames, rows;
+    };
+    Counters counters(int64_t id) const {
+        Counters c{0, 0, 0};
+        check(lele_hip_frontend_stream_counters(h_, id, &c.samples, &c.frames, &c.rows));
+        return c;
+    }
+
+   private:
+    LeleFrontendStream* h_ = nullptr;
+    int64_t streams_ = 0;
+};
+// the closed forms of one push (host arithmetic): rows emitted, frames completed, samples and log-mel rows carried after it
+struct StreamRows {
+    int64_t rows, new_frames, pcm_carry, mel_carry;
+};
+inline StreamRows stream_rows(const FeatureConfig& cfg, int64_t samples_before, int64_t chunk_len, bool final) {
+    LeleFeatureConfig c{cfg.sample_rate, cfg.n_mels, cfg.frame_length_ms, cfg.frame_shift_ms, cfg.lfr_m, cfg.lfr_n};
+    StreamRows r{0, 0, 0, 0};
+    check(lele_hip_frontend_stream_rows(&c, samples_before, chunk_len, final ? 1 : 0, &r.rows, &r.new_frames, &r.pcm_carry, &r.mel_carry));
+    return r;
+}
 
 struct Cmvn {  // cmvn.rs
     float eps = 1e-5f;
