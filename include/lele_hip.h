@@ -740,6 +740,65 @@ int lele_hip_ctc_beam_search_segments(LeleCtx* ctx, const LeleTensor* ids, const
                                       int64_t count, int64_t skip_rows, int32_t blank, int32_t beam, int32_t nbest, int64_t width,
                                       LeleBuf* out_tokens, LeleBuf* out_lengths, LeleBuf* out_scores, LeleBuf* out_counts,
                                       int64_t* out_shape, int32_t* out_rank);
+/* The decode head with the log-probabilities of the columns the CALLER names (tokenizer.rs:50-71 behind quantization.rs:77-169), for
+ * forced alignment of a known transcript and for rescoring under the full-vocabulary posterior.  cols is a HOST array of ncols columns,
+ * strictly ascending, every one in [0, N), 1 <= ncols <= N; an error names the offending index.  out_ids and out_logprob are
+ * lele_hip_fused_quantized_linear_argmax_logprob bit for bit (the reported shape is theirs): one call serves greedy decoding and
+ * alignment.  out_at is f32 of that shape plus a trailing axis of ncols: out_at[r, u] = (v[r, cols[u]] - v[r, id_r]) + logprob[r] in
+ * f32, v the result elements of lele_hip_fused_quantized_linear (apply_relu = 0).  That is the formula of slot j of
+ * lele_hip_fused_quantized_linear_topk, so a listed column that is among a row's k best holds the k-best head's log-probability bit for
+ * bit, and the arg-max column holds logprob[r] itself; against the float64 log-soft-max it is within 1.1e-5 + 2^-23 |value| (the scored
+ * head's 1e-5, then two f32 roundings).  The logits are never stored and no buffer of rows x N elements is reserved: the workspace is
+ * the scored head's, rows * ceil(N / 128) * 12 bytes, plus the column -> slot map, 4 N bytes, in the call's layout table.  No atomics,
+ * nothing depends on workgroup order.  A row holding a NaN or +-inf logit is unspecified.  The three buffers must be distinct.  rows ==
+ * 0 gives empty results of the right shape; K == 0 or N == 0 is an error.  Everything, the columns included, is checked before anything
+ * is launched or resized; graph-capturable after one eager run of the same shape AND the same columns (the table is keyed by them). */
+int lele_hip_fused_quantized_linear_logprob_at(LeleCtx* ctx, const LeleTensor* input, const LeleTensor* weight_int8,
+                                               const LeleTensor* weight_scale, const LeleTensor* weight_zero, const LeleTensor* bias_or_null,
+                                               const int32_t* cols, int64_t ncols, LeleBuf* out_ids, LeleBuf* out_logprob, LeleBuf* out_at,
+                                               int64_t* out_shape, int32_t* out_rank);
+/* ... of a packed batch: input f32 [R, K] -> out_ids i32 [R], out_logprob f32 [R], out_at f32 [R, ncols]; the checks and per-segment
+ * range pass of lele_hip_fused_quantized_linear_argmax_segments, so segment i's rows are bit for bit
+ * lele_hip_fused_quantized_linear_logprob_at of input[off[i]:off[i+1]] alone.  The call's ONE layout table holds the offsets, the row ->
+ * segment map and the column -> slot map (8 (count + 1) + 4 R + 4 N bytes), keyed by the layout and the columns.  0-row segments are
+ * skipped.  Graph-capturable after one eager run of the same layout and the same columns. */
+int lele_hip_fused_quantized_linear_logprob_at_segments(LeleCtx* ctx, const LeleTensor* input, const int64_t* row_offsets, int64_t count,
+                                                        const LeleTensor* weight_int8, const LeleTensor* weight_scale,
+                                                        const LeleTensor* weight_zero, const LeleTensor* bias_or_null, const int32_t* cols,
+                                                        int64_t ncols, LeleBuf* out_ids, LeleBuf* out_logprob, LeleBuf* out_at,
+                                                        int64_t* out_shape, int32_t* out_rank);
+/* CTC forced alignment of a known transcript per segment of a packed batch (the consumer of
+ * lele_hip_fused_quantized_linear_logprob_at_segments; lele_amd.apps.ctc_forced_align is the host reference): at f32 [R, U] holds the
+ * log-probabilities of the U = ncols columns cols (host, strictly ascending), row_offsets host [count + 1] from 0 to R.  Segment i's
+ * frames are rows off[i] + skip_rows .. off[i + 1] (none when it has at most skip_rows rows), its transcript the L_i labels
+ * tokens[token_offsets[i] : token_offsets[i + 1]] (host; token_offsets [count + 1] from 0).  Every label and `blank` must be listed in
+ * cols, no label may be the blank, L_i <= 511 (1023 lattice states, 16 a lane of the wavefront): an error names the segment and the
+ * position.  W = width, or with width == 0 the longest transcript, at least 1; a transcript longer than a given width is an error that
+ * names the segment.
+ * The lattice has states s = 0 .. 2 L, even = blank, odd = label (s - 1) / 2.  Viterbi, exactly: alpha_0(0) = e_0(blank), alpha_0(1) =
+ * e_0(label 0), the rest -inf; alpha_t(s) = best + (double)e_t(s), best over alpha_{t-1}(s), alpha_{t-1}(s - 1) and -- for an odd s whose
+ * label differs from the one before it -- alpha_{t-1}(s - 2), a later candidate replacing an earlier one only if strictly greater (stay
+ * wins over step, step over skip); the end is state 2 L unless alpha(2 L - 1) is strictly greater.  All in float64, one addition a
+ * frame: the path score is the float64 sum in frame order of the path's f32 emissions, and the results EQUAL the host function's.
+ * -> out_spans i32 [count, W, 2]: first and last row of label j within its segment (prompt rows counted, as the frames of
+ * lele_hip_token_align_segments), unused slots -1; out_scores f32 [count, W] (the reported shape): the float64 sum in frame order of
+ * label j's emissions over its span, rounded once, unused slots 0.0; out_path f32 [count]: the path score rounded once; out_ok i32
+ * [count]: 1, or 0 when no alignment exists (fewer frames than L + the number of adjacent equal labels, or a best end of -inf): then
+ * spans -1, scores 0.0, path and total -inf.  A segment without frames and with an empty transcript is ok, its scores +0.0.
+ * out_total_or_null f32 [count]: the log of the summed probability of ALL alignments of the transcript (the CTC likelihood), the same
+ * recurrence with a float64 logaddexp paired ((stay + step) + skip) in the same pass; without it the kernel does not compute it.  It
+ * passes through exp / log1p: within 2^-24 |total| + 40 T 2^-53 max(1, largest |alpha|) of the host function's float64.
+ * Workspace: the back-pointers, 2 bits a state a frame, 64 words of 2 SPL bits a frame with SPL = 4 states a lane while every transcript
+ * has at most 127 labels, else 16: 16 SPL * (most frames of a segment) bytes a segment -- in LDS while that is at most 56 KiB (896 frames
+ * at SPL 4, 224 at SPL 16), beyond it count times as much of the context's scratch block.  The call's one layout table holds the
+ * offsets, the token offsets and the labels' slots, keyed by all three.  The output buffers must be distinct.  NaN or +inf emissions:
+ * unspecified, but the call terminates and stays inside its buffers.  A dense [B, T, U] batch is the packed layout with off[i] = i * T:
+ * there is no dense twin.  Everything is checked before anything is launched or resized; count == 0 and R == 0 give empty results of
+ * the right shape.  Graph-capturable after one eager run of the same layout and transcripts. */
+int lele_hip_ctc_align_segments(LeleCtx* ctx, const LeleTensor* at, const int32_t* cols, int64_t ncols, const int64_t* row_offsets,
+                                int64_t count, int64_t skip_rows, int32_t blank, const int32_t* tokens, const int64_t* token_offsets,
+                                int64_t width, LeleBuf* out_spans, LeleBuf* out_scores, LeleBuf* out_path, LeleBuf* out_total_or_null,
+                                LeleBuf* out_ok, int64_t* out_shape, int32_t* out_rank);
 /* lele_hip_attention_view per segment: qkv f32 [R, P] holds Q, K, V of `heads` heads of width dh at columns q_offset, k_offset,
  * v_offset (head h at + h * dh); for every segment and head softmax(Q K^T * scale) V over THAT SEGMENT's rows only, queries and keys
  * alike (gemm.rs:112-222, norm.rs:8) -> out [R, heads * dh], heads merged.  Supported: dh == 128, every segment <= 512 rows, q_offset,

@@ -9,6 +9,8 @@ The device halves are in csrc/app.hip (`kernels.wav_to_f32`, `argmax_last`, `tok
   * `token_times`         -- encoder frames of kept tokens (kernels.token_align_segments) -> start times in seconds
   * `ctc_prefix_beam_search` -- the reference of kernels.ctc_beam_search_segments, one utterance on the host
   * `beam_results`        -- that kernel's four arrays -> the reference's list format
+  * `ctc_forced_align`    -- the reference of kernels.ctc_align_segments: a known transcript's Viterbi alignment and CTC likelihood
+  * `align_results`       -- that kernel's five arrays -> the reference's format
 """
 import numpy as np
 
@@ -86,6 +88,128 @@ def beam_results(tokens, lengths, scores, counts):
         raise ValueError("beam_results: tokens [count, nbest, W], lengths / scores [count, nbest] and counts [count] required")
     return [[(tuple(int(v) for v in tokens[i, n, :int(lengths[i, n])]), float(scores[i, n])) for n in range(int(counts[i]))]
             for i in range(tokens.shape[0])]
+
+
+def ctc_forced_align(logprob_at, cols, tokens, blank=0, skip_rows=0, return_bound=False):
+    """CTC forced alignment of a known transcript for ONE utterance: logprob_at float32 [rows, U], the log-probabilities of the U
+    strictly ascending columns `cols` as kernels.fused_quantized_linear_logprob_at gives them; the frames are the rows behind the first
+    `skip_rows`; `tokens` the transcript's L labels (every one and `blank` listed in cols, none the blank, L <= 511)
+    -> (ok, spans, token_scores, path_score, total): spans [(first, last)] the rows (within logprob_at, prompt rows counted) of every
+    label on the best path, token_scores the float64 sum in frame order of the label's emissions over its span, path_score the best
+    path's, total the log of the summed probability of ALL alignments (the CTC likelihood).  Without an alignment -- fewer frames than L
+    + the number of adjacent equal labels, or a best end of -inf -- (False, [], [], -inf, -inf); no frames and no labels is (True, [],
+    [], 0.0, 0.0).
+    The lattice has states s = 0 .. 2 L, even = blank, odd = label (s - 1) / 2; alpha_0(0) = e_0(blank), alpha_0(1) = e_0(label 0);
+    alpha_t(s) = best + e_t(s) with best over alpha_{t-1}(s) (stay), (s - 1) (step) and, for an odd s whose label differs from the one
+    before it, (s - 2) (skip), a later candidate replacing an earlier one only if strictly greater; the end is state 2 L unless 2 L - 1 is
+    strictly greater.  float64 with one addition a frame, so the path score is the sum in frame order of the path's float32 emissions:
+    the device kernel performs the same IEEE additions, its spans and scores are EQUAL to these.  The total is the same recurrence with
+    logaddexp paired ((stay, step), skip).  return_bound appends the largest finite |alpha| either recurrence met (what a tolerance on
+    the total is stated in).  Pure host code."""
+    e32 = np.asarray(logprob_at, np.float32)
+    cols = np.asarray(cols, np.int64).reshape(-1)
+    if e32.ndim != 2 or e32.shape[1] != len(cols) or len(cols) < 1:
+        raise ValueError("ctc_forced_align: logprob_at must be [rows, U] with one column per entry of cols")
+    if np.any(cols[1:] <= cols[:-1]):
+        raise ValueError("ctc_forced_align: cols must be strictly ascending")
+    tokens = [int(t) for t in tokens]
+    n = len(tokens)
+    if n > 511:
+        raise ValueError("ctc_forced_align: a transcript of %d labels, more than 511" % n)
+
+    def slot(c, what):
+        i = int(np.searchsorted(cols, c))
+        if i >= len(cols) or int(cols[i]) != c:
+            raise ValueError("ctc_forced_align: %s %d is not among the listed columns" % (what, c))
+        return i
+
+    bslot = slot(int(blank), "blank")
+    for j, t in enumerate(tokens):
+        if t == int(blank):
+            raise ValueError("ctc_forced_align: position %d: the label is the blank (%d)" % (j, t))
+    slots = [slot(t, "position %d: label" % j) for j, t in enumerate(tokens)]
+    ninf = -np.inf
+    fail = (False, [], [], ninf, ninf)
+    bound = 0.0
+
+    def done(res):
+        return res + (bound,) if return_bound else res
+
+    frames = e32[int(skip_rows):]
+    nt, ns = frames.shape[0], 2 * n + 1
+    if nt == 0:
+        return done((True, [], [], 0.0, 0.0) if n == 0 else fail)
+    state_slot = np.full(ns, bslot, np.int64)
+    state_slot[1::2] = slots
+    allowed = np.zeros(ns, bool)
+    for j in range(1, n):
+        allowed[2 * j + 1] = tokens[j] != tokens[j - 1]
+    em = frames[:, state_slot].astype(np.float64)
+    a = np.full(ns, ninf)
+    a[0] = em[0, 0]
+    if n:
+        a[1] = em[0, 1]
+    tot = a.copy()
+    back = np.zeros((nt, ns), np.uint8)
+
+    def finite_max(x):
+        f = np.abs(x[np.isfinite(x)])
+        return float(f.max()) if f.size else 0.0
+
+    bound = max(finite_max(a), 0.0)
+    for t in range(1, nt):
+        p = np.concatenate(([ninf, ninf], a))
+        step, skip = p[1:-1], np.where(allowed, p[:-2], ninf)
+        best, frm = a.copy(), np.zeros(ns, np.uint8)
+        m = step > best
+        best[m], frm[m] = step[m], 1
+        m = skip > best
+        best[m], frm[m] = skip[m], 2
+        a = best + em[t]
+        back[t] = frm
+        p = np.concatenate(([ninf, ninf], tot))
+        tot = np.logaddexp(np.logaddexp(tot, p[1:-1]), np.where(allowed, p[:-2], ninf)) + em[t]
+        bound = max(bound, finite_max(a), finite_max(tot))
+    repeats = sum(1 for j in range(1, n) if tokens[j] == tokens[j - 1])
+    s = 2 * n if n == 0 or a[2 * n] >= a[2 * n - 1] else 2 * n - 1
+    if nt < n + repeats or a[s] == ninf:
+        return done(fail)
+    path_score = float(a[s])
+    total = float(np.logaddexp(tot[2 * n], tot[2 * n - 1])) if n else float(tot[0])
+    first, last = [0] * n, [-1] * n
+    prev = -1
+    for t in range(nt - 1, -1, -1):
+        if s & 1:
+            if s != prev:
+                last[s >> 1] = t
+            first[s >> 1] = t
+        prev = s
+        s -= int(back[t, s])
+    scores = []
+    for j in range(n):
+        acc = 0.0
+        for t in range(first[j], last[j] + 1):
+            acc += float(em[t, 2 * j + 1])
+        scores.append(acc)
+    k = int(skip_rows)
+    return done((True, [(first[j] + k, last[j] + k) for j in range(n)], scores, path_score, total))
+
+
+def align_results(spans, scores, path, total, ok, lengths):
+    """the five host arrays of kernels.ctc_align_segments (spans [count, W, 2], scores [count, W], path / total / ok [count]; total may
+    be None) and the transcripts' lengths -> per utterance what ctc_forced_align returns, the scores as the float32 values the kernel
+    rounded them to: (ok, [(first, last)], [score], path score, total or None)"""
+    spans, scores, path, ok = np.asarray(spans), np.asarray(scores), np.asarray(path), np.asarray(ok)
+    total = None if total is None else np.asarray(total)
+    if spans.ndim != 3 or spans.shape[2] != 2 or scores.shape != spans.shape[:2] or path.shape != spans.shape[:1] or \
+            ok.shape != spans.shape[:1] or (total is not None and total.shape != spans.shape[:1]) or len(lengths) != spans.shape[0]:
+        raise ValueError("align_results: spans [count, W, 2], scores [count, W], path / total / ok [count] and count lengths required")
+    out = []
+    for i, n in enumerate(lengths):
+        n = int(n) if ok[i] else 0
+        out.append((bool(ok[i]), [(int(spans[i, j, 0]), int(spans[i, j, 1])) for j in range(n)], [float(scores[i, j]) for j in range(n)],
+                    float(path[i]), None if total is None else float(total[i])))
+    return out
 
 
 def _ms_to_samples(ms, sample_rate):

@@ -9,6 +9,8 @@
 //   lele_hip_token_align_segments  <- ... and with every kept id its frame within the segment and its score
 //   lele_hip_ctc_beam_search_segments <- apps.ctc_prefix_beam_search per segment of a packed batch of k-best candidates (no upstream
 //                             counterpart: the reference decodes greedily); float64, one wavefront a segment
+//   lele_hip_ctc_align_segments <- apps.ctc_forced_align per segment of a packed batch of listed-column log-probabilities (no upstream
+//                             counterpart); Viterbi and the CTC likelihood in float64, one wavefront a segment
 //   lele_hip_image_preprocess   <-/root/reference/examples/yolo26n-seg/src/image.rs:62-111 (PIL-style nearest resize to
 //                             target x target, HWC u8 -> CHW f32 / 255)
 //   lele_hip_yolo_seg_postprocess <- image.rs:127-265 (score / box filter in query order, box rescale, per-detection mask =
@@ -474,6 +476,169 @@ __global__ __launch_bounds__(64) void ctc_beam_seg_kernel(const int32_t* __restr
     }
 }
 
+// ---- CTC forced alignment of a known transcript (apps.ctc_forced_align on the device) ---------------------------------------------
+// The lattice of a transcript of L labels has states s = 0 .. 2 L, even = blank, odd = label (s - 1) / 2.  One wavefront a segment:
+// lane l owns the SPL states [SPL l, SPL l + SPL) in registers, float64.  A frame is, per state from the lane's last down to its first
+// (in place: a state's predecessors are the ones below it, not yet overwritten),
+//     best = stay;  if (step > best) best = step;  if (skip allowed && skip > best) best = skip;      alpha = best + (double)emission
+// a skip being allowed into an odd state whose label differs from the label before it.  SPL is even, so a lane's first state is a blank
+// (no skip into it) and its second an odd one: the ONE value that crosses the lane boundary is lane l - 1's last state, which is the
+// first state's step and the second state's skip (one 64-bit move up the wave a frame).  The choice made, 0 / 1 / 2 = how far down the
+// predecessor is, is the state's back-pointer: 2 bits a state, one word of 2 SPL bits a lane a frame, 64 words a frame whatever the
+// transcript's length -- 16 SPL bytes a frame; the words of a segment's frames live in LDS while the longest segment's fit
+// kAlignLdsBytes, else in the context's scratch block (16 SPL * most frames of a segment bytes a segment).
+// TOTAL: beside alpha the same recurrence with logaddexp64 for the maximum, paired ((stay + step) + skip): the CTC likelihood.
+// The next frame's emissions (the blank's and the lane's SPL / 2 labels') are requested before this frame's maxima are taken.
+// Lane 0 then walks the back-pointers from the better end state (2 L unless 2 L - 1 is strictly greater) and notes every label's first
+// and last frame; the lanes share the labels for the per-token scores: the float64 sum of the label's emissions over its span in frame
+// order, as the path score (alpha itself) is the sum of the path's emissions in frame order.
+constexpr int64_t kAlignLdsBytes = 56 * 1024;
+
+extern __shared__ unsigned char align_bp_lds[];
+
+template <int SPL, bool TOTAL, bool LDS_BP>
+__global__ __launch_bounds__(64) void ctc_align_seg_kernel(const float* __restrict__ at, int64_t u, const int64_t* __restrict__ off,
+                                                           const int64_t* __restrict__ tok_off, const int32_t* __restrict__ slots, int bslot,
+                                                           int64_t skip_rows, int64_t w, int64_t bp_stride, unsigned char* bp_all,
+                                                           int32_t* __restrict__ out_spans, float* __restrict__ out_scores,
+                                                           float* __restrict__ out_path, float* __restrict__ out_total,
+                                                           int32_t* __restrict__ out_ok) {
+    static_assert(SPL == 4 || SPL == 16, "a lane's back-pointers of a frame are one byte or one 32-bit word");
+    using Word = typename std::conditional<SPL == 16, uint32_t, uint8_t>::type;
+    constexpr int HALF = SPL / 2;
+    const int64_t seg = blockIdx.x;
+    const int lane = threadIdx.x;
+    const int64_t r0 = off[seg] + skip_rows, r1 = off[seg + 1];
+    const int frames = r1 > r0 ? (int)(r1 - r0) : 0;
+    const int64_t tk0 = tok_off[seg];
+    const int len = (int)(tok_off[seg + 1] - tk0), nstates = 2 * len + 1;
+    Word* const bp = reinterpret_cast<Word*>(LDS_BP ? align_bp_lds : bp_all + seg * bp_stride);
+    __shared__ double s_end[4];  // alpha(2 L), alpha(2 L - 1), and the totals there
+    __shared__ int s_first[512], s_last[512], s_ok;
+    for (int64_t j = lane; j < w; j += 64) {
+        out_spans[(seg * w + j) * 2] = -1;
+        out_spans[(seg * w + j) * 2 + 1] = -1;
+        out_scores[seg * w + j] = 0.0f;
+    }
+    for (int j = lane; j < len; j += 64) s_first[j] = 0, s_last[j] = -1;  // an empty span until the walk finds the label
+    // the lane's labels as slots of `at` (a state past the last: the blank's, loaded and never used) and where a skip is allowed
+    int slot[HALF];
+    unsigned skip_ok = 0;
+#pragma unroll
+    for (int k = 0; k < HALF; ++k) {
+        const int j = HALF * lane + k;
+        slot[k] = j < len ? slots[tk0 + j] : bslot;
+        if (j >= 1 && j < len && slots[tk0 + j - 1] != slot[k]) skip_ok |= 1u << k;
+    }
+    double a[SPL], tot[TOTAL ? SPL : 1];
+#pragma unroll
+    for (int i = 0; i < SPL; ++i) a[i] = -INFINITY;
+#pragma unroll
+    for (int i = 0; i < (TOTAL ? SPL : 1); ++i) tot[i] = -INFINITY;
+    float eb_next = 0.0f, e_next[HALF];
+    auto request = [&](int t) {
+        const float* row = at + (r0 + t) * u;
+        eb_next = row[bslot];
+#pragma unroll
+        for (int k = 0; k < HALF; ++k) e_next[k] = row[slot[k]];
+    };
+    if (frames > 0) request(0);
+    for (int t = 0; t < frames; ++t) {
+        const float eb = eb_next;
+        float e[HALF];
+#pragma unroll
+        for (int k = 0; k < HALF; ++k) e[k] = e_next[k];
+        if (t + 1 < frames) request(t + 1);
+        unsigned word = 0;
+        if (t == 0) {
+            if (lane == 0) {
+                a[0] = (double)eb;
+                if (len >= 1) a[1] = (double)e[0];
+                if (TOTAL) {
+                    tot[0] = a[0];
+                    if (len >= 1) tot[1] = a[1];
+                }
+            }
+        } else {
+            const double up_a = __shfl_up(a[SPL - 1], 1);
+            const double below = lane == 0 ? -INFINITY : up_a;
+            double below_tot = -INFINITY;
+            if (TOTAL) {
+                const double up_t = __shfl_up(tot[SPL - 1], 1);
+                below_tot = lane == 0 ? -INFINITY : up_t;
+            }
+#pragma unroll
+            for (int i = SPL - 1; i >= 0; --i) {
+                const bool odd = (i & 1) != 0;
+                const bool live = SPL * lane + i < nstates;
+                const bool skip = odd && ((skip_ok >> (i >> 1)) & 1u);
+                const double em = (double)(odd ? e[i >> 1] : eb);
+                const double step = i >= 1 ? a[i - 1] : below;
+                const double far = i >= 2 ? a[i - 2] : below;  // (read for odd i only: i >= 1)
+                double best = a[i];
+                unsigned from = 0;
+                if (step > best) best = step, from = 1;
+                if (skip && far > best) best = far, from = 2;
+                a[i] = live ? best + em : -INFINITY;
+                word |= from << (2 * i);
+                if (TOTAL) {
+                    const double step_t = i >= 1 ? tot[i - 1] : below_tot;
+                    const double far_t = i >= 2 ? tot[i - 2] : below_tot;
+                    double sum = logaddexp64(tot[i], step_t);
+                    if (skip) sum = logaddexp64(sum, far_t);
+                    tot[i] = live ? sum + em : -INFINITY;
+                }
+            }
+        }
+        bp[(int64_t)t * 64 + lane] = (Word)word;
+    }
+#pragma unroll
+    for (int i = 0; i < SPL; ++i) {
+        const int s = SPL * lane + i;
+        if (s == 2 * len) s_end[0] = a[i];
+        if (s == 2 * len - 1) s_end[1] = a[i];
+        if (TOTAL && s == 2 * len) s_end[2] = tot[i];
+        if (TOTAL && s == 2 * len - 1) s_end[3] = tot[i];
+    }
+    __syncthreads();  // s_end and the back-pointers (LDS or global) of every lane
+    if (lane == 0) {
+        const double x2 = s_end[0], x1 = len ? s_end[1] : -INFINITY;
+        int s = (len == 0 || x2 >= x1) ? 2 * len : 2 * len - 1;
+        const double best = frames == 0 ? (len == 0 ? 0.0 : -INFINITY) : s == 2 * len ? x2 : x1;
+        const int ok = best != -INFINITY;
+        s_ok = ok;
+        out_ok[seg] = ok;
+        out_path[seg] = (float)best;
+        if (TOTAL) {
+            double total = frames == 0 ? (len == 0 ? 0.0 : -INFINITY) : len ? logaddexp64(s_end[2], s_end[3]) : s_end[2];
+            out_total[seg] = ok ? (float)total : -INFINITY;
+        }
+        if (ok) {
+            int prev = -1;
+            for (int t = frames - 1; t >= 0 && s >= 0; --t) {  // (s < 0: emissions that are no log-probabilities, NaN or +inf)
+                if (s & 1) {
+                    if (s != prev) s_last[s >> 1] = t;
+                    s_first[s >> 1] = t;
+                }
+                prev = s;
+                const unsigned wd = bp[(int64_t)t * 64 + s / SPL];
+                s -= (int)((wd >> (2 * (s % SPL))) & 3u);
+            }
+        }
+    }
+    __syncthreads();
+    if (!s_ok) return;
+    for (int j = lane; j < len; j += 64) {
+        const int first = s_first[j], last = s_last[j];
+        const float* col = at + r0 * u + slots[tk0 + j];
+        double sum = 0.0;
+        for (int t = first; t <= last; ++t) sum += (double)col[(int64_t)t * u];
+        out_spans[(seg * w + j) * 2] = (int32_t)(first + skip_rows);
+        out_spans[(seg * w + j) * 2 + 1] = (int32_t)(last + skip_rows);
+        out_scores[seg * w + j] = (float)sum;
+    }
+}
+
 // image.rs:84-105 + 69-79: dst(y, x) <-src(min(floor((y + 0.5) * H / T), H - 1), min(floor((x + 0.5) * W / T), W - 1)) / 255
 __global__ void image_preprocess_kernel(const uint8_t* __restrict__ rgb, int h, int w, int target, float* __restrict__ out) {
     const int total = target * target;
@@ -778,6 +943,116 @@ int lele_hip_ctc_beam_search_segments(LeleCtx* ctx, const LeleTensor* ids, const
         LELE_HIP_CHECK(hipGetLastError());
     }
     return set_shape(out_shape, out_rank, {count, (int64_t)nbest, w});
+}
+
+namespace {
+// the aligner's one table: [int64 off[count + 1]][int64 tok_off[count + 1]][int slot[labels]], a label's slot its place in `cols`
+struct AlignTableArg {
+    const int64_t *off, *tok_off;
+    int64_t count;
+    const std::vector<int32_t>* slots;
+};
+void build_align_table(const void* arg, std::vector<char>& blob) {
+    const AlignTableArg& a = *(const AlignTableArg*)arg;
+    const size_t ob = (size_t)(a.count + 1) * 8;
+    blob.resize(2 * ob + a.slots->size() * 4);
+    memcpy(blob.data(), a.off, ob);
+    memcpy(blob.data() + ob, a.tok_off, ob);
+    if (!a.slots->empty()) memcpy(blob.data() + 2 * ob, a.slots->data(), a.slots->size() * 4);
+}
+// a column's slot in the strictly ascending cols[ncols], or -1
+int64_t align_slot(const int32_t* cols, int64_t ncols, int32_t col) {
+    const int32_t* p = std::lower_bound(cols, cols + ncols, col);
+    return p != cols + ncols && *p == col ? p - cols : -1;
+}
+}  // namespace
+
+int lele_hip_ctc_align_segments(LeleCtx* ctx, const LeleTensor* at, const int32_t* cols, int64_t ncols, const int64_t* row_offsets, int64_t count,
+                                int64_t skip_rows, int32_t blank, const int32_t* tokens, const int64_t* token_offsets, int64_t width,
+                                LeleBuf* out_spans, LeleBuf* out_scores, LeleBuf* out_path, LeleBuf* out_total, LeleBuf* out_ok, int64_t* out_shape,
+                                int32_t* out_rank) {
+    LELE_REQUIRE(ctx && at && cols && out_spans && out_scores && out_path && out_ok, "ctc_align_segments: NULL argument");
+    LeleBuf* const outs[5] = {out_spans, out_scores, out_path, out_ok, out_total};
+    for (int i = 0; i < 5; ++i)
+        for (int j = i + 1; j < 5; ++j) LELE_REQUIRE(!outs[j] || outs[i] != outs[j], "ctc_align_segments: the output buffers must be distinct");
+    LELE_REQUIRE(at->dtype == LELE_F32 && at->rank == 2 && ncols >= 1 && at->shape[1] == ncols,
+                 "ctc_align_segments: at must be f32 [R, U] with U = ncols = %lld columns", (long long)ncols);
+    const int64_t rows = at->shape[0];
+    for (int64_t c = 0; c < ncols; ++c)
+        LELE_REQUIRE(cols[c] >= 0 && (c == 0 || cols[c] > cols[c - 1]), "ctc_align_segments: cols[%lld] = %d (strictly ascending, >= 0 required)",
+                     (long long)c, (int)cols[c]);
+    LELE_REQUIRE(skip_rows >= 0 && width >= 0, "ctc_align_segments: negative skip_rows or width");
+    LELE_REQUIRE(count >= 0 && row_offsets && token_offsets, "ctc_align_segments: bad row_offsets or token_offsets (count %lld)", (long long)count);
+    LELE_REQUIRE(row_offsets[0] == 0 && row_offsets[count] == rows, "ctc_align_segments: row_offsets must run from 0 to R = %lld (got %lld .. %lld)",
+                 (long long)rows, (long long)row_offsets[0], (long long)row_offsets[count]);
+    LELE_REQUIRE(token_offsets[0] == 0, "ctc_align_segments: token_offsets must start at 0 (got %lld)", (long long)token_offsets[0]);
+    const int64_t bslot = align_slot(cols, ncols, blank);
+    LELE_REQUIRE(bslot >= 0, "ctc_align_segments: blank = %d is not among the %lld listed columns", (int)blank, (long long)ncols);
+    int64_t tmax = 0, lmax = 0;
+    for (int64_t i = 0; i < count; ++i) {
+        const int64_t len = row_offsets[i + 1] - row_offsets[i], labels = token_offsets[i + 1] - token_offsets[i];
+        LELE_REQUIRE(len >= 0, "ctc_align_segments: row_offsets decrease at segment %lld", (long long)i);
+        LELE_REQUIRE(labels >= 0, "ctc_align_segments: token_offsets decrease at segment %lld", (long long)i);
+        LELE_REQUIRE(labels <= 511, "ctc_align_segments: segment %lld has a transcript of %lld labels, more than 511", (long long)i, (long long)labels);
+        LELE_REQUIRE(width == 0 || labels <= width, "ctc_align_segments: segment %lld has a transcript of %lld labels, more than width = %lld",
+                     (long long)i, (long long)labels, (long long)width);
+        tmax = std::max(tmax, std::max<int64_t>(len - skip_rows, 0));
+        lmax = std::max(lmax, labels);
+    }
+    const int64_t total_labels = token_offsets[count];
+    LELE_REQUIRE(total_labels == 0 || tokens, "ctc_align_segments: NULL tokens");
+    std::vector<int32_t> slots((size_t)total_labels);
+    for (int64_t i = 0; i < count; ++i)
+        for (int64_t j = token_offsets[i]; j < token_offsets[i + 1]; ++j) {
+            LELE_REQUIRE(tokens[j] != blank, "ctc_align_segments: segment %lld, position %lld: the label is the blank (%d)", (long long)i,
+                         (long long)(j - token_offsets[i]), (int)blank);
+            const int64_t s = align_slot(cols, ncols, tokens[j]);
+            LELE_REQUIRE(s >= 0, "ctc_align_segments: segment %lld, position %lld: label %d is not among the listed columns", (long long)i,
+                         (long long)(j - token_offsets[i]), (int)tokens[j]);
+            slots[(size_t)j] = (int32_t)s;
+        }
+    const int64_t w = width ? width : std::max<int64_t>(lmax, 1);
+    LELE_REQUIRE(count < (int64_t(1) << 31) && tmax < (int64_t(1) << 27), "ctc_align_segments: more than 2^31 segments, or a segment of 2^27 frames");
+    LELE_HIP_CHECK(hipSetDevice(ctx->device));
+    const void* tab = nullptr;
+    if (count > 0) {
+        // keyed by the layout, the transcripts' lengths and their slots
+        std::vector<int64_t> key(row_offsets, row_offsets + count + 1);
+        key.insert(key.end(), token_offsets, token_offsets + count + 1);
+        key.insert(key.end(), slots.begin(), slots.end());
+        const AlignTableArg arg{row_offsets, token_offsets, count, &slots};
+        LELE_TRY(layout_table(ctx, "calg", count, 0, key.data(), (int64_t)key.size() - 1, build_align_table, &arg, &tab));
+    }
+    LELE_TRY(ctx->arena_reset());
+    const void* da = nullptr;
+    if (rows > 0) LELE_TRY(ctx->dev_ptr(at, &da));
+    // back-pointers: 2 bits a state, a lane's SPL states of a frame one word, 64 words a frame: 16 SPL bytes a frame.  4 states a lane
+    // while every transcript fits them (L <= 127), else 16.
+    const int spl = lmax <= 127 ? 4 : 16;
+    const int64_t bp_stride = std::max<int64_t>(tmax, 1) * 16 * spl;
+    const bool lds_bp = bp_stride <= kAlignLdsBytes;
+    void* bp = nullptr;
+    if (count > 0 && !lds_bp) LELE_TRY(ctx->get_scratch((size_t)(count * bp_stride), &bp));
+    const size_t cells = (size_t)std::max<int64_t>(count * w, 1) * 4, segs = (size_t)std::max<int64_t>(count, 1) * 4;
+    LELE_TRY(out_spans->reserve(2 * cells));
+    LELE_TRY(out_scores->reserve(cells));
+    LELE_TRY(out_path->reserve(segs));
+    if (out_total) LELE_TRY(out_total->reserve(segs));
+    LELE_TRY(out_ok->reserve(segs));
+    if (count > 0) {
+        const int which = (spl == 16 ? 4 : 0) + (out_total ? 2 : 0) + (lds_bp ? 1 : 0);
+        using Kernel = decltype(&ctc_align_seg_kernel<4, false, false>);
+        static const Kernel kernels[8] = {ctc_align_seg_kernel<4, false, false>,  ctc_align_seg_kernel<4, false, true>,  ctc_align_seg_kernel<4, true, false>,
+                                     ctc_align_seg_kernel<4, true, true>,    ctc_align_seg_kernel<16, false, false>, ctc_align_seg_kernel<16, false, true>,
+                                     ctc_align_seg_kernel<16, true, false>,  ctc_align_seg_kernel<16, true, true>};
+        const size_t ob = (size_t)(count + 1) * 8;
+        hipLaunchKernelGGL(kernels[which], dim3((unsigned)count), dim3(64), lds_bp ? (size_t)bp_stride : 0, ctx->stream, (const float*)da, ncols,
+                           (const int64_t*)tab, (const int64_t*)((const char*)tab + ob), (const int32_t*)((const char*)tab + 2 * ob), (int)bslot,
+                           skip_rows, w, bp_stride, (unsigned char*)bp, (int32_t*)out_spans->data, (float*)out_scores->data, (float*)out_path->data,
+                           out_total ? (float*)out_total->data : (float*)nullptr, (int32_t*)out_ok->data);
+        LELE_HIP_CHECK(hipGetLastError());
+    }
+    return set_shape(out_shape, out_rank, {count, w});
 }
 
 int lele_hip_image_preprocess(LeleCtx* ctx, const LeleTensor* rgb, int32_t target, LeleBuf* out, int64_t* out_shape,

@@ -14,6 +14,9 @@
 //                       epi.arg_keys[tile][j][row]; a column that has won a row takes no part in that row from then on (masked by COLUMN
 //                       -- the lane clears its own key word of that row: equal values in other columns stay candidates), and a round that
 //                       finds nothing left stores key 0.  Round 0 is EM 3's key, the sums are EM 4's, taken behind round 0.
+//   EM 6 (Head::At)     lele_hip_fused_quantized_linear_logprob_at: EM 4, and a lane whose column the caller listed (epi.at_slot()[column] >= 0)
+//                       stores the logits it holds of the tile's rows, raw, to epi.at_out()[row][slot]; the finish kernel, which knows the
+//                       row's maximum and its log-probability, rewrites them in place as (x - maximum) + logprob -- MODE 5's slot j.
 // The contracts between the heads -- scored ids are the ids-only head's, slot 0 of the k best is the scored head bit for bit -- hold
 // because every step below exists once: the three modes are three instantiations of the same fold, join, sums and finish.
 #pragma once
@@ -133,7 +136,8 @@ __device__ __forceinline__ void head_epilogue(const IgemmEpi& epi, const v16i (&
                                               int tid, int wm, int wn, unsigned tx, int64_t m0, int64_t rows, int n) {
     constexpr int NT = WM * WN * 64;
     static_assert(TMT == 2, "half_wave_fold folds 32 rows a lane onto the 32 lanes of a half-wave");
-    static_assert(EM == 3 || (TNT == 1 && NT >= BM), "EM 4 / 5: one column a lane, one thread a row in the joins");
+    static_assert(EM == 3 || (TNT == 1 && NT >= BM), "EM 4 / 5 / 6: one column a lane, one thread a row in the joins");
+    constexpr bool SUMS = EM == 4 || EM == 6;  // EM 6 is EM 4 with the listed columns' values stored behind it
     const HeadPos p{tid, tid & 63, wm, wn, tx, m0, rows, (int)(rows - m0 < BM ? rows - m0 : BM)};
     const int hv = p.hv(), rows_here = p.rows_here;
     auto value = [&](int i, int j, int r) {
@@ -181,7 +185,7 @@ __device__ __forceinline__ void head_epilogue(const IgemmEpi& epi, const v16i (&
                     kb[i * 16 + r] = s_win[acc_row<TMT>(wm, hv, i, r)] == (unsigned)cols[0] ? 0u : kb[i * 16 + r];
         }
     } else {
-        float val[EM == 4 ? TMT * 16 : 1];  // EM 4: the lane's 32 logits, kept for the sums
+        float val[SUMS ? TMT * 16 : 1];  // EM 4 / 6: the lane's 32 logits, kept for the sums
         // a lane holds 32 rows x TNT columns: its best key per row over its own valid columns (a padded column's context is the clamped
         // column's, so it is masked to 0, below every real key)
         unsigned long long key[TMT * 16];
@@ -193,7 +197,7 @@ __device__ __forceinline__ void head_epilogue(const IgemmEpi& epi, const v16i (&
 #pragma unroll
                 for (int j = 0; j < TNT; ++j) {
                     const float v = value(i, j, r);
-                    if constexpr (EM == 4) val[i * 16 + r] = v;
+                    if constexpr (SUMS) val[i * 16 + r] = v;
                     const unsigned long long kj = argmax_key(v, cols[j]);
                     best = max(best, cols[j] < n ? kj : 0ull);
                 }
@@ -202,7 +206,7 @@ __device__ __forceinline__ void head_epilogue(const IgemmEpi& epi, const v16i (&
         // across the WN waves in the K loop's LDS, then one store per row of the tile
         s_key[wn * BM + mine] = half_wave_fold<unsigned long long>(p.lane, HeadMax(), [&](int t) { return key[t]; });
         __syncthreads();
-        if constexpr (EM == 4) {
+        if constexpr (SUMS) {
             if (tid < BM) {  // rows past the last are the last row again (clamped context): computed, never stored
                 const unsigned long long best = wave_join<BM, WN>(s_key, tid, HeadMax());
                 if (tid < rows_here) epi.arg_keys[(int64_t)tx * rows + m0 + tid] = best;
@@ -210,6 +214,19 @@ __device__ __forceinline__ void head_epilogue(const IgemmEpi& epi, const v16i (&
             }
             __syncthreads();
             tile_sums<BM, WN, TMT>(epi, p, cols[0] < n, s_max, s_sum, [&](int t) { return val[t]; });
+            if constexpr (EM == 6) {  // a listed column: the lane's values of the tile's real rows, each to its row's slot
+                const int slot = cols[0] < n ? epi.at_slot()[cols[0]] : -1;
+                if (slot >= 0) {
+#pragma unroll
+                    for (int i = 0; i < TMT; ++i)
+#pragma unroll
+                        for (int r = 0; r < 16; ++r) {
+                            const int lr = acc_row<TMT>(wm, hv, i, r);
+                            LELE_DEV_ASSERT(slot < epi.at_ncols());
+                            if (lr < rows_here) epi.at_out()[(m0 + lr) * epi.at_ncols() + slot] = val[i * 16 + r];
+                        }
+                }
+            }
         } else {
             for (int t = tid; t < rows_here; t += NT) epi.arg_keys[(int64_t)tx * rows + m0 + t] = wave_join<BM, WN>(s_key, t, HeadMax());
         }
@@ -226,13 +243,17 @@ __device__ __forceinline__ void head_epilogue(const IgemmEpi& epi, const v16i (&
 //   MODE 5: keys [tiles][k][rows] -> a row's k greatest keys as ids [rows][k] and log-probabilities: thread g keeps the 8 greatest keys
 //           of its tiles, thread 0 merges the 16 lists.  Slot 0's log-probability is MODE 4's, from the tiles' round-0 keys and sums;
 //           slot j's is (v_j - v_0) + logprob_0 with the values the keys carry.  Key 0 is "no candidate" (fewer than k columns): id -1, -inf.
+//   MODE 6: MODE 4, then the workgroup's 16 rows x ncols raw values in `at` (one contiguous stretch) in place as (x - v_0) + logprob_0,
+//           MODE 5's formula, by all 256 threads.
 template <int MODE>
 __global__ __launch_bounds__(256) void head_finish_kernel(const unsigned long long* __restrict__ keys, const float* __restrict__ sums, int64_t rows,
-                                                          int tiles, int k, int32_t* __restrict__ ids, float* __restrict__ logprob) {
-    constexpr bool SCORED = MODE >= 4, LIST = MODE == 5;
+                                                          int tiles, int k, int32_t* __restrict__ ids, float* __restrict__ logprob,
+                                                          float* __restrict__ at, int ncols) {
+    constexpr bool SCORED = MODE >= 4, LIST = MODE == 5, AT = MODE == 6;
     constexpr int L = LIST ? 8 : 1;
     __shared__ unsigned long long s_list[16][L][17];
     __shared__ float s_part[SCORED ? 16 : 1][17];
+    __shared__ float s_row[AT ? 2 : 1][16];  // MODE 6: a row's maximum and log-probability
     const int rr = threadIdx.x & 15, g = threadIdx.x >> 4;
     const int64_t r = (int64_t)blockIdx.x * 16 + rr;
     unsigned long long list[L] = {};
@@ -300,18 +321,36 @@ __global__ __launch_bounds__(256) void head_finish_kernel(const unsigned long lo
         } else if constexpr (SCORED) {
             logprob[r] = lp0;
         }
+        if constexpr (AT) s_row[0][rr] = mx, s_row[1][rr] = lp0;
+    }
+    if constexpr (AT) {
+        __syncthreads();
+        const int64_t r0 = (int64_t)blockIdx.x * 16;
+        const int here = (int)(rows - r0 < 16 ? rows - r0 : 16);
+        float* const a = at + r0 * ncols;
+        for (int e = threadIdx.x; e < here * ncols; e += 256) {
+            const int row = e / ncols;
+            a[e] = (a[e] - s_row[0][row]) + s_row[1][row];
+        }
     }
 }
 
 // ------------------------------------------------------------------------------------------ host side
-enum class Head { None, Ids, Scored, TopK };  // igemm_kernel EM 0 / 3 / 4 / 5
+enum class Head { None, Ids, Scored, TopK, At };  // igemm_kernel EM 0 / 3 / 4 / 5 / 6
 // what a caller wants in place of the product
 struct HeadReq {
     Head mode = Head::None;  // Ids: `out` receives argmax_last of the result as i32 [rows], the result itself is never stored
     int k = 1;               // TopK: the k best a row, 1 .. 8 -- `out` i32 [rows][k], logprob f32 [rows][k]
-    LeleBuf* logprob = nullptr;  // Scored / TopK: the log-probabilities of the ids, f32
+    LeleBuf* logprob = nullptr;  // Scored / TopK / At: the log-probabilities of the ids, f32
+    // At: the caller's columns (host, strictly ascending, validated), `at` f32 [rows][ncols] their log-probabilities; at_slot is the
+    // column -> slot map [n] on the device (-1: not listed), part of the call's one table
+    const int32_t* cols = nullptr;
+    int64_t ncols = 0;
+    LeleBuf* at = nullptr;
+    const int* at_slot = nullptr;
     explicit operator bool() const { return mode != Head::None; }
-    bool scored() const { return mode == Head::Scored || mode == Head::TopK; }
+    bool scored() const { return mode == Head::Scored || mode == Head::TopK || mode == Head::At; }
+    bool listed() const { return mode == Head::At; }
     bool topk() const { return mode == Head::TopK; }
 };
 // the tables between the two kernels and the results: keys [column tiles][k][rows], sums [column tiles][rows], ids / logprob [rows][k]
@@ -320,8 +359,10 @@ struct HeadOut {
     float* sums = nullptr;  // scored heads only, logprob with it
     int32_t* ids = nullptr;
     float* logprob = nullptr;
-    void results(const LeleBuf* out, const HeadReq& head) {  // both reserved
+    float* at = nullptr;
+    void results(const LeleBuf* out, const HeadReq& head) {  // all reserved
         ids = (int32_t*)out->data, logprob = head.scored() ? (float*)head.logprob->data : nullptr;
+        at = head.listed() ? (float*)head.at->data : nullptr;
     }
 };
 size_t head_key_bytes(int64_t rows, int64_t n) { return (size_t)rows * (size_t)((n + 127) / 128) * 8; }
@@ -354,14 +395,18 @@ int launch_igemm_head(LeleCtx* ctx, const int8_t* aq, const int8_t* wt, int64_t 
     constexpr size_t lds = (size_t)2 * (128 + 128) * (128 + 16);
     IgemmEpi epi = epi_in;
     epi.arg_keys = o.keys, epi.arg_sums = o.sums, epi.topk = head.topk() ? head.k : 0;
+    if (head.listed()) epi.out = o.at, epi.q_rowsum = const_cast<int*>(head.at_slot), epi.topk = (int)head.ncols;  // (IgemmEpi: EM 6)
     const dim3 grid((n + 127) / 128, (unsigned)((rows + 127) / 128));
     // EM 5, <= 128 registers: two workgroups a CU, as EM 3 / EM 4 get by themselves
-    auto kern = head.topk() ? igemm_kernel<128, 128, 2, 4, 128, 4, 5> : head.scored() ? igemm_kernel<128, 128, 2, 4, 128, 1, 4> : igemm_kernel<128, 128, 2, 4, 128, 1, 3>;
-    auto finish = head.topk() ? head_finish_kernel<5> : head.scored() ? head_finish_kernel<4> : head_finish_kernel<3>;
+    auto kern = head.topk()     ? igemm_kernel<128, 128, 2, 4, 128, 4, 5>
+                : head.listed() ? igemm_kernel<128, 128, 2, 4, 128, 1, 6>
+                : head.scored() ? igemm_kernel<128, 128, 2, 4, 128, 1, 4>
+                                : igemm_kernel<128, 128, 2, 4, 128, 1, 3>;
+    auto finish = head.topk() ? head_finish_kernel<5> : head.listed() ? head_finish_kernel<6> : head.scored() ? head_finish_kernel<4> : head_finish_kernel<3>;
     LELE_HIP_CHECK(ensure_dyn_lds(reinterpret_cast<const void*>(kern), (int)lds));
     hipLaunchKernelGGL(kern, grid, dim3(512), lds, ctx->stream, aq, wt, rows, n, kp, (int64_t)0, m, epi);
     hipLaunchKernelGGL(finish, dim3((unsigned)((rows + 15) / 16)), dim3(256), 0, ctx->stream, (const unsigned long long*)o.keys, (const float*)o.sums, rows,
-                       (int)grid.x, head.k, o.ids, o.logprob);
+                       (int)grid.x, head.k, o.ids, o.logprob, o.at, (int)head.ncols);
     LELE_HIP_CHECK(hipGetLastError());
     return 0;
 }

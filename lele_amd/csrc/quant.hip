@@ -422,6 +422,12 @@ struct IgemmEpi {
     unsigned long long* arg_keys = nullptr;  // EM 3 / 4: [column tiles][rows], a tile's best argmax_key(value, column) per row (plain stores)
     float* arg_sums = nullptr;  // EM 4: [column tiles][rows], sum over the tile's columns of exp(value - the tile's maximum) (plain stores)
     int topk = 0;               // EM 5: keys kept per (row, column tile), 1 .. 8; arg_keys is [column tiles][topk][rows] then
+    // EM 6 (the listed columns' values, igemm_head.h) adds no field: it reads three that no head uses, so that the kernel's argument
+    // block -- and with it the code of every other mode -- stays what it was.  `out`: [rows][topk] values (plain stores, one lane a
+    // (row, slot)); `topk`: the listed columns a row; `q_rowsum`: [n], a column's slot or -1.
+    __device__ __forceinline__ float* at_out() const { return out; }
+    __device__ __forceinline__ const int* at_slot() const { return q_rowsum; }
+    __device__ __forceinline__ int at_ncols() const { return topk; }
     // Everything that depends only on the row (slice parameters, row-sum term, output row pointer) or only on the
     // column (column sum, weight scale, bias) is computed once per row / column of a thread's tile, not per element.
     struct RowCtx {
@@ -494,7 +500,7 @@ namespace {
 //   EM 1: only the per-slice maximum of the (ReLU) result, by atomic max into epi.slice_max;
 //   EM 2: the result again, quantised with the slice's now-known range exactly as qrows_kernel would quantise the stored f32
 //         (SIMD body: rint(fma(v, 1/scale, zp)), saturated), written as i8 with its row sums -- what the next GEMM consumes.
-// EM 3 / 4 / 5 are the decode heads (ids, ids with log-probabilities, the k best): head_epilogue, igemm_head.h, where the kernel is
+// EM 3 / 4 / 5 / 6 are the decode heads (ids, ids with log-probabilities, the k best, listed columns): head_epilogue, igemm_head.h, where the kernel is
 // declared with its default arguments (OCC = 1, EM = 0).
 template <int BM, int BN, int WM, int WN, int BKB /* bytes of K per LDS tile: 64 or 128 */, int OCC, int EM>
 __global__ __launch_bounds__(WM* WN * 64) __attribute__((amdgpu_waves_per_eu(OCC))) void igemm_kernel(const int8_t* __restrict__ a, const int8_t* __restrict__ b,
@@ -1456,6 +1462,7 @@ const char* fql_who(const HeadReq& head, bool packed) {
         case Head::Ids: return packed ? "fused_quantized_linear_argmax_segments" : "fused_quantized_linear_argmax";
         case Head::Scored: return packed ? "fused_quantized_linear_argmax_logprob_segments" : "fused_quantized_linear_argmax_logprob";
         case Head::TopK: return packed ? "fused_quantized_linear_topk_segments" : "fused_quantized_linear_topk";
+        case Head::At: return packed ? "fused_quantized_linear_logprob_at_segments" : "fused_quantized_linear_logprob_at";
         case Head::None: break;
     }
     return packed ? "fused_quantized_linear_segments" : "fused_quantized_linear";
@@ -1466,7 +1473,48 @@ int head_shape(const char* who, const HeadReq& head, QCall* c) {
     LELE_REQUIRE(c->n >= 1 && c->k >= 1, "%s: empty K or N (K = %lld, N = %lld)", who, (long long)c->k, (long long)c->n);
     c->shp.pop_back();
     if (head.topk()) c->shp.push_back(head.k);
+    if (head.listed()) {  // the caller's columns: strictly ascending inside [0, N)
+        LELE_REQUIRE(head.cols && head.ncols >= 1 && head.ncols <= c->n, "%s: %lld columns listed, 1 .. N = %lld required", who, (long long)head.ncols,
+                     (long long)c->n);
+        LELE_REQUIRE(head.ncols < (int64_t(1) << 27), "%s: more than 2^27 listed columns", who);  // (the finish kernel counts 16 rows of them in an int)
+        for (int64_t u = 0; u < head.ncols; ++u) {
+            LELE_REQUIRE(head.cols[u] >= 0 && head.cols[u] < c->n, "%s: cols[%lld] = %d outside [0, N = %lld)", who, (long long)u, (int)head.cols[u],
+                         (long long)c->n);
+            LELE_REQUIRE(u == 0 || head.cols[u] > head.cols[u - 1], "%s: cols[%lld] = %d is not greater than cols[%lld] = %d (strictly ascending required)",
+                         who, (long long)u, (int)head.cols[u], (long long)(u - 1), (int)head.cols[u - 1]);
+        }
+    }
     return 0;
+}
+// Head::At: the call's one table.  Behind what the packed call keeps there anyway (offsets and the row -> segment map; the dense call:
+// nothing) the column -> slot map, int [N] with -1 for a column that is not listed: 4 N bytes.  The key is the layout AND the columns
+// (as int64 behind the offsets), so that a captured graph's table is the one of its own columns.
+struct AtTableArg {
+    const int64_t* off;  // NULL: dense
+    int64_t count;
+    const int32_t* cols;
+    int64_t ncols, n;
+};
+void build_rowseg(const void* arg, std::vector<char>& blob);
+void build_at_table(const void* arg, std::vector<char>& blob) {
+    const AtTableArg& a = *(const AtTableArg*)arg;
+    size_t head = 0;
+    if (a.off) {
+        const std::pair<const int64_t*, int64_t> rs{a.off, a.count};
+        build_rowseg(&rs, blob);
+        head = blob.size();
+    }
+    blob.resize(head + (size_t)a.n * 4);
+    int* slot = (int*)(blob.data() + head);
+    for (int64_t j = 0; j < a.n; ++j) slot[j] = -1;
+    for (int64_t u = 0; u < a.ncols; ++u) slot[a.cols[u]] = (int)u;
+}
+int at_table(LeleCtx* ctx, const HeadReq& head, const int64_t* off, int64_t count, int64_t n, const void** tab) {
+    std::vector<int64_t> key;
+    if (off) key.assign(off, off + count + 1);
+    key.insert(key.end(), head.cols, head.cols + head.ncols);
+    const AtTableArg arg{off, count, head.cols, head.ncols, n};
+    return layout_table(ctx, "qsat", off ? count : -1, n, key.data(), (int64_t)key.size() - 1, build_at_table, &arg, tab);
 }
 // one layer, validated and staged: what a route's body reads
 struct QLayer {
@@ -1658,8 +1706,11 @@ int fql_impl(LeleCtx* ctx, const LeleTensor* input, const QW& w, const QReq& rq,
     LELE_TRY(head_shape(who, rq.head, &c));
     const size_t out_bytes = (size_t)c.rows * (rq.head ? rq.head.k : c.n) * 4;
     LELE_HIP_CHECK(hipSetDevice(ctx->device));
+    const void* at_tab = nullptr;
+    if (rq.head.listed() && c.rows > 0) LELE_TRY(at_table(ctx, rq.head, nullptr, 0, c.n, &at_tab));
     LELE_TRY(out->reserve(out_bytes));
     if (rq.head.scored()) LELE_TRY(rq.head.logprob->reserve(out_bytes));
+    if (rq.head.listed()) LELE_TRY(rq.head.at->reserve((size_t)c.rows * rq.head.ncols * 4));
     if (c.rows == 0 || c.n == 0) return set_shape_v(out_shape, out_rank, c.shp);
     LELE_TRY(ctx->arena_reset());
     const void *dx = nullptr, *dws = nullptr, *db = nullptr, *dr1 = nullptr, *dr2 = nullptr;
@@ -1674,6 +1725,7 @@ int fql_impl(LeleCtx* ctx, const LeleTensor* input, const QW& w, const QReq& rq,
     LELE_TRY(ctx->arena_alloc((size_t)c.batch * sizeof(QParams), &prm));
     l.weight = w.w, l.x = (const float*)dx, l.ws = (const float*)dws, l.bias = (const float*)db, l.relu = rq.relu;
     l.res1 = (const float*)dr1, l.res2 = (const float*)dr2, l.prm = (QParams*)prm, l.out = out, l.head = rq.head;
+    l.head.at_slot = (const int*)at_tab;
     LELE_TRY(qprof_mark(ctx, 0));
     if (!l.partial) LELE_TRY(launch_range(ctx, l.x, c.batch, c.m * c.k, l.prm, nullptr, nullptr, &l.partial, &l.nblk));
     LELE_TRY(qprof_mark(ctx, 1));
@@ -1912,11 +1964,14 @@ int fql_segments_impl(LeleCtx* ctx, const LeleTensor* input, const int64_t* row_
     const void* tab = nullptr;
     if (rows > 0 && n > 0 && k > 0) {
         const std::pair<const int64_t*, int64_t> arg{row_offsets, count};
-        LELE_TRY(layout_table(ctx, "qseg", 0, 0, row_offsets, count, build_rowseg, &arg, &tab));
+        if (rq.head.listed()) LELE_TRY(at_table(ctx, rq.head, row_offsets, count, n, &tab));
+        else LELE_TRY(layout_table(ctx, "qseg", 0, 0, row_offsets, count, build_rowseg, &arg, &tab));
     }
+    const size_t at_bytes = rq.head.listed() ? (size_t)rows * rq.head.ncols * 4 : 0;
     if (rows == 0 || n == 0 || k == 0) {
         LELE_TRY(out->reserve(out_bytes));
         if (logprob) LELE_TRY(logprob->reserve(out_bytes));
+        if (rq.head.listed()) LELE_TRY(rq.head.at->reserve(at_bytes));
         return set_shape_v(out_shape, out_rank, c.shp);
     }
     const int64_t* doff = (const int64_t*)tab;
@@ -1955,14 +2010,17 @@ int fql_segments_impl(LeleCtx* ctx, const LeleTensor* input, const int64_t* row_
     // those of `input` describe equal slices and are not read)
     LELE_TRY(out->reserve(out_bytes));
     if (logprob) LELE_TRY(logprob->reserve(out_bytes));
+    if (rq.head.listed()) LELE_TRY(rq.head.at->reserve(at_bytes));
     LELE_TRY(launch_qrows(ctx, rows <= 2048 || kp <= 2048, l.x, rows, (int)k, kp, (int)rows, l.prm, (int8_t*)aq, (int*)rs, (const float*)partial,
                           nblk, nullptr, nullptr, drowseg));
     LELE_TRY(qprof_mark(ctx, 2));
     IgemmEpi epi = make_epi(l, rq.head ? nullptr : (float*)out->data, (const int*)rs, pw.col_sums);
     epi.row_seg = drowseg;
     if (rq.head) {
-        ho.results(out, rq.head);
-        LELE_TRY(launch_igemm_head(ctx, (const int8_t*)aq, pw.wt, rows, (int)n, kp, (int)rows, epi, rq.head, ho));
+        HeadReq head = rq.head;
+        head.at_slot = (const int*)((const char*)tab + (size_t)(count + 1) * 8 + (size_t)rows * 4);  // (Head::At; read by no other head)
+        ho.results(out, head);
+        LELE_TRY(launch_igemm_head(ctx, (const int8_t*)aq, pw.wt, rows, (int)n, kp, (int)rows, epi, head, ho));
     } else {
         LELE_TRY(launch_igemm(ctx, (const int8_t*)aq, pw.wt, rows, (int)n, kp, (int)rows, epi));
     }
@@ -1970,13 +2028,16 @@ int fql_segments_impl(LeleCtx* ctx, const LeleTensor* input, const int64_t* row_
     return set_shape_v(out_shape, out_rank, c.shp);
 }
 
-// the six head entry points: what they require of k and of their outputs, then the dense or the packed linear (row_offsets / count)
+// the eight head entry points: what they require of k and of their outputs, then the dense or the packed linear (row_offsets / count)
 int fql_head(LeleCtx* ctx, Head mode, int32_t k, bool packed, const LeleTensor* input, const int64_t* row_offsets, int64_t count, const QW& w,
-             LeleBuf* out_ids, LeleBuf* out_logprob, int64_t* out_shape, int32_t* out_rank) {
+             LeleBuf* out_ids, LeleBuf* out_logprob, int64_t* out_shape, int32_t* out_rank, const int32_t* cols = nullptr, int64_t ncols = 0,
+             LeleBuf* out_at = nullptr) {
     QReq rq;
-    rq.head = HeadReq{mode, mode == Head::TopK ? (int)k : 1, out_logprob};
+    rq.head = HeadReq{mode, mode == Head::TopK ? (int)k : 1, out_logprob, cols, ncols, out_at};
     const char* const who = fql_who(rq.head, packed);
     if (rq.head.scored()) LELE_REQUIRE(out_ids && out_logprob && out_ids != out_logprob, "%s: two distinct output buffers required", who);
+    if (rq.head.listed())
+        LELE_REQUIRE(out_at && out_at != out_ids && out_at != out_logprob, "%s: three distinct output buffers required", who);
     if (rq.head.topk()) LELE_REQUIRE(k >= 1 && k <= 8, "%s: k = %d outside [1, 8]", who, (int)k);
     return packed ? fql_segments_impl(ctx, input, row_offsets, count, w, rq, out_ids, out_shape, out_rank)
                   : fql_impl(ctx, input, w, rq, out_ids, out_shape, out_rank);
@@ -2044,6 +2105,25 @@ int lele_hip_fused_quantized_linear_topk_segments(LeleCtx* ctx, const LeleTensor
                                                   int64_t* out_shape, int32_t* out_rank) {
     return fql_head(ctx, Head::TopK, k, true, input, row_offsets, count, {weight_int8, weight_scale, weight_zero, bias}, out_ids, out_logprob, out_shape,
                     out_rank);
+}
+
+/* ... and the log-probabilities of the columns the CALLER lists (forced alignment, rescoring): out_ids / out_logprob are the scored head's
+ * bit for bit, out_at[r, u] = (v[r, cols[u]] - v[r, id_r]) + logprob[r], the k-best head's formula, from the same epilogue (igemm_kernel
+ * EM 6): a lane whose column is listed stores the values it holds, the finish kernel rewrites them in place. */
+int lele_hip_fused_quantized_linear_logprob_at(LeleCtx* ctx, const LeleTensor* input, const LeleTensor* weight_int8, const LeleTensor* weight_scale,
+                                               const LeleTensor* weight_zero, const LeleTensor* bias, const int32_t* cols, int64_t ncols,
+                                               LeleBuf* out_ids, LeleBuf* out_logprob, LeleBuf* out_at, int64_t* out_shape, int32_t* out_rank) {
+    return fql_head(ctx, Head::At, 1, false, input, nullptr, 0, {weight_int8, weight_scale, weight_zero, bias}, out_ids, out_logprob, out_shape, out_rank,
+                    cols, ncols, out_at);
+}
+
+int lele_hip_fused_quantized_linear_logprob_at_segments(LeleCtx* ctx, const LeleTensor* input, const int64_t* row_offsets, int64_t count,
+                                                        const LeleTensor* weight_int8, const LeleTensor* weight_scale,
+                                                        const LeleTensor* weight_zero, const LeleTensor* bias, const int32_t* cols, int64_t ncols,
+                                                        LeleBuf* out_ids, LeleBuf* out_logprob, LeleBuf* out_at, int64_t* out_shape,
+                                                        int32_t* out_rank) {
+    return fql_head(ctx, Head::At, 1, true, input, row_offsets, count, {weight_int8, weight_scale, weight_zero, bias}, out_ids, out_logprob, out_shape,
+                    out_rank, cols, ncols, out_at);
 }
 
 int lele_hip_fused_quantized_linear_residual(LeleCtx* ctx, const LeleTensor* input, const LeleTensor* weight_int8,

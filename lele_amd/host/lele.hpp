@@ -1095,6 +1095,60 @@ inline BeamHypotheses ctc_beam_search_segments(const TensorView& ids, const Tens
     return {TensorView::from_device(out_tokens, s, LELE_I32), TensorView::from_device(out_lengths, h, LELE_I32),
             TensorView::from_device(out_scores, h, LELE_F32), TensorView::from_device(out_counts, c, LELE_I32)};
 }
+// the decode head with the log-probabilities of the listed columns (strictly ascending, inside [0, N)) -> ids / logprob as
+// fused_quantized_linear_argmax_logprob bit for bit, at f32 [.., cols.size()]: at[.., u] = (v[cols[u]] - v[id]) + logprob
+struct LogprobAt {
+    TensorView ids, logprob, at;
+};
+inline LogprobAt fused_quantized_linear_logprob_at(const TensorView& input, const TensorView& weight_int8, const TensorView& weight_scale,
+                                                   const TensorView& weight_zero, const TensorView* bias, const std::vector<int32_t>& cols,
+                                                   Buffer& out_ids, Buffer& out_logprob, Buffer& out_at) {
+    Shape sh;
+    LeleTensor a = input.c(), b = weight_int8.c(), s = weight_scale.c(), z = weight_zero.c();
+    Opt ob(bias);
+    check(lele_hip_fused_quantized_linear_logprob_at(ctx(), &a, &b, &s, &z, ob.p, cols.data(), (int64_t)cols.size(), out_ids.raw(),
+                                                     out_logprob.raw(), out_at.raw(), sh.dims, &sh.rank));
+    std::vector<int64_t> shp(sh.dims, sh.dims + sh.rank), sha(shp);
+    sha.push_back((int64_t)cols.size());
+    return {TensorView::from_device(out_ids, shp, LELE_I32), TensorView::from_device(out_logprob, shp, LELE_F32),
+            TensorView::from_device(out_at, sha, LELE_F32)};
+}
+inline LogprobAt fused_quantized_linear_logprob_at_segments(const TensorView& input, const std::vector<int64_t>& offsets,
+                                                            const TensorView& weight_int8, const TensorView& weight_scale,
+                                                            const TensorView& weight_zero, const TensorView* bias,
+                                                            const std::vector<int32_t>& cols, Buffer& out_ids, Buffer& out_logprob,
+                                                            Buffer& out_at) {
+    Shape sh;
+    LeleTensor a = input.c(), b = weight_int8.c(), s = weight_scale.c(), z = weight_zero.c();
+    Opt ob(bias);
+    check(lele_hip_fused_quantized_linear_logprob_at_segments(ctx(), &a, offsets.data(), (int64_t)offsets.size() - 1, &b, &s, &z, ob.p, cols.data(),
+                                                              (int64_t)cols.size(), out_ids.raw(), out_logprob.raw(), out_at.raw(), sh.dims,
+                                                              &sh.rank));
+    std::vector<int64_t> shp(sh.dims, sh.dims + sh.rank), sha(shp);
+    sha.push_back((int64_t)cols.size());
+    return {TensorView::from_device(out_ids, shp, LELE_I32), TensorView::from_device(out_logprob, shp, LELE_F32),
+            TensorView::from_device(out_at, sha, LELE_F32)};
+}
+// CTC forced alignment of known transcripts over the listed columns' log-probabilities (at f32 [R, cols.size()]), a segment's frames
+// being its rows behind the first skip_rows: spans i32 [count, W, 2] (first / last row of each label within its segment, then -1),
+// scores f32 [count, W], path / ok [count], total [count] (the CTC likelihood; an empty view when out_total is NULL)
+struct Alignment {
+    TensorView spans, scores, path, total, ok;
+};
+inline Alignment ctc_align_segments(const TensorView& at, const std::vector<int32_t>& cols, const std::vector<int64_t>& offsets, int64_t skip_rows,
+                                    int32_t blank, const std::vector<int32_t>& tokens, const std::vector<int64_t>& token_offsets, int64_t width,
+                                    Buffer& out_spans, Buffer& out_scores, Buffer& out_path, Buffer* out_total, Buffer& out_ok) {
+    Shape sh;
+    LeleTensor ta = at.c();
+    check(lele_hip_ctc_align_segments(ctx(), &ta, cols.data(), (int64_t)cols.size(), offsets.data(), (int64_t)offsets.size() - 1, skip_rows, blank,
+                                      tokens.data(), token_offsets.data(), width, out_spans.raw(), out_scores.raw(), out_path.raw(),
+                                      out_total ? out_total->raw() : nullptr, out_ok.raw(), sh.dims, &sh.rank));
+    std::vector<int64_t> s(sh.dims, sh.dims + sh.rank), p(s), c(sh.dims, sh.dims + (sh.rank > 0 ? 1 : 0));
+    p.push_back(2);
+    return {TensorView::from_device(out_spans, p, LELE_I32), TensorView::from_device(out_scores, s, LELE_F32),
+            TensorView::from_device(out_path, c, LELE_F32), out_total ? TensorView::from_device(*out_total, c, LELE_F32) : TensorView(),
+            TensorView::from_device(out_ok, c, LELE_I32)};
+}
 inline TensorView attention_segments(const TensorView& qkv, const std::vector<int64_t>& offsets, int64_t q_offset, int64_t k_offset,
                                      int64_t v_offset, int64_t heads, int64_t dh, const TensorView* scale, Buffer& out) {
     Shape sh;

@@ -1216,10 +1216,20 @@ def fused_quantized_linear_segments(input, offsets, weight_int8, weight_scale, w
     return TensorView(_lib.DevTensor(out, sh.get(), np.float32))
 
 
-def _decode_head(input, offsets, weights, k, outs, ctx):
-    """the six decode heads' calls differ in the entry point, the packed forms' `offsets`, the k-best forms' `k` (None where there is
-    none) and one or two outputs -> (args, result): the entry point's arguments and, called behind it, what the wrapper returns --
-    the ids for outs = (out,), (ids, logprob) for outs = (out_ids, out_logprob)"""
+def _i32_list(a):
+    """a host list of int32 (columns, labels) as a contiguous array"""
+    return np.ascontiguousarray(np.asarray(a, dtype=np.int64).reshape(-1).astype(np.int32))
+
+
+def _i32_ptr(a):
+    return a.ctypes.data_as(C.POINTER(C.c_int32))
+
+
+def _decode_head(input, offsets, weights, k, outs, ctx, cols=None):
+    """the eight decode heads' calls differ in the entry point, the packed forms' `offsets`, the k-best forms' `k` (None where there is
+    none), the listed-columns forms' `cols` and one to three outputs -> (args, result): the entry point's arguments and, called behind
+    it, what the wrapper returns -- the ids for outs = (out,), (ids, logprob) for outs = (out_ids, out_logprob), (ids, logprob, at) with
+    `cols`, at carrying a trailing axis of len(cols)"""
     ctx = _ctx(ctx)
     keep = []
     bufs = [o or ctx.buf() for o in outs]
@@ -1232,11 +1242,18 @@ def _decode_head(input, offsets, weights, k, outs, ctx):
     args += [_t(w, keep) for w in weights]
     if k is not None:
         args.append(C.c_int32(int(k)))
+    if cols is not None:
+        cols = _i32_list(cols)
+        keep.append(cols)
+        args += [_i32_ptr(cols), C.c_int64(len(cols))]
     args += [b._h for b in bufs] + [sh.shape, C.byref(sh.rank)]
 
     def result():
         del keep[:]  # (held until the call was made)
-        views = [TensorView(_lib.DevTensor(b, sh.get(), dt)) for b, dt in zip(bufs, (np.int32, np.float32))]
+        shape = sh.get()
+        views = [TensorView(_lib.DevTensor(b, shape, dt)) for b, dt in zip(bufs[:2], (np.int32, np.float32))]
+        if cols is not None:
+            views.append(TensorView(_lib.DevTensor(bufs[2], tuple(shape) + (len(cols),), np.float32)))
         return views[0] if len(views) == 1 else tuple(views)
     return args, result
 
@@ -1307,6 +1324,57 @@ def fused_quantized_linear_topk_segments(input, offsets, weight_int8, weight_sca
     args, result = _decode_head(input, offsets, (weight_int8, weight_scale, weight_zero, bias), k, (out_ids, out_logprob), ctx)
     _lib.check(_lib.lib().lele_hip_fused_quantized_linear_topk_segments(*args))
     return result()
+
+
+def fused_quantized_linear_logprob_at(input, weight_int8, weight_scale, weight_zero, bias, cols, out_ids=None, out_logprob=None,
+                                      out_at=None, ctx=None):
+    """the decode head with the log-probabilities of the listed columns -> (ids int32, logprob float32, at float32): ids and logprob are
+    fused_quantized_linear_argmax_logprob's bit for bit, at has a trailing axis of len(cols) and at[.., u] = (v[cols[u]] - v[id]) + logprob,
+    the k-best head's formula (a listed column among the k best holds that head's value bit for bit).  `cols`: host integers, strictly
+    ascending, inside [0, N).  The logits are never stored."""
+    args, result = _decode_head(input, None, (weight_int8, weight_scale, weight_zero, bias), None, (out_ids, out_logprob, out_at), ctx, cols)
+    _lib.check(_lib.lib().lele_hip_fused_quantized_linear_logprob_at(*args))
+    return result()
+
+
+def fused_quantized_linear_logprob_at_segments(input, offsets, weight_int8, weight_scale, weight_zero, bias, cols, out_ids=None,
+                                               out_logprob=None, out_at=None, ctx=None):
+    """fused_quantized_linear_logprob_at with every segment of the packed input [R, K] as a batch slice of its own -> (int32 [R], float32
+    [R], float32 [R, len(cols)]): rows offsets[i] .. offsets[i + 1] are, bit for bit, the dense call on that range alone"""
+    args, result = _decode_head(input, offsets, (weight_int8, weight_scale, weight_zero, bias), None, (out_ids, out_logprob, out_at), ctx, cols)
+    _lib.check(_lib.lib().lele_hip_fused_quantized_linear_logprob_at_segments(*args))
+    return result()
+
+
+def ctc_align_segments(at, cols, offsets, transcripts, blank=0, skip_rows=0, width=0, total=True, out_spans=None, out_scores=None,
+                       out_path=None, out_total=None, out_ok=None, ctx=None):
+    """CTC forced alignment on the device, one segment of the packed log-probabilities a wavefront: at float32 [R, len(cols)] as
+    fused_quantized_linear_logprob_at_segments gives it, frames of segment i = rows offsets[i] + skip_rows .. offsets[i + 1], its
+    transcript transcripts[i] (at most 511 labels, every one and `blank` listed in `cols`) -> (spans int32 [count, W, 2]: first and last row
+    of each label within its segment, then -1; scores float32 [count, W]: the label's summed emissions, then 0.0; path float32 [count];
+    total float32 [count], the CTC likelihood, or None with total=False; ok int32 [count]): apps.ctc_forced_align of every segment,
+    float64 inside, spans / scores / path equal to it.  apps.align_results turns the five into that function's format."""
+    ctx = _ctx(ctx)
+    keep = []
+    osp, osc, opa, ook = out_spans or ctx.buf(), out_scores or ctx.buf(), out_path or ctx.buf(), out_ok or ctx.buf()
+    oto = (out_total or ctx.buf()) if total else None
+    sh = _lib.OutShape()
+    off = _offsets(offsets)
+    cols = _i32_list(cols)
+    tok_off = np.zeros(len(transcripts) + 1, np.int64)
+    tok_off[1:] = np.cumsum([len(t) for t in transcripts])
+    if len(tok_off) != len(off):
+        raise ValueError("ctc_align_segments: %d transcripts for %d segments" % (len(transcripts), len(off) - 1))
+    toks = _i32_list([x for t in transcripts for x in t])
+    _lib.check(_lib.lib().lele_hip_ctc_align_segments(
+        ctx._h, _t(at, keep), _i32_ptr(cols), C.c_int64(len(cols)), _lib.i64_ptr(off), C.c_int64(len(off) - 1), C.c_int64(int(skip_rows)),
+        C.c_int32(int(blank)), _i32_ptr(toks), _lib.i64_ptr(tok_off), C.c_int64(int(width)), osp._h, osc._h, opa._h,
+        oto._h if oto is not None else None, ook._h, sh.shape, C.byref(sh.rank)))
+    shape = tuple(sh.get())
+    return (TensorView(_lib.DevTensor(osp, shape + (2,), np.int32)), TensorView(_lib.DevTensor(osc, shape, np.float32)),
+            TensorView(_lib.DevTensor(opa, shape[:1], np.float32)),
+            None if oto is None else TensorView(_lib.DevTensor(oto, shape[:1], np.float32)),
+            TensorView(_lib.DevTensor(ook, shape[:1], np.int32)))
 
 
 def token_align_segments(ids, logprob, offsets, skip, width=0, out_ids=None, out_frames=None, out_logprob=None, out_counts=None, ctx=None):

@@ -301,6 +301,38 @@ class Encoder:
                                                np.arange(b + 1, dtype=np.int64) * t4, 0, beam, nbest, 4, 0, out_tokens=h[0], out_lengths=h[1],
                                                out_scores=h[2], out_counts=h[3], ctx=self.ctx)
 
+    @staticmethod
+    def align_cols(transcripts, blank=0):
+        """the columns an alignment of these transcripts needs: the sorted union of their labels and the blank"""
+        return sorted({int(blank)} | {int(t) for tr in transcripts for t in tr})
+
+    def align_segments(self, feats, offsets, transcripts, width=0):
+        """forced alignment of one known transcript per utterance of the packed batch: the trunk, the CTC projection with the
+        log-probabilities of the transcripts' labels and the blank (fused_quantized_linear_logprob_at_segments; the logits are never
+        stored), then the lattice on the device over every utterance's frames behind its four prompt rows -> (spans int32 [count, W, 2],
+        scores float32 [count, W], path float32 [count], total float32 [count], ok int32 [count]): lele_amd.apps.align_results turns
+        them into ctc_forced_align's format, apps.token_times(spans[..., 0]) into start times.  W = width, or the longest transcript."""
+        K, ctx, p = self.K, self.ctx, self.ctc
+        cols = self.align_cols(transcripts)
+        _, xn, off = self.trunk_segments(feats, offsets)
+        _, _, at = K.fused_quantized_linear_logprob_at_segments(xn, off, p.w, p.scale, p.zero, p.bias, cols, out_ids=self.dec[0],
+                                                                out_logprob=self.sco[0], out_at=self.sco[1], ctx=ctx)
+        h = self.hyp
+        return K.ctc_align_segments(at, cols, off, transcripts, 0, 4, width, out_spans=h[0], out_scores=h[1], out_path=h[2], out_total=h[3],
+                                    out_ok=self.dec[1], ctx=ctx)
+
+    def align(self, feats, transcripts):
+        """feats: [B, T, 560] -> align_segments' five results for the dense batch, read as the packed layout off[i] = i * (T + 4)"""
+        K, ctx, p = self.K, self.ctx, self.ctc
+        cols = self.align_cols(transcripts)
+        xn = K.layer_norm(self.trunk(feats), self.ln_out[0], self.ln_out[1], -1, 1e-5, out=self.ws[1], ctx=ctx)
+        ids, _, at = K.fused_quantized_linear_logprob_at(xn, p.w, p.scale, p.zero, p.bias, cols, out_ids=self.dec[0], out_logprob=self.sco[0],
+                                                         out_at=self.sco[1], ctx=ctx)
+        b, t4 = ids.shape[0], ids.shape[1]
+        h = self.hyp
+        return K.ctc_align_segments(K.reshape(at, [b * t4, len(cols)]), cols, np.arange(b + 1, dtype=np.int64) * t4, transcripts, 0, 4, 0,
+                                    out_spans=h[0], out_scores=h[1], out_path=h[2], out_total=h[3], out_ok=self.dec[1], ctx=ctx)
+
 
 def encoder_arrays(enc):
     """the Encoder's weights as plain numpy arrays, in the layout oracle/sensevoice_ref.py consumes"""
