@@ -224,6 +224,40 @@ FE_HD void phase_a_fast(const float* x, cf* a, const TW& tw_re, const TW& tw_im)
     }
 }
 
+// ---- the entries phase_a_fast reads, as compile-time constants -------------------------------------
+// Stages 2..5 use wave-uniform entries tw_off(2)+1, tw_off(3)+0..3, tw_off(4)+1..7 and tw_off(5)+1..15: 27 of the first 31
+// table entries, the same in every pass of every launch.  Below are the f32 bit patterns of entries 0..30 as
+// precompute_twiddles(512) gives them (cosf / sinf of the f32 angle); an accessor over them hands phase_a_fast literals, so the
+// kernel fetches nothing for these stages.  The host compares them with the table it builds before it selects that form
+// (tw_const_matches): a libm that rounds one entry differently keeps the table-reading kernel.
+constexpr int kTwConstN = 31;
+constexpr uint32_t kTwConstRe[kTwConstN] = {
+    0x3f800000u, 0x3f800000u, 0xb33bbd2eu, 0x3f800000u, 0x3f3504f3u, 0xb33bbd2eu, 0xbf3504f3u, 0x3f800000u,
+    0x3f6c835eu, 0x3f3504f3u, 0x3ec3ef15u, 0xb33bbd2eu, 0xbec3ef18u, 0xbf3504f3u, 0xbf6c8360u, 0x3f800000u,
+    0x3f7b14beu, 0x3f6c835eu, 0x3f54db31u, 0x3f3504f3u, 0x3f0e39d9u, 0x3ec3ef15u, 0x3e47c5bcu, 0xb33bbd2eu,
+    0xbe47c5c2u, 0xbec3ef18u, 0xbf0e39dcu, 0xbf3504f3u, 0xbf54db32u, 0xbf6c8360u, 0xbf7b14bfu};
+constexpr uint32_t kTwConstIm[kTwConstN] = {
+    0x80000000u, 0x80000000u, 0xbf800000u, 0x80000000u, 0xbf3504f3u, 0xbf800000u, 0xbf3504f3u, 0x80000000u,
+    0xbec3ef16u, 0xbf3504f3u, 0xbf6c835eu, 0xbf800000u, 0xbf6c835eu, 0xbf3504f3u, 0xbec3ef10u, 0x80000000u,
+    0xbe47c5c2u, 0xbec3ef16u, 0xbf0e39dau, 0xbf3504f3u, 0xbf54db32u, 0xbf6c835eu, 0xbf7b14bfu, 0xbf800000u,
+    0xbf7b14beu, 0xbf6c835eu, 0xbf54db30u, 0xbf3504f3u, 0xbf0e39d9u, 0xbec3ef10u, 0xbe47c5c1u};
+FE_HD bool tw_const_used(int i) {  // the 27 entries phase_a_fast reads
+    return i == tw_off(2) + 1 || (i >= tw_off(3) && i < tw_off(4)) || (i > tw_off(4) && i < tw_off(5)) ||
+           (i > tw_off(5) && i < kTwConstN);
+}
+struct TwConst {  // table accessor for phase_a_fast ({false}: real parts, {true}: imaginary): operator[] of a compile-time index is a literal
+    bool im;
+    FE_HD float operator[](int i) const { return __builtin_bit_cast(float, im ? kTwConstIm[i] : kTwConstRe[i]); }
+};
+// true where the table (tw_re, tw_im) holds exactly the constants at every entry phase_a_fast reads
+inline bool tw_const_matches(const float* tw_re, const float* tw_im) {
+    for (int i = 0; i < kTwConstN; ++i) {
+        if (!tw_const_used(i)) continue;
+        if (__builtin_bit_cast(uint32_t, tw_re[i]) != kTwConstRe[i] || __builtin_bit_cast(uint32_t, tw_im[i]) != kTwConstIm[i]) return false;
+    }
+    return true;
+}
+
 // ---- phase B: stages 6..9 on 16 points (register v = j[8:5]) of lane c, round rho -------------------
 // Twiddles are per lane: index = tw_off(s) + (v mod 2^(s-6))*32 + rho*16 + c; TWF(i) returns (wr, wi) of entry i.
 // After the call: b[v] for v<8 hold bins j = (2v+rho)*16 + c; *re256 = re of position 256 (meaningful for
@@ -251,6 +285,7 @@ FE_HD void phase_b(cf* b, int c, int rho, const TWF& twf, float* re256) {
     }
 }
 
+
 // power spectrum exactly as features/pipeline.rs:165-169 after kernels/fft.rs:256-265 forced
 // im[0] = im[256] = 0:  re*re + im*im  (two products, one add, no fma).
 FE_HD float power(float re, float im) { return fadd(fmul(re, re), fmul(im, im)); }
@@ -265,5 +300,13 @@ FE_HD float power(cf z) {
 // lane_base + compile-time immediate (no per-access address arithmetic).
 constexpr int kXchgPitch = 17;
 FE_HD constexpr int xchg_slot(int v, int c) { return v * kXchgPitch + c; }
+
+// LDS image of the default mel bank's weights (80 filters = 5 rounds of 3, 4, 6, 10, 17 steps: 40 weights a lane, 640 in all).
+// Weight s (0..39, rounds back to back) of lane p sits at word mel_lds_index(s, p): chunk j = s / 4 holds weights 4j .. 4j+3 of every
+// lane, 16 bytes a lane, lanes consecutive.  A lane reads a chunk with one 16-byte load at lane_base + 256 j bytes; the 16 lanes of a
+// frame then cover 64 consecutive words, every bank once (the four frames of a wave read the same addresses).
+constexpr int kMelLdsWeights = 40;
+constexpr int kMelLdsChunks = kMelLdsWeights / 4;
+FE_HD constexpr int mel_lds_index(int s, int p) { return ((s >> 2) * kLanes + p) * 4 + (s & 3); }
 
 }  // namespace fe

@@ -35,6 +35,7 @@ struct FeDev {                 // device tables (all owned by LeleFrontend)
     const float2* tw;          // same, interleaved, for LDS staging
     const float* window;       // [frame_len]
     const float* melw;         // [total_steps][16]: weight of step t for lane pm
+    const float* melw_lds;     // default bank only: the same 640 weights as the kernel's LDS image ([chunk][lane][4], kMelLdsFloats)
     const int* mel_start;      // [rounds*16] first bin of filter m (0 for padding filters)
     const int* mel_step_off;   // [rounds+1] first step of each round in melw
     int mel_rounds;            // ceil(n_mels/16)
@@ -195,7 +196,14 @@ constexpr int kStdMelOff[6] = {0, 3, 7, 13, 23, 40};
 // that four workgroups' LDS fits a CU) were measured twice in round 4: <3, true> with 48 spilled registers 7.41 ms per 2048 x 30 s, and
 // -- after the pass body lost its copies -- <3, false> at 128 registers without a spill in the loop 3.59 ms against 3.47 ms for
 // <4, false> at three waves (148 registers) in the same call: the product instantiates <4, false> only; docs/experiments.md.
-template <int MODE, bool STDMEL, bool FUSED, int PASSES, bool LOWREG, class Blk>
+// OPT (the default bank's fused kernels only; 0 elsewhere): bit 0 (kFeConstTw) -- phase A's 27 wave-uniform twiddles are literals
+// (fe::TwConst) instead of scalar loads from the table; bit 1 (kFeLdsMel) -- the 640 mel weights are read from an LDS copy, ten
+// ds_read_b128 a pass, instead of 40 global loads a pass.  OPT = 0 is the table-reading form; the host selects (frontend_create).
+constexpr int kFeConstTw = 1, kFeLdsMel = 2;
+constexpr int kMelLdsFloats = 768;  // 640 weights at fe::mel_lds_index (fe_core.h), padded to three 1 KiB loads
+static_assert(fe::mel_lds_index(fe::kMelLdsWeights - 1, 15) < kMelLdsFloats && kStdMelOff[5] == fe::kMelLdsWeights, "the image holds the default bank");
+
+template <int MODE, bool STDMEL, bool FUSED, int PASSES, bool LOWREG, int OPT, class Blk>
 __device__ __forceinline__ void fe_main_body(const float* __restrict__ pcm, int64_t utt_stride,
                                              int64_t num_frames, int64_t t_lfr,
                                              const float* __restrict__ means, const FeDev& tb,
@@ -211,6 +219,12 @@ __device__ __forceinline__ void fe_main_body(const float* __restrict__ pcm, int6
     __shared__ int s_mstart[16 * (STDMEL ? 5 : kMaxMelRounds)];
     __shared__ int s_moff[kMaxMelRounds + 1];
     constexpr int kTwBase = LOWREG ? 31 : 0;
+    constexpr bool kConstTw = (OPT & kFeConstTw) != 0;
+    constexpr bool kLdsMel = (OPT & kFeLdsMel) != 0;
+    static_assert(OPT == 0 || (STDMEL && FUSED && !LOWREG), "the constant / LDS table forms belong to the default bank's fused kernel");
+    __shared__ __attribute__((aligned(16))) float s_melt[kLdsMel ? kMelLdsFloats : 4];
+    // three workgroups a CU: 160 KiB / 3 = 54 613 bytes each (the table-driven mel loop's dynamic s_melw comes on top where OPT == 0)
+    static_assert(sizeof(s_tw) + sizeof(s_x) + sizeof(s_mean) + sizeof(s_mstart) + sizeof(s_moff) + sizeof(s_melt) <= 54613, "LDS of three workgroups fits a CU");
 
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int g = lane >> 4, p = lane & 15;
@@ -259,6 +273,12 @@ __device__ __forceinline__ void fe_main_body(const float* __restrict__ pcm, int6
 #pragma unroll
             for (int k = 0; k < 4; ++k)
                 fe_dma16(reinterpret_cast<const char*>(tb.tw) + 1024 * k + 16 * lane, tw_lds + 1024 * k);
+        }
+        if (kLdsMel && wave == 2) {  // s_melt: three 1 KiB loads of the host-built image, beside the twiddle table's
+            auto* mel_lds = (__attribute__((address_space(3))) char*)s_melt;
+#pragma unroll
+            for (int k = 0; k < kMelLdsFloats / 256; ++k)
+                fe_dma16(reinterpret_cast<const char*>(tb.melw_lds) + 1024 * k + 16 * lane, mel_lds + 1024 * k);
         }
         if (!tile_dma) {
             // register staging (unaligned runs -- most compute_segments blocks): 256 threads, all loads of a thread issued before the
@@ -431,7 +451,10 @@ __device__ __forceinline__ void fe_main_body(const float* __restrict__ pcm, int6
 
         // 5. FFT stages 1..5 (wave-uniform twiddles straight from the table)
         fe::cf a[fe::kRegs];
-        fe::phase_a_fast(xin, a, fe_const_table(tb.tw_re, pass), fe_const_table(tb.tw_im, pass));
+        if constexpr (kConstTw)
+            fe::phase_a_fast(xin, a, fe::TwConst{false}, fe::TwConst{true});
+        else
+            fe::phase_a_fast(xin, a, fe_const_table(tb.tw_re, pass), fe_const_table(tb.tw_im, pass));
 
         float pw[2][8];
         float p256 = 0.0f;
@@ -477,6 +500,16 @@ __device__ __forceinline__ void fe_main_body(const float* __restrict__ pcm, int6
         // 7. sparse mel: lane pm = p owns filters m = 16*rd + p; sequential sum += w*P (mel.rs:92-104)
         // 8. ln(max(x, 1e-5)) (mel.rs:124-128) and LFR scatter (lfr.rs:18-54)
         float vals[STDMEL ? 5 : kMaxMelRounds];
+        // kLdsMel: the lane's 40 weights come from the LDS image, ten 16-byte reads (fe::mel_lds_index: the 16 lanes of a frame read 16
+        // consecutive slots, every bank once; the four frames of the wave read the same addresses), each the lane's base plus an immediate
+        float wl[kLdsMel ? fe::kMelLdsWeights : 1];
+        if constexpr (kLdsMel) {
+#pragma unroll
+            for (int j = 0; j < fe::kMelLdsChunks; ++j) {
+                const float4 c = *reinterpret_cast<const float4*>(s_melt + fe::mel_lds_index(4 * j, p));
+                wl[4 * j] = c.x, wl[4 * j + 1] = c.y, wl[4 * j + 2] = c.z, wl[4 * j + 3] = c.w;
+            }
+        }
 #pragma unroll
         for (int rd = 0; rd < (STDMEL ? 5 : kMaxMelRounds); ++rd) {
             vals[rd] = 0.0f;
@@ -491,7 +524,7 @@ __device__ __forceinline__ void fe_main_body(const float* __restrict__ pcm, int6
                 float w[17], pv[17];
 #pragma unroll
                 for (int t = 0; t < 17; ++t)
-                    if (t < kStdMelLen[rd < 5 ? rd : 0]) w[t] = wp[t * 16];
+                    if (t < kStdMelLen[rd < 5 ? rd : 0]) w[t] = kLdsMel ? wl[kLdsMel ? kStdMelOff[rd < 5 ? rd : 0] + t : 0] : wp[t * 16];
 #pragma unroll
                 for (int t = 0; t < 17; ++t)
                     if (t < kStdMelLen[rd < 5 ? rd : 0]) pv[t] = pp[t];
@@ -561,12 +594,12 @@ __device__ __forceinline__ void fe_main_body(const float* __restrict__ pcm, int6
     run_pass(PASSES - 1, std::false_type{});
 }
 
-template <int MODE, bool STDMEL, bool FUSED>
+template <int MODE, bool STDMEL, bool FUSED, int OPT = 0>
 __global__ __launch_bounds__(256) void fe_main_kernel(const float* __restrict__ pcm, int64_t utt_stride, int64_t num_frames, int64_t t_lfr,
                                                       const float* __restrict__ means, FeDev tb, float* __restrict__ out,
                                                       float* __restrict__ logmel_out, int aligned16) {
     extern __shared__ float s_melw[];  // [mel_steps][16] (the table-driven mel loop only)
-    fe_main_body<MODE, STDMEL, FUSED, 4, false>(pcm, utt_stride, num_frames, t_lfr, means, tb, out, logmel_out, aligned16, s_melw,
+    fe_main_body<MODE, STDMEL, FUSED, 4, false, OPT>(pcm, utt_stride, num_frames, t_lfr, means, tb, out, logmel_out, aligned16, s_melw,
                                                 GridBlock{});
 }
 
@@ -578,14 +611,14 @@ __global__ __launch_bounds__(256) void fe_main_kernel(const float* __restrict__ 
 // block of table.  Everything after the lookup is fe_main_body on that segment alone, with the segment's own length
 // for the float4 / scalar clamp and its own alignment, so each segment's rows are those compute() gives for it, bit for bit.
 // ------------------------------------------------------------------------------------------------------
-template <int MODE, bool STDMEL>
+template <int MODE, bool STDMEL, int OPT = 0>
 __global__ __launch_bounds__(256) void fe_seg_main_kernel(const float* __restrict__ pcm, const FeSeg* __restrict__ segs,
                                                           const int* __restrict__ blk_seg, FeDev tb, float* __restrict__ out) {
     extern __shared__ float s_melw[];
     const FeSeg s = segs[blk_seg[blockIdx.x]];
     const float* base = pcm + s.start;
     const int aligned16 = (((uintptr_t)base & 15) == 0) && (s.len % 4 == 0);  // per block: the segment's own alignment and length
-    fe_main_body<MODE, STDMEL, true, 4, false>(base, s.len, s.num_frames, s.t_lfr, nullptr, tb, out + s.row0 * (tb.n_mels * tb.lfr_m),
+    fe_main_body<MODE, STDMEL, true, 4, false, OPT>(base, s.len, s.num_frames, s.t_lfr, nullptr, tb, out + s.row0 * (tb.n_mels * tb.lfr_m),
                                                nullptr, aligned16, s_melw, SegBlock{(unsigned)(blockIdx.x - s.block0)});
 }
 // ------------------------------------------------------------------------------------------------------
@@ -846,7 +879,7 @@ struct StreamBlock {
     __device__ __forceinline__ unsigned x() const { return bx; }
     __device__ __forceinline__ unsigned y() const { return 0u; }
 };
-template <int MODE, bool STDMEL>
+template <int MODE, bool STDMEL, int OPT = 0>
 __global__ __launch_bounds__(256) void fe_stream_main_kernel(const float* __restrict__ pcm_state, int64_t pcm_pitch,
                                                              const FeStreamRec* __restrict__ recs, const int* __restrict__ blk_stream, FeDev tb,
                                                              float* __restrict__ mel_state, int64_t mel_pitch) {
@@ -856,7 +889,7 @@ __global__ __launch_bounds__(256) void fe_stream_main_kernel(const float* __rest
     const float* base = pcm_state + (int64_t)s * pcm_pitch;  // 16-byte aligned: the region's base is, and the pitch is a multiple of 4
     const int64_t len = (int64_t)r.carry + r.chunk;
     const int aligned16 = len % 4 == 0;
-    fe_main_body<MODE, STDMEL, true, 4, false>(base, len, r.nf, 0, nullptr, tb, nullptr,
+    fe_main_body<MODE, STDMEL, true, 4, false, OPT>(base, len, r.nf, 0, nullptr, tb, nullptr,
                                                mel_state + (int64_t)s * mel_pitch + (int64_t)r.mel_carry * tb.n_mels, aligned16, s_melw,
                                                StreamBlock{(unsigned)(blockIdx.x - r.block0)});
 }
@@ -937,6 +970,7 @@ struct LeleFrontend {
     bool std_mel = false;  // mel bank has the default round structure (fully unrolled kernel variant)
     int dpp_mode = 0;  // 0: __shfl, 1: DPP row_ror (selected after a self-test)
     bool fused = true;  // frame sums computed inside fe_main_kernel (LELE_HIP_FE_FUSED=0 selects the two-kernel form)
+    int opt = 0;        // kFeConstTw | kFeLdsMel: the form of the default bank's fused kernels (0: every table read as before)
     // generic path tables (configs other than 400/160/512)
     const float* g_window = nullptr;
     const int* g_mstart = nullptr;
@@ -1153,6 +1187,12 @@ int lele_hip_frontend_create(LeleCtx* ctx, const LeleFeatureConfig* cfg, LeleFro
     rc |= upload(fe, tw, &d.tw);
     rc |= upload(fe, win, &d.window);
     rc |= upload(fe, melw, &d.melw);
+    {   // the default bank's weights as the kernel's LDS image: weight s = step_off[rd] + t of lane pm at [s / 4][pm][s % 4]
+        std::vector<float> img(kMelLdsFloats, 0.0f);
+        for (int sidx = 0; fe->std_mel && sidx < fe::kMelLdsWeights; ++sidx)
+            for (int pm = 0; pm < 16; ++pm) img[fe::mel_lds_index(sidx, pm)] = melw[sidx * 16 + pm];
+        rc |= upload(fe, img, &d.melw_lds);
+    }
     rc |= upload(fe, start_pad, &d.mel_start);
     rc |= upload(fe, step_off, &d.mel_step_off);
     if (rc) {
@@ -1167,9 +1207,28 @@ int lele_hip_frontend_create(LeleCtx* ctx, const LeleFeatureConfig* cfg, LeleFro
     // the on-device cross-check of the direct-to-LDS tile
     const char* envd = getenv("LELE_HIP_FE_TILE_DMA");
     d.tile_dma = envd && *envd ? atoi(envd) != 0 : 1;
+    // product switches, same bits either way: LELE_HIP_FE_CONST_TW=0 keeps the kernels that read every twiddle from the table -- also
+    // what a table that differs from the compiled-in constants in any bit selects (another libm; "mismatch" is the tests' way to get
+    // there) -- and LELE_HIP_FE_LDS_TABLES=0 keeps the mel weights in global memory
+    const char* envc = getenv("LELE_HIP_FE_CONST_TW");
+    const char* envl = getenv("LELE_HIP_FE_LDS_TABLES");
+    bool const_tw = fe::tw_const_matches(twr.data(), twi.data());
+    if (envc && !strcmp(envc, "mismatch")) {
+        std::vector<float> other = twr;
+        other[fe::tw_off(5) + 3] = nextafterf(other[fe::tw_off(5) + 3], 2.0f);
+        const_tw = fe::tw_const_matches(other.data(), twi.data());
+    } else if (envc && *envc && atoi(envc) == 0) {
+        const_tw = false;
+    }
+    if (const_tw && fe->std_mel && fe->fused && fe->dpp_mode == 1)
+        fe->opt = kFeConstTw | ((envl && *envl && atoi(envl) == 0) ? 0 : kFeLdsMel);
     *out = fe;
     return 0;
 }
+
+/* test hook (not part of include/lele_hip.h): the form frontend_create selected for the default bank's fused kernels -- bit 0: phase A's
+ * twiddles are compiled-in constants, bit 1: the mel weights are read from LDS; 0: the table-reading kernels */
+int lele_hip_frontend_kernel_form(const LeleFrontend* fe) { return fe ? fe->opt : -1; }
 
 int lele_hip_frontend_destroy(LeleFrontend* fe) {
     if (!fe) return 0;
@@ -1334,16 +1393,16 @@ static int fe_run(LeleFrontend* fe, const LeleTensor* pcm, int64_t batch, int64_
                            (float*)dmean + c0 * nf, aligned16);
     }
     if (ev) LELE_HIP_CHECK(hipEventRecord(ev[1], ctx->stream));
-    const size_t mel_lds = (size_t)fe->dev.mel_steps * 16 * sizeof(float);
-#define FE_LAUNCH(MODE, STD, FUS)                                                                                                    \
-    hipLaunchKernelGGL((fe_main_kernel<MODE, STD, FUS>), grid, dim3(256), mel_lds, ctx->stream, cpcm, pcm_len, nf, t_lfr, cmean, fe->dev, \
+    const size_t mel_lds = fe->opt ? 0 : (size_t)fe->dev.mel_steps * 16 * sizeof(float);  // (the table-driven mel loop's; opt != 0: its own static tables instead)
+#define FE_LAUNCH(MODE, STD, FUS, OPT)                                                                                               \
+    hipLaunchKernelGGL((fe_main_kernel<MODE, STD, FUS, OPT>), grid, dim3(256), mel_lds, ctx->stream, cpcm, pcm_len, nf, t_lfr, cmean, fe->dev, \
                        o, lm, aligned16)
 #define FE_LAUNCH2(MODE, STD) \
     do {                      \
         if (fe->fused)        \
-            FE_LAUNCH(MODE, STD, true); \
+            FE_LAUNCH(MODE, STD, true, 0); \
         else                  \
-            FE_LAUNCH(MODE, STD, false); \
+            FE_LAUNCH(MODE, STD, false, 0); \
     } while (0)
     for (int64_t c0 = 0; c0 < batch; c0 += kMaxGridY) {  // every chunk's utterances land where the one launch would put them
         const dim3 grid((unsigned)((nf + 63) / 64), (unsigned)std::min<int64_t>(kMaxGridY, batch - c0));
@@ -1351,7 +1410,11 @@ static int fe_run(LeleFrontend* fe, const LeleTensor* pcm, int64_t batch, int64_
         const float* cmean = (const float*)dmean + c0 * nf;
         float* o = want_logmel ? nullptr : (float*)out->data + c0 * t_lfr * cols;
         float* lm = want_logmel ? (float*)out->data + c0 * nf * fe->cfg.n_mels : nullptr;
-        if (fe->dpp_mode == 1) {
+        if (fe->opt == (kFeConstTw | kFeLdsMel)) {  // (opt != 0: the default bank, fused, DPP -- frontend_create)
+            FE_LAUNCH(1, true, true, kFeConstTw | kFeLdsMel);
+        } else if (fe->opt == kFeConstTw) {
+            FE_LAUNCH(1, true, true, kFeConstTw);
+        } else if (fe->dpp_mode == 1) {
             if (fe->std_mel) FE_LAUNCH2(1, true); else FE_LAUNCH2(1, false);
         } else {
             if (fe->std_mel) FE_LAUNCH2(0, true); else FE_LAUNCH2(0, false);
@@ -1489,7 +1552,7 @@ int lele_hip_frontend_compute_segments(LeleFrontend* fe, const LeleTensor* pcm, 
     for (int64_t i = 0; i < count; ++i) nseg += lengths[i] >= fe->frame_len;
     const FeSeg* dsegs = (const FeSeg*)table;
     const int* dblk = (const int*)(dsegs + nseg);
-    const size_t mel_lds = (size_t)fe->dev.mel_steps * 16 * sizeof(float);
+    const size_t mel_lds = fe->opt ? 0 : (size_t)fe->dev.mel_steps * 16 * sizeof(float);  // (the table-driven mel loop's; opt != 0: its own static tables instead)
     // lele_hip_last_route: the kernel, then the tile staging of its blocks -- fe_seg_main_kernel's own per-segment condition, evaluated
     // here on the same values; one name for a launch that holds both kinds
     int64_t n_dma = 0;
@@ -1497,10 +1560,14 @@ int lele_hip_frontend_compute_segments(LeleFrontend* fe, const LeleTensor* pcm, 
         if (lengths[i] >= fe->frame_len)
             n_dma += (((uintptr_t)((const float*)dpcm + starts[i]) & 15) == 0) && (lengths[i] % 4 == 0) && fe->dev.tile_dma;
     ctx->set_route(fe->std_mel ? "fe.seg_std" : "fe.seg_table", n_dma == nseg ? "fe.tile_dma" : n_dma == 0 ? "fe.tile_regs" : "fe.tile_mixed");
-#define FE_SEG_LAUNCH(MODE, STD)                                                                                                 \
-    hipLaunchKernelGGL((fe_seg_main_kernel<MODE, STD>), dim3((unsigned)blocks), dim3(256), mel_lds, ctx->stream, (const float*)dpcm, \
+#define FE_SEG_LAUNCH(MODE, STD, ...)                                                                                            \
+    hipLaunchKernelGGL((fe_seg_main_kernel<MODE, STD, ##__VA_ARGS__>), dim3((unsigned)blocks), dim3(256), mel_lds, ctx->stream, (const float*)dpcm, \
                        dsegs, dblk, fe->dev, o)
-    if (fe->dpp_mode == 1) {
+    if (fe->opt == (kFeConstTw | kFeLdsMel)) {
+        FE_SEG_LAUNCH(1, true, kFeConstTw | kFeLdsMel);
+    } else if (fe->opt == kFeConstTw) {
+        FE_SEG_LAUNCH(1, true, kFeConstTw);
+    } else if (fe->dpp_mode == 1) {
         if (fe->std_mel) FE_SEG_LAUNCH(1, true); else FE_SEG_LAUNCH(1, false);
     } else {
         if (fe->std_mel) FE_SEG_LAUNCH(0, true); else FE_SEG_LAUNCH(0, false);
@@ -1745,11 +1812,15 @@ int lele_hip_frontend_stream_push(LeleFrontendStream* st, const LeleTensor* pcm,
     } else if (n_live) {
         // lele_hip_last_route: this is the segment kernel's body over the streams' regions, so it reports the segment names
         ctx->set_route(fe->std_mel ? "fe.seg_std" : "fe.seg_table", n_dma == n_live ? "fe.tile_dma" : n_dma == 0 ? "fe.tile_regs" : "fe.tile_mixed");
-        const size_t mel_lds = (size_t)fe->dev.mel_steps * 16 * sizeof(float);
-#define FE_STREAM_LAUNCH(MODE, STD)                                                                                                \
-    hipLaunchKernelGGL((fe_stream_main_kernel<MODE, STD>), dim3((unsigned)blk.size()), dim3(256), mel_lds, ctx->stream,              \
+        const size_t mel_lds = fe->opt ? 0 : (size_t)fe->dev.mel_steps * 16 * sizeof(float);  // (the table-driven mel loop's; opt != 0: its own static tables instead)
+#define FE_STREAM_LAUNCH(MODE, STD, ...)                                                                                           \
+    hipLaunchKernelGGL((fe_stream_main_kernel<MODE, STD, ##__VA_ARGS__>), dim3((unsigned)blk.size()), dim3(256), mel_lds, ctx->stream,              \
                        (const float*)st->pcm_state, st->pcm_pitch, drecs, dblk, fe->dev, st->mel_state, st->mel_pitch)
-        if (fe->dpp_mode == 1) {
+        if (fe->opt == (kFeConstTw | kFeLdsMel)) {
+            FE_STREAM_LAUNCH(1, true, kFeConstTw | kFeLdsMel);
+        } else if (fe->opt == kFeConstTw) {
+            FE_STREAM_LAUNCH(1, true, kFeConstTw);
+        } else if (fe->dpp_mode == 1) {
             if (fe->std_mel) FE_STREAM_LAUNCH(1, true); else FE_STREAM_LAUNCH(1, false);
         } else {
             if (fe->std_mel) FE_STREAM_LAUNCH(0, true); else FE_STREAM_LAUNCH(0, false);
