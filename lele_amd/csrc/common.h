@@ -209,6 +209,7 @@ struct LeleCtx {
         route[1] = op;
         route[2] = core;
     }
+    void set_route_family(const char* family) { route[0] = family; }  // in front of what set_route recorded ("ci.f32/conv.gemm_tap/...")
 
     // two library-owned result buffers for ops that fall back to an unfused sequence and need somewhere to put the intermediate
     // (add3 / fused_quantized_linear_residual with an operand that broadcasts OUTWARD: the in-place second pass is not possible)

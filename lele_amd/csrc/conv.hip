@@ -1431,237 +1431,249 @@ int window_frags(LeleCtx* ctx, const LeleTensor* wt, const float* dw, const Conv
     });
 }
 
-int run_conv2d(LeleCtx* ctx, const LeleTensor* wt, const float* dx, const float* dw, const float* db, ConvGeom g, int act,
-               float* out) {
-    ctx->set_route(nullptr);
-    if ((int64_t)g.n * g.oc * g.plane == 0) return 0;
-    // no input channels (K = 0): the result is bias + activation (+ residual), which the implicit GEMM's epilogue alone produces
-    // (gemm::launch reads no operand then); every other route assumes at least one channel chunk
-    const bool empty_k = g.K == 0;
-    const bool pitched = (g.xbs != 0 && g.xbs != (long long)g.c * g.ih * g.iw) || (g.obs != 0 && g.obs != (long long)g.oc * g.plane);
-    if (g.xbs == 0) g.xbs = (long long)g.c * g.ih * g.iw;
-    if (g.obs == 0) g.obs = (long long)g.oc * g.plane;
-    LELE_REQUIRE(!pitched || g.group == 1, "conv2d: channel views (a batch pitch) are supported for group == 1 only");
+// ---- the dispatch of a 2-D convolution: conv_route() decides, run_conv2d() switches over its verdict, one body per route below.
+// In every body ONE table row (or one statement) holds both the kernel that is launched and the name that is reported.
+enum class ConvKind { DwLds, DwRow4, DwGeneric, Win, WinS2, Direct, GemmPw, GemmTap, GemmGeneric };  // in the order they are tried
+struct ConvRoute {
+    ConvKind kind;
+    int oct = 0;             // Win / WinS2: output channels a block (32 or 64; 128 for a 1 x 1)
+    int ocb = 0;             // Direct: output channels a thread (8 or 16)
+    int64_t pb = 0;          // DwLds: planes a workgroup
+    bool dw_direct = false;  // DwLds: rows a multiple of four wide are stored straight from registers, only the input planes need LDS
+};
+
+// Which kernel family runs g (xbs / obs filled in, the result not empty).  Launches nothing, touches no cache; the only reader of
+// the w1_* / win_min_* thresholds, of the CU count as a threshold and of the NO_LDS / NO_S2_WINDOW / OCT128 switches.
+ConvRoute conv_route(const LeleCtx* ctx, const ConvGeom& g, bool pitched, const float* out) {
+    ConvRoute r{};
+    const int64_t cus = ctx->num_cus;
     if (g.icg == 1 && g.ocg == 1 && !pitched) {
-        const int64_t total = (int64_t)g.n * g.oc * g.plane;
-        LELE_REQUIRE(total < (int64_t(1) << 32), "depthwise conv: more than 2^32 output elements");
-        const unsigned ngroups = (unsigned)((g.ow + 3) / 4);
-        const int64_t threads = (int64_t)g.n * g.oc * g.oh * ngroups;
-        const DwGeom dg{g.ih, g.iw, g.oh, g.ow, g.oc, g.kh, g.sh, g.dh, g.pt, g.pl, g.plane & ~7};
-        const dim3 rgrid((unsigned)((threads + 255) / 256));
-#define LELE_DW_ROW(KW) \
-    hipLaunchKernelGGL(depthwise_row4_kernel<KW>, rgrid, dim3(256), 0, ctx->stream, dx, dw, db, out, dg, act, (unsigned)threads, ngroups)
-        const bool row_ok = g.sw == 1 && g.dw == 1 && g.ow >= 8 && threads < (int64_t(1) << 31);
+        const int64_t threads = (int64_t)g.n * g.oc * g.oh * ((g.ow + 3) / 4), planes = (int64_t)g.n * g.oc;
+        const bool row_ok = g.sw == 1 && g.dw == 1 && g.ow >= 8 && threads < (int64_t(1) << 31) && (g.kw == 3 || g.kw == 5 || g.kw == 7 || g.kw == 11);
         // planes per workgroup for the LDS-staged form: input + output planes within 64 KB, enough workgroups to fill the chip
-        // (rows a multiple of four wide are stored straight from registers: then only the input planes need LDS)
-        const bool dw_direct = (g.ow & 3) == 0 && (g.plane & 3) == 0 && (((uintptr_t)out) & 15) == 0;
-        const int64_t ihw = (int64_t)g.ih * g.iw, plane_floats = ihw + (dw_direct ? 0 : g.plane) + 8, planes = (int64_t)g.n * g.oc;
+        r.dw_direct = (g.ow & 3) == 0 && (g.plane & 3) == 0 && (((uintptr_t)out) & 15) == 0;
+        const int64_t plane_floats = (int64_t)g.ih * g.iw + (r.dw_direct ? 0 : g.plane) + 8;
         int64_t pb = (16 * 1024 - 8) / plane_floats;
         // ... but no more planes than 16 KB worth (one plane if it is larger): a workgroup copies its planes in and only then computes, so
         // what overlaps one workgroup's copy with another's arithmetic is the number of workgroups a CU holds (80 x 80 planes over 64
         // images: two planes a workgroup 119 us, one 84; 40 x 40: five 44 us, two 37.5)
         if (pb >= 1) pb = std::max<int64_t>(1, std::min<int64_t>(pb, ((int64_t)conv_env("LELE_HIP_DW_LDS_KB", 16) * 256 - 8) / plane_floats));
-        while (pb > 1 && (planes + pb - 1) / pb < 4 * (int64_t)ctx->num_cus) pb = (pb + 1) / 2;
-        const bool lds_ok = row_ok && pb >= 1 && (g.kw == 3 || g.kw == 5 || g.kw == 7 || g.kw == 11) && !lab_env("LELE_HIP_DW_NO_LDS");
-        if (lds_ok) {
-            const size_t lds = (size_t)((((pb * ihw + 3) & ~int64_t(3)) + (dw_direct ? 0 : pb * g.plane)) * 4);
-            const dim3 lgrid((unsigned)((planes + pb - 1) / pb));
-#define LELE_DW_LDS(KW) \
-    hipLaunchKernelGGL(depthwise_lds_kernel<KW>, lgrid, dim3(256), lds, ctx->stream, dx, dw, db, out, dg, act, (unsigned)planes, \
-                       (unsigned)pb, ngroups)
-            static const char* const names[2][4] = {{"conv.dw_lds_k3", "conv.dw_lds_k5", "conv.dw_lds_k7", "conv.dw_lds_k11"},
-                                                    {"conv.dw_lds_k3_direct", "conv.dw_lds_k5_direct", "conv.dw_lds_k7_direct", "conv.dw_lds_k11_direct"}};
-            if (g.kw == 3) LELE_DW_LDS(3);
-            else if (g.kw == 5) LELE_DW_LDS(5);
-            else if (g.kw == 7) LELE_DW_LDS(7);
-            else LELE_DW_LDS(11);
-            ctx->set_route(names[dw_direct][g.kw == 3 ? 0 : g.kw == 5 ? 1 : g.kw == 7 ? 2 : 3]);
-#undef LELE_DW_LDS
-        } else if (row_ok && g.kw == 3) {
-            LELE_DW_ROW(3);
-            ctx->set_route("conv.dw_row4_k3");
-        } else if (row_ok && g.kw == 5) {
-            LELE_DW_ROW(5);
-            ctx->set_route("conv.dw_row4_k5");
-        } else if (row_ok && g.kw == 7) {
-            LELE_DW_ROW(7);
-            ctx->set_route("conv.dw_row4_k7");
-        } else if (row_ok && g.kw == 11) {
-            LELE_DW_ROW(11);
-            ctx->set_route("conv.dw_row4_k11");
-#undef LELE_DW_ROW
-        } else {
-            hipLaunchKernelGGL(depthwise_conv2d_kernel, dim3(grid_for(total)), dim3(256), 0, ctx->stream, dx, dw, db, out, g, act,
-                               (unsigned)total);
-            ctx->set_route("conv.dw_generic");
-        }
-        if (g.res)
-            hipLaunchKernelGGL(conv_residual_kernel, dim3((unsigned)std::min<int64_t>(((int64_t)g.oc * g.plane + 255) / 256, 1024), (unsigned)g.n),
-                               dim3(256), 0, ctx->stream, out, g.res, (unsigned)((int64_t)g.oc * g.plane), g.obs, g.rbs);
-    } else if (g.group == 1 && !empty_k &&
-               ((g.kh == 3 && g.kw == 3) ||
-                // 1 x 1: where it measured faster than the tiled GEMM on the Yolo-shaped network at batch 64 (w1_max_oc() and friends above)
-                (g.kh == 1 && g.kw == 1 && g.pt == 0 && g.pl == 0 && g.oh == g.ih && g.ow == g.iw && g.oc <= w1_max_oc() && g.plane >= w1_min_plane() &&
-                 g.c >= w1_min_c())) &&
-               g.dh == 1 && g.dw == 1 && g.sh == 1 && g.sw == 1 && g.c % 16 == 0 && (g.oc > 16 || (g.oc > win_min_oc_narrow() && g.c >= win_min_c_narrow())) && g.ow >= 16 && g.n <= 65535 &&
-               (int64_t)g.c * g.ih * g.iw < (int64_t(1) << 31) &&
-               (int64_t)g.n * ((g.oc + 63) / 64) * (((int64_t)g.plane + 255) / 256) >= (int64_t)ctx->num_cus / 2) {
+        while (pb > 1 && (planes + pb - 1) / pb < 4 * cus) pb = (pb + 1) / 2;
+        r.pb = pb;
+        r.kind = !row_ok ? ConvKind::DwGeneric : pb >= 1 && !lab_env("LELE_HIP_DW_NO_LDS") ? ConvKind::DwLds : ConvKind::DwRow4;
+        return r;
+    }
+    // what the window and the direct kernels share: one group with channels to multiply (K = 0 is the GEMM's: its epilogue alone
+    // produces bias + activation (+ residual), gemm::launch reads no operand then), taps side by side, rows of 16 outputs, images in grid.y
+    const bool batch = g.group == 1 && g.K != 0 && g.dh == 1 && g.dw == 1 && g.ow >= 16 && g.n <= 65535, k3 = g.kh == 3 && g.kw == 3;
+    const bool chunks16 = g.c % 16 == 0 && (int64_t)g.c * g.ih * g.iw < (int64_t(1) << 31);  // the window kernels' 16-channel chunks, 32-bit offsets
+    const bool pointwise = g.kh == 1 && g.kw == 1 && g.pt == 0 && g.pl == 0 && g.oh == g.ih && g.ow == g.iw;
+    if (batch && chunks16 && g.sh == 1 && g.sw == 1 &&
+        // 1 x 1: where it measured faster than the tiled GEMM on the Yolo-shaped network at batch 64 (w1_max_oc() and friends above)
+        (k3 || (pointwise && g.oc <= w1_max_oc() && g.plane >= w1_min_plane() && g.c >= w1_min_c())) &&
+        (g.oc > 16 || (g.oc > win_min_oc_narrow() && g.c >= win_min_c_narrow())) &&
+        (int64_t)g.n * ((g.oc + 63) / 64) * (((int64_t)g.plane + 255) / 256) >= cus / 2) {
         // stride 1 over a batch, 16-channel chunks: the window-once MFMA kernel (see conv_window_p_kernel); 32-channel blocks when that
         // wastes fewer output channels than 64-channel ones
-        const int taps = g.kh * g.kw;
+        r.kind = ConvKind::Win;
+        r.oct = ((g.oc + 31) / 32) * 32 < ((g.oc + 63) / 64) * 64 ? 32 : 64;
         // ... and when 64-channel blocks would not give every CU its two workgroups (256 -> 64 channels at 20 x 20 x 64 images: 115 us
         // with 256 workgroups of 64 channels, 78 with 512 of 32)
-        int oct = ((g.oc + 31) / 32) * 32 < ((g.oc + 63) / 64) * 64 ? 32 : 64;
-        if (oct == 64) {
-            const int ow_ = taps == 1 ? g.plane : g.ow, oh_ = taps == 1 ? 1 : g.oh;
-            const WinTile t64 = pick_win_tile(ow_, oh_, 256, g.kh, 1, taps == 9 ? C3M<3>::POS : C3M<1>::POS, (int64_t)g.n * ((g.oc + 63) / 64), ctx->num_cus);
-            if ((int64_t)g.n * ((g.oc + 63) / 64) * t64.tiles_x * ((oh_ + t64.th - 1) / t64.th) < 2 * (int64_t)ctx->num_cus) oct = 32;
+        if (r.oct == 64) {
+            const int ow_ = k3 ? g.ow : g.plane, oh_ = k3 ? g.oh : 1;  // (a 1 x 1's plane is one row: see run_window)
+            const WinTile t64 = pick_win_tile(ow_, oh_, 256, g.kh, 1, k3 ? C3M<3>::POS : C3M<1>::POS, (int64_t)g.n * ((g.oc + 63) / 64), ctx->num_cus);
+            if ((int64_t)g.n * ((g.oc + 63) / 64) * t64.tiles_x * ((oh_ + t64.th - 1) / t64.th) < 2 * cus) r.oct = 32;
         }
         // 1 x 1 with more than one block of output channels: blocks of 128 over tiles of 128 positions, so that the window is fetched and
         // split once per 128 channels (where the tiles still go round the chip twice, and no more than a quarter of the block is padding).
         // Same call, batch 64: 96 -> 128 at 80 x 80 148 -> 139 us, 384 -> 128 at 40 x 40 92 -> 82, 512 / 384 / 256 / 128 -> 256 at 20 x 20
         // -10 ... -11 %; 80 output channels (48 of 128 padding) +4 ... +7 %: those keep their 64- / 32-channel blocks
-        if (taps == 1 && (g.oc + oct - 1) / oct >= 2 && ((g.oc + 127) / 128) * 128 * 4 <= g.oc * 5 && conv_env("LELE_HIP_CONV_OCT128", 1) != 0 &&
-            (int64_t)g.n * ((g.oc + 127) / 128) * (((int64_t)g.plane + 127) / 128) >= 2 * (int64_t)ctx->num_cus)
-            oct = 128;
-        const int positions = oct == 128 ? 128 : 256;
-        const size_t wbytes = oct == 128 ? (size_t)(((g.oc + 127) / 128) * 4) * (g.c / 16) * taps * 3 * 1024  // whole blocks: the padding tiles are zeros
-                                         : (size_t)((g.oc + 31) / 32) * (g.c / 16) * taps * 3 * 1024 + (size_t)(g.c / 16) * taps * 3 * 1024;  // (+ one padding tile)
-        void* dwf = nullptr;
-        LELE_TRY(window_frags(ctx, wt, dw, g, taps, oct, wbytes, &dwf));
-        // a 1 x 1 convolution has no rows: its plane is ONE row, cut into tiles of 256 positions (only the last one has padding)
-        if (taps == 1) {
-            g.ih = g.oh = 1;
-            g.iw = g.ow = g.plane;
-        }
-#ifdef LELE_HIP_LAB
-        g.dh |= conv_env("LELE_HIP_CONV_KO", 0) << 8;  // the window kernels never read the dilation (it is 1 here): lab knock-out flags ride in it
-#endif
-        ConvEpi epi{out, db, g, act};
-#ifdef LELE_HIP_LAB
-        if (const char* e = lab_env("LELE_HIP_CONV_STAMPS")) epi.dbg = (long long*)(uintptr_t)strtoull(e, nullptr, 0);
-#endif
-        const WinTile tile = pick_win_tile(g.ow, g.oh, positions, g.kh, 1, taps == 9 ? C3M<3>::POS : C3M<1>::POS, (int64_t)g.n * ((g.oc + oct - 1) / oct),
-                                           ctx->num_cus);
-        // at most two workgroups per CU, each walking through its share of the items (see conv_window_p_kernel)
-        const int ntiles = tile.tiles_x * ((g.oh + tile.th - 1) / tile.th), nblocks = (g.oc + oct - 1) / oct;
-        const int osplit = (int64_t)g.n * ntiles >= 2 * (int64_t)ctx->num_cus ? 1 : nblocks, nocb = nblocks / osplit;
-        const int64_t items = (int64_t)g.n * ntiles * osplit;
-        LELE_REQUIRE(items < (int64_t(1) << 31), "conv2d: more than 2^31 tiles");
-        const dim3 pgrid((unsigned)std::min<int64_t>(items, conv_env("LELE_HIP_CONV_WG_PER_CU", 2) * (int64_t)ctx->num_cus));
-#define LELE_CW(KS_, OCT_)                                                                                                              \
-    do {                                                                                                                                \
-        auto kern = conv_window_p_kernel<KS_, OCT_>;                                                                                     \
-        LELE_HIP_CHECK(lele::ensure_dyn_lds(reinterpret_cast<const void*>(kern), 2 * C3M<KS_>::STAGE));                                  \
-        hipLaunchKernelGGL(kern, pgrid, dim3(512), 2 * C3M<KS_>::STAGE, ctx->stream, dx, (const cu32x4*)dwf, epi, tile, ntiles, nocb, osplit, \
-                           (int)items);                                                                                                 \
-    } while (0)
-        if (taps == 9) {
-            if (oct == 64) LELE_CW(3, 64);
-            else LELE_CW(3, 32);
-        } else {
-            if (oct == 128) LELE_CW(1, 128);
-            else if (oct == 64) LELE_CW(1, 64);
-            else LELE_CW(1, 32);
-        }
-#undef LELE_CW
-        static const char* const names[2][2][3] = {
-            {{"conv.win1_oct32", "conv.win1_oct64", "conv.win1_oct128"}, {"conv.win1_oct32_osplit", "conv.win1_oct64_osplit", "conv.win1_oct128_osplit"}},
-            {{"conv.win3_oct32", "conv.win3_oct64", nullptr}, {"conv.win3_oct32_osplit", "conv.win3_oct64_osplit", nullptr}}};
-        ctx->set_route(names[taps == 9][osplit > 1][oct == 32 ? 0 : oct == 64 ? 1 : 2]);
-    } else if (g.group == 1 && !empty_k && g.kh == 3 && g.kw == 3 && g.dh == 1 && g.dw == 1 && g.sh == 2 && g.sw == 2 && g.c % 16 == 0 && g.oc > 16 &&
-               g.ow >= 16 && g.n <= 65535 && (int64_t)g.c * g.ih * g.iw < (int64_t(1) << 31) &&
-               (int64_t)g.n * ((g.oc + 63) / 64) * (((int64_t)g.plane + 127) / 128) >= 2 * (int64_t)ctx->num_cus &&
-               !lab_env("LELE_HIP_CONV_NO_S2_WINDOW")) {
+        if (!k3 && (g.oc + r.oct - 1) / r.oct >= 2 && ((g.oc + 127) / 128) * 128 * 4 <= g.oc * 5 && conv_env("LELE_HIP_CONV_OCT128", 1) != 0 &&
+            (int64_t)g.n * ((g.oc + 127) / 128) * (((int64_t)g.plane + 127) / 128) >= 2 * cus)
+            r.oct = 128;
+    } else if (batch && chunks16 && k3 && g.sh == 2 && g.sw == 2 && g.oc > 16 &&
+               (int64_t)g.n * ((g.oc + 63) / 64) * (((int64_t)g.plane + 127) / 128) >= 2 * cus && !lab_env("LELE_HIP_CONV_NO_S2_WINDOW")) {
         // stride 2 over a batch: the de-interleaved window kernel (see conv_window_s2_kernel); weights as for the stride-1 kernel,
         // blocks of 32 output channels when that wastes fewer of them than blocks of 64
-        const int oct = ((g.oc + 31) / 32) * 32 < ((g.oc + 63) / 64) * 64 ? 32 : 64;
-        const size_t wbytes = (size_t)((g.oc + 31) / 32) * (g.c / 16) * 9 * 3 * 1024 + (oct == 64 ? (size_t)(g.c / 16) * 9 * 3 * 1024 : 0);
-        void* dwf = nullptr;
-        LELE_TRY(window_frags(ctx, wt, dw, g, 9, oct, wbytes, &dwf));
-        ConvEpi epi{out, db, g, act};
-        const WinTile tile = pick_win_tile(g.ow, g.oh, 128, 3, 2, C3S2::POS, (int64_t)g.n * ((g.oc + oct - 1) / oct), ctx->num_cus);
-        const int ntiles = tile.tiles_x * ((g.oh + tile.th - 1) / tile.th), nblocks = (g.oc + oct - 1) / oct;
-        const int osplit = (int64_t)g.n * ntiles >= 2 * (int64_t)ctx->num_cus ? 1 : nblocks, nocb = nblocks / osplit;
-        const int64_t items = (int64_t)g.n * ntiles * osplit;
-        LELE_REQUIRE(items < (int64_t(1) << 31), "conv2d: more than 2^31 tiles");
-        const dim3 pgrid((unsigned)std::min<int64_t>(items, conv_env("LELE_HIP_CONV_WG_PER_CU", 2) * (int64_t)ctx->num_cus));
-        if (oct == 64) {
-            auto kern = conv_window_s2_kernel<64>;
-            LELE_HIP_CHECK(lele::ensure_dyn_lds(reinterpret_cast<const void*>(kern), C3S2::STAGE));
-            hipLaunchKernelGGL(kern, pgrid, dim3(512), C3S2::STAGE, ctx->stream, dx, (const cu32x4*)dwf, epi, tile, ntiles, nocb, osplit, (int)items);
-        } else {
-            auto kern = conv_window_s2_kernel<32>;
-            LELE_HIP_CHECK(lele::ensure_dyn_lds(reinterpret_cast<const void*>(kern), C3S2::STAGE));
-            hipLaunchKernelGGL(kern, pgrid, dim3(512), C3S2::STAGE, ctx->stream, dx, (const cu32x4*)dwf, epi, tile, ntiles, nocb, osplit, (int)items);
-        }
-        static const char* const names[2][2] = {{"conv.win3s2_oct32", "conv.win3s2_oct64"}, {"conv.win3s2_oct32_osplit", "conv.win3s2_oct64_osplit"}};
-        ctx->set_route(names[osplit > 1][oct == 64]);
-    } else if (g.group == 1 && !empty_k && g.kh == 3 && g.kw == 3 && g.dh == 1 && g.dw == 1 && g.sh == g.sw && (g.sh == 1 || g.sh == 2) && g.oc <= 16 &&
-               g.c <= 64 && g.ow >= 16 && g.n <= 65535 &&
-               (int64_t)g.n * ((g.ow + 31) / 32) * ((g.oh + 7) / 8) >= 2 * (int64_t)ctx->num_cus) {
+        r.kind = ConvKind::WinS2;
+        r.oct = ((g.oc + 31) / 32) * 32 < ((g.oc + 63) / 64) * 64 ? 32 : 64;
+    } else if (batch && k3 && g.sh == g.sw && (g.sh == 1 || g.sh == 2) && g.oc <= 16 && g.c <= 64 &&
+               (int64_t)g.n * ((g.ow + 31) / 32) * ((g.oh + 7) / 8) >= 2 * cus) {
         // few channels over a batch: the direct kernel (see conv3x3_direct_kernel).  Measured on the Yolo-shaped network at batch 64
         // against the implicit GEMM: 3 -> 16 stride 2 at 320 x 320: 227 against 579 us, 16 -> 8 at 160 x 160: 88 against 251,
         // 8 -> 16: ~95 against 180; with 32 output channels the MFMA tile is full and the GEMM wins (16 -> 32 stride 2: 322 against
         // 596), and one image does not fill the chip with 8 x 32 tiles -- both stay on the GEMM
-        const int ocb = g.oc <= 8 ? 8 : 16;
-        const size_t wbytes = (size_t)g.c * 9 * ocb * 4;
-        void* dwq = nullptr;
-        LELE_TRY(ctx->weight_form(wt, WeightForm::ConvDirect, {ocb}, wbytes, &dwq, [&](void* d) {
-            hipLaunchKernelGGL(conv3x3_wperm_kernel, dim3(grid_for((int64_t)g.c * 9 * ocb)), dim3(256), 0, ctx->stream, dw, (float*)d, g.oc, g.c, ocb);
+        r.kind = ConvKind::Direct;
+        r.ocb = g.oc <= 8 ? 8 : 16;
+    } else {
+        // the implicit GEMM: a pointwise convolution's B operand is plain column-major; otherwise tap-major K where the channels of a
+        // group come in fours; the general loader for the rest
+        r.kind = pointwise && g.sh == 1 && g.sw == 1 ? ConvKind::GemmPw : g.icg % 4 == 0 && g.K != 0 ? ConvKind::GemmTap : ConvKind::GemmGeneric;
+    }
+    return r;
+}
+
+inline int kw_slot(int kw) { return kw == 3 ? 0 : kw == 5 ? 1 : kw == 7 ? 2 : 3; }  // the depthwise kernels' widths: 3, 5, 7, 11
+
+int run_dw(LeleCtx* ctx, const ConvRoute& r, const float* dx, const float* dw, const float* db, const ConvGeom& g, int act, float* out) {
+    const int64_t total = (int64_t)g.n * g.oc * g.plane;
+    LELE_REQUIRE(total < (int64_t(1) << 32), "depthwise conv: more than 2^32 output elements");
+    const unsigned ngroups = (unsigned)((g.ow + 3) / 4);
+    const int64_t threads = (int64_t)g.n * g.oc * g.oh * ngroups, planes = (int64_t)g.n * g.oc;
+    const DwGeom dg{g.ih, g.iw, g.oh, g.ow, g.oc, g.kh, g.sh, g.dh, g.pt, g.pl, g.plane & ~7};
+    if (r.kind == ConvKind::DwLds) {
+        static const struct { decltype(&depthwise_lds_kernel<3>) kern; const char* name[2]; } lds_kernels[4] = {
+            {depthwise_lds_kernel<3>, {"conv.dw_lds_k3", "conv.dw_lds_k3_direct"}}, {depthwise_lds_kernel<5>, {"conv.dw_lds_k5", "conv.dw_lds_k5_direct"}},
+            {depthwise_lds_kernel<7>, {"conv.dw_lds_k7", "conv.dw_lds_k7_direct"}}, {depthwise_lds_kernel<11>, {"conv.dw_lds_k11", "conv.dw_lds_k11_direct"}}};
+        const auto& k = lds_kernels[kw_slot(g.kw)];
+        const size_t lds = (size_t)((((r.pb * g.ih * g.iw + 3) & ~int64_t(3)) + (r.dw_direct ? 0 : r.pb * g.plane)) * 4);
+        hipLaunchKernelGGL(k.kern, dim3((unsigned)((planes + r.pb - 1) / r.pb)), dim3(256), lds, ctx->stream, dx, dw, db, out, dg, act, (unsigned)planes,
+                           (unsigned)r.pb, ngroups);
+        ctx->set_route(k.name[r.dw_direct]);
+    } else if (r.kind == ConvKind::DwRow4) {
+        static const struct { decltype(&depthwise_row4_kernel<3>) kern; const char* name; } row_kernels[4] = {
+            {depthwise_row4_kernel<3>, "conv.dw_row4_k3"}, {depthwise_row4_kernel<5>, "conv.dw_row4_k5"},
+            {depthwise_row4_kernel<7>, "conv.dw_row4_k7"}, {depthwise_row4_kernel<11>, "conv.dw_row4_k11"}};
+        const auto& k = row_kernels[kw_slot(g.kw)];
+        hipLaunchKernelGGL(k.kern, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, ctx->stream, dx, dw, db, out, dg, act, (unsigned)threads, ngroups);
+        ctx->set_route(k.name);
+    } else {
+        hipLaunchKernelGGL(depthwise_conv2d_kernel, dim3(grid_for(total)), dim3(256), 0, ctx->stream, dx, dw, db, out, g, act, (unsigned)total);
+        ctx->set_route("conv.dw_generic");
+    }
+    if (g.res)  // these kernels have their own epilogues: the residual is a pass of its own behind them
+        hipLaunchKernelGGL(conv_residual_kernel, dim3((unsigned)std::min<int64_t>(((int64_t)g.oc * g.plane + 255) / 256, 1024), (unsigned)g.n),
+                           dim3(256), 0, ctx->stream, out, g.res, (unsigned)((int64_t)g.oc * g.plane), g.obs, g.rbs);
+    return 0;
+}
+
+// the window kernels: stride 1 (3 x 3 and 1 x 1: two stages of LDS) and stride 2, by taps, stride and block of output channels;
+// `positions` outputs a tile at the most whose window fits `slots` LDS slots; name[1] where the blocks of an item are split over workgroups
+struct WinKernel {
+    int taps, stride, oct;
+    decltype(&conv_window_s2_kernel<64>) kern;
+    int lds, positions, slots;
+    const char* name[2];
+};
+const WinKernel kWinKernels[] = {
+    {9, 1, 64, conv_window_p_kernel<3, 64>, 2 * C3M<3>::STAGE, 256, C3M<3>::POS, {"conv.win3_oct64", "conv.win3_oct64_osplit"}},
+    {9, 1, 32, conv_window_p_kernel<3, 32>, 2 * C3M<3>::STAGE, 256, C3M<3>::POS, {"conv.win3_oct32", "conv.win3_oct32_osplit"}},
+    {1, 1, 128, conv_window_p_kernel<1, 128>, 2 * C3M<1>::STAGE, 128, C3M<1>::POS, {"conv.win1_oct128", "conv.win1_oct128_osplit"}},
+    {1, 1, 64, conv_window_p_kernel<1, 64>, 2 * C3M<1>::STAGE, 256, C3M<1>::POS, {"conv.win1_oct64", "conv.win1_oct64_osplit"}},
+    {1, 1, 32, conv_window_p_kernel<1, 32>, 2 * C3M<1>::STAGE, 256, C3M<1>::POS, {"conv.win1_oct32", "conv.win1_oct32_osplit"}},
+    {9, 2, 64, conv_window_s2_kernel<64>, C3S2::STAGE, 128, C3S2::POS, {"conv.win3s2_oct64", "conv.win3s2_oct64_osplit"}},
+    {9, 2, 32, conv_window_s2_kernel<32>, C3S2::STAGE, 128, C3S2::POS, {"conv.win3s2_oct32", "conv.win3s2_oct32_osplit"}},
+};
+
+int run_window(LeleCtx* ctx, const ConvRoute& r, const LeleTensor* wt, const float* dx, const float* dw, const float* db, ConvGeom g, int act,
+               float* out) {
+    const int taps = g.kh * g.kw, cus = ctx->num_cus;
+    const WinKernel* k = nullptr;
+    for (const WinKernel& e : kWinKernels)
+        if (e.taps == taps && e.stride == g.sh && e.oct == r.oct) k = &e;
+    LELE_REQUIRE(k, "conv2d: no window kernel for %d taps, stride %d, blocks of %d channels", taps, g.sh, r.oct);
+    // split-bf16 fragments of ceil(OC / 32) tiles of 32 output channels; the kernels read whole blocks, so a padding tile of zeros
+    // follows where a block may end past them (blocks of 128: whole blocks; stride 2 with blocks of 32 reads none)
+    const size_t tile_bytes = (size_t)(g.c / 16) * taps * 3 * 1024;
+    const size_t wbytes = r.oct == 128 ? (size_t)(((g.oc + 127) / 128) * 4) * tile_bytes
+                                       : (size_t)((g.oc + 31) / 32) * tile_bytes + (g.sh == 2 && r.oct == 32 ? 0 : tile_bytes);
+    void* dwf = nullptr;
+    LELE_TRY(window_frags(ctx, wt, dw, g, taps, r.oct, wbytes, &dwf));
+    // a 1 x 1 convolution has no rows: its plane is ONE row, cut into tiles of 256 positions (only the last one has padding)
+    if (taps == 1) g.ih = g.oh = 1, g.iw = g.ow = g.plane;
+#ifdef LELE_HIP_LAB
+    if (g.sh == 1) g.dh |= conv_env("LELE_HIP_CONV_KO", 0) << 8;  // the window kernels never read the dilation (it is 1 here): lab knock-out flags ride in it
+#endif
+    ConvEpi epi{out, db, g, act};
+#ifdef LELE_HIP_LAB
+    if (const char* e = g.sh == 1 ? lab_env("LELE_HIP_CONV_STAMPS") : nullptr) epi.dbg = (long long*)(uintptr_t)strtoull(e, nullptr, 0);
+#endif
+    // the plan: persistent workgroups, at most two per CU, each walking through its share of the items (see conv_window_p_kernel); an
+    // item is a tile of an image and all its blocks of output channels, or -- too few tiles to go round twice -- one block of them
+    const WinTile tile = pick_win_tile(g.ow, g.oh, k->positions, g.kh, g.sh, k->slots, (int64_t)g.n * ((g.oc + r.oct - 1) / r.oct), cus);
+    const int ntiles = tile.tiles_x * ((g.oh + tile.th - 1) / tile.th), nblocks = (g.oc + r.oct - 1) / r.oct;
+    const int osplit = (int64_t)g.n * ntiles >= 2 * (int64_t)cus ? 1 : nblocks, nocb = nblocks / osplit;
+    const int64_t items = (int64_t)g.n * ntiles * osplit;
+    LELE_REQUIRE(items < (int64_t(1) << 31), "conv2d: more than 2^31 tiles");
+    const dim3 grid((unsigned)std::min<int64_t>(items, conv_env("LELE_HIP_CONV_WG_PER_CU", 2) * (int64_t)cus));
+    LELE_HIP_CHECK(lele::ensure_dyn_lds(reinterpret_cast<const void*>(k->kern), k->lds));
+    hipLaunchKernelGGL(k->kern, grid, dim3(512), k->lds, ctx->stream, dx, (const cu32x4*)dwf, epi, tile, ntiles, nocb, osplit, (int)items);
+    ctx->set_route(k->name[osplit > 1]);
+    return 0;
+}
+
+int run_direct(LeleCtx* ctx, const ConvRoute& r, const LeleTensor* wt, const float* dx, const float* dw, const float* db, const ConvGeom& g, int act,
+               float* out) {
+    // by output channels a thread and stride; name[1] where the window of all channels does not fit one LDS pass
+    static const struct { int ocb, stride; decltype(&conv3x3_direct_kernel<8, 1>) kern; const char* name[2]; } kernels[4] = {
+        {8, 1, conv3x3_direct_kernel<8, 1>, {"conv.direct_ocb8_s1", "conv.direct_ocb8_s1_passes"}},
+        {16, 1, conv3x3_direct_kernel<16, 1>, {"conv.direct_ocb16_s1", "conv.direct_ocb16_s1_passes"}},
+        {8, 2, conv3x3_direct_kernel<8, 2>, {"conv.direct_ocb8_s2", "conv.direct_ocb8_s2_passes"}},
+        {16, 2, conv3x3_direct_kernel<16, 2>, {"conv.direct_ocb16_s2", "conv.direct_ocb16_s2_passes"}}};
+    const auto& k = kernels[(g.sh == 2 ? 2 : 0) + (r.ocb == 16 ? 1 : 0)];
+    const int ocb = r.ocb;
+    void* dwq = nullptr;
+    LELE_TRY(ctx->weight_form(wt, WeightForm::ConvDirect, {ocb}, (size_t)g.c * 9 * ocb * 4, &dwq, [&](void* d) {
+        hipLaunchKernelGGL(conv3x3_wperm_kernel, dim3(grid_for((int64_t)g.c * 9 * ocb)), dim3(256), 0, ctx->stream, dw, (float*)d, g.oc, g.c, ocb);
+        LELE_HIP_CHECK(hipGetLastError());
+        return 0;
+    }));
+    const int ph = 7 * g.sh + 3, pp = 31 * g.sh + 3 + 1;
+    int icc = g.c;
+    while ((size_t)icc * ph * pp * 4 > 36 * 1024) icc = (icc + 1) / 2;  // the window of `icc` channels per LDS pass: four workgroups a CU
+    const size_t lds = (size_t)icc * ph * pp * 4;
+    const int tiles_x = (g.ow + 31) / 32, tiles_y = (g.oh + 7) / 8;
+    if (lds > 60 * 1024) LELE_HIP_CHECK(lele::ensure_dyn_lds(reinterpret_cast<const void*>(k.kern), (int)lds));
+    hipLaunchKernelGGL(k.kern, dim3((unsigned)(tiles_x * tiles_y), (unsigned)g.n), dim3(256), lds, ctx->stream, dx, (const float*)dwq, db, out, g, act,
+                       tiles_x, icc);
+    ctx->set_route(k.name[icc < g.c]);
+    return 0;
+}
+
+// the implicit GEMM (gemm_core.h) behind one of three B loaders; gemm::launch names its own kernel, in the statement that launches it
+int run_gemm(LeleCtx* ctx, const ConvRoute& r, const LeleTensor* wt, const float* dx, const float* dw, const float* db, const ConvGeom& g, int act,
+             float* out) {
+    ConvWLoad al{dw, g, (int)((((uintptr_t)dw & 15) == 0) && g.K % 4 == 0)};
+    ConvEpi epi{out, db, g, act};
+    const int64_t img_elems = (int64_t)g.icg * g.ih * g.iw;
+    LELE_REQUIRE(img_elems < (int64_t(1) << 31), "conv2d: one image group exceeds 2^31 elements");
+    if (r.kind == ConvKind::GemmPw) {
+        // pointwise: B[p][k] = x[img][grp*ICg + k][p] is a plain column-major operand; batch b = img*G + grp
+        gemm::LoadKRow bl{dx, g.group == 1 ? (int64_t)g.xbs : img_elems, (int64_t)g.plane, g.plane, g.K};
+        ctx->set_route("conv.gemm_pw", gemm::launch(ctx->stream, al, bl, epi, g.ocg, g.plane, g.K, g.n * g.group, ctx->num_cus));
+    } else if (r.kind == ConvKind::GemmTap) {
+        // tap-major K: weights permuted to [OC][tap][ic] once (cached when the caller declared them immutable)
+        const int khw = g.kh * g.kw;
+        void* dwt = nullptr;
+        LELE_TRY(ctx->weight_form(wt, WeightForm::ConvTapMajor, {}, (size_t)g.oc * g.K * 4, &dwt, [&](void* d) {
+            hipLaunchKernelGGL(conv_wperm_kernel, dim3(grid_for((int64_t)g.oc * g.K)), dim3(256), 0, ctx->stream, dw, (float*)d, g.oc, g.icg, khw);
             LELE_HIP_CHECK(hipGetLastError());
             return 0;
         }));
-        const int s_ = g.sh, ph = 7 * s_ + 3, pp = 31 * s_ + 3 + 1;
-        int icc = g.c;
-        while ((size_t)icc * ph * pp * 4 > 36 * 1024) icc = (icc + 1) / 2;  // the window of `icc` channels per LDS pass: four workgroups a CU
-        const size_t lds = (size_t)icc * ph * pp * 4;
-        const int tiles_x = (g.ow + 31) / 32, tiles_y = (g.oh + 7) / 8;
-        const dim3 dgrid((unsigned)(tiles_x * tiles_y), (unsigned)g.n);
-#define LELE_C3(OCB_, S_)                                                                                            \
-    do {                                                                                                             \
-        auto kern = conv3x3_direct_kernel<OCB_, S_>;                                                                  \
-        if (lds > 60 * 1024) LELE_HIP_CHECK(lele::ensure_dyn_lds(reinterpret_cast<const void*>(kern), (int)lds));     \
-        hipLaunchKernelGGL(kern, dgrid, dim3(256), lds, ctx->stream, dx, (const float*)dwq, db, out, g, act, tiles_x, icc); \
-    } while (0)
-        if (s_ == 1) {
-            if (ocb == 8) LELE_C3(8, 1);
-            else LELE_C3(16, 1);
-        } else {
-            if (ocb == 8) LELE_C3(8, 2);
-            else LELE_C3(16, 2);
-        }
-#undef LELE_C3
-        static const char* const names[2][2][2] = {
-            {{"conv.direct_ocb8_s1", "conv.direct_ocb8_s1_passes"}, {"conv.direct_ocb8_s2", "conv.direct_ocb8_s2_passes"}},
-            {{"conv.direct_ocb16_s1", "conv.direct_ocb16_s1_passes"}, {"conv.direct_ocb16_s2", "conv.direct_ocb16_s2_passes"}}};
-        ctx->set_route(names[ocb == 16][s_ == 2][icc < g.c]);
+        ConvWLoad alt{(const float*)dwt, g, 1};  // hipMalloc / arena chunks are 16-B aligned and K % 4 == 0
+        ConvXLoadTap bl{dx, g, make_fastdiv(g.ow, g.plane), make_fastdiv(g.icg, g.K), make_fastdiv(g.kw, khw)};
+        ctx->set_route("conv.gemm_tap", gemm::launch(ctx->stream, alt, bl, epi, g.ocg, g.plane, g.K, g.n * g.group, ctx->num_cus));
     } else {
-        ConvWLoad al{dw, g, (int)((((uintptr_t)dw & 15) == 0) && g.K % 4 == 0)};
-        ConvEpi epi{out, db, g, act};
-        const int64_t img_elems = (int64_t)g.icg * g.ih * g.iw;
-        LELE_REQUIRE(img_elems < (int64_t(1) << 31), "conv2d: one image group exceeds 2^31 elements");
-        if (g.kh == 1 && g.kw == 1 && g.sh == 1 && g.sw == 1 && g.pt == 0 && g.pl == 0 && g.oh == g.ih && g.ow == g.iw) {
-            // pointwise: B[p][k] = x[img][grp*ICg + k][p] is a plain column-major operand; batch b = img*G + grp
-            gemm::LoadKRow bl{dx, g.group == 1 ? (int64_t)g.xbs : img_elems, (int64_t)g.plane, g.plane, g.K};
-            ctx->set_route("conv.gemm_pw", gemm::launch(ctx->stream, al, bl, epi, g.ocg, g.plane, g.K, g.n * g.group, ctx->num_cus));
-        } else if (g.icg % 4 == 0 && !empty_k) {
-            // tap-major K: weights permuted to [OC][tap][ic] once (cached when the caller declared them immutable)
-            const int khw = g.kh * g.kw;
-            const size_t wbytes = (size_t)g.oc * g.K * 4;
-            void* dwt = nullptr;
-            LELE_TRY(ctx->weight_form(wt, WeightForm::ConvTapMajor, {}, wbytes, &dwt, [&](void* d) {
-                hipLaunchKernelGGL(conv_wperm_kernel, dim3(grid_for((int64_t)g.oc * g.K)), dim3(256), 0, ctx->stream, dw, (float*)d, g.oc, g.icg, khw);
-                LELE_HIP_CHECK(hipGetLastError());
-                return 0;
-            }));
-            ConvWLoad alt{(const float*)dwt, g, 1};  // hipMalloc / arena chunks are 16-B aligned and K % 4 == 0
-            ConvXLoadTap bl{dx, g, make_fastdiv(g.ow, g.plane), make_fastdiv(g.icg, g.K), make_fastdiv(g.kw, khw)};
-            ctx->set_route("conv.gemm_tap", gemm::launch(ctx->stream, alt, bl, epi, g.ocg, g.plane, g.K, g.n * g.group, ctx->num_cus));
-        } else {
-            ConvXLoad bl{dx, g, make_fastdiv(g.ow, g.plane), make_fastdiv(g.kh * g.kw, g.K), make_fastdiv(g.kw, g.kh * g.kw)};
-            ctx->set_route("conv.gemm_generic", gemm::launch(ctx->stream, al, bl, epi, g.ocg, g.plane, g.K, g.n * g.group, ctx->num_cus));
-        }
+        ConvXLoad bl{dx, g, make_fastdiv(g.ow, g.plane), make_fastdiv(g.kh * g.kw, g.K), make_fastdiv(g.kw, g.kh * g.kw)};
+        ctx->set_route("conv.gemm_generic", gemm::launch(ctx->stream, al, bl, epi, g.ocg, g.plane, g.K, g.n * g.group, ctx->num_cus));
+    }
+    return 0;
+}
+
+int run_conv2d(LeleCtx* ctx, const LeleTensor* wt, const float* dx, const float* dw, const float* db, ConvGeom g, int act,
+               float* out) {
+    ctx->set_route(nullptr);
+    if ((int64_t)g.n * g.oc * g.plane == 0) return 0;
+    const bool pitched = (g.xbs != 0 && g.xbs != (long long)g.c * g.ih * g.iw) || (g.obs != 0 && g.obs != (long long)g.oc * g.plane);
+    if (g.xbs == 0) g.xbs = (long long)g.c * g.ih * g.iw;
+    if (g.obs == 0) g.obs = (long long)g.oc * g.plane;
+    LELE_REQUIRE(!pitched || g.group == 1, "conv2d: channel views (a batch pitch) are supported for group == 1 only");
+    const ConvRoute r = conv_route(ctx, g, pitched, out);
+    switch (r.kind) {
+        case ConvKind::DwLds: case ConvKind::DwRow4: case ConvKind::DwGeneric: LELE_TRY(run_dw(ctx, r, dx, dw, db, g, act, out)); break;
+        case ConvKind::Win: case ConvKind::WinS2: LELE_TRY(run_window(ctx, r, wt, dx, dw, db, g, act, out)); break;
+        case ConvKind::Direct: LELE_TRY(run_direct(ctx, r, wt, dx, dw, db, g, act, out)); break;
+        case ConvKind::GemmPw: case ConvKind::GemmTap: case ConvKind::GemmGeneric: LELE_TRY(run_gemm(ctx, r, wt, dx, dw, db, g, act, out)); break;
     }
     LELE_HIP_CHECK(hipGetLastError());
     return 0;
@@ -1894,46 +1906,57 @@ __global__ void ci_scale_bias_kernel(const float* __restrict__ d, int64_t total,
     }
 }
 
-int conv_geom_from(const LeleTensor* x, const int64_t* xshape, const LeleTensor* w, const int64_t* dilations, size_t ndil,
-                   int64_t group, const int64_t* pads, size_t npads, const int64_t* strides, size_t nstr, ConvGeom* out) {
+// The one geometry builder: an NCHW image shape, a weight shape [OC, C_in/g, kh, kw], the group and RESOLVED per-axis attributes
+// (dilation and stride as [h, w], pads as [top, left, bottom, right]: every entry resolves its own conventions and defaults) ->
+// ConvGeom, dense and without a residual (xbs, obs, res, rbs = 0).  An entry keeps its wording: `say` holds what it answers to
+// channels that the group does not divide, to a weight of another C_in/g (a format of that (long long) and the image's (int)
+// channels per group) and to an output that would be empty.
+struct ConvWording {
+    const char *divisible, *cin, *positive;
+};
+constexpr ConvWording kSayConv2d{"conv2d: channels not divisible by group", "conv2d: weight C_in/g = %lld but input has %d channels per group",
+                                 "conv2d: output dimensions must be positive"};  // conv2d.rs:286
+constexpr ConvWording kSayConv1d{"conv1d: channels not divisible by group", "conv1d: weight C_in/g mismatch", "conv1d: output length must be positive"};
+constexpr ConvWording kSayConvInteger{"conv_integer: channels not divisible by group", "conv_integer: weight C_in/g mismatch",
+                                      "conv2d_with_zero_points: output dimensions must be positive"};  // conv2d.rs:1602
+int conv_geom(const ConvWording& say, const int64_t* xshape, const int64_t* wshape, int64_t group, const int64_t* dil, const int64_t* stride,
+              const int64_t* pads, ConvGeom* out) {
     ConvGeom g{};
-    g.n = (int)xshape[0];
-    g.c = (int)xshape[1];
-    g.ih = (int)xshape[2];
-    g.iw = (int)xshape[3];
-    g.oc = (int)w->shape[0];
-    g.kh = (int)w->shape[2];
-    g.kw = (int)w->shape[3];
+    g.n = (int)xshape[0], g.c = (int)xshape[1], g.ih = (int)xshape[2], g.iw = (int)xshape[3];
+    g.oc = (int)wshape[0], g.kh = (int)wshape[2], g.kw = (int)wshape[3];
     g.group = (int)group;
-    LELE_REQUIRE(group >= 1 && g.c % g.group == 0 && g.oc % g.group == 0, "conv_integer: channels not divisible by group");
-    g.icg = g.c / g.group;
-    g.ocg = g.oc / g.group;
-    LELE_REQUIRE(w->shape[1] == g.icg, "conv_integer: weight C_in/g mismatch");
-    g.dh = (int)attr(dilations, ndil, 0, 1);
-    g.dw = (int)attr(dilations, ndil, 1, 1);
-    g.sh = (int)attr(strides, nstr, 0, 1);
-    g.sw = (int)attr(strides, nstr, 1, 1);
-    int pb, pr;
-    if (npads >= 4) {
-        g.pt = (int)pads[0];
-        g.pl = (int)pads[1];
-        pb = (int)pads[2];
-        pr = (int)pads[3];
-    } else if (npads >= 2) {
-        g.pt = pb = (int)pads[0];
-        g.pl = pr = (int)pads[1];
-    } else {
-        g.pt = g.pl = pb = pr = 0;
-    }
-    const int64_t nh = (int64_t)g.ih + g.pt + pb - (int64_t)g.dh * (g.kh - 1) - 1;
-    const int64_t nw = (int64_t)g.iw + g.pl + pr - (int64_t)g.dw * (g.kw - 1) - 1;
-    LELE_REQUIRE(nh >= 0 && nw >= 0 && g.sh > 0 && g.sw > 0,
-                 "conv2d_with_zero_points: output dimensions must be positive");  // conv2d.rs:1602
-    g.oh = (int)(nh / g.sh + 1);
-    g.ow = (int)(nw / g.sw + 1);
-    g.K = g.icg * g.kh * g.kw;
-    g.plane = g.oh * g.ow;
+    LELE_REQUIRE(group >= 1 && g.c % g.group == 0 && g.oc % g.group == 0, "%s", say.divisible);
+    g.icg = g.c / g.group, g.ocg = g.oc / g.group;
+    LELE_REQUIRE(wshape[1] == g.icg, say.cin, (long long)wshape[1], g.icg);
+    g.dh = (int)dil[0], g.dw = (int)dil[1], g.sh = (int)stride[0], g.sw = (int)stride[1];
+    g.pt = (int)pads[0], g.pl = (int)pads[1];
+    const int64_t nh = (int64_t)g.ih + g.pt + (int)pads[2] - (int64_t)g.dh * (g.kh - 1) - 1;
+    const int64_t nw = (int64_t)g.iw + g.pl + (int)pads[3] - (int64_t)g.dw * (g.kw - 1) - 1;
+    LELE_REQUIRE(nh >= 0 && nw >= 0 && g.sh > 0 && g.sw > 0, "%s", say.positive);
+    g.oh = (int)(nh / g.sh + 1), g.ow = (int)(nw / g.sw + 1);
+    g.K = g.icg * g.kh * g.kw, g.plane = g.oh * g.ow;
     *out = g;
+    return 0;
+}
+// ... of the 2-D entries: one value of `dilations` / `strides` serves both axes (conv2d.rs:208-243), pads are [top, left, bottom,
+// right] or [h, w] for both sides (:246-273)
+int conv_geom_2d(const ConvWording& say, const int64_t* xshape, const LeleTensor* w, const int64_t* dilations, size_t ndil, int64_t group,
+                 const int64_t* pads, size_t npads, const int64_t* strides, size_t nstr, ConvGeom* out) {
+    const int64_t dil[2] = {attr(dilations, ndil, 0, 1), attr(dilations, ndil, 1, 1)}, stride[2] = {attr(strides, nstr, 0, 1), attr(strides, nstr, 1, 1)};
+    int64_t p[4] = {0, 0, 0, 0};
+    if (npads >= 4) p[0] = pads[0], p[1] = pads[1], p[2] = pads[2], p[3] = pads[3];
+    else if (npads >= 2) p[0] = p[2] = pads[0], p[1] = p[3] = pads[1];
+    return conv_geom(say, xshape, w->shape, group, dil, stride, p, out);
+}
+
+// arena_reset, then the device addresses of x, w and the optional bias: the prologue of the entries that stage exactly these, in this order
+int stage_xwb(LeleCtx* ctx, const LeleTensor* x, const LeleTensor* w, const LeleTensor* bias, const float** dx, const float** dw, const float** db) {
+    LELE_TRY(ctx->arena_reset());
+    const void *px = nullptr, *pw = nullptr, *pb = nullptr;
+    LELE_TRY(ctx->dev_ptr(x, &px));
+    LELE_TRY(ctx->dev_ptr(w, &pw));
+    if (bias) LELE_TRY(ctx->dev_ptr(bias, &pb));
+    *dx = (const float*)px, *dw = (const float*)pw, *db = (const float*)pb;
     return 0;
 }
 
@@ -1966,89 +1989,110 @@ int centred_weights(LeleCtx* ctx, const LeleTensor* w, float w_zp, const float**
 inline bool steps_lt8(int steps) { return steps < 8; }  // too few (tap, chunk) steps to share among four waves
 // One ConvInteger: `nsrc` f32 sources [N, c_i, H, W] concatenated along C (u8 codes, or -- dq != NULL -- values to be quantised with
 // the parameters at dq), weights w (u8 codes as f32), zero points zx_host (ignored when dq) and w_zp.  See the section comment.
-int ci_run(LeleCtx* ctx, ConvGeom g, const LeleTensor* w, float w_zp, const float* const* srcs, const int64_t* src_c, int nsrc, const QParamsDev* dq,
-           float zx_host, float* out) {
-    ctx->set_route(nullptr);
-    if ((int64_t)g.n * g.oc * g.plane == 0) return 0;
-    const int taps = g.kh * g.kw;
-    const int64_t spatial = (int64_t)g.ih * g.iw, K = (int64_t)g.c * taps;
-    auto code = [](float v) { return v >= 0.0f && v <= 255.0f && v == (float)(int)v; };
-    bool i8 = g.group == 1 && code(w_zp) && (dq || code(zx_host)) && K * 65025 < (int64_t(1) << 31) && w->mem != LELE_MEM_DEVICE &&
-              spatial * (((int64_t)g.c + 31) & ~int64_t(31)) < (int64_t(1) << 31) - 512 && g.n <= 65535 && (g.oc + 31) / 32 <= 65535 &&
-              !lab_env("LELE_HIP_CONV_INTEGER_F32");
-    const int cp = (g.c + 31) & ~31, chunks = cp / 32, tiles = (g.oc + 31) / 32;
-    const size_t fbytes = (size_t)tiles * taps * chunks * 1024, wbytes = fbytes + (size_t)g.oc * 4;
-    // the weights must be u8 codes: a host array, scanned when the fragments are made (once per immutable tensor, every call otherwise);
-    // the verdict "not u8 codes" of an immutable tensor is remembered too
-    if (i8 && ctx->weight_noted(w, WeightForm::CiNotU8)) i8 = false;
-    void* fw = nullptr;
-    if (i8) {
-        const int rc = ctx->weight_form(w, WeightForm::CiI8Frag, {}, wbytes, &fw, [&](void* d) {
-            const float* hw = (const float*)w->data;
-            const int64_t nw = numel(w);
-            for (int64_t i = 0; i < nw && i8; ++i) i8 = code(hw[i]);
-            if (!i8) return -1;  // not an error: the f32 route below
-            const void* dw = nullptr;
-            LELE_TRY(ctx->dev_ptr(w, &dw));
-            hipLaunchKernelGGL(ci8_wfrag_kernel, dim3(grid_for((int64_t)tiles * taps * chunks * 64)), dim3(256), 0, ctx->stream, (const float*)dw, g.oc, g.c,
-                               taps, chunks, (ci_v4i*)d, (int*)((char*)d + fbytes));
-            LELE_HIP_CHECK(hipGetLastError());
-            return 0;
-        });
-        if (!i8) ctx->note_weight(w, WeightForm::CiNotU8);
-        else LELE_TRY(rc);
-    }
-    if (i8) {
-        void *img = nullptr, *ts = nullptr;
-        LELE_TRY(ctx->arena_alloc((size_t)g.n * spatial * cp + 512, &img));
-        LELE_TRY(ctx->arena_alloc((size_t)g.n * spatial * 4, &ts));
-        LELE_HIP_CHECK(hipMemsetAsync(ts, 0, (size_t)g.n * spatial * 4, ctx->stream));
-        int ch_off = 0;
-        for (int i = 0; i < nsrc; ++i) {
-            const int64_t work = (int64_t)g.n * ((src_c[i] + 3) / 4) * spatial;
-            if (work && dq)
-                hipLaunchKernelGGL(ci8_pack_kernel<true>, dim3(grid_for(work)), dim3(256), 0, ctx->stream, srcs[i], (int64_t)g.n, (int)src_c[i], ch_off, cp,
-                                   spatial, dq, (unsigned*)img, (int*)ts);
-            else if (work)
-                hipLaunchKernelGGL(ci8_pack_kernel<false>, dim3(grid_for(work)), dim3(256), 0, ctx->stream, srcs[i], (int64_t)g.n, (int)src_c[i], ch_off, cp,
-                                   spatial, dq, (unsigned*)img, (int*)ts);
-            ch_off += (int)src_c[i];
-        }
-        const Ci8Prm prm{dq, (int)zx_host, (int)w_zp};
-        // the widest wave tile that still gives every CU two workgroups; below that the waves of a workgroup split K instead
-        const int64_t units = (int64_t)g.n * tiles, want = 2 * (int64_t)ctx->num_cus;
-        auto blocks = [&](int nj, bool ks) { return ((int64_t)g.plane + (ks ? 1 : 4) * 32 * nj - 1) / ((ks ? 1 : 4) * 32 * nj); };
-        // lele_hip_last_route: how the image was packed (codes taken as they are / quantised on the way), then the kernel
-#define LELE_CI8(NJ_, KS_, NAME_)                                                                                                   \
-    do {                                                                                                                            \
-        ctx->set_route(dq ? "ci8.quant" : "ci8.codes", NAME_);                                                                      \
-        hipLaunchKernelGGL((ci8_conv_kernel<NJ_, KS_>), dim3((unsigned)blocks(NJ_, KS_), (unsigned)tiles, (unsigned)g.n), dim3(256), 0, ctx->stream, \
-                           (const unsigned char*)img, (const int*)ts, (const ci_v4i*)fw, (const int*)((char*)fw + fbytes), prm, g, cp, out); \
-    } while (0)
-        if (units * blocks(4, false) >= want) LELE_CI8(4, false, "ci8.nj4");
-        else if (units * blocks(2, false) >= want) LELE_CI8(2, false, "ci8.nj2");
-        else if (units * blocks(1, false) >= want || steps_lt8(taps * chunks)) LELE_CI8(1, false, "ci8.nj1");
-        else if (units * blocks(2, true) >= want) LELE_CI8(2, true, "ci8.nj2_ksplit");
-        else LELE_CI8(1, true, "ci8.nj1_ksplit");
-#undef LELE_CI8
+struct CiArgs {
+    ConvGeom g;
+    const LeleTensor* w;
+    float w_zp;
+    const float* const* srcs;  // nsrc sources of src_c[i] channels each
+    const int64_t* src_c;
+    int nsrc;
+    const QParamsDev* dq;
+    float zx_host, *out;
+    int taps() const { return g.kh * g.kw; }
+    int64_t spatial() const { return (int64_t)g.ih * g.iw; }
+    int cp() const { return (g.c + 31) & ~31; }  // channels of the packed u8 image: whole chunks of 32
+};
+inline bool is_u8_code(float v) { return v >= 0.0f && v <= 255.0f && v == (float)(int)v; }
+constexpr int kCiNotCodes = -1;  // what the fragments' builder answers to a weight that is not a u8 code: no error, the f32 route
+
+// The decision: *fw = the weights as i8 fragments (+ their sums per output channel, `*fbytes` in) where the call runs on the i8
+// matrix cores, NULL where it takes the f32 route.  The weights must be u8 codes: a host array, scanned when the fragments are made
+// (once per immutable tensor, every call otherwise); the verdict "not u8 codes" of an immutable tensor is remembered too.
+int ci_i8_frags(LeleCtx* ctx, const CiArgs& a, void** fw, size_t* fbytes) {
+    const ConvGeom& g = a.g;
+    const int taps = a.taps(), chunks = a.cp() / 32, tiles = (g.oc + 31) / 32;
+    const int64_t K = (int64_t)g.c * taps;
+    *fw = nullptr;
+    *fbytes = (size_t)tiles * taps * chunks * 1024;
+    if (!(g.group == 1 && is_u8_code(a.w_zp) && (a.dq || is_u8_code(a.zx_host)) && K * 65025 < (int64_t(1) << 31) && a.w->mem != LELE_MEM_DEVICE &&
+          a.spatial() * (((int64_t)g.c + 31) & ~int64_t(31)) < (int64_t(1) << 31) - 512 && g.n <= 65535 && (g.oc + 31) / 32 <= 65535 &&
+          !lab_env("LELE_HIP_CONV_INTEGER_F32")) ||
+        ctx->weight_noted(a.w, WeightForm::CiNotU8))
+        return 0;
+    void* frags = nullptr;
+    const int rc = ctx->weight_form(a.w, WeightForm::CiI8Frag, {}, *fbytes + (size_t)g.oc * 4, &frags, [&](void* d) {
+        const float* hw = (const float*)a.w->data;
+        for (int64_t i = 0, nw = numel(a.w); i < nw; ++i)
+            if (!is_u8_code(hw[i])) return kCiNotCodes;
+        const void* dw = nullptr;
+        LELE_TRY(ctx->dev_ptr(a.w, &dw));
+        hipLaunchKernelGGL(ci8_wfrag_kernel, dim3(grid_for((int64_t)tiles * taps * chunks * 64)), dim3(256), 0, ctx->stream, (const float*)dw, g.oc, g.c,
+                           taps, chunks, (ci_v4i*)d, (int*)((char*)d + *fbytes));
         LELE_HIP_CHECK(hipGetLastError());
         return 0;
+    });
+    if (rc == kCiNotCodes) {
+        ctx->note_weight(a.w, WeightForm::CiNotU8);
+        return 0;
     }
-    // ---- f32: codes -> zero-padded, centred image -> lele's f32 convolution without padding
+    LELE_TRY(rc);
+    *fw = frags;
+    return 0;
+}
+
+// the i8 route: the sources packed as one u8 image [N, H, W, Cp] with its per-pixel channel sums, then the convolution
+int ci_run_i8(LeleCtx* ctx, const CiArgs& a, const void* fw, size_t fbytes) {
+    const ConvGeom& g = a.g;
+    const int taps = a.taps(), cp = a.cp(), chunks = cp / 32, tiles = (g.oc + 31) / 32;
+    const int64_t spatial = a.spatial();
+    void *img = nullptr, *ts = nullptr;
+    LELE_TRY(ctx->arena_alloc((size_t)g.n * spatial * cp + 512, &img));
+    LELE_TRY(ctx->arena_alloc((size_t)g.n * spatial * 4, &ts));
+    LELE_HIP_CHECK(hipMemsetAsync(ts, 0, (size_t)g.n * spatial * 4, ctx->stream));
+    int ch_off = 0;
+    for (int i = 0; i < a.nsrc; ++i) {
+        const int64_t work = (int64_t)g.n * ((a.src_c[i] + 3) / 4) * spatial;
+        if (work)
+            hipLaunchKernelGGL(a.dq ? ci8_pack_kernel<true> : ci8_pack_kernel<false>, dim3(grid_for(work)), dim3(256), 0, ctx->stream, a.srcs[i],
+                               (int64_t)g.n, (int)a.src_c[i], ch_off, cp, spatial, a.dq, (unsigned*)img, (int*)ts);
+        ch_off += (int)a.src_c[i];
+    }
+    const Ci8Prm prm{a.dq, (int)a.zx_host, (int)a.w_zp};
+    // the widest wave tile that still gives every CU two workgroups; below that the waves of a workgroup split K instead
+    static const struct Ci8Kernel { int nj; bool ksplit; decltype(&ci8_conv_kernel<4, false>) kern; const char* name; } kernels[5] = {
+        {4, false, ci8_conv_kernel<4, false>, "ci8.nj4"}, {2, false, ci8_conv_kernel<2, false>, "ci8.nj2"}, {1, false, ci8_conv_kernel<1, false>, "ci8.nj1"},
+        {2, true, ci8_conv_kernel<2, true>, "ci8.nj2_ksplit"}, {1, true, ci8_conv_kernel<1, true>, "ci8.nj1_ksplit"}};  // the widest wave tile first
+    const int64_t units = (int64_t)g.n * tiles, want = 2 * (int64_t)ctx->num_cus;
+    auto blocks = [&](const Ci8Kernel& k) { return ((int64_t)g.plane + (k.ksplit ? 1 : 4) * 32 * k.nj - 1) / ((k.ksplit ? 1 : 4) * 32 * k.nj); };
+    const Ci8Kernel* k = &kernels[4];
+    for (int i = 3; i >= 0; --i)  // the first row in order that qualifies; the last one otherwise
+        if (units * blocks(kernels[i]) >= want || (i == 2 && steps_lt8(taps * chunks))) k = &kernels[i];
+    // lele_hip_last_route: how the image was packed (codes taken as they are / quantised on the way), then the kernel
+    ctx->set_route(a.dq ? "ci8.quant" : "ci8.codes", k->name);
+    hipLaunchKernelGGL(k->kern, dim3((unsigned)blocks(*k), (unsigned)tiles, (unsigned)g.n), dim3(256), 0, ctx->stream, (const unsigned char*)img,
+                       (const int*)ts, (const ci_v4i*)fw, (const int*)((const char*)fw + fbytes), prm, g, cp, a.out);
+    LELE_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
+// the f32 route: codes -> zero-padded, centred image -> lele's f32 convolution without padding
+int ci_run_f32(LeleCtx* ctx, const CiArgs& a) {
+    const ConvGeom& g = a.g;
+    const int64_t spatial = a.spatial();
     const float* dwc = nullptr;
-    LELE_TRY(centred_weights(ctx, w, w_zp, &dwc));
-    const float* codes = srcs[0];
-    if (dq || nsrc > 1) {
+    LELE_TRY(centred_weights(ctx, a.w, a.w_zp, &dwc));
+    const float* codes = a.srcs[0];
+    if (a.dq || a.nsrc > 1) {
         void* q = nullptr;
         LELE_TRY(ctx->arena_alloc((size_t)std::max<int64_t>((int64_t)g.n * g.c * spatial, 1) * 4, &q));
         int64_t ch_off = 0;
-        for (int i = 0; i < nsrc; ++i) {
-            const int64_t len = (int64_t)g.n * src_c[i] * spatial;
-            LELE_REQUIRE(dq, "conv_integer: several sources need the dynamic quantisation");
+        for (int i = 0; i < a.nsrc; ++i) {
+            const int64_t len = (int64_t)g.n * a.src_c[i] * spatial;
+            LELE_REQUIRE(a.dq, "conv_integer: several sources need the dynamic quantisation");
             if (len)
-                hipLaunchKernelGGL(ci_quant_codes_kernel, dim3(grid_for(len)), dim3(256), 0, ctx->stream, srcs[i], (int64_t)g.n, src_c[i], (int64_t)g.c,
-                                   ch_off, spatial, dq, (float*)q);
-            ch_off += src_c[i];
+                hipLaunchKernelGGL(ci_quant_codes_kernel, dim3(grid_for(len)), dim3(256), 0, ctx->stream, a.srcs[i], (int64_t)g.n, a.src_c[i],
+                                   (int64_t)g.c, ch_off, spatial, a.dq, (float*)q);
+            ch_off += a.src_c[i];
         }
         codes = (const float*)q;
     }
@@ -2058,15 +2102,24 @@ int ci_run(LeleCtx* ctx, ConvGeom g, const LeleTensor* w, float w_zp, const floa
     const int64_t planes = (int64_t)g.n * g.c;
     LELE_TRY(ctx->arena_alloc((size_t)std::max<int64_t>(planes * ph * pw, 1) * 4, &xc));
     hipLaunchKernelGGL(ci_pad_center_kernel, dim3(grid_for(planes * ph * pw)), dim3(256), 0, ctx->stream, codes, planes, g.ih, g.iw, g.pt, g.pl, ph, pw,
-                       zx_host, dq, (float*)xc);
+                       a.zx_host, a.dq, (float*)xc);
     ConvGeom gp = g;
     gp.ih = ph, gp.iw = pw, gp.pt = gp.pl = 0;
-    LeleTensor wv = *w;
+    LeleTensor wv = *a.w;
     wv.mem = LELE_MEM_DEVICE;  // the centred copy is what run_conv2d sees (its own weight cache keys on the pointer below)
     wv.data = dwc;
-    LELE_TRY(run_conv2d(ctx, &wv, (const float*)xc, dwc, nullptr, gp, LELE_ACT_NONE, out));
-    ctx->route[0] = "ci.f32";
+    LELE_TRY(run_conv2d(ctx, &wv, (const float*)xc, dwc, nullptr, gp, LELE_ACT_NONE, a.out));
+    ctx->set_route_family("ci.f32");  // in front of the convolution's own route
     return 0;
+}
+
+int ci_run(LeleCtx* ctx, const CiArgs& a) {
+    ctx->set_route(nullptr);
+    if ((int64_t)a.g.n * a.g.oc * a.g.plane == 0) return 0;
+    void* fw = nullptr;
+    size_t fbytes = 0;
+    LELE_TRY(ci_i8_frags(ctx, a, &fw, &fbytes));
+    return fw ? ci_run_i8(ctx, a, fw, fbytes) : ci_run_f32(ctx, a);
 }
 
 }  // namespace
@@ -2088,51 +2141,13 @@ static int conv2d_entry(LeleCtx* ctx, const LeleTensor* x, const LeleTensor* w, 
     }
     LELE_REQUIRE(group >= 1, "conv2d: group must be >= 1");
     LELE_HIP_CHECK(hipSetDevice(ctx->device));
-    ConvGeom g{};
-    g.n = (int)x->shape[0];
-    g.c = (int)x->shape[1];
-    g.ih = (int)x->shape[2];
-    g.iw = (int)x->shape[3];
-    g.oc = (int)w->shape[0];
-    g.kh = (int)w->shape[2];
-    g.kw = (int)w->shape[3];
-    g.group = (int)group;
-    LELE_REQUIRE(g.c % g.group == 0 && g.oc % g.group == 0, "conv2d: channels not divisible by group");
-    g.icg = g.c / g.group;
-    g.ocg = g.oc / g.group;
-    LELE_REQUIRE(w->shape[1] == g.icg, "conv2d: weight C_in/g = %lld but input has %d channels per group",
-                 (long long)w->shape[1], g.icg);
-    g.dh = (int)attr(dilations, ndil, 0, 1);
-    g.dw = (int)attr(dilations, ndil, 1, 1);
-    g.sh = (int)attr(strides, nstr, 0, 1);
-    g.sw = (int)attr(strides, nstr, 1, 1);
-    int pb, pr;
-    if (npads >= 4) {  // [top, left, bottom, right], conv2d.rs:246-273
-        g.pt = (int)pads[0];
-        g.pl = (int)pads[1];
-        pb = (int)pads[2];
-        pr = (int)pads[3];
-    } else if (npads >= 2) {
-        g.pt = pb = (int)pads[0];
-        g.pl = pr = (int)pads[1];
-    } else {
-        g.pt = g.pl = pb = pr = 0;
-    }
-    const int64_t nh = (int64_t)g.ih + g.pt + pb - (int64_t)g.dh * (g.kh - 1) - 1;
-    const int64_t nw = (int64_t)g.iw + g.pl + pr - (int64_t)g.dw * (g.kw - 1) - 1;
-    LELE_REQUIRE(nh >= 0 && nw >= 0 && g.sh > 0 && g.sw > 0, "conv2d: output dimensions must be positive");  // :286
-    g.oh = (int)(nh / g.sh + 1);
-    g.ow = (int)(nw / g.sw + 1);
-    g.K = g.icg * g.kh * g.kw;
+    ConvGeom g;
+    LELE_TRY(conv_geom_2d(kSayConv2d, x->shape, w, dilations, ndil, group, pads, npads, strides, nstr, &g));
     ctx->conv_calls += 1;  // reset_conv_stats / print_conv_stats (conv2d.rs:75,101)
     ctx->conv_macs += (int64_t)g.n * g.oc * g.oh * g.ow * g.K;
-    g.plane = g.oh * g.ow;
     if (bias) LELE_REQUIRE(numel(bias) >= g.oc, "conv2d: bias has %lld entries for %d channels", (long long)numel(bias), g.oc);
-    LELE_TRY(ctx->arena_reset());
-    const void *dx = nullptr, *dwp = nullptr, *db = nullptr;
-    LELE_TRY(ctx->dev_ptr(x, &dx));
-    LELE_TRY(ctx->dev_ptr(w, &dwp));
-    if (bias) LELE_TRY(ctx->dev_ptr(bias, &db));
+    const float *dx = nullptr, *dwp = nullptr, *db = nullptr;
+    LELE_TRY(stage_xwb(ctx, x, w, bias, &dx, &dwp, &db));
     float* dst = nullptr;
     if (res) {  // out = act(conv + bias) + res
         LELE_REQUIRE(res->dtype == LELE_F32 && res->rank == 4 && res->shape[0] == g.n && res->shape[1] == g.oc && res->shape[2] == g.oh &&
@@ -2158,7 +2173,7 @@ static int conv2d_entry(LeleCtx* ctx, const LeleTensor* x, const LeleTensor* w, 
         LELE_TRY(out->reserve((size_t)g.n * g.oc * g.plane * 4));
         dst = (float*)out->data;
     }
-    LELE_TRY(run_conv2d(ctx, w, (const float*)dx, (const float*)dwp, (const float*)db, g, act, dst));
+    LELE_TRY(run_conv2d(ctx, w, dx, dwp, db, g, act, dst));
     return set_shape(out_shape, out_rank, {(int64_t)g.n, (int64_t)g.oc, (int64_t)g.oh, (int64_t)g.ow});
 }
 
@@ -2208,41 +2223,17 @@ int lele_hip_conv1d(LeleCtx* ctx, const LeleTensor* x, const LeleTensor* w, cons
     LELE_REQUIRE(x->dtype == LELE_F32 && w->dtype == LELE_F32, "conv1d: f32 tensors required");
     LELE_REQUIRE(group >= 1, "conv1d: group must be >= 1");
     LELE_HIP_CHECK(hipSetDevice(ctx->device));
-    ConvGeom g{};
-    g.n = (int)x->shape[0];
-    g.c = x->rank == 3 ? (int)x->shape[1] : 1;  // [N, L] is a single channel
-    g.ih = 1;
-    g.iw = (int)x->shape[x->rank - 1];
-    g.oc = (int)w->shape[0];
-    g.kh = 1;
-    g.kw = (int)w->shape[2];
-    g.group = (int)group;
-    LELE_REQUIRE(g.c % g.group == 0 && g.oc % g.group == 0, "conv1d: channels not divisible by group");
-    g.icg = g.c / g.group;
-    g.ocg = g.oc / g.group;
-    LELE_REQUIRE(w->shape[1] == g.icg, "conv1d: weight C_in/g mismatch");
-    g.dh = 1;
-    g.dw = ndil ? (int)dilations[0] : 1;
-    g.sh = 1;
-    g.sw = nstr ? (int)strides[0] : 1;
-    const int pl = npads >= 1 ? (int)pads[0] : 0, pr = npads >= 2 ? (int)pads[1] : 0;  // conv1d.rs:886-887
-    g.pt = 0;
-    g.pl = pl;
-    const int64_t nw = (int64_t)g.iw + pl + pr - (int64_t)g.dw * (g.kw - 1) - 1;  // conv1d.rs:888-889
-    LELE_REQUIRE(nw >= 0 && g.sw > 0, "conv1d: output length must be positive");
-    g.oh = 1;
-    g.ow = (int)(nw / g.sw + 1);
-    g.K = g.icg * g.kw;
-    g.plane = g.ow;
+    // a row of height 1: [N, L] is a single channel; the one dilation and stride are the width's, pads are [left, right] (conv1d.rs:886-889)
+    const int64_t xs[4] = {x->shape[0], x->rank == 3 ? x->shape[1] : 1, 1, x->shape[x->rank - 1]}, ws[4] = {w->shape[0], w->shape[1], 1, w->shape[2]};
+    const int64_t dil[2] = {1, ndil ? dilations[0] : 1}, stride[2] = {1, nstr ? strides[0] : 1};
+    const int64_t p[4] = {0, npads >= 1 ? pads[0] : 0, 0, npads >= 2 ? pads[1] : 0};
+    ConvGeom g;
+    LELE_TRY(conv_geom(kSayConv1d, xs, ws, group, dil, stride, p, &g));
     if (bias) LELE_REQUIRE(numel(bias) >= g.oc, "conv1d: bias shorter than C_out");
-    LELE_TRY(ctx->arena_reset());
-    const void *dx = nullptr, *dwp = nullptr, *db = nullptr;
-    LELE_TRY(ctx->dev_ptr(x, &dx));
-    LELE_TRY(ctx->dev_ptr(w, &dwp));
-    if (bias) LELE_TRY(ctx->dev_ptr(bias, &db));
+    const float *dx = nullptr, *dwp = nullptr, *db = nullptr;
+    LELE_TRY(stage_xwb(ctx, x, w, bias, &dx, &dwp, &db));
     LELE_TRY(out->reserve((size_t)g.n * g.oc * g.plane * 4));
-    LELE_TRY(run_conv2d(ctx, w, (const float*)dx, (const float*)dwp, (const float*)db, g, relu ? LELE_ACT_RELU : LELE_ACT_NONE,
-                        (float*)out->data));
+    LELE_TRY(run_conv2d(ctx, w, dx, dwp, db, g, relu ? LELE_ACT_RELU : LELE_ACT_NONE, (float*)out->data));
     return set_shape(out_shape, out_rank, {(int64_t)g.n, (int64_t)g.oc, (int64_t)g.ow});
 }
 
@@ -2262,11 +2253,8 @@ int lele_hip_depthwise_conv1d_tlc(LeleCtx* ctx, const LeleTensor* x, int64_t x_o
     LELE_REQUIRE(!add_input || (t_out == t_in && pad_left <= k - 1), "depthwise_conv1d_tlc: the input can only be added to an output of the same length");
     if (bias) LELE_REQUIRE(numel(bias) >= c, "conv1d: bias shorter than C_out");
     LELE_HIP_CHECK(hipSetDevice(ctx->device));
-    LELE_TRY(ctx->arena_reset());
-    const void *dx = nullptr, *dwp = nullptr, *db = nullptr;
-    LELE_TRY(ctx->dev_ptr(x, &dx));
-    LELE_TRY(ctx->dev_ptr(w, &dwp));
-    if (bias) LELE_TRY(ctx->dev_ptr(bias, &db));
+    const float *dx = nullptr, *dwp = nullptr, *db = nullptr;
+    LELE_TRY(stage_xwb(ctx, x, w, bias, &dx, &dwp, &db));
     LELE_TRY(out->reserve((size_t)(bsz * t_out * c) * 4));
     // time steps per thread: 8 (a window of 18 loads for 8 results); a grid that would not give every CU a workgroup that way -- one
     // utterance -- takes 4 (3.4 against 4.2 us at [504, 512]; at [32 x 171, 512]: 4 -> 12.4, 8 -> 10.2, 16 -> 10.0 us)
@@ -2275,26 +2263,123 @@ int lele_hip_depthwise_conv1d_tlc(LeleCtx* ctx, const LeleTensor* x, int64_t x_o
     const int64_t tiles = (t_out + tt - 1) / tt, total = bsz * tiles * c;
     LELE_REQUIRE(total < (int64_t(1) << 31) && pitch < (int64_t(1) << 31), "depthwise_conv1d_tlc: tensor too large");
     if (bsz && c) {
-        const dim3 grid((unsigned)((total + 255) / 256));
-#define LELE_TLC2(KW, TT_)                                                                                                      \
-    hipLaunchKernelGGL((dwconv1d_tlc_kernel<KW, TT_>), grid, dim3(256), 0, ctx->stream, (const float*)dx + x_offset, (const float*)dwp, \
-                       (const float*)db, (float*)out->data, (int)t_in, (int)t_out, (int)c, (int)pitch, (int)pad_left, relu, add_input,  \
-                       (unsigned)tiles, (unsigned)total)
-#define LELE_TLC(KW)                      \
-    do {                                  \
-        if (tt == 16) LELE_TLC2(KW, 16);  \
-        else if (tt <= 4) LELE_TLC2(KW, 4); \
-        else LELE_TLC2(KW, 8);            \
-    } while (0)
-        if (k == 3) LELE_TLC(3);
-        else if (k == 5) LELE_TLC(5);
-        else if (k == 7) LELE_TLC(7);
-        else LELE_TLC(11);
-#undef LELE_TLC
-#undef LELE_TLC2
+        // [kernel size 3, 5, 7, 11][time steps a thread: 4 (or fewer asked for), 8]
+        static const decltype(&dwconv1d_tlc_kernel<3, 8>) kernels[4][2] = {{dwconv1d_tlc_kernel<3, 4>, dwconv1d_tlc_kernel<3, 8>},
+                                                                           {dwconv1d_tlc_kernel<5, 4>, dwconv1d_tlc_kernel<5, 8>},
+                                                                           {dwconv1d_tlc_kernel<7, 4>, dwconv1d_tlc_kernel<7, 8>},
+                                                                           {dwconv1d_tlc_kernel<11, 4>, dwconv1d_tlc_kernel<11, 8>}};
+        auto kern = kernels[kw_slot((int)k)][tt <= 4 ? 0 : 1];
+#ifdef LELE_HIP_LAB  // 16 steps a thread: only LELE_HIP_TLC_TT asks for them, and only the developer's build reads it
+        static const decltype(kern) kernels16[4] = {dwconv1d_tlc_kernel<3, 16>, dwconv1d_tlc_kernel<5, 16>, dwconv1d_tlc_kernel<7, 16>,
+                                                    dwconv1d_tlc_kernel<11, 16>};
+        if (tt == 16) kern = kernels16[kw_slot((int)k)];
+#endif
+        hipLaunchKernelGGL(kern, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, ctx->stream, dx + x_offset, dwp, db, (float*)out->data, (int)t_in,
+                           (int)t_out, (int)c, (int)pitch, (int)pad_left, relu, add_input, (unsigned)tiles, (unsigned)total);
         LELE_HIP_CHECK(hipGetLastError());
     }
     return set_shape(out_shape, out_rank, {bsz, t_out, c});
+}
+
+// "convt.ks", kernel == stride without padding: one GEMM with a scattering epilogue (see ConvTKsEpi)
+static int convt_ks(LeleCtx* ctx, const CtGeom& g, const LeleTensor* w, const float* dx, const float* dwp, const float* db, float* out) {
+    const int taps = g.kh * g.kw, mrows = g.oc * taps, plane_in = g.ih * g.iw;
+    void* dwk = nullptr;
+    LELE_TRY(ctx->weight_form(w, WeightForm::ConvTKernelStride, {}, (size_t)g.c * mrows * 4, &dwk, [&](void* d) {
+        hipLaunchKernelGGL(convt_wks_kernel, dim3(grid_for((int64_t)g.c * mrows)), dim3(256), 0, ctx->stream, dwp, (float*)d, g.c, g.oc, taps);
+        LELE_HIP_CHECK(hipGetLastError());
+        return 0;
+    }));
+    ConvGeom q{};
+    q.group = 1, q.ocg = mrows, q.K = g.c;
+    ConvWLoad al{(const float*)dwk, q, (int)(g.c % 4 == 0)};
+    gemm::LoadKRow bl{dx, (int64_t)g.c * plane_in, (int64_t)plane_in, plane_in, g.c};
+    ConvTKsEpi epi{out, db, make_fastdiv(g.iw, plane_in), make_fastdiv(taps, mrows), make_fastdiv(g.kw, taps), g.oc, g.oh, g.ow, g.kh, g.kw, g.iw, plane_in,
+                   taps};
+    ctx->set_route("convt.ks", gemm::launch(ctx->stream, al, bl, epi, mrows, plane_in, g.c, g.n, ctx->num_cus));
+    LELE_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
+// The outputs (oy, ox) with oy % sh == py and ox % sw == px are one stride-1 convolution of the input with the taps that reach them:
+// a phase.  Along an axis those taps are the first (a0 / b0), their spacing (sa / sb) and their number (na / nb); kp = C na nb is the
+// phase's K, woff where its [OC][kp] block starts in the weights' per-phase form, nj x ni its outputs.
+struct CtPhase {
+    int py, px, a0, sa, na, b0, sb, nb, kp, nj, ni;
+    size_t woff;
+};
+static std::vector<CtPhase> convt_phases(const CtGeom& g) {
+    auto taps = [](int p, int pad, int k, int dil, int stride, int* t0, int* st, int* nt) {
+        *t0 = -1, *st = 1, *nt = 0;
+        for (int t = 0; t < k; ++t)
+            if ((((p + pad - t * dil) % stride) + stride) % stride == 0) {
+                if (*nt == 0) *t0 = t;
+                if (*nt == 1) *st = t - *t0;
+                ++*nt;
+            }
+    };
+    std::vector<CtPhase> phases;
+    size_t woff = 0;
+    for (int py = 0; py < g.sh; ++py)
+        for (int px = 0; px < g.sw; ++px) {
+            CtPhase p{py, px};
+            taps(py, g.pt, g.kh, g.dh, g.sh, &p.a0, &p.sa, &p.na);
+            taps(px, g.pl, g.kw, g.dw, g.sw, &p.b0, &p.sb, &p.nb);
+            p.kp = g.c * p.na * p.nb;
+            p.nj = py < g.oh ? (g.oh - py + g.sh - 1) / g.sh : 0;
+            p.ni = px < g.ow ? (g.ow - px + g.sw - 1) / g.sw : 0;
+            p.woff = woff;
+            woff += (size_t)g.oc * p.kp;
+            phases.push_back(p);
+        }
+    return phases;
+}
+
+// "convt.phase": one GEMM per phase (their own tiles each, so the route names no GEMM kernel); "convt.phase_fill" where a phase
+// that no tap reaches was filled with the bias
+static int convt_phase(LeleCtx* ctx, const CtGeom& g, const LeleTensor* w, const float* dx, const float* dwp, const float* db, float* out) {
+    const std::vector<CtPhase> phases = convt_phases(g);
+    const int tap_major = g.c % 4 == 0;
+    // one buffer holding every phase's [OC][K_phase] block (each tap belongs to exactly one phase); the phase structure depends on
+    // stride / dilation / pad-begin, so they are part of the key
+    void* dwt = nullptr;
+    LELE_TRY(ctx->weight_form(w, WeightForm::ConvTPhase, {g.sh, g.sw, g.dh, g.dw, g.pt, g.pl}, (size_t)g.c * g.oc * g.kh * g.kw * 4, &dwt, [&](void* d) {
+        for (const CtPhase& p : phases)
+            if (p.kp)
+                hipLaunchKernelGGL(convt_wphase_kernel, dim3(grid_for((int64_t)g.oc * p.kp)), dim3(256), 0, ctx->stream, dwp, (float*)d + p.woff, g.c, g.oc,
+                                   g.kh, g.kw, p.a0, p.sa, p.na, p.b0, p.sb, p.nb, tap_major);
+        LELE_HIP_CHECK(hipGetLastError());
+        return 0;
+    }));
+    ctx->set_route("convt.phase");
+    for (const CtPhase& p : phases) {
+        if (p.nj == 0 || p.ni == 0) continue;
+        if (p.kp == 0) {  // no tap reaches this phase: bias only
+            hipLaunchKernelGGL(convt_fill_phase_kernel, dim3(grid_for((int64_t)g.n * g.oc * p.nj * p.ni)), dim3(256), 0, ctx->stream, out, db, g.n, g.oc,
+                               g.oh, g.ow, p.py, p.px, g.sh, g.sw, p.nj, p.ni);
+            ctx->set_route("convt.phase_fill");
+            continue;
+        }
+        ConvGeom q{};  // the phase as a stride-1 convolution: iy = j - pt + t*dh with dh = -(sa*dh/sh)
+        q.n = g.n, q.c = q.icg = g.c, q.ih = g.ih, q.iw = g.iw, q.oc = q.ocg = g.oc, q.group = 1;
+        q.kh = p.na, q.kw = p.nb, q.sh = q.sw = 1;
+        q.pt = -((p.py + g.pt - p.a0 * g.dh) / g.sh), q.pl = -((p.px + g.pl - p.b0 * g.dw) / g.sw);
+        q.dh = -(p.sa * g.dh / g.sh), q.dw = -(p.sb * g.dw / g.sw);
+        q.oh = p.nj, q.ow = p.ni, q.K = p.kp, q.plane = p.nj * p.ni;
+        q.xbs = (long long)g.c * g.ih * g.iw;  // the loaders address images through it (run_conv2d fills it in; this path builds its own)
+        const float* wph = (const float*)dwt + p.woff;
+        ConvWLoad al{wph, q, (int)((((uintptr_t)wph & 15) == 0) && p.kp % 4 == 0)};
+        ConvTEpi epi{out, db, make_fastdiv(p.ni, q.plane), g.oc, g.oh, g.ow, p.py, p.px, g.sh, g.sw, p.ni, q.plane};
+        if (tap_major) {
+            ConvXLoadTap bl{dx, q, make_fastdiv(p.ni, q.plane), make_fastdiv(g.c, p.kp), make_fastdiv(p.nb, p.na * p.nb)};
+            gemm::launch(ctx->stream, al, bl, epi, g.oc, q.plane, p.kp, g.n, ctx->num_cus);
+        } else {
+            ConvXLoad bl{dx, q, make_fastdiv(p.ni, q.plane), make_fastdiv(p.na * p.nb, p.kp), make_fastdiv(p.nb, p.na * p.nb)};
+            gemm::launch(ctx->stream, al, bl, epi, g.oc, q.plane, p.kp, g.n, ctx->num_cus);
+        }
+    }
+    LELE_HIP_CHECK(hipGetLastError());
+    return 0;
 }
 
 int lele_hip_conv_transpose(LeleCtx* ctx, const LeleTensor* x, const LeleTensor* w, const LeleTensor* bias,
@@ -2328,128 +2413,22 @@ int lele_hip_conv_transpose(LeleCtx* ctx, const LeleTensor* x, const LeleTensor*
     g.oh = (int)oh;
     g.ow = (int)ow;
     if (bias) LELE_REQUIRE(numel(bias) >= g.oc, "conv_transpose: bias shorter than C_out");
-    LELE_TRY(ctx->arena_reset());
-    const void *dx = nullptr, *dwp = nullptr, *db = nullptr;
-    LELE_TRY(ctx->dev_ptr(x, &dx));
-    LELE_TRY(ctx->dev_ptr(w, &dwp));
-    if (bias) LELE_TRY(ctx->dev_ptr(bias, &db));
+    const float *dx = nullptr, *dwp = nullptr, *db = nullptr;
+    LELE_TRY(stage_xwb(ctx, x, w, bias, &dx, &dwp, &db));
     const int64_t total = (int64_t)g.n * g.oc * oh * ow;
     LELE_TRY(out->reserve((size_t)total * 4));
     ctx->set_route(nullptr);
-    if (total == 0) return set_shape(out_shape, out_rank, {(int64_t)g.n, (int64_t)g.oc, oh, ow});
-    if (lab_env("LELE_HIP_CONVT_GATHER")) {  // reference gather kernel, kept for A/B checks
-        hipLaunchKernelGGL(conv_transpose_kernel, dim3(grid_for(total)), dim3(256), 0, ctx->stream, (const float*)dx,
-                           (const float*)dwp, (const float*)db, (float*)out->data, g);
+    if (total == 0) {
+        // nothing to launch
+    } else if (lab_env("LELE_HIP_CONVT_GATHER")) {  // reference gather kernel, kept for A/B checks
+        hipLaunchKernelGGL(conv_transpose_kernel, dim3(grid_for(total)), dim3(256), 0, ctx->stream, dx, dwp, db, (float*)out->data, g);
         LELE_HIP_CHECK(hipGetLastError());
-        return set_shape(out_shape, out_rank, {(int64_t)g.n, (int64_t)g.oc, oh, ow});
+    } else if (g.kh == g.sh && g.kw == g.sw && g.dh == 1 && g.dw == 1 && g.pt == 0 && g.pl == 0 && pb == 0 && pr == 0 &&
+               (int64_t)g.oc * g.kh * g.kw < (int64_t(1) << 31) && !lab_env("LELE_HIP_CONVT_PHASES")) {
+        LELE_TRY(convt_ks(ctx, g, w, dx, dwp, db, (float*)out->data));
+    } else {
+        LELE_TRY(convt_phase(ctx, g, w, dx, dwp, db, (float*)out->data));
     }
-    if (g.kh == g.sh && g.kw == g.sw && g.dh == 1 && g.dw == 1 && g.pt == 0 && g.pl == 0 && pb == 0 && pr == 0 &&
-        (int64_t)g.oc * g.kh * g.kw < (int64_t(1) << 31) && !lab_env("LELE_HIP_CONVT_PHASES")) {
-        // kernel == stride: one GEMM with a scattering epilogue (see ConvTKsEpi)
-        const int taps = g.kh * g.kw, mrows = g.oc * taps, plane_in = g.ih * g.iw;
-        const size_t wb = (size_t)g.c * mrows * 4;
-        void* dwk = nullptr;
-        LELE_TRY(ctx->weight_form(w, WeightForm::ConvTKernelStride, {}, wb, &dwk, [&](void* d) {
-            hipLaunchKernelGGL(convt_wks_kernel, dim3(grid_for((int64_t)g.c * mrows)), dim3(256), 0, ctx->stream, (const float*)dwp, (float*)d, g.c,
-                               g.oc, taps);
-            LELE_HIP_CHECK(hipGetLastError());
-            return 0;
-        }));
-        ConvGeom q{};
-        q.group = 1;
-        q.ocg = mrows;
-        q.K = g.c;
-        ConvWLoad al{(const float*)dwk, q, (int)(g.c % 4 == 0)};
-        gemm::LoadKRow bl{(const float*)dx, (int64_t)g.c * plane_in, (int64_t)plane_in, plane_in, g.c};
-        ConvTKsEpi epi{(float*)out->data, (const float*)db, make_fastdiv(g.iw, plane_in), make_fastdiv(taps, mrows), make_fastdiv(g.kw, taps),
-                       g.oc, g.oh, g.ow, g.kh, g.kw, g.iw, plane_in, taps};
-        ctx->set_route("convt.ks", gemm::launch(ctx->stream, al, bl, epi, mrows, plane_in, g.c, g.n, ctx->num_cus));
-        LELE_HIP_CHECK(hipGetLastError());
-        return set_shape(out_shape, out_rank, {(int64_t)g.n, (int64_t)g.oc, oh, ow});
-    }
-    // per-phase weights: one buffer holding every phase's [OC][K_phase] block (each tap belongs to exactly one phase)
-    const size_t wbytes = (size_t)g.c * g.oc * g.kh * g.kw * 4;
-    const int tap_major = g.c % 4 == 0;
-    // the taps of a phase along one axis: the first, their spacing and their number
-    auto phase_taps = [](int p, int pad, int k, int dil, int stride, int* t0, int* st, int* nt) {
-        *t0 = -1, *st = 1, *nt = 0;
-        for (int t = 0; t < k; ++t)
-            if ((((p + pad - t * dil) % stride) + stride) % stride == 0) {
-                if (*nt == 0) *t0 = t;
-                if (*nt == 1) *st = t - *t0;
-                ++*nt;
-            }
-    };
-    // the phase structure depends on stride / dilation / pad-begin, so they are part of the key
-    void* dwt = nullptr;
-    LELE_TRY(ctx->weight_form(w, WeightForm::ConvTPhase, {g.sh, g.sw, g.dh, g.dw, g.pt, g.pl}, wbytes, &dwt, [&](void* d) {
-        size_t woff = 0;
-        for (int py = 0; py < g.sh; ++py)
-            for (int px = 0; px < g.sw; ++px) {
-                int a0, sa, na, b0, sb, nb;
-                phase_taps(py, g.pt, g.kh, g.dh, g.sh, &a0, &sa, &na);
-                phase_taps(px, g.pl, g.kw, g.dw, g.sw, &b0, &sb, &nb);
-                const int kp = g.c * na * nb;
-                if (kp)
-                    hipLaunchKernelGGL(convt_wphase_kernel, dim3(grid_for((int64_t)g.oc * kp)), dim3(256), 0, ctx->stream, (const float*)dwp,
-                                       (float*)d + woff, g.c, g.oc, g.kh, g.kw, a0, sa, na, b0, sb, nb, tap_major);
-                woff += (size_t)g.oc * kp;
-            }
-        LELE_HIP_CHECK(hipGetLastError());
-        return 0;
-    }));
-    size_t woff = 0;
-    ctx->set_route("convt.phase");  // one GEMM per phase (their own tiles each): the route names no GEMM kernel
-    for (int py = 0; py < g.sh; ++py)
-        for (int px = 0; px < g.sw; ++px) {
-            const int nj = py < g.oh ? (g.oh - py + g.sh - 1) / g.sh : 0, ni = px < g.ow ? (g.ow - px + g.sw - 1) / g.sw : 0;
-            int a0, sa, na, b0, sb, nb;
-            phase_taps(py, g.pt, g.kh, g.dh, g.sh, &a0, &sa, &na);
-            phase_taps(px, g.pl, g.kw, g.dw, g.sw, &b0, &sb, &nb);
-            const int kp = g.c * na * nb;
-            float* wph = (float*)dwt + woff;
-            woff += (size_t)g.oc * kp;
-            if (nj == 0 || ni == 0) continue;
-            if (kp == 0) {  // no tap reaches this phase: bias only
-                hipLaunchKernelGGL(convt_fill_phase_kernel, dim3(grid_for((int64_t)g.n * g.oc * nj * ni)), dim3(256), 0,
-                                   ctx->stream, (float*)out->data, (const float*)db, g.n, g.oc, g.oh, g.ow, py, px, g.sh,
-                                   g.sw, nj, ni);
-                ctx->set_route("convt.phase_fill");
-                continue;
-            }
-            ConvGeom q{};
-            q.n = g.n;
-            q.c = g.c;
-            q.ih = g.ih;
-            q.iw = g.iw;
-            q.oc = g.oc;
-            q.kh = na;
-            q.kw = nb;
-            q.group = 1;
-            q.icg = g.c;
-            q.ocg = g.oc;
-            q.sh = q.sw = 1;
-            q.pt = -((py + g.pt - a0 * g.dh) / g.sh);  // iy = j - pt + t*dh with dh = -(sa*dh/sh)
-            q.pl = -((px + g.pl - b0 * g.dw) / g.sw);
-            q.dh = -(sa * g.dh / g.sh);
-            q.dw = -(sb * g.dw / g.sw);
-            q.oh = nj;
-            q.ow = ni;
-            q.K = kp;
-            q.plane = nj * ni;
-            q.xbs = (long long)g.c * g.ih * g.iw;  // the loaders address images through it (run_conv2d fills it in; this path builds its own)
-            ConvWLoad al{wph, q, (int)((((uintptr_t)wph & 15) == 0) && kp % 4 == 0)};
-            ConvTEpi epi{(float*)out->data, (const float*)db, make_fastdiv(ni, q.plane), g.oc, g.oh, g.ow, py, px, g.sh, g.sw, ni,
-                         q.plane};
-            if (tap_major) {
-                ConvXLoadTap bl{(const float*)dx, q, make_fastdiv(ni, q.plane), make_fastdiv(g.c, kp), make_fastdiv(nb, na * nb)};
-                gemm::launch(ctx->stream, al, bl, epi, g.oc, q.plane, kp, g.n, ctx->num_cus);
-            } else {
-                ConvXLoad bl{(const float*)dx, q, make_fastdiv(ni, q.plane), make_fastdiv(na * nb, kp), make_fastdiv(nb, na * nb)};
-                gemm::launch(ctx->stream, al, bl, epi, g.oc, q.plane, kp, g.n, ctx->num_cus);
-            }
-        }
-    LELE_HIP_CHECK(hipGetLastError());
     return set_shape(out_shape, out_rank, {(int64_t)g.n, (int64_t)g.oc, oh, ow});
 }
 
@@ -2464,7 +2443,7 @@ int lele_hip_conv_integer(LeleCtx* ctx, const LeleTensor* x, const LeleTensor* w
                  "conv_integer: zero points are scalar attributes and must be host tensors");
     LELE_HIP_CHECK(hipSetDevice(ctx->device));
     ConvGeom g;
-    LELE_TRY(conv_geom_from(x, x->shape, w, dilations, ndil, group, pads, npads, strides, nstr, &g));
+    LELE_TRY(conv_geom_2d(kSayConvInteger, x->shape, w, dilations, ndil, group, pads, npads, strides, nstr, &g));
     const float x_zp = host_scalar(x_zero_point), w_zp = host_scalar(w_zero_point);
     LELE_TRY(ctx->arena_reset());
     const void* dx = nullptr;
@@ -2472,7 +2451,7 @@ int lele_hip_conv_integer(LeleCtx* ctx, const LeleTensor* x, const LeleTensor* w
     LELE_TRY(out->reserve((size_t)g.n * g.oc * g.plane * 4));
     const float* src = (const float*)dx;
     const int64_t src_c = g.c;
-    LELE_TRY(ci_run(ctx, g, w, w_zp, &src, &src_c, 1, nullptr, x_zp, (float*)out->data));
+    LELE_TRY(ci_run(ctx, CiArgs{g, w, w_zp, &src, &src_c, 1, nullptr, x_zp, (float*)out->data}));
     return set_shape(out_shape, out_rank, {(int64_t)g.n, (int64_t)g.oc, (int64_t)g.oh, (int64_t)g.ow});
 }
 
@@ -2496,7 +2475,7 @@ int lele_hip_conv_integer_from_f32(LeleCtx* ctx, const LeleTensor* const* source
     }
     const int64_t xshape[4] = {sources[0]->shape[0], total_c, sources[0]->shape[2], sources[0]->shape[3]};
     ConvGeom g;
-    LELE_TRY(conv_geom_from(sources[0], xshape, w, dilations, ndil, group, pads, npads, strides, nstr, &g));
+    LELE_TRY(conv_geom_2d(kSayConvInteger, xshape, w, dilations, ndil, group, pads, npads, strides, nstr, &g));
     const float w_zp = host_scalar(w_zero_point);
     LELE_TRY(ctx->arena_reset());
     std::vector<const float*> ds(nsrc);
@@ -2515,7 +2494,7 @@ int lele_hip_conv_integer_from_f32(LeleCtx* ctx, const LeleTensor* const* source
     hipLaunchKernelGGL(ci_scale_out_kernel, dim3(1), dim3(1), 0, ctx->stream, (const QParamsDev*)prm, (float*)out_scale->data);
     std::vector<int64_t> chans(nsrc);
     for (size_t i = 0; i < nsrc; ++i) chans[i] = sources[i]->shape[1];
-    LELE_TRY(ci_run(ctx, g, w, w_zp, ds.data(), chans.data(), (int)nsrc, (const QParamsDev*)prm, 0.0f, (float*)out->data));
+    LELE_TRY(ci_run(ctx, CiArgs{g, w, w_zp, ds.data(), chans.data(), (int)nsrc, (const QParamsDev*)prm, 0.0f, (float*)out->data}));
     return set_shape(out_shape, out_rank, {(int64_t)g.n, (int64_t)g.oc, (int64_t)g.oh, (int64_t)g.ow});
 }
 
