@@ -206,6 +206,57 @@ int lele_hip_frontend_stream_counters(const LeleFrontendStream* st, int64_t id, 
 int lele_hip_frontend_stream_push(LeleFrontendStream* st, const LeleTensor* pcm, const int64_t* starts, const int64_t* lengths,
                                   const uint8_t* final_or_null, LeleBuf* out, int64_t* row_offsets, int64_t* out_shape, int32_t* out_rank);
 
+/* ---- audio resampling: other sample rates in front of the front-end.  A LeleResampler converts from_rate -> to_rate in one of two
+ * modes; its packed call and its live-stream form return f32 [N'] packed + out_offsets, which together with the offsets' differences
+ * are the (pcm, starts, lengths) that lele_hip_frontend_compute_segments and lele_hip_frontend_stream_push take.
+ *   LELE_RESAMPLE_LINEAR  the reference's `resample` (examples/web-demo/src/audio.rs:114-138) bit for bit: ratio = from as f64 / to as
+ *     f64, output_len = (len as f64 / ratio) as usize, output i at src_pos = i as f64 * ratio between samples idx = floor(src_pos) and
+ *     idx + 1 in f64 (two multiplies and an add, not contracted), the last sample as it is where idx + 1 == len, nothing where
+ *     idx >= len (the result is then shorter than output_len; lele_hip_resampler_out_len gives the true length).  from == to copies.
+ *   LELE_RESAMPLE_SINC    a Kaiser-windowed polyphase FIR: g = gcd(from, to), L = to / g, M = from / g; output i sits at input time
+ *     i*M / L: base = (i*M) div L, phase = (i*M) mod L (64-bit integers); T = 2 * ceil(z / min(1, L/M)) taps a phase; tap t weighs input
+ *     sample base - T/2 + 1 + t by w(d) = s sinc(s d) kaiser_beta(d / (T/2)) at d = (t - T/2 + 1) - phase/L, s = rolloff * min(1, L/M),
+ *     each phase normalised to sum 1 in f64 and rounded to f32 (built on the host, uploaded at create).  The input is zero outside
+ *     [0, len); output_len = ceil(len * L / M).  Accumulation: acc = fmaf(h[t], x[t], acc) in f32 for t = 0 .. T-1 in this order from
+ *     +0 -- the order depends on T alone, never on the position in the buffer, the cut into chunks or the number of streams.
+ * Routes (lele_hip_last_route): resample.copy, resample.linear, resample.fir1 (L == 1: coefficients by scalar loads), resample.fir.
+ * A rate pair whose L * (T + 1) table and input tile exceed 160 KiB of LDS is refused at create. */
+typedef enum { LELE_RESAMPLE_LINEAR = 0, LELE_RESAMPLE_SINC = 1 } LeleResampleMode;
+typedef struct LeleResampler LeleResampler;
+typedef struct LeleResamplerStream LeleResamplerStream;
+/* z zero crossings a side (16), beta (8.6) and rolloff (0.9) shape the SINC table and are ignored by LINEAR.  ctx == NULL creates a
+ * host-only object: lengths and the table, no GPU; it cannot resample.  Destroy it after its streams and before its ctx. */
+int lele_hip_resampler_create(LeleCtx* ctx, int64_t from_rate, int64_t to_rate, int32_t mode, int32_t z, double beta, double rolloff,
+                              LeleResampler** out);
+int lele_hip_resampler_destroy(LeleResampler* rs);
+/* The f32 table as uploaded, [L][T] (LINEAR and from == to: L = M = 1 ... and T = 0, no table); table may be NULL to ask for the sizes */
+int lele_hip_resampler_table(const LeleResampler* rs, float* table, int64_t capacity, int64_t* l, int64_t* m, int64_t* taps);
+/* Host arithmetic, nothing is launched: the outputs that become final when chunk_len samples follow samples_before, and the input
+ * samples carried after that (0 after a final chunk).  samples_before = 0 with final = 1: the length of a whole utterance's result.
+ * An output is final, LINEAR: once sample idx + 1 has arrived and i < output_len of what has arrived; the rest (the tail rule) with
+ * `final`.  SINC: once its last tap's sample base + T/2 has arrived; with `final` the input is zero-extended. */
+int lele_hip_resampler_out_len(const LeleResampler* rs, int64_t samples_before, int64_t chunk_len, int32_t final, int64_t* out_len,
+                               int64_t* carry);
+/* Segments of ONE pcm buffer (f32 [N], host or device), taken exactly as lele_hip_frontend_compute_segments takes them (any order,
+ * overlaps, repeats, any 4-byte-aligned start), each resampled on its own in ONE launch.  out f32 [N'] packed, out_offsets
+ * (count + 1, written on the host).  N' == 0 gives rank 0.  Everything is checked before anything is launched; a failing call leaves
+ * out and out_offsets as they were.  The layout is shape metadata uploaded once per distinct layout, so a graph may record the call
+ * (run the layout once before capturing it). */
+int lele_hip_resample_segments(LeleResampler* rs, const LeleTensor* pcm, const int64_t* starts, const int64_t* lengths, int64_t count,
+                               LeleBuf* out, int64_t* out_offsets, int64_t* out_shape, int32_t* out_rank);
+/* `streams` live streams of at most max_chunk samples a push.  Per stream the device keeps the input samples the next output still
+ * needs (LINEAR: at most ceil(ratio) + 2, SINC: fewer than T), in two halves that a push reads and writes in turn; the host keeps the
+ * samples received and the absolute output index.  Concatenated per stream, the pushes are bit for bit lele_hip_resample_segments on
+ * the whole utterance for any cut into chunks, zero-length chunks and a final push without audio included.  A final push resets the
+ * stream.  reset / counters (samples received, outputs emitted, samples carried) / push mirror lele_hip_frontend_stream_*: one entry a
+ * stream, everything checked before the one launch, a failing push leaves out and the streams as they were. */
+int lele_hip_resampler_stream_create(LeleResampler* rs, int64_t streams, int64_t max_chunk, LeleResamplerStream** out);
+int lele_hip_resampler_stream_destroy(LeleResamplerStream* st);
+int lele_hip_resampler_stream_reset(LeleResamplerStream* st, const int64_t* ids, int64_t count);
+int lele_hip_resampler_stream_counters(const LeleResamplerStream* st, int64_t id, int64_t* samples, int64_t* outputs, int64_t* carry);
+int lele_hip_resampler_stream_push(LeleResamplerStream* st, const LeleTensor* pcm, const int64_t* starts, const int64_t* lengths,
+                                   const uint8_t* final_or_null, LeleBuf* out, int64_t* out_offsets, int64_t* out_shape, int32_t* out_rank);
+
 /* Lfr::compute, src/features/lfr.rs:18-54: [T, D] (or [1,T,D]) -> [ceil(T/n), D*m] */
 int lele_hip_lfr(LeleCtx* ctx, const LeleTensor* x, int64_t m, int64_t n, LeleBuf* out, int64_t* out_shape,
                  int32_t* out_rank);

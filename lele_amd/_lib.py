@@ -65,6 +65,14 @@ def lib():
                 ("lele_hip_frontend_stream_push", [C.c_void_p, C.c_void_p, _i64p, _i64p, C.POINTER(C.c_uint8), C.c_void_p, _i64p, _i64p, _i32p]),
                 ("lele_hip_frontend_stream_reset", [C.c_void_p, _i64p, C.c_int64]),
                 ("lele_hip_cmvn_segments", [C.c_void_p, C.c_void_p, _i64p, C.c_int64, C.c_float, C.c_void_p, _i64p, _i32p]),
+                ("lele_hip_resampler_create", [C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_double, C.c_double, C.POINTER(C.c_void_p)]),
+                ("lele_hip_resampler_table", [C.c_void_p, C.c_void_p, C.c_int64, _i64p, _i64p, _i64p]),
+                ("lele_hip_resampler_out_len", [C.c_void_p, C.c_int64, C.c_int64, C.c_int32, _i64p, _i64p]),
+                ("lele_hip_resample_segments", [C.c_void_p, C.c_void_p, _i64p, _i64p, C.c_int64, C.c_void_p, _i64p, _i64p, _i32p]),
+                ("lele_hip_resampler_stream_create", [C.c_void_p, C.c_int64, C.c_int64, C.POINTER(C.c_void_p)]),
+                ("lele_hip_resampler_stream_reset", [C.c_void_p, _i64p, C.c_int64]),
+                ("lele_hip_resampler_stream_counters", [C.c_void_p, C.c_int64, _i64p, _i64p, _i64p]),
+                ("lele_hip_resampler_stream_push", [C.c_void_p, C.c_void_p, _i64p, _i64p, C.POINTER(C.c_uint8), C.c_void_p, _i64p, _i64p, _i32p]),
                 ("lele_hip_segments_to_padded", [C.c_void_p, C.c_void_p, _i64p, C.c_int64, C.c_int64, C.c_float, C.c_void_p, _i64p, _i32p])):
             fn = getattr(_lib, name, None)
             if fn is not None:
@@ -115,14 +123,15 @@ class Ctx:
         self._bufs = []
         self._graphs = []  # weak references: ctx_destroy destroys the graphs recorded on it, their wrappers must not do it again
         self._comms = []   # likewise the communicators bound to this ctx's stream
+        self._children = []  # likewise the wrappers of objects that keep this ctx's stream (features.Resampler, ResamplerStream)
 
     def close(self):
         if self._h:
-            for r in self._graphs + self._comms:
+            for r in self._graphs + self._comms + self._children:
                 g = r()
                 if g is not None:
                     g.close()
-            self._graphs, self._comms = [], []
+            self._graphs, self._comms, self._children = [], [], []
             for b in self._bufs:
                 b.close()
             lib().lele_hip_ctx_destroy(self._h)

@@ -11,6 +11,8 @@ The device halves are in csrc/app.hip (`kernels.wav_to_f32`, `argmax_last`, `tok
   * `beam_results`        -- that kernel's four arrays -> the reference's list format
   * `ctc_forced_align`    -- the reference of kernels.ctc_align_segments: a known transcript's Viterbi alignment and CTC likelihood
   * `align_results`       -- that kernel's five arrays -> the reference's format
+  * `resample_linear`, `resample_fir_table`, `resample_fir` -- the references of features.Resampler: the reference's linear
+    `resample` and the Kaiser-windowed polyphase FIR in float64 (never used by the device path)
 """
 import numpy as np
 
@@ -252,3 +254,100 @@ def vad_segments(probs, chunk_size, padded_len, audio_len, sample_rate=16000, th
                 continue
         merged.append(list(seg))
     return [(a, b) for a, b in merged]
+
+
+def resample_linear(samples, from_rate, to_rate):
+    """examples/web-demo/src/audio.rs:114-138 (the reference of features.Resampler(mode="linear")): f32 in, f32 out, every output by
+    the reference's own float64 operations in its own order -- written over arrays; resample_linear_loop is the same line by line"""
+    s = np.asarray(samples, np.float32).reshape(-1)
+    if from_rate == to_rate:                                        # :116-118
+        return s.copy()
+    ratio = float(from_rate) / float(to_rate)                       # :120
+    output_len = int(float(len(s)) / ratio)                         # :121
+    i = np.arange(output_len, dtype=np.int64)
+    src_pos = i.astype(np.float64) * ratio                          # :125
+    idx = src_pos.astype(np.int64)                                  # :126 (src_pos >= 0: `as usize` truncates)
+    frac = src_pos - idx.astype(np.float64)                         # :127
+    keep = idx < len(s)                                             # :132: past the end nothing is pushed
+    idx, frac = idx[keep], frac[keep]
+    if len(idx) == 0:
+        return np.zeros(0, np.float32)
+    s64 = s.astype(np.float64)
+    nxt = np.minimum(idx + 1, len(s) - 1)
+    val = (s64[idx] * (1.0 - frac) + s64[nxt] * frac).astype(np.float32)   # :130-131: two products, one sum, then `as f32`
+    return np.where(idx + 1 < len(s), val, s[idx])                  # :129 / :132-133: the last sample as it is
+
+
+def resample_linear_loop(samples, from_rate, to_rate):
+    """audio.rs:114-138 line by line, one output at a time (slow; tests pin resample_linear to it)"""
+    s = np.asarray(samples, np.float32).reshape(-1)
+    if from_rate == to_rate:
+        return s.copy()
+    ratio = float(from_rate) / float(to_rate)
+    output_len = int(float(len(s)) / ratio)
+    out = []
+    for i in range(output_len):
+        src_pos = float(i) * ratio
+        idx = int(src_pos)
+        frac = src_pos - float(idx)
+        if idx + 1 < len(s):
+            val = float(s[idx]) * (1.0 - frac) + float(s[idx + 1]) * frac
+            out.append(np.float32(val))
+        elif idx < len(s):
+            out.append(s[idx])
+    return np.asarray(out, np.float32)
+
+
+def _bessel_i0(x):
+    """modified Bessel function of the first kind, order 0: its power series (every term positive)"""
+    x = np.asarray(x, np.float64)
+    q = x * x / 4.0
+    total = np.ones_like(x)
+    term = np.ones_like(x)
+    for k in range(1, 500):
+        term = term * q / (float(k) * float(k))
+        total = total + term
+        if np.all(term < total * 1e-18):
+            break
+    return total
+
+
+def resample_fir_shape(from_rate, to_rate, z=16):
+    """(L, M, T) of the polyphase FIR: L = to / gcd, M = from / gcd, T = 2 * ceil(z / min(1, L/M)) taps a phase"""
+    import math
+    g = math.gcd(int(from_rate), int(to_rate))
+    L, M = int(to_rate) // g, int(from_rate) // g
+    return L, M, 2 * int(math.ceil(float(z) / min(1.0, float(L) / float(M))))
+
+
+def resample_fir_table(from_rate, to_rate, z=16, beta=8.6, rolloff=0.9):
+    """The Kaiser-windowed sinc table of features.Resampler(mode="sinc") in float64, [L, T]: tap t of phase p weighs input sample
+    base - T/2 + 1 + t, at distance d = (t - T/2 + 1) - p/L from the output's instant, by s sinc(s d) kaiser_beta(d / (T/2)),
+    s = rolloff * min(1, L/M); every phase normalised to sum 1.  The library uploads this table rounded to float32."""
+    L, M, T = resample_fir_shape(from_rate, to_rate, z)
+    s = float(rolloff) * min(1.0, float(L) / float(M))
+    W = float(T) / 2.0
+    d = (np.arange(T, dtype=np.float64)[None, :] - float(T // 2 - 1)) - np.arange(L, dtype=np.float64)[:, None] / float(L)
+    a = np.pi * s * d
+    sinc = np.where(a == 0.0, 1.0, np.sin(a) / np.where(a == 0.0, 1.0, a))
+    u = d / W
+    win = _bessel_i0(float(beta) * np.sqrt(np.maximum(0.0, 1.0 - u * u))) / _bessel_i0(float(beta))
+    w = s * sinc * win
+    return w / w.sum(axis=1, keepdims=True)
+
+
+def resample_fir(samples, table, L, M):
+    """The polyphase FIR on the host: float64 accumulation of `table` [L, T] as given (pass the float32-rounded table to get the
+    reference of the device kernel).  The input is zero outside [0, len); ceil(len * L / M) outputs, float64."""
+    s = np.asarray(samples, np.float64).reshape(-1)
+    tab = np.asarray(table, np.float64)
+    T = tab.shape[1]
+    n = len(s)
+    n_out = (n * L + M - 1) // M
+    i = np.arange(n_out, dtype=np.int64)
+    base, phase = (i * M) // L, (i * M) % L
+    pad = np.concatenate([np.zeros(T, np.float64), s, np.zeros(T, np.float64)])
+    out = np.zeros(n_out, np.float64)
+    for t in range(T):
+        out += tab[phase, t] * pad[base - T // 2 + 1 + t + T]
+    return out

@@ -23,6 +23,13 @@ def _ctx(ctx):
     return ctx if ctx is not None else default_ctx()
 
 
+def _adopt(ctx, obj):
+    """obj keeps ctx's stream: ctx.close() closes it first.  Destroying it AFTER its context (an object still alive when the interpreter
+    exits, e.g. in the traceback of an uncaught exception) would synchronise a stream that is gone."""
+    import weakref
+    ctx._children.append(weakref.ref(obj))
+
+
 class SenseVoiceFrontend:
     """SenseVoiceFrontend (pipeline.rs:28-193): compute(pcm) -> TensorView [T, n_mels*lfr_m]."""
 
@@ -34,12 +41,16 @@ class SenseVoiceFrontend:
         self._h = C.c_void_p()
         _lib.check(_lib.lib().lele_hip_frontend_create(self.ctx._h, C.byref(cfg), C.byref(self._h)))
         self._out = self.ctx.buf()
+        _adopt(self.ctx, self)
+
+    def close(self):
+        if self._h:
+            _lib.lib().lele_hip_frontend_destroy(self._h)
+            self._h = C.c_void_p()
 
     def __del__(self):
         try:
-            if self._h:
-                _lib.lib().lele_hip_frontend_destroy(self._h)
-                self._h = C.c_void_p()
+            self.close()
         except Exception:
             pass
 
@@ -119,6 +130,7 @@ class FrontendStream:
         self._h = C.c_void_p()
         _lib.check(_lib.lib().lele_hip_frontend_stream_create(fe._h, C.c_int64(self.streams), C.c_int64(self.max_chunk), C.byref(self._h)))
         self._out = fe.ctx.buf()
+        _adopt(fe.ctx, self)
 
     def close(self):
         if self._h:
@@ -191,6 +203,143 @@ class FrontendStream:
     @property
     def rows_emitted(self):
         return self._counters(2)
+
+
+RESAMPLE_MODES = {"linear": 0, "sinc": 1}
+
+
+class Resampler:
+    """from_rate -> to_rate on the device (include/lele_hip.h, "audio resampling").  mode "linear": the reference's `resample`
+    (examples/web-demo/src/audio.rs:114-138) bit for bit; "sinc": a Kaiser-windowed polyphase FIR (z zero crossings a side, beta,
+    rolloff).  device=False: a host-only object (out_len, table) that needs no GPU."""
+
+    def __init__(self, from_rate, to_rate, mode="linear", ctx=None, z=16, beta=8.6, rolloff=0.9, device=True):
+        if mode not in RESAMPLE_MODES:
+            raise _lib.LeleError("Resampler: mode %r is neither 'linear' nor 'sinc'" % (mode,))
+        self.from_rate, self.to_rate, self.mode = int(from_rate), int(to_rate), mode
+        self.ctx = _ctx(ctx) if device else None
+        self._h = C.c_void_p()
+        _lib.check(_lib.lib().lele_hip_resampler_create(self.ctx._h if device else None, C.c_int64(self.from_rate), C.c_int64(self.to_rate),
+                                                        C.c_int32(RESAMPLE_MODES[mode]), C.c_int32(int(z)), C.c_double(beta), C.c_double(rolloff),
+                                                        C.byref(self._h)))
+        self._out = self.ctx.buf() if device else None
+        if device:
+            _adopt(self.ctx, self)
+
+    def close(self):
+        if self._h:
+            _lib.lib().lele_hip_resampler_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def out_len(self, n, samples_before=0, final=True, with_carry=False):
+        """outputs that become final when n samples follow samples_before (lele_hip_resampler_out_len; host arithmetic, no GPU);
+        the defaults give the length of a whole utterance's result.  with_carry: -> (outputs, input samples carried afterwards)"""
+        o, c = C.c_int64(), C.c_int64()
+        _lib.check(_lib.lib().lele_hip_resampler_out_len(self._h, C.c_int64(int(samples_before)), C.c_int64(int(n)), C.c_int32(1 if final else 0),
+                                                         C.byref(o), C.byref(c)))
+        return (o.value, c.value) if with_carry else o.value
+
+    def table(self):
+        """-> (f32 table [L, T] as uploaded, L, M); "linear" has none: shape (1, 0)"""
+        l, m, t = C.c_int64(), C.c_int64(), C.c_int64()
+        _lib.check(_lib.lib().lele_hip_resampler_table(self._h, None, C.c_int64(0), C.byref(l), C.byref(m), C.byref(t)))
+        tab = np.zeros((l.value, t.value), np.float32)
+        _lib.check(_lib.lib().lele_hip_resampler_table(self._h, tab.ctypes.data_as(C.c_void_p), C.c_int64(tab.size), None, None, None))
+        return tab, l.value, m.value
+
+    def compute_segments(self, pcm, segments, out=None):
+        """The (start, end) ranges of ONE pcm buffer [N], each resampled on its own, in one launch.  -> (TensorView [N'], segments'
+        np.int64 [count, 2]): range i of the result is the resampled range i -- what SenseVoiceFrontend.compute_segments takes."""
+        seg = np.asarray(segments, np.int64).reshape(-1, 2)
+        starts = np.ascontiguousarray(seg[:, 0])
+        lengths = np.ascontiguousarray(seg[:, 1] - seg[:, 0])
+        offsets = np.zeros(len(seg) + 1, np.int64)
+        keep = []
+        t = _lib.as_tensor(unwrap(pcm), keep)
+        sh = _lib.OutShape()
+        out = out or self._out
+        _lib.check(_lib.lib().lele_hip_resample_segments(self._h, t, _lib.i64_ptr(starts), _lib.i64_ptr(lengths), len(seg), out._h,
+                                                         _lib.i64_ptr(offsets), sh.shape, C.byref(sh.rank)))
+        segs = np.stack([offsets[:-1], offsets[1:]], axis=1)
+        if sh.rank.value == 0:
+            return TensorView(np.zeros(0, np.float32)), segs
+        return TensorView(_lib.DevTensor(out, sh.get(), np.float32)), segs
+
+
+class ResamplerStream:
+    """`streams` live streams through one Resampler, at most max_chunk input samples a stream and push.  push() returns every output
+    sample that has become final; concatenated per stream they are rs.compute_segments on the whole utterance, bit for bit, for any
+    cut into chunks."""
+
+    def __init__(self, rs, streams, max_chunk):
+        self.rs, self.streams, self.max_chunk = rs, int(streams), int(max_chunk)
+        self._h = C.c_void_p()
+        _lib.check(_lib.lib().lele_hip_resampler_stream_create(rs._h, C.c_int64(self.streams), C.c_int64(self.max_chunk), C.byref(self._h)))
+        self._out = rs.ctx.buf()
+        _adopt(rs.ctx, self)
+
+    def close(self):
+        if self._h:
+            _lib.lib().lele_hip_resampler_stream_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def push(self, chunks, final=None, out=None):
+        """chunks and final as FrontendStream.push takes them.  -> (TensorView [N'], starts, lengths): stream i's new samples are
+        [starts[i], starts[i] + lengths[i]) of the result -- the tuple FrontendStream.push takes."""
+        if isinstance(chunks, tuple) and len(chunks) == 3:
+            pcm, starts, lengths = chunks
+            starts = np.ascontiguousarray(starts, np.int64).reshape(-1)
+            lengths = np.ascontiguousarray(lengths, np.int64).reshape(-1)
+        else:
+            pcm, segs = pack(chunks)
+            starts = np.asarray([s for s, _ in segs], np.int64)
+            lengths = np.asarray([e - s for s, e in segs], np.int64)
+        if len(starts) != self.streams or len(lengths) != self.streams:
+            raise _lib.LeleError("ResamplerStream.push: %d chunks for %d streams (one entry per stream; an empty chunk for a silent one)"
+                                 % (len(starts), self.streams))
+        fin = None
+        if final is not None:
+            fin = np.ascontiguousarray(np.asarray(final).astype(bool), np.uint8).reshape(-1)
+            if len(fin) != self.streams:
+                raise _lib.LeleError("ResamplerStream.push: %d final flags for %d streams" % (len(fin), self.streams))
+        offsets = np.zeros(self.streams + 1, np.int64)
+        keep = []
+        t = _lib.as_tensor(unwrap(pcm), keep)
+        sh = _lib.OutShape()
+        out = out or self._out
+        _lib.check(_lib.lib().lele_hip_resampler_stream_push(
+            self._h, t, _lib.i64_ptr(starts), _lib.i64_ptr(lengths), fin.ctypes.data_as(C.POINTER(C.c_uint8)) if fin is not None else None,
+            out._h, _lib.i64_ptr(offsets), sh.shape, C.byref(sh.rank)))
+        o_starts, o_lengths = offsets[:-1].copy(), np.diff(offsets)
+        if sh.rank.value == 0:
+            return TensorView(np.zeros(0, np.float32)), o_starts, o_lengths
+        return TensorView(_lib.DevTensor(out, sh.get(), np.float32)), o_starts, o_lengths
+
+    def reset(self, ids=None):
+        """a new utterance in the streams `ids` (None: in all of them); host counters only"""
+        if ids is None:
+            _lib.check(_lib.lib().lele_hip_resampler_stream_reset(self._h, None, C.c_int64(0)))
+        else:
+            a = np.ascontiguousarray(ids, np.int64).reshape(-1)
+            _lib.check(_lib.lib().lele_hip_resampler_stream_reset(self._h, _lib.i64_ptr(a), C.c_int64(len(a))))
+
+    def counters(self, i):
+        """(samples received, outputs emitted, samples carried) of stream i since its last reset or final push"""
+        v = [C.c_int64(), C.c_int64(), C.c_int64()]
+        _lib.check(_lib.lib().lele_hip_resampler_stream_counters(self._h, C.c_int64(int(i)), *[C.byref(x) for x in v]))
+        return tuple(x.value for x in v)
 
 
 def pack(arrays):

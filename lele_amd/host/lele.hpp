@@ -1413,6 +1413,105 @@ inline StreamRows stream_rows(const FeatureConfig& cfg, int64_t samples_before, 
     return r;
 }
 
+// from_rate -> to_rate on the device (lele_hip.h, "audio resampling"): LELE_RESAMPLE_LINEAR is the reference's `resample`
+// (examples/web-demo/src/audio.rs:114-138) bit for bit, LELE_RESAMPLE_SINC a Kaiser-windowed polyphase FIR.  Outlived by the context.
+class Resampler {
+   public:
+    Resampler(int64_t from_rate, int64_t to_rate, LeleResampleMode mode = LELE_RESAMPLE_LINEAR, int32_t z = 16, double beta = 8.6,
+              double rolloff = 0.9, bool device = true) {
+        check(lele_hip_resampler_create(device ? detail::ctx() : nullptr, from_rate, to_rate, (int32_t)mode, z, beta, rolloff, &h_));
+    }
+    ~Resampler() {
+        if (h_) lele_hip_resampler_destroy(h_);
+    }
+    Resampler(const Resampler&) = delete;
+    Resampler& operator=(const Resampler&) = delete;
+    // outputs that become final when chunk_len samples follow samples_before (host arithmetic); carry: input samples kept afterwards
+    int64_t out_len(int64_t chunk_len, int64_t samples_before = 0, bool final = true, int64_t* carry = nullptr) const {
+        int64_t n = 0;
+        check(lele_hip_resampler_out_len(h_, samples_before, chunk_len, final ? 1 : 0, &n, carry));
+        return n;
+    }
+    // the f32 table as uploaded, [l][taps] (none for LINEAR)
+    std::vector<float> table(int64_t* l = nullptr, int64_t* m = nullptr, int64_t* taps = nullptr) const {
+        int64_t a = 0, b = 0, t = 0;
+        check(lele_hip_resampler_table(h_, nullptr, 0, &a, &b, &t));
+        std::vector<float> tab((size_t)(a * t));
+        check(lele_hip_resampler_table(h_, tab.data(), (int64_t)tab.size(), l, m, taps));
+        return tab;
+    }
+    // (start, end) ranges of ONE pcm buffer [N], each resampled on its own, in one launch -> f32 [N'] packed; segments_out: range i of
+    // the result, what SenseVoiceFrontend::compute_segments takes.  An empty TensorView when N' == 0.
+    TensorView compute_segments(const TensorView& pcm, const std::vector<std::pair<int64_t, int64_t>>& segments, Buffer& out,
+                                std::vector<std::pair<int64_t, int64_t>>& segments_out) const {
+        std::vector<int64_t> starts, lengths, offsets(segments.size() + 1, 0);
+        for (const auto& s : segments) {
+            starts.push_back(s.first);
+            lengths.push_back(s.second - s.first);
+        }
+        Shape sh;
+        LeleTensor t = pcm.c();
+        check(lele_hip_resample_segments(h_, &t, starts.data(), lengths.data(), (int64_t)segments.size(), out.raw(), offsets.data(), sh.dims,
+                                         &sh.rank));
+        segments_out.clear();
+        for (size_t i = 0; i < segments.size(); ++i) segments_out.emplace_back(offsets[i], offsets[i + 1]);
+        if (sh.rank == 0) return TensorView();
+        return TensorView::from_device(out, sh.vec());
+    }
+    LeleResampler* raw() const { return h_; }
+
+   private:
+    LeleResampler* h_ = nullptr;
+};
+
+// `streams` live streams through one Resampler: push() returns every output sample that has become final; per stream they concatenate
+// to Resampler::compute_segments of the whole utterance, bit for bit, for any cut into chunks.  Outlived by its Resampler.
+class ResamplerStream {
+   public:
+    ResamplerStream(const Resampler& rs, int64_t streams, int64_t max_chunk) : streams_(streams) {
+        check(lele_hip_resampler_stream_create(rs.raw(), streams, max_chunk, &h_));
+    }
+    ~ResamplerStream() {
+        if (h_) lele_hip_resampler_stream_destroy(h_);
+    }
+    ResamplerStream(const ResamplerStream&) = delete;
+    ResamplerStream& operator=(const ResamplerStream&) = delete;
+    // chunks and final as FrontendStream::push takes them -> f32 [N'] packed; chunks_out: stream i's new samples in the result, the
+    // chunks FrontendStream::push takes.  An empty TensorView when nothing became final.
+    TensorView push(const TensorView& pcm, const std::vector<std::pair<int64_t, int64_t>>& chunks, const std::vector<uint8_t>& final, Buffer& out,
+                    std::vector<std::pair<int64_t, int64_t>>& chunks_out) {
+        if ((int64_t)chunks.size() != streams_ || (!final.empty() && (int64_t)final.size() != streams_))
+            throw Error("ResamplerStream::push: one chunk (and one final flag) per stream");
+        std::vector<int64_t> starts, lengths, offsets(chunks.size() + 1, 0);
+        for (const auto& s : chunks) {
+            starts.push_back(s.first);
+            lengths.push_back(s.second - s.first);
+        }
+        Shape sh;
+        LeleTensor t = pcm.c();
+        check(lele_hip_resampler_stream_push(h_, &t, starts.data(), lengths.data(), final.empty() ? nullptr : final.data(), out.raw(),
+                                             offsets.data(), sh.dims, &sh.rank));
+        chunks_out.clear();
+        for (size_t i = 0; i < chunks.size(); ++i) chunks_out.emplace_back(offsets[i], offsets[i + 1]);
+        if (sh.rank == 0) return TensorView();
+        return TensorView::from_device(out, sh.vec());
+    }
+    void reset() { check(lele_hip_resampler_stream_reset(h_, nullptr, 0)); }
+    void reset(const std::vector<int64_t>& ids) { check(lele_hip_resampler_stream_reset(h_, ids.data(), (int64_t)ids.size())); }
+    struct Counters {
+        int64_t samples, outputs, carry;
+    };
+    Counters counters(int64_t id) const {
+        Counters c{0, 0, 0};
+        check(lele_hip_resampler_stream_counters(h_, id, &c.samples, &c.outputs, &c.carry));
+        return c;
+    }
+
+   private:
+    LeleResamplerStream* h_ = nullptr;
+    int64_t streams_ = 0;
+};
+
 struct Cmvn {  // cmvn.rs
     float eps = 1e-5f;
     TensorView compute(const TensorView& x, Buffer& out) const {
