@@ -199,7 +199,22 @@ constexpr int kStdMelOff[6] = {0, 3, 7, 13, 23, 40};
 // OPT (the default bank's fused kernels only; 0 elsewhere): bit 0 (kFeConstTw) -- phase A's 27 wave-uniform twiddles are literals
 // (fe::TwConst) instead of scalar loads from the table; bit 1 (kFeLdsMel) -- the 640 mel weights are read from an LDS copy, ten
 // ds_read_b128 a pass, instead of 40 global loads a pass.  OPT = 0 is the table-reading form; the host selects (frontend_create).
-constexpr int kFeConstTw = 1, kFeLdsMel = 2;
+// bit 2 (kFeLeanLds, with the other two only) -- the 64 eight-byte accesses of a pass's exchange are single ds_write_b64 /
+// ds_read_b64 instead of pairs (ds_read2_b64 moves two slots at half the LDS rate: 64 LDS-array cycles a pass and wave less, measured;
+// ds_write2_b64's five-dword transfer costs the store path more than two ds_write_b64 do: the LDS waits fell by a sixth), and the next
+// pass's sample pointer is carried instead of rebuilt from the frame index.  The
+// phase-B twiddle reads stay paired: read singly, their (-wi, wi) operand is no longer an operand modifier of the packed multiply
+// but two more instructions a twiddle, which costs more than the LDS cycles give (docs/experiments.md).
+constexpr int kFeConstTw = 1, kFeLdsMel = 2, kFeLeanLds = 4;
+// One eight-byte LDS access that stays one ds_read_b64 / ds_write_b64: a volatile access is not merged with its neighbour.  The
+// compiler still counts it (lgkmcnt) and still folds the constant part of the address into the instruction's offset.
+typedef float fe_f2 __attribute__((ext_vector_type(2)));
+typedef volatile __attribute__((address_space(3))) fe_f2* fe_lds_f2v;
+__device__ __forceinline__ fe::cf fe_lds_read8(const float* p) {
+    const fe_f2 t = *(fe_lds_f2v)p;
+    return fe::cmk(t.x, t.y);
+}
+__device__ __forceinline__ void fe_lds_write8(float* p, fe::cf v) { *(fe_lds_f2v)p = (fe_f2){v.x, v.y}; }
 constexpr int kMelLdsFloats = 768;  // 640 weights at fe::mel_lds_index (fe_core.h), padded to three 1 KiB loads
 static_assert(fe::mel_lds_index(fe::kMelLdsWeights - 1, 15) < kMelLdsFloats && kStdMelOff[5] == fe::kMelLdsWeights, "the image holds the default bank");
 
@@ -221,6 +236,8 @@ __device__ __forceinline__ void fe_main_body(const float* __restrict__ pcm, int6
     constexpr int kTwBase = LOWREG ? 31 : 0;
     constexpr bool kConstTw = (OPT & kFeConstTw) != 0;
     constexpr bool kLdsMel = (OPT & kFeLdsMel) != 0;
+    constexpr bool kLean = (OPT & kFeLeanLds) != 0;
+    static_assert(!kLean || (kConstTw && kLdsMel), "the lean pass is a form of the constant-table kernel");
     static_assert(OPT == 0 || (STDMEL && FUSED && !LOWREG), "the constant / LDS table forms belong to the default bank's fused kernel");
     __shared__ __attribute__((aligned(16))) float s_melt[kLdsMel ? kMelLdsFloats : 4];
     // three workgroups a CU: 160 KiB / 3 = 54 613 bytes each (the table-driven mel loop's dynamic s_melw comes on top where OPT == 0)
@@ -338,10 +355,17 @@ __device__ __forceinline__ void fe_main_body(const float* __restrict__ pcm, int6
     // unconditional (clamped to frame 0 for the tail) so that all 25 are in flight together.
     float xr[fe::kQ];
     float mean_next = 0.0f;
+    // kLean: the lane's frame advances by four a pass, so its first sample's address is carried (one 64-bit add) and the tail clamp is a
+    // select between it and frame 0's; the frame index is compared in 32 bits, as everywhere below
+    const float* src_carry = base + ((int64_t)bl.x() * FR + wave * (4 * PASSES) + g) * fe::kHop + p;
     auto issue_loads = [&](int pass) {
         const int64_t f = (int64_t)bl.x() * FR + wave * (4 * PASSES) + pass * 4 + g;
         const int64_t fc = f < num_frames ? f : 0;
         const float* src = base + fc * fe::kHop + p;
+        if constexpr (kLean) {
+            src = (int)(bl.x() * FR) + wave * (4 * PASSES) + g + pass * 4 < (int)num_frames ? src_carry : base + p;
+            src_carry += 4 * fe::kHop;
+        }
         if (!FUSED) mean_next = mean_u[fc];
 #pragma unroll
         for (int q = 0; q < fe::kQ; ++q) xr[q] = src[16 * q];
@@ -465,14 +489,21 @@ __device__ __forceinline__ void fe_main_body(const float* __restrict__ pcm, int6
 #pragma unroll
             for (int cc = 0; cc < 16; ++cc) {
                 const int slot = fe::xchg_slot(h, cc);
-                *reinterpret_cast<float2*>(xf + 2 * slot) = make_float2(a[rho * 16 + cc].x, a[rho * 16 + cc].y);
+                if constexpr (kLean)
+                    fe_lds_write8(xf + 2 * slot, a[rho * 16 + cc]);
+                else
+                    *reinterpret_cast<float2*>(xf + 2 * slot) = make_float2(a[rho * 16 + cc].x, a[rho * 16 + cc].y);
             }
             __builtin_amdgcn_wave_barrier();
             fe::cf bq[16];
 #pragma unroll
             for (int vv = 0; vv < 16; ++vv) {
-                const float2 t = *reinterpret_cast<const float2*>(xf + 2 * fe::xchg_slot(vv, p));
-                bq[vv] = fe::cmk(t.x, t.y);
+                if constexpr (kLean) {
+                    bq[vv] = fe_lds_read8(xf + 2 * fe::xchg_slot(vv, p));
+                } else {
+                    const float2 t = *reinterpret_cast<const float2*>(xf + 2 * fe::xchg_slot(vv, p));
+                    bq[vv] = fe::cmk(t.x, t.y);
+                }
             }
             __builtin_amdgcn_wave_barrier();
             // stages 6..9 with per-lane twiddles from LDS
@@ -971,6 +1002,7 @@ struct LeleFrontend {
     int dpp_mode = 0;  // 0: __shfl, 1: DPP row_ror (selected after a self-test)
     bool fused = true;  // frame sums computed inside fe_main_kernel (LELE_HIP_FE_FUSED=0 selects the two-kernel form)
     int opt = 0;        // kFeConstTw | kFeLdsMel: the form of the default bank's fused kernels (0: every table read as before)
+    bool lean = false;  // kFeLeanLds on top of opt == kFeConstTw | kFeLdsMel (LELE_HIP_FE_LEAN_LDS=0 keeps the pass without it)
     // generic path tables (configs other than 400/160/512)
     const float* g_window = nullptr;
     const int* g_mstart = nullptr;
@@ -1222,6 +1254,10 @@ int lele_hip_frontend_create(LeleCtx* ctx, const LeleFeatureConfig* cfg, LeleFro
     }
     if (const_tw && fe->std_mel && fe->fused && fe->dpp_mode == 1)
         fe->opt = kFeConstTw | ((envl && *envl && atoi(envl) == 0) ? 0 : kFeLdsMel);
+    // product switch, same bits either way: LELE_HIP_FE_LEAN_LDS=0 keeps the pass loop with the exchange's paired LDS accesses and the
+    // sample address rebuilt every pass
+    const char* envn = getenv("LELE_HIP_FE_LEAN_LDS");
+    fe->lean = fe->opt == (kFeConstTw | kFeLdsMel) && !(envn && *envn && atoi(envn) == 0);
     *out = fe;
     return 0;
 }
@@ -1229,6 +1265,8 @@ int lele_hip_frontend_create(LeleCtx* ctx, const LeleFeatureConfig* cfg, LeleFro
 /* test hook (not part of include/lele_hip.h): the form frontend_create selected for the default bank's fused kernels -- bit 0: phase A's
  * twiddles are compiled-in constants, bit 1: the mel weights are read from LDS; 0: the table-reading kernels */
 int lele_hip_frontend_kernel_form(const LeleFrontend* fe) { return fe ? fe->opt : -1; }
+/* test hook: 1 where the default bank's fused kernels run the lean pass (kFeLeanLds), 0 where LELE_HIP_FE_LEAN_LDS=0 or another form keeps it out */
+int lele_hip_frontend_lean_lds(const LeleFrontend* fe) { return fe ? (int)fe->lean : -1; }
 
 int lele_hip_frontend_destroy(LeleFrontend* fe) {
     if (!fe) return 0;
@@ -1410,7 +1448,9 @@ static int fe_run(LeleFrontend* fe, const LeleTensor* pcm, int64_t batch, int64_
         const float* cmean = (const float*)dmean + c0 * nf;
         float* o = want_logmel ? nullptr : (float*)out->data + c0 * t_lfr * cols;
         float* lm = want_logmel ? (float*)out->data + c0 * nf * fe->cfg.n_mels : nullptr;
-        if (fe->opt == (kFeConstTw | kFeLdsMel)) {  // (opt != 0: the default bank, fused, DPP -- frontend_create)
+        if (fe->lean) {  // (opt != 0: the default bank, fused, DPP -- frontend_create)
+            FE_LAUNCH(1, true, true, kFeConstTw | kFeLdsMel | kFeLeanLds);
+        } else if (fe->opt == (kFeConstTw | kFeLdsMel)) {
             FE_LAUNCH(1, true, true, kFeConstTw | kFeLdsMel);
         } else if (fe->opt == kFeConstTw) {
             FE_LAUNCH(1, true, true, kFeConstTw);
@@ -1563,7 +1603,9 @@ int lele_hip_frontend_compute_segments(LeleFrontend* fe, const LeleTensor* pcm, 
 #define FE_SEG_LAUNCH(MODE, STD, ...)                                                                                            \
     hipLaunchKernelGGL((fe_seg_main_kernel<MODE, STD, ##__VA_ARGS__>), dim3((unsigned)blocks), dim3(256), mel_lds, ctx->stream, (const float*)dpcm, \
                        dsegs, dblk, fe->dev, o)
-    if (fe->opt == (kFeConstTw | kFeLdsMel)) {
+    if (fe->lean) {
+        FE_SEG_LAUNCH(1, true, kFeConstTw | kFeLdsMel | kFeLeanLds);
+    } else if (fe->opt == (kFeConstTw | kFeLdsMel)) {
         FE_SEG_LAUNCH(1, true, kFeConstTw | kFeLdsMel);
     } else if (fe->opt == kFeConstTw) {
         FE_SEG_LAUNCH(1, true, kFeConstTw);
@@ -1816,7 +1858,9 @@ int lele_hip_frontend_stream_push(LeleFrontendStream* st, const LeleTensor* pcm,
 #define FE_STREAM_LAUNCH(MODE, STD, ...)                                                                                           \
     hipLaunchKernelGGL((fe_stream_main_kernel<MODE, STD, ##__VA_ARGS__>), dim3((unsigned)blk.size()), dim3(256), mel_lds, ctx->stream,              \
                        (const float*)st->pcm_state, st->pcm_pitch, drecs, dblk, fe->dev, st->mel_state, st->mel_pitch)
-        if (fe->opt == (kFeConstTw | kFeLdsMel)) {
+        if (fe->lean) {
+            FE_STREAM_LAUNCH(1, true, kFeConstTw | kFeLdsMel | kFeLeanLds);
+        } else if (fe->opt == (kFeConstTw | kFeLdsMel)) {
             FE_STREAM_LAUNCH(1, true, kFeConstTw | kFeLdsMel);
         } else if (fe->opt == kFeConstTw) {
             FE_STREAM_LAUNCH(1, true, kFeConstTw);
