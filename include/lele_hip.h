@@ -486,7 +486,18 @@ int lele_hip_conv_stats(LeleCtx* ctx, int64_t* calls, int64_t* macs);
  * last segment's route.  frontend_stream_push adds no name: its log-mel launch is the segment kernel's body over the streams' regions and
  * reports "fe.seg_std" / "fe.seg_table", then "fe.tile_dma" / "fe.tile_regs" / "fe.tile_mixed" by the same per-record condition (a region's carry +
  * chunk is a multiple of 4 samples); the generic names on another framing (the last stream's); "" when no stream gained a frame.
- * The route never names an earlier call.  Recorded on the
+ * And the quantised linears: fused_quantized_linear[_residual[_ln]], sanm_out_block and fused_dq_gemm_prepared report "q.rs_fq" / "q.rs_frag"
+ * (register-stationary, one level), "q.as" / "q.as_ln" / "q.as_ln_fsmn" then "as.two" / "as.tpw8" / "as.tpw4" (activation-stationary: all, 8 or 4
+ * column tiles a workgroup), or "q.tiled" / "q.tiled_stream" (rows to i8 in memory by the prefetching / streaming row quantiser) then the tiled
+ * GEMM: "igemm.big", "igemm.small_k4", "igemm.small_k16", "igemm.t128x128", "igemm.t32x128", "igemm.t128x64"; the decode heads "q.head" then
+ * "igemm.head_ids" / "head_scored" / "head_topk" / "head_at"; the packed calls "q.seg" / "q.seg_stream" / "q.seg_head" then the same cores;
+ * fused_ffn_quantized[_ln] "qffn.rs_one" / "qffn.rs_two" (the first product's two passes in one launch or two) then "rs.ks4" / "rs.ask_ln"
+ * ("rs.ask": lab build), or "qffn.tiled" / "qffn.tiled_stream" then the tiled GEMM; mat_mul_integer* "mmi.rows" then the tiled GEMM (a batched
+ * B: its last launch); dynamic_quantize_linear "dql.w1".  Where one of these issued the calls it stands for instead of a fused form (the two
+ * linears of the feed-forward block, a residual that broadcasts, a LayerNorm or the three calls of sanm_out_block behind the linear), "q.calls"
+ * stands in front of the (last) quantised linear's route: "q.calls/q.as/as.tpw8".
+ * After a call that succeeded the route never names an earlier call; after one that returned an error it is undefined (an argument
+ * check may fail before the route is cleared).  Recorded on the
  * host when the call is issued (a call recorded into a graph reports the route it recorded).  NUL-terminated into buf; an error when cap is too small.
  * lele_hip_route_names: every level name a route can hold, one per line; host only, no GPU needed. */
 int lele_hip_last_route(LeleCtx* ctx, char* buf, size_t cap);

@@ -203,6 +203,9 @@ struct LeleCtx {
     // The data-movement (manip.hip), element-wise / reduce / norm (eltwise.hip) and LSTM / GRU (rnn.hip) entry points record theirs the same way,
     // and so does the i8 ConvInteger of conv.hip: how the image was packed ("ci8.codes" / "ci8.quant"), then the kernel ("ci8.nj2_ksplit")
     // and the audio front-end of frontend.hip: the kernel ("fe.main_std"), then how its PCM tile was staged ("fe.tile_dma")
+    // and the quantised linears of quant.hip: the route of the entry point ("q.as_ln", "qffn.rs_one", "mmi.rows"), then the GEMM kernel
+    // that launch_igemm / launch_as / the feed-forward block's second product chose ("igemm.big", "as.two", "rs.ks4"); route[0] is
+    // "q.calls" where the entry point issued the calls it stands for instead of a fused form ("q.calls/q.as/as.tpw8")
     const char* route[3] = {nullptr, nullptr, nullptr};
     void set_route(const char* op, const char* core = nullptr) {
         route[0] = nullptr;

@@ -116,6 +116,19 @@ const char* const kRouteNames[] = {
     // (direct-to-LDS, through registers, or -- a segment launch -- both); fe.two_kernel: the lab form with the separate frame-sum kernel
     "fe.main_std", "fe.main_table", "fe.seg_std", "fe.seg_table", "fe.generic_fused", "fe.generic_four",
     "fe.tile_dma", "fe.tile_regs", "fe.tile_mixed", "fe.two_kernel",
+    // resample.hip: the kernel of resample / resample_segments / a stream's step
+    "resample.copy", "resample.linear", "resample.fir1", "resample.fir",
+    // quant.hip.  The dense linear: the member of QRoute (q.tiled / q.tiled_stream: by which row quantiser ran, prefetching or streaming),
+    // the packed linear (q.seg*), the feed-forward block (EM 3 in one launch, EM 1 then EM 2, the tiled form), mat_mul_integer and
+    // dynamic_quantize_linear; then what launch_igemm / launch_igemm_head / launch_as launched, or the feed-forward block's second product
+    // (rs.ask: the lab build only).  The register-stationary single linear has no second level.  "q.calls" stands in front where an entry
+    // point issued the calls it stands for instead of a fused form; the rest is then the (last) quantised linear's route
+    "q.rs_fq", "q.rs_frag", "q.as", "q.as_ln", "q.as_ln_fsmn", "q.tiled", "q.tiled_stream", "q.head", "q.seg", "q.seg_stream", "q.seg_head",
+    "qffn.rs_one", "qffn.rs_two", "qffn.tiled", "qffn.tiled_stream", "mmi.rows", "dql.w1",
+    "igemm.big", "igemm.small_k4", "igemm.small_k16", "igemm.t128x128", "igemm.t32x128", "igemm.t128x64",
+    "igemm.head_ids", "igemm.head_scored", "igemm.head_topk", "igemm.head_at",
+    "as.two", "as.tpw8", "as.tpw4", "rs.ks4", "rs.ask_ln", "rs.ask",
+    "q.calls",
 };
 
 }  // namespace

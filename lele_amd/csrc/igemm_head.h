@@ -389,8 +389,10 @@ __global__ __launch_bounds__(WM* WN * 64) __attribute__((amdgpu_waves_per_eu(OCC
                                                             int64_t rows, int n, int kp, int64_t b_batch_stride,
                                                             int m_per_batch, IgemmEpi epi);  // (quant.hip)
 // a head: the tiled kernel in its big-shape configuration with the head's epilogue, then the finish kernel over its column tiles
+// *name: what was launched, as lele_hip_last_route reports it
 int launch_igemm_head(LeleCtx* ctx, const int8_t* aq, const int8_t* wt, int64_t rows, int n, int kp, int m, const IgemmEpi& epi_in,
-                      const HeadReq& head, const HeadOut& o) {
+                      const HeadReq& head, const HeadOut& o, const char** name) {
+    *name = head.topk() ? "igemm.head_topk" : head.listed() ? "igemm.head_at" : head.scored() ? "igemm.head_scored" : "igemm.head_ids";
     LELE_REQUIRE(rows < (int64_t(128) * 65535), "quantized GEMM: more than 128 x 65535 rows");
     constexpr size_t lds = (size_t)2 * (128 + 128) * (128 + 16);
     IgemmEpi epi = epi_in;

@@ -970,7 +970,10 @@ int launch_range(LeleCtx* ctx, const float* dx, int64_t slices, int64_t slice_le
     return 0;
 }
 
-int launch_igemm(LeleCtx* ctx, const int8_t* aq, const int8_t* wt, int64_t rows, int n, int kp, int m_per_batch, const IgemmEpi& epi_in) {
+// *name: what was launched, as lele_hip_last_route reports it (NULL when nothing was, or a lab build's forced tile)
+int launch_igemm(LeleCtx* ctx, const int8_t* aq, const int8_t* wt, int64_t rows, int n, int kp, int m_per_batch, const IgemmEpi& epi_in,
+                 const char** name) {
+    *name = nullptr;
     if (rows == 0 || n == 0) return 0;
     IgemmEpi epi = epi_in;
     epi.flags = lab_int("LELE_HIP_IGEMM_FLAGS", 0);
@@ -1011,6 +1014,7 @@ int launch_igemm(LeleCtx* ctx, const int8_t* aq, const int8_t* wt, int64_t rows,
         ((rows + 255) / 256) * (((int64_t)n + 255) / 256) * 2 >= (int64_t)ctx->num_cus && ((((uintptr_t)epi.out) | ((uintptr_t)epi.res1) | ((uintptr_t)epi.res2)) & 15) == 0 &&
         !epi.blockstat) {
         dim3 grid((unsigned)((n + 255) / 256), (unsigned)((rows + 255) / 256));
+        *name = "igemm.big";
 #ifdef LELE_HIP_LAB
         if (lab_int("LELE_HIP_IGEMM_BIG", 1) == 2) {   // (lab) four waves of 128 x 128
             auto kern = igemm_big_kernel<2>;
@@ -1030,6 +1034,7 @@ int launch_igemm(LeleCtx* ctx, const int8_t* aq, const int8_t* wt, int64_t rows,
     } else if (b64 < 2 * (int64_t)ctx->num_cus) {
         // small problem (SenseVoice at M = 504): 32x32 tiles, K split over the four waves, operands straight from L2
         dim3 grid((unsigned)((n + 31) / 32), (unsigned)((rows + 31) / 32));
+        *name = kp <= 512 ? "igemm.small_k4" : "igemm.small_k16";
         if (kp <= 512)
             hipLaunchKernelGGL((gemm::igemm_small_kernel<IgemmEpi, 4>), grid, dim3(256), 0, ctx->stream, aq, wt, rows, n, kp, (int64_t)0,
                                m_per_batch, epi);
@@ -1041,14 +1046,17 @@ int launch_igemm(LeleCtx* ctx, const int8_t* aq, const int8_t* wt, int64_t rows,
         // Measured on the configs[3] shard shapes (profiles/r02_qlinear_variants.json): 29.3 / 30.0 / 41.1 us for qkv / ffn1 / ffn2
         // against 32.5 / 32.9 / 48.7 us with 64-byte tiles -- the second, nearly empty round of workgroups costs less than that.
         IGEMM_LAUNCH(128, 128, 2, 4, 128, 1);
+        *name = "igemm.t128x128";
     } else if (rows <= 32) {
         IGEMM_LAUNCH(32, 128, 1, 4, 64, 1);
+        *name = "igemm.t32x128";
     } else {
         // narrow results over many rows (out projection, second feed-forward layer: N = 512 over a batch of utterances): 128 x 64
         // tiles, eight waves, 128-byte K tiles -- 40.0 us against 45.9 us with 64 x 64 tiles at K = 2048, 16.3 against 16.8 at K = 512.
         // (They always cover the chip here: b64 >= 2 CUs and ceil(rows / 64) <= 2 ceil(rows / 128) give ceil(rows / 128) * ceil(n / 64)
         // >= CUs, so the 64 x 64 tile that once stood behind this one is the lab's LELE_HIP_IGEMM_TILE=5 only.)
         IGEMM_LAUNCH(128, 64, 4, 2, 128, 4);
+        *name = "igemm.t128x64";
     }
 #undef IGEMM_LAUNCH
     LELE_HIP_CHECK(hipGetLastError());
@@ -1218,11 +1226,12 @@ struct AsLn {  // the LayerNorm behind the projection, in the same launch (n == 
     int fs_pl = 0;
 };
 int launch_as(LeleCtx* ctx, const float* x, const int8_t* wf, int64_t rows, int n, const float* partial, int nblk, QParams* prm,
-              const IgemmEpi& epi, const AsLn* ln = nullptr) {
+              const IgemmEpi& epi, const AsLn* ln, const char** name) {
     AsArgs g{x, wf, (unsigned)rows, n, (n + 31) / 32, partial, nblk, prm, 16};
     const int64_t nrt = (rows + 31) / 32;
     const bool two = as_two(ctx, rows, n);
     if (!two) g.tpw = lab_int("LELE_HIP_IGEMM_AS_TPW", nrt * 6 >= (int64_t)ctx->num_cus ? 8 : 4);
+    *name = two ? "as.two" : g.tpw == 8 ? "as.tpw8" : g.tpw == 4 ? "as.tpw4" : nullptr;  // (no name: a lab build's LELE_HIP_IGEMM_AS_TPW)
     const dim3 grid((unsigned)nrt, two ? 1u : (unsigned)((g.nct + g.tpw - 1) / g.tpw));
     const int nres = epi.res1 ? (epi.res2 ? 2 : 1) : 0;
     if (ln) {
@@ -1273,7 +1282,8 @@ int launch_as(LeleCtx* ctx, const float* x, const int8_t* wf, int64_t rows, int 
     LELE_HIP_CHECK(hipGetLastError());
     return 0;
 }
-int launch_rs_ks4(LeleCtx* ctx, const int8_t* af, const int8_t* wf, int64_t rows, int n, const IgemmEpi& epi) {
+int launch_rs_ks4(LeleCtx* ctx, const int8_t* af, const int8_t* wf, int64_t rows, int n, const IgemmEpi& epi, const char** name) {
+    *name = "rs.ks4";
     RsArgs g{af, wf, (unsigned)rows, n, (int)((rows + 31) / 32), (n + 31) / 32, 0, 0, nullptr};
 #ifdef LELE_HIP_LAB
     g.dbg = nullptr;
@@ -1294,7 +1304,8 @@ bool ask_fits(LeleCtx* ctx, int64_t rows, int64_t n, int64_t k) {
     return env_int("LELE_HIP_IGEMM_RS", 1) != 0 && env_int("LELE_HIP_IGEMM_ASK", 1) != 0 && k == 2048 && n == 512 && rows * n < (int64_t(1) << 30) &&
            as_two(ctx, rows, (int)n);
 }
-int launch_ask(LeleCtx* ctx, const int8_t* af, const int8_t* wf, int64_t rows, const IgemmEpi& epi, const AsLn* ln) {
+int launch_ask(LeleCtx* ctx, const int8_t* af, const int8_t* wf, int64_t rows, const IgemmEpi& epi, const AsLn* ln, const char** name) {
+    *name = ln ? "rs.ask_ln" : "rs.ask";
     AskArgs g{af, wf, (unsigned)rows};
     if (ln) g.ln_g = ln->g, g.ln_b = ln->b, g.ln_eps = ln->eps, g.ln_out = ln->out, g.ln_rowstat = ln->rowstat;
     const dim3 grid((unsigned)((rows + 31) / 32));
@@ -1574,13 +1585,22 @@ void publish_ln(LnReq* ln, const QCall& c, const AsLn& aln) {
     ln->out->rowstat_rows = c.rows, ln->out->rowstat_len = c.n;
     ln->out->rowstat_kind = 0, ln->out->rowstat_valid = true;
 }
+// an entry point issued the calls it stands for instead of a fused form: "q.calls" in front of the (last) quantised linear's route
+void calls_family(LeleCtx* ctx) {
+    if (ctx->route[1]) ctx->set_route_family("q.calls");
+}
 // ... and where no kernel took it: the call it stands for, on the sum in `out`
+// (lele_hip_last_route keeps the linear's route, "q.calls" in front of it)
 int finish_ln(LeleCtx* ctx, const LnReq& ln, LeleBuf* out, const int64_t* sh, int32_t r) {
     if (ln.done) return 0;
     const LeleTensor x1{out->data, sh, r, LELE_F32, LELE_MEM_DEVICE};
     int64_t sh2[LELE_MAX_RANK];
     int32_t r2 = 0;
-    return lele_hip_layer_norm(ctx, &x1, ln.g, ln.b, -1, ln.eps, ln.out, sh2, &r2);
+    const char *const op = ctx->route[1], *const core = ctx->route[2];
+    LELE_TRY(lele_hip_layer_norm(ctx, &x1, ln.g, ln.b, -1, ln.eps, ln.out, sh2, &r2));
+    ctx->set_route(op, core);
+    calls_family(ctx);
+    return 0;
 }
 
 // rows -> i8 [rows][kp] + row sums in HBM, for the tiled kernels.  prefetch: the whole row in flight at once (8 x 16 bytes per lane)
@@ -1642,7 +1662,7 @@ int run_rs(LeleCtx* ctx, const QLayer& l, bool fq) {
 }
 
 // few column tiles, K = 512: quantise and multiply in one kernel, with the LayerNorm (and the memory block) where the route says so
-int run_as(LeleCtx* ctx, const QLayer& l, QRoute route, LnReq* ln) {
+int run_as(LeleCtx* ctx, const QLayer& l, QRoute route, LnReq* ln, const char** core) {
     const QCall& c = l.c;
     FragW fw;
     LELE_TRY(frag_weights_of(ctx, l.weight, (int)c.k, (int)c.n, 512, &fw));
@@ -1660,7 +1680,7 @@ int run_as(LeleCtx* ctx, const QLayer& l, QRoute route, LnReq* ln) {
     }
     const bool fuse_ln = route != QRoute::As;
     if (fuse_ln) LELE_TRY(attach_ln(ctx, ln, c, &aln));  // (a first reserve of ln->out cannot move `out`: they are different buffers)
-    LELE_TRY(launch_as(ctx, l.x, fw.wf, c.rows, (int)c.n, l.partial, l.nblk, l.prm, epi, fuse_ln ? &aln : nullptr));
+    LELE_TRY(launch_as(ctx, l.x, fw.wf, c.rows, (int)c.n, l.partial, l.nblk, l.prm, epi, fuse_ln ? &aln : nullptr, core));
     if (fuse_ln) publish_ln(ln, c, aln);
     LELE_TRY(qprof_mark(ctx, 3));
     publish_blockstat(l.out, c, epi);
@@ -1668,7 +1688,7 @@ int run_as(LeleCtx* ctx, const QLayer& l, QRoute route, LnReq* ln) {
 }
 
 // three-kernel chain: rows -> i8 (+ row sums) in HBM, then the tiled i8 GEMM (a head: l.out receives the ids)
-int run_tiled(LeleCtx* ctx, const QLayer& l) {
+int run_tiled(LeleCtx* ctx, const QLayer& l, const char** op, const char** core) {
     const QCall& c = l.c;
     const int kp = (int)((c.k + 15) & ~int64_t(15));
     PackedW pw;
@@ -1676,20 +1696,22 @@ int run_tiled(LeleCtx* ctx, const QLayer& l) {
     void *aq = nullptr, *rs = nullptr;
     LELE_TRY(ctx->arena_alloc((size_t)c.rows * kp, &aq));
     LELE_TRY(ctx->arena_alloc((size_t)c.rows * 4, &rs));
-    LELE_TRY(launch_qrows(ctx, c.rows <= 2048 || (kp <= 2048 && !lab_int("LELE_HIP_QROWS_STREAM", 0)), l.x, c.rows, (int)c.k, kp, (int)c.m, l.prm,
+    const bool prefetch = c.rows <= 2048 || (kp <= 2048 && !lab_int("LELE_HIP_QROWS_STREAM", 0));
+    *op = l.head ? "q.head" : prefetch ? "q.tiled" : "q.tiled_stream";
+    LELE_TRY(launch_qrows(ctx, prefetch, l.x, c.rows, (int)c.k, kp, (int)c.m, l.prm,
                           (int8_t*)aq, (int*)rs, l.partial, l.nblk, nullptr, nullptr, nullptr));
     LELE_TRY(qprof_mark(ctx, 2));
     if (l.head) {
         HeadOut o;
         LELE_TRY(head_workspace(ctx, l.head, c.rows, c.n, &o));
         o.results(l.out, l.head);
-        LELE_TRY(launch_igemm_head(ctx, (const int8_t*)aq, pw.wt, c.rows, (int)c.n, kp, (int)c.m, make_epi(l, nullptr, (const int*)rs, pw.col_sums), l.head, o));
+        LELE_TRY(launch_igemm_head(ctx, (const int8_t*)aq, pw.wt, c.rows, (int)c.n, kp, (int)c.m, make_epi(l, nullptr, (const int*)rs, pw.col_sums), l.head, o, core));
         return qprof_mark(ctx, 3);
     }
     IgemmEpi epi = make_epi(l, (float*)l.out->data, (const int*)rs, pw.col_sums);
     // small-problem kernel: publish one {min, max} pair per workgroup next to the result (for the linear that may follow)
     if (((c.rows + 63) / 64) * ((c.n + 63) / 64) < 2 * (int64_t)ctx->num_cus) LELE_TRY(attach_blockstat(l.out, c, &epi));
-    LELE_TRY(launch_igemm(ctx, (const int8_t*)aq, pw.wt, c.rows, (int)c.n, kp, (int)c.m, epi));
+    LELE_TRY(launch_igemm(ctx, (const int8_t*)aq, pw.wt, c.rows, (int)c.n, kp, (int)c.m, epi, core));
     LELE_TRY(qprof_mark(ctx, 3));
     publish_blockstat(l.out, c, epi);
     return 0;
@@ -1711,6 +1733,7 @@ int fql_impl(LeleCtx* ctx, const LeleTensor* input, const QW& w, const QReq& rq,
     LELE_TRY(out->reserve(out_bytes));
     if (rq.head.scored()) LELE_TRY(rq.head.logprob->reserve(out_bytes));
     if (rq.head.listed()) LELE_TRY(rq.head.at->reserve((size_t)c.rows * rq.head.ncols * 4));
+    ctx->set_route(nullptr);  // lele_hip_last_route: "" for a call that launches nothing
     if (c.rows == 0 || c.n == 0) return set_shape_v(out_shape, out_rank, c.shp);
     LELE_TRY(ctx->arena_reset());
     const void *dx = nullptr, *dws = nullptr, *db = nullptr, *dr1 = nullptr, *dr2 = nullptr;
@@ -1730,15 +1753,23 @@ int fql_impl(LeleCtx* ctx, const LeleTensor* input, const QW& w, const QReq& rq,
     if (!l.partial) LELE_TRY(launch_range(ctx, l.x, c.batch, c.m * c.k, l.prm, nullptr, nullptr, &l.partial, &l.nblk));
     LELE_TRY(qprof_mark(ctx, 1));
     const QRoute route = fql_route(ctx, c, rq, dx, out->data);
+    const char *op = nullptr, *core = nullptr;  // (the register-stationary kernel has no second level)
     switch (route) {
         case QRoute::RsFq:
-        case QRoute::RsFrag: LELE_TRY(run_rs(ctx, l, route == QRoute::RsFq)); break;
+        case QRoute::RsFrag:
+            op = route == QRoute::RsFq ? "q.rs_fq" : "q.rs_frag";
+            LELE_TRY(run_rs(ctx, l, route == QRoute::RsFq));
+            break;
         case QRoute::As:
         case QRoute::AsLn:
-        case QRoute::AsLnFsmn: LELE_TRY(run_as(ctx, l, route, rq.ln)); break;
+        case QRoute::AsLnFsmn:
+            op = route == QRoute::As ? "q.as" : route == QRoute::AsLn ? "q.as_ln" : "q.as_ln_fsmn";
+            LELE_TRY(run_as(ctx, l, route, rq.ln, &core));
+            break;
         case QRoute::Tiled:
-        case QRoute::TiledHead: LELE_TRY(run_tiled(ctx, l)); break;
+        case QRoute::TiledHead: LELE_TRY(run_tiled(ctx, l, &op, &core)); break;
     }
+    ctx->set_route(op, core);
     return set_shape_v(out_shape, out_rank, c.shp);
 }
 
@@ -1809,12 +1840,14 @@ int ffn_unfused(LeleCtx* ctx, const LeleTensor* input, const QW& w1, const QW& w
     int32_t r = 0;
     LELE_TRY(fql_impl(ctx, input, w1, QReq{1}, hid, sh, &r));
     LeleTensor h{hid->data, sh, r, LELE_F32, LELE_MEM_DEVICE};
-    if (rq.res1) return lele_hip_fused_quantized_linear_residual(ctx, &h, w2.w, w2.scale, w2.zero, w2.bias, rq.relu, rq.res1, rq.res2, out, out_shape, out_rank);
-    return fql_impl(ctx, &h, w2, QReq{rq.relu}, out, out_shape, out_rank);
+    if (rq.res1) LELE_TRY(lele_hip_fused_quantized_linear_residual(ctx, &h, w2.w, w2.scale, w2.zero, w2.bias, rq.relu, rq.res1, rq.res2, out, out_shape, out_rank));
+    else LELE_TRY(fql_impl(ctx, &h, w2, QReq{rq.relu}, out, out_shape, out_rank));
+    calls_family(ctx);  // in front of the second linear's route
+    return 0;
 }
 
 // l1.partial: the {min, max} pairs of the input; both layers' parameters are reduced inside the kernels
-int ffn_rs(LeleCtx* ctx, const QLayer& l1, const QLayer& l2, LnReq* ln) {
+int ffn_rs(LeleCtx* ctx, const QLayer& l1, const QLayer& l2, LnReq* ln, const char** op, const char** core) {
     const QCall &c1 = l1.c, &c2 = l2.c;
     const int64_t rows = c1.rows, nrt = (rows + 31) / 32;
     FragW fw1, fw2;
@@ -1848,6 +1881,7 @@ int ffn_rs(LeleCtx* ctx, const QLayer& l1, const QLayer& l2, LnReq* ln) {
                  RS_NS_BOTH);
     IgemmEpi e1 = make_epi(l1, nullptr, (const int*)rs1, fw1.col_sums);
     e1.slice_max = (unsigned*)hmax;
+    *op = fqa.sync ? "qffn.rs_one" : "qffn.rs_two";
     if (fqa.sync) {  // both passes in one launch (igemm_rs.h, EM 3)
         e1.q_prm = l2.prm;
         LELE_TRY(launch_rs(ctx, 3, nullptr, fw1.wf, rows, (int)c1.n, (int8_t*)hid, e1, fqa));
@@ -1859,17 +1893,17 @@ int ffn_rs(LeleCtx* ctx, const QLayer& l1, const QLayer& l2, LnReq* ln) {
     const IgemmEpi e2 = make_epi(l2, (float*)l2.out->data, nullptr, fw2.col_sums);
     const FfnSecond second = ffn_second(ctx, c2, l2.relu, ln, l2.out->data);
     if (second == FfnSecond::Ks4) {
-        LELE_TRY(launch_rs_ks4(ctx, (const int8_t*)hid, fw2.wf, rows, (int)c2.n, e2));
+        LELE_TRY(launch_rs_ks4(ctx, (const int8_t*)hid, fw2.wf, rows, (int)c2.n, e2, core));
     } else {
         AsLn aln;
         if (second == FfnSecond::AskLn) LELE_TRY(attach_ln(ctx, ln, c2, &aln));
-        LELE_TRY(launch_ask(ctx, (const int8_t*)hid, fw2.wf, rows, e2, second == FfnSecond::AskLn ? &aln : nullptr));
+        LELE_TRY(launch_ask(ctx, (const int8_t*)hid, fw2.wf, rows, e2, second == FfnSecond::AskLn ? &aln : nullptr, core));
         if (second == FfnSecond::AskLn) publish_ln(ln, c2, aln);
     }
     return qprof_mark(ctx, 3);
 }
 
-int ffn_tiled(LeleCtx* ctx, const QLayer& l1, const QLayer& l2) {
+int ffn_tiled(LeleCtx* ctx, const QLayer& l1, const QLayer& l2, const char** op, const char** core) {
     const QCall &c1 = l1.c, &c2 = l2.c;
     const int64_t rows = c1.rows;
     const int kp1 = (int)((c1.k + 15) & ~int64_t(15)), kp2 = (int)c1.n;
@@ -1883,7 +1917,9 @@ int ffn_tiled(LeleCtx* ctx, const QLayer& l1, const QLayer& l2) {
     LELE_TRY(ctx->arena_alloc((size_t)rows * 4, &rs2));
     LELE_TRY(ctx->arena_alloc((size_t)c1.batch * 4, &hmax));
     // rows -> i8 for the first GEMM; the same launch clears the accumulators of the two hidden-layer passes
-    LELE_TRY(launch_qrows(ctx, kp1 <= 2048 && !lab_int("LELE_HIP_QROWS_STREAM", 0), l1.x, rows, (int)c1.k, kp1, (int)c1.m, l1.prm, (int8_t*)aq1,
+    const bool prefetch = kp1 <= 2048 && !lab_int("LELE_HIP_QROWS_STREAM", 0);
+    *op = prefetch ? "qffn.tiled" : "qffn.tiled_stream";
+    LELE_TRY(launch_qrows(ctx, prefetch, l1.x, rows, (int)c1.k, kp1, (int)c1.m, l1.prm, (int8_t*)aq1,
                           (int*)rs1, l1.partial, l1.nblk, (unsigned*)hmax, (int*)rs2, nullptr));
     LELE_TRY(qprof_mark(ctx, 2));
     IgemmEpi e1 = make_epi(l1, nullptr, (const int*)rs1, pw1.col_sums);
@@ -1894,7 +1930,7 @@ int ffn_tiled(LeleCtx* ctx, const QLayer& l1, const QLayer& l2) {
     e1.q_prm = l2.prm;
     LELE_TRY(launch_igemm_hidden(ctx, 2, (const int8_t*)aq1, pw1.wt, rows, (int)c1.n, kp1, (int)c1.m, e1));
     const IgemmEpi e2 = make_epi(l2, (float*)l2.out->data, (const int*)rs2, pw2.col_sums);
-    LELE_TRY(launch_igemm(ctx, (const int8_t*)aq2, pw2.wt, rows, (int)c2.n, kp2, (int)c1.m, e2));
+    LELE_TRY(launch_igemm(ctx, (const int8_t*)aq2, pw2.wt, rows, (int)c2.n, kp2, (int)c1.m, e2, core));
     return qprof_mark(ctx, 3);
 }
 
@@ -1938,8 +1974,10 @@ int ffn_impl(LeleCtx* ctx, const LeleTensor* input, const QW& w1, const QW& w2, 
     LELE_TRY(qprof_mark(ctx, 0));
     if (!l1.partial) LELE_TRY(launch_range(ctx, l1.x, c1.batch, c1.m * c1.k, l1.prm, nullptr, nullptr, &l1.partial, &l1.nblk));
     LELE_TRY(qprof_mark(ctx, 1));
-    if (route == FfnRoute::Rs) LELE_TRY(ffn_rs(ctx, l1, l2, rq.ln));
-    else LELE_TRY(ffn_tiled(ctx, l1, l2));
+    const char *op = nullptr, *core = nullptr;
+    if (route == FfnRoute::Rs) LELE_TRY(ffn_rs(ctx, l1, l2, rq.ln, &op, &core));
+    else LELE_TRY(ffn_tiled(ctx, l1, l2, &op, &core));
+    ctx->set_route(op, core);
     return set_shape_v(out_shape, out_rank, c2.shp);
 }
 
@@ -1968,6 +2006,7 @@ int fql_segments_impl(LeleCtx* ctx, const LeleTensor* input, const int64_t* row_
         else LELE_TRY(layout_table(ctx, "qseg", 0, 0, row_offsets, count, build_rowseg, &arg, &tab));
     }
     const size_t at_bytes = rq.head.listed() ? (size_t)rows * rq.head.ncols * 4 : 0;
+    ctx->set_route(nullptr);  // lele_hip_last_route: "" for a call that launches nothing
     if (rows == 0 || n == 0 || k == 0) {
         LELE_TRY(out->reserve(out_bytes));
         if (logprob) LELE_TRY(logprob->reserve(out_bytes));
@@ -2011,7 +2050,9 @@ int fql_segments_impl(LeleCtx* ctx, const LeleTensor* input, const int64_t* row_
     LELE_TRY(out->reserve(out_bytes));
     if (logprob) LELE_TRY(logprob->reserve(out_bytes));
     if (rq.head.listed()) LELE_TRY(rq.head.at->reserve(at_bytes));
-    LELE_TRY(launch_qrows(ctx, rows <= 2048 || kp <= 2048, l.x, rows, (int)k, kp, (int)rows, l.prm, (int8_t*)aq, (int*)rs, (const float*)partial,
+    const bool prefetch = rows <= 2048 || kp <= 2048;
+    const char* core = nullptr;
+    LELE_TRY(launch_qrows(ctx, prefetch, l.x, rows, (int)k, kp, (int)rows, l.prm, (int8_t*)aq, (int*)rs, (const float*)partial,
                           nblk, nullptr, nullptr, drowseg));
     LELE_TRY(qprof_mark(ctx, 2));
     IgemmEpi epi = make_epi(l, rq.head ? nullptr : (float*)out->data, (const int*)rs, pw.col_sums);
@@ -2020,10 +2061,11 @@ int fql_segments_impl(LeleCtx* ctx, const LeleTensor* input, const int64_t* row_
         HeadReq head = rq.head;
         head.at_slot = (const int*)((const char*)tab + (size_t)(count + 1) * 8 + (size_t)rows * 4);  // (Head::At; read by no other head)
         ho.results(out, head);
-        LELE_TRY(launch_igemm_head(ctx, (const int8_t*)aq, pw.wt, rows, (int)n, kp, (int)rows, epi, head, ho));
+        LELE_TRY(launch_igemm_head(ctx, (const int8_t*)aq, pw.wt, rows, (int)n, kp, (int)rows, epi, head, ho, &core));
     } else {
-        LELE_TRY(launch_igemm(ctx, (const int8_t*)aq, pw.wt, rows, (int)n, kp, (int)rows, epi));
+        LELE_TRY(launch_igemm(ctx, (const int8_t*)aq, pw.wt, rows, (int)n, kp, (int)rows, epi, &core));
     }
+    ctx->set_route(rq.head ? "q.seg_head" : prefetch ? "q.seg" : "q.seg_stream", core);
     LELE_TRY(qprof_mark(ctx, 3));
     return set_shape_v(out_shape, out_rank, c.shp);
 }
@@ -2144,6 +2186,7 @@ int lele_hip_fused_quantized_linear_residual(LeleCtx* ctx, const LeleTensor* inp
     LELE_TRY(ctx->tmp_buf(0, &t0));
     LELE_TRY(ctx->tmp_buf(1, &t1));
     LELE_TRY(fql_impl(ctx, input, {weight_int8, weight_scale, weight_zero, bias}, QReq{apply_relu}, t0, sh, &r));
+    const char *const op = ctx->route[1], *const core = ctx->route[2];  // the linear's, put back behind the adds
     LeleBuf* cur = t0;
     for (int i = 0; i < nres; ++i) {
         const LeleTensor* res = i == 0 ? res1 : res2;
@@ -2156,6 +2199,8 @@ int lele_hip_fused_quantized_linear_residual(LeleCtx* ctx, const LeleTensor* inp
         r = r2;
         cur = dst;
     }
+    ctx->set_route(op, core);
+    calls_family(ctx);
     return set_shape_v(out_shape, out_rank, std::vector<int64_t>(sh, sh + r));
 }
 
@@ -2218,8 +2263,10 @@ int lele_hip_sanm_out_block(LeleCtx* ctx, const LeleTensor* input, const LeleTen
     int32_t mr = 0;
     LELE_TRY(lele_hip_depthwise_conv1d_tlc(ctx, v_src, x_offset, fsmn_w, fsmn_bias, pad_left, pad_right, 0, 1, mem, msh, &mr));
     LeleTensor mt{mem->data, msh, mr, LELE_F32, LELE_MEM_DEVICE};
-    return lele_hip_fused_quantized_linear_residual_ln(ctx, input, weight_int8, weight_scale, weight_zero, bias, apply_relu, &mt, res2, ln_scale,
-                                                       ln_bias, epsilon, out, ln_out, out_shape, out_rank);
+    LELE_TRY(lele_hip_fused_quantized_linear_residual_ln(ctx, input, weight_int8, weight_scale, weight_zero, bias, apply_relu, &mt, res2, ln_scale,
+                                                         ln_bias, epsilon, out, ln_out, out_shape, out_rank));
+    calls_family(ctx);  // in front of the linear's route, which the call above left (or put back)
+    return 0;
 }
 
 int lele_hip_fused_ffn_quantized(LeleCtx* ctx, const LeleTensor* input, const LeleTensor* w1_int8, const LeleTensor* w1_scale,
@@ -2340,6 +2387,7 @@ int lele_hip_dynamic_quantize_linear(LeleCtx* ctx, const LeleTensor* x, LeleBuf*
     LELE_TRY(out_y->reserve((size_t)len * 4));
     LELE_TRY(out_scale->reserve(4));
     LELE_TRY(out_zp->reserve(4));
+    ctx->set_route(len ? "dql.w1" : nullptr);
     if (len == 0) {  // avx/quantization.rs:845-851: scale 1.0, zero point 0.0
         const float one = 1.0f, zero = 0.0f;
         LELE_HIP_CHECK(hipMemcpyAsync(out_scale->data, &one, 4, hipMemcpyHostToDevice, ctx->stream));
@@ -2385,6 +2433,7 @@ int lele_hip_mat_mul_integer_with_scale_bias(LeleCtx* ctx, const LeleTensor* a, 
     shp.push_back(m);
     shp.push_back(n);
     LELE_TRY(out->reserve((size_t)fb * m * n * 4));
+    ctx->set_route(nullptr);  // lele_hip_last_route: "" for a call that launches nothing
     if (fb * m * n == 0) return set_shape_v(out_shape, out_rank, shp);
     float za = 0.0f, zb = 0.0f;  // `.data.first().map(|&v| v as i32).unwrap_or(0)`
     LELE_TRY(first_scalar_of(ctx, a_zero_point, &za));
@@ -2418,7 +2467,9 @@ int lele_hip_mat_mul_integer_with_scale_bias(LeleCtx* ctx, const LeleTensor* a, 
         IgemmEpi epi{(float*)out->data + (launches == 1 ? 0 : bi * m * n), rows, n, (int)m, (int)k, rsp,
                      pw.col_sums + (batch_b == 1 ? 0 : bi * n), nullptr, zp_a, zp_b, (const float*)ds, (int)slen,
                      (const float*)dbi, apply_relu};
-        LELE_TRY(launch_igemm(ctx, aptr, pw.wt + (batch_b == 1 ? 0 : bi * n * kp), rows, (int)n, kp, (int)m, epi));
+        const char* core = nullptr;
+        LELE_TRY(launch_igemm(ctx, aptr, pw.wt + (batch_b == 1 ? 0 : bi * n * kp), rows, (int)n, kp, (int)m, epi, &core));
+        ctx->set_route("mmi.rows", core);  // a batched B: the last slice's launch
     }
     return set_shape_v(out_shape, out_rank, shp);
 }

@@ -652,7 +652,8 @@ def conv_stats(ctx=None):
 
 def last_route(ctx=None):
     """name of the kernel route the last f32 GEMM, convolution, attention, data-movement, element-wise, reduce, norm, LSTM, GRU,
-    ConvInteger, fused_scale_bias or audio front-end call on the context dispatched, its levels joined by '/' (lele_hip_last_route: recorded by the library at the launch site, e.g.
+    ConvInteger, fused_scale_bias, audio front-end or quantised-linear ("q.as_ln/as.two", "qffn.rs_one/rs.ks4", "q.calls/q.tiled/igemm.small_k4")
+    call on the context dispatched, its levels joined by '/' (lele_hip_last_route: recorded by the library at the launch site, e.g.
     "conv.gemm_tap/gemm.small", "attn.rows16/attn.nt6", "copy.tile_w4", "pool.lds_sep/pool.pbn", "topk.select_lds", "bin.fast",
     "reduce.parts", "ln.reg16/rows.rpb4", "rnn.lstm/gemm.thin_m", "rnns.gru/rnns.reg32", "ci8.codes/ci8.nj2_ksplit", "fsb.w1", "fe.main_std/fe.tile_dma", "fe.generic_fused"); "" for an empty result, which launches
     nothing"""

@@ -527,7 +527,9 @@ def test_labels_cover_every_route_name():
               "unary.", "bin.", "binp.", "where.", "clip.", "reduce.", "ln.", "softmax.", "rows.", "rms.", "bn.", "add3.", "hpas.",   # tests/test_eltwise_routes.py
               "rnn.", "rnns.",   # tests/test_rnn_routes.py
               "ci8.", "fsb.",   # tests/test_conv_integer_routes.py
-              "fe.")   # tests/test_frontend_routes.py
+              "fe.",   # tests/test_frontend_routes.py
+              "q.", "qffn.", "mmi.", "dql.", "igemm.", "as.", "rs.",   # tests/test_quant_routes.py
+              "resample.")   # tests/test_resample.py
     mine = {s for s in names if not s.startswith(theirs)}
     assert not used - mine, "labels the library cannot report: %s" % sorted(used - mine)
     assert not mine - used - {"gemm.k0"}, "routes no case reaches: %s" % sorted(mine - used)   # gemm.k0: test_empty_k

@@ -366,24 +366,47 @@ def test_dynamic_quantize_linear_on_adversarial_slices(ctx, orc, length):
             assert _same(y.numpy(), ry), (kind, length, at_min, _diff(y.numpy(), ry))
 
 
-# (b, m, k, n) -> the route fql_route (quant.hip) selects for it
+# (b, m, k, n) -> the route fql_route (quant.hip) selects for it, in words, then as lele_hip_last_route reports it on 256 CUs and, with
+# LELE_HIP_IGEMM_RS=0, for the tiled chain alone.  On any CU count the test asserts what tests/test_quant_routes.py::dispatch derives.
 ROUTES = [
-    ((1, 93, 560, 1536), "tiled: K = 560 pads to 576 (rs_fits needs kp == 512) -> qrows_kernel + igemm_kernel"),
-    ((2, 5, 37, 19), "tiled chain on a tiny product (launch_igemm's small-problem kernel); K = 37: a scalar tail of 5 per row"),
-    ((32, 171, 512, 512), "activation-stationary igemm_as_kernel (as_fits: K = 512, N <= 512, >= 256 rows): rows quantised in the GEMM"),
+    ((1, 93, 560, 1536), "tiled: K = 560 pads to 576 (rs_fits needs kp == 512) -> qrows_kernel + igemm_kernel",
+     ("q.tiled/igemm.small_k16", "q.tiled/igemm.small_k16")),
+    ((2, 5, 37, 19), "tiled chain on a tiny product (launch_igemm's small-problem kernel); K = 37: a scalar tail of 5 per row",
+     ("q.tiled/igemm.small_k4", "q.tiled/igemm.small_k4")),
+    ((32, 171, 512, 512), "activation-stationary igemm_as_kernel (as_fits: K = 512, N <= 512, >= 256 rows): rows quantised in the GEMM",
+     ("q.as/as.two", "q.tiled/igemm.t128x64")),
     ((32, 171, 512, 1024), "register-stationary igemm_rs_kernel (rs_fits: kp 512, N >= 1024, >= 2 tiles per CU) with rs_fq: the loader "
-                           "waves quantise the rows"),
-    ((9, 1000, 500, 1536), "register-stationary with K = 500 padded to 512: launch_qrows_frag quantises first (scalar tail of 4)"),
-    ((1, 504, 2048, 512), "K = 2048 stand-alone: tiled (rs_fits needs kp == 512; igemm_rs_ks4 runs only inside fused_ffn_quantized)"),
-    ((1, 2125, 1024, 3844), "compute-bound igemm_big_kernel (K a multiple of 128 >= 1024, half a chip of 256 x 256 results)"),
-    ((5, 700, 1152, 2048), "compute-bound igemm_big_kernel, slices straddling the 256-row results"),
-    ((1, 33, 100, 130), "tiled, generic K with a scalar tail of 4 per row"),
+                           "waves quantise the rows", ("q.rs_fq", "q.tiled/igemm.t128x64")),
+    ((9, 1000, 500, 1536), "register-stationary with K = 500 padded to 512: launch_qrows_frag quantises first (scalar tail of 4)",
+     ("q.rs_frag", "q.tiled/igemm.t128x128")),
+    ((1, 504, 2048, 512), "K = 2048 stand-alone: tiled (rs_fits needs kp == 512; igemm_rs_ks4 runs only inside fused_ffn_quantized)",
+     ("q.tiled/igemm.small_k16", "q.tiled/igemm.small_k16")),
+    ((1, 2125, 1024, 3844), "compute-bound igemm_big_kernel (K a multiple of 128 >= 1024, half a chip of 256 x 256 results)",
+     ("q.tiled/igemm.big", "q.tiled/igemm.big")),
+    # (14 x 8 results of 256 x 256 are 112, short of half of 256 CUs: not the compute-bound kernel, as this line once said.  Its slices
+    # straddling the 256-row results: tests/test_quant_routes.py, the row "tiled-big-slices-straddle")
+    ((5, 700, 1152, 2048), "K a multiple of 128 >= 1024 on too few 256 x 256 results for igemm_big_kernel: 128 x 64 tiles, 128-byte K steps",
+     ("q.tiled/igemm.t128x64", "q.tiled/igemm.t128x64")),
+    ((1, 33, 100, 130), "tiled, generic K with a scalar tail of 4 per row", ("q.tiled/igemm.small_k4", "q.tiled/igemm.small_k4")),
 ]
 
 
+def _route_is(ctx, b, m, k, n, named=None):
+    """last_route() is what the restated dispatch derives for this device and environment -- and, on 256 CUs, the string written down"""
+    from lele_amd import kernels as K
+    # (imported here, not at the top: tests/test_quant_routes.py imports this module's constructors when it is loaded)
+    from tests.test_quant_routes import ENV, dispatch
+    env = {name: int(os.environ.get(name, dflt)) for name, dflt in ENV.items()}
+    cus = K.num_cus(ctx)
+    want = dispatch("fql", b, m, k, n, cus, env)[0]
+    assert K.last_route(ctx) == want, (K.last_route(ctx), want, (b, m, k, n), cus)
+    if named is not None and cus == 256:
+        assert want == named, (want, named)
+
+
 @pytest.mark.gpu
-@pytest.mark.parametrize("shape,route", ROUTES, ids=[str(r[0]) for r in ROUTES])
-def test_fused_quantized_linear_routes_on_adversarial_slices(ctx, orc, shape, route):
+@pytest.mark.parametrize("shape,route,named", ROUTES, ids=[str(r[0]) for r in ROUTES])
+def test_fused_quantized_linear_routes_on_adversarial_slices(ctx, orc, shape, route, named):
     """fused_quantized_linear on each route: every slice kind, the single extremes in rows at slice, 32-row tile and ragged-last-tile
     boundaries, equal to the oracle bit for bit -- and the tiled chain alone (LELE_HIP_IGEMM_RS=0) as well"""
     from lele_amd import kernels as K
@@ -399,10 +422,12 @@ def test_fused_quantized_linear_routes_on_adversarial_slices(ctx, orc, shape, ro
         ref = orc.fused_quantized_linear(x, w[0].arr, w[1].arr, w[2].arr, w[3].arr, False)
         xd = ctx.buf().upload(x)
         got = K.fused_quantized_linear(xd, *w, False, ctx=ctx).numpy()
+        _route_is(ctx, b, m, k, n, named[0])
         assert _same(got, ref), (route, kinds, _diff(got, ref))
         if not big:
             with _env(LELE_HIP_IGEMM_RS=0):
                 got = K.fused_quantized_linear(xd, *w, False, ctx=ctx).numpy()
+                _route_is(ctx, b, m, k, n, named[1])
                 assert _same(got, ref), ("tiled", route, kinds, _diff(got, ref))
 
 
@@ -589,16 +614,22 @@ def _spiky(b, m, k, rng, row):
 
 
 def _consume(ctx, t, w):
+    """the consumer linear on t, its route asserted (CONSUMERS: which kernel reads the producer's statistics)"""
     from lele_amd import kernels as K
-    return K.fused_quantized_linear(t, *w, False, ctx=ctx).numpy()
+    got = K.fused_quantized_linear(t, *w, False, ctx=ctx).numpy()
+    shp = tuple(t.shape)
+    _route_is(ctx, int(np.prod(shp[:-2])), shp[-2], shp[-1], w[0].arr.shape[-1])
+    return got
 
 
 def _want(orc, host, w):
     return orc.fused_quantized_linear(host, w[0].arr, w[1].arr, w[2].arr, w[3].arr, False)
 
 
-# consumers: (n, LELE_HIP_IGEMM_RS) -> (1024, 1) register-stationary where the rows fill the chip, (1024, 0) the tiled route
+# consumers: (n, LELE_HIP_IGEMM_RS) -> (1024, 1) register-stationary where the rows fill the chip, (1024, 0) the tiled route; on 256 CUs
+# the (32, 171) and (3, 1000) activations of K = 512 report CONSUMER_ROUTES (asserted below, every other call through _consume's _route_is)
 CONSUMERS = ((1024, 1), (1024, 0))
+CONSUMER_ROUTES = {(1024, 1): "q.rs_fq", (1024, 0): "q.tiled/igemm.t128x64"}
 
 
 def _rewrites(ctx, orc, buf, shape, w, rng):
@@ -652,6 +683,7 @@ def test_layer_norm_statistics_feed_consumers_and_go_stale(ctx, orc, b, m, n, rs
         xn = K.layer_norm(ctx.buf().upload(x), g, be, -1, 1e-5, out=buf, ctx=ctx)
         host = xn.numpy()
         assert _same(_consume(ctx, xn, w), _want(orc, host, w))
+        _route_is(ctx, b, m, k, n, CONSUMER_ROUTES[(n, rs)])
         rows = b * m
         for bb in [d for d in (1, 2, 3, 19, b, rows) if rows % d == 0]:   # kind 0 is one pair per row: any batching of the rows
             view = DevTensor(buf, (bb, rows // bb, k))
@@ -675,6 +707,7 @@ def test_residual_ln_statistics_feed_consumers_and_go_stale(ctx, orc, n, rs):
     with _env(LELE_HIP_IGEMM_RS=rs):
         _, xn = K.fused_quantized_linear_residual_ln(ctx.buf().upload(x), *w0, False, r1, None, g, be, 1e-5, outs=[ctx.buf(), buf], ctx=ctx)
         assert _same(_consume(ctx, xn, w), _want(orc, xn.numpy(), w))
+        _route_is(ctx, b, m, 512, n, CONSUMER_ROUTES[(n, rs)])
         _rewrites(ctx, orc, buf, (b, m, 512), w, rng)
 
 
