@@ -571,6 +571,39 @@ int lele_hip_image_preprocess(LeleCtx* ctx, const LeleTensor* rgb, int32_t targe
 int lele_hip_yolo_seg_postprocess(LeleCtx* ctx, const LeleTensor* logits, const LeleTensor* mask_features, int32_t img_width,
                                   int32_t img_height, float threshold, int32_t num_classes, LeleBuf* out_dets,
                                   LeleBuf* out_count, LeleBuf* out_mask);
+/* A queue of camera frames of different sizes, one call each way (image.rs:62-111 in, image.rs:127-265 out).
+ *
+ * lele_hip_image_preprocess_batch: image i is HWC RGB at bytes[offsets[i] .. offsets[i] + 3 heights[i] widths[i]) of ONE byte buffer
+ * (bytes: U8 [total]); the offsets may come in any order, be unaligned, leave gaps and repeat.  offsets / heights / widths are HOST
+ * arrays of `count` entries: shape metadata, held on the device as one table per distinct layout (like the row offsets of the
+ * *_segments calls), so the call is graph-capturable once the layout has run eagerly once -- a replay reads whatever bytes the same
+ * device buffer then holds.  out: f32 [count, 3, target, target]; image i of it is bit for bit lele_hip_image_preprocess of that image
+ * alone (image.rs:84-105 + 69-79: src = min(floor((dst + 0.5f) * src_size / target), src_size - 1) in f32, then / 255).  One launch,
+ * grid (pixel tiles, image).  Refused before anything is launched, `out` left as it was: a NULL argument, count < 0 or >= 65536,
+ * target < 1 or > 16384, a side < 1 or >= 2^24, an image that does not lie inside the buffer (the message names the image).
+ * count == 0: shape [0, 3, target, target], no launch. */
+int lele_hip_image_preprocess_batch(LeleCtx* ctx, const LeleTensor* bytes, const int64_t* offsets, const int32_t* heights,
+                                    const int32_t* widths, int64_t count, int32_t target, LeleBuf* out, int64_t* out_shape,
+                                    int32_t* out_rank);
+/* lele_hip_yolo_seg_postprocess_sized: lele_hip_yolo_seg_postprocess (image.rs:127-265) with a size of its own for every image of
+ * the batch.  img_widths / img_heights: HOST arrays of count == N entries (shape metadata, one device table per distinct list of
+ * sizes).  out_dets f32 [N, 300, 38] and out_count i32 [N] as above; out_mask: U8 [sum h_n w_n], image n's [h_n, w_n] mask at
+ * mask_offsets[n] .. mask_offsets[n + 1] (mask_offsets: HOST out [N + 1], may be NULL).  out_mask may be NULL: detections only, no mask
+ * work.  All three outputs of image n are EQUAL to what lele_hip_yolo_seg_postprocess leaves for that image alone at (w_n, h_n) --
+ * whatever its neighbours and its place in the batch; like that call the mask grid is the reference's square one of side
+ * S = floor(sqrt(Hm Wm)) over the first S S values of each of an image's 32 planes (image.rs:142-145).  Inputs are finite (a NaN in
+ * logits: unspecified, as there).  The counts stay on the device: graph-capturable once the layout has run eagerly once.
+ * The mask is not computed pixel by detection (image.rs:213-262) but from three bit tables of 10 words (300 detections) per entry,
+ * each predicate of the reference evaluated once: per mask cell the detections whose sigmoid passes both thresholds there (evaluated
+ * only inside the cells the box's pixels map to), per image column and per image row the detections whose box covers it; a pixel is set
+ * iff the AND of its column's, its row's and its cell's words is non-zero.  Workspace, from the context's arena (its scratch block
+ * where the arena is too small; no allocation after the first call of a size): exactly 40 * sum_n (S S + w_n + h_n) bytes.
+ * Refused before launch: a NULL argument other than out_mask / mask_offsets, count != N, N >= 65536, a size < 1 or >= 2^24,
+ * sum h_n w_n >= 2^31. */
+int lele_hip_yolo_seg_postprocess_sized(LeleCtx* ctx, const LeleTensor* logits, const LeleTensor* mask_features,
+                                        const int32_t* img_widths, const int32_t* img_heights, int64_t count, float threshold,
+                                        int32_t num_classes, LeleBuf* out_dets, LeleBuf* out_count, LeleBuf* out_mask,
+                                        int64_t* mask_offsets);
 
 /* ---- multi-GPU: the one exchange step of the utterance-sharded recogniser ------------------------------ */
 /* lele is single-process; its route to several devices is one instance per shard of the utterances (one process per GPU here).

@@ -11,6 +11,8 @@ The device halves are in csrc/app.hip (`kernels.wav_to_f32`, `argmax_last`, `tok
   * `beam_results`        -- that kernel's four arrays -> the reference's list format
   * `ctc_forced_align`    -- the reference of kernels.ctc_align_segments: a known transcript's Viterbi alignment and CTC likelihood
   * `align_results`       -- that kernel's five arrays -> the reference's format
+  * `pack_images`, `unpack_masks` -- a queue of images of different sizes into kernels.image_preprocess_batch's one byte buffer, and
+    kernels.yolo_seg_postprocess_sized's packed masks back into one array per image
   * `resample_linear`, `resample_fir_table`, `resample_fir` -- the references of features.Resampler: the reference's linear
     `resample` and the Kaiser-windowed polyphase FIR in float64 (never used by the device path)
 """
@@ -254,6 +256,41 @@ def vad_segments(probs, chunk_size, padded_len, audio_len, sample_rate=16000, th
                 continue
         merged.append(list(seg))
     return [(a, b) for a, b in merged]
+
+
+def pack_images(images):
+    """a queue of [H, W, 3] u8 images of different sizes -> (bytes u8 [total], offsets int64 [n], heights int32 [n], widths int32 [n]),
+    the arguments of kernels.image_preprocess_batch.  An array listed more than once (the same object) is stored once: its entries
+    share an offset."""
+    offsets, heights, widths, parts, seen, total = [], [], [], [], {}, 0
+    for img in images:
+        a = np.asarray(img)
+        if a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] != 3:
+            raise ValueError("pack_images: u8 [H, W, 3] images required, got %s %s" % (a.dtype, a.shape))
+        if id(img) not in seen:
+            seen[id(img)] = total
+            parts.append(np.ascontiguousarray(a).reshape(-1))
+            total += a.size
+        offsets.append(seen[id(img)])
+        heights.append(a.shape[0])
+        widths.append(a.shape[1])
+    data = np.concatenate(parts) if parts else np.zeros(0, np.uint8)
+    return data, np.array(offsets, np.int64), np.array(heights, np.int32), np.array(widths, np.int32)
+
+
+def unpack_masks(mask, mask_offsets, sizes):
+    """kernels.yolo_seg_postprocess_sized's packed mask u8 [sum h * w] -> one [h, w] array per image; sizes = [(width, height)]"""
+    flat = np.asarray(mask.numpy() if hasattr(mask, "numpy") else mask).reshape(-1)
+    sz = np.asarray(sizes, dtype=np.int64).reshape(-1, 2)
+    if len(mask_offsets) != len(sz) + 1:
+        raise ValueError("unpack_masks: %d offsets for %d sizes" % (len(mask_offsets), len(sz)))
+    out = []
+    for n, (w, h) in enumerate(sz):
+        a, b = int(mask_offsets[n]), int(mask_offsets[n + 1])
+        if b - a != w * h or b > flat.size:
+            raise ValueError("unpack_masks: image %d is %d x %d but its mask holds %d bytes" % (n, w, h, b - a))
+        out.append(flat[a:b].reshape(int(h), int(w)))
+    return out
 
 
 def resample_linear(samples, from_rate, to_rate):

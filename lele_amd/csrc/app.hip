@@ -15,6 +15,9 @@
 //                             target x target, HWC u8 -> CHW f32 / 255)
 //   lele_hip_yolo_seg_postprocess <- image.rs:127-265 (score / box filter in query order, box rescale, per-detection mask =
 //                             sigmoid(coeffs . mask_features), nearest upscale, box crop, thresholds)
+//   lele_hip_image_preprocess_batch <- image.rs:62-111 per image of a packed byte buffer of images of different sizes, one launch
+//   lele_hip_yolo_seg_postprocess_sized <- image.rs:127-265 per image at a size of its own; the mask (image.rs:213-262) from bit tables
+//                             of its exact predicates, each evaluated once, instead of pixel by detection
 // All exact: one IEEE operation per sample / pure comparisons / the reference's operation order; the only transcendental
 // (the mask sigmoid's expf, libm upstream) is evaluated in double and rounded once, i.e. correctly rounded like glibc's.
 #include "common.h"
@@ -726,6 +729,198 @@ __global__ void yolo_mask_kernel(const float* __restrict__ dets_all, const int32
     }
 }
 
+// ---- a queue of images of different sizes: one launch in, one call out ---------------------------------------------------------------
+
+// image_preprocess_batch's device table: where image blockIdx.y lies in the byte buffer
+struct ImgSrc {
+    int64_t off;
+    int32_t h, w;
+};
+
+// image_preprocess_kernel per image of a packed byte buffer, grid (pixel tiles, image): every image's output is target x target
+// whatever its source size.  VEC4 (target % 4 == 0: four consecutive x share a row and a plane's offset is a multiple of 16 bytes):
+// a thread writes 4 x of each plane as one 16-byte store; the source reads are byte loads at whatever alignment the offsets give.
+template <bool VEC4>
+__global__ __launch_bounds__(256) void image_preprocess_batch_kernel(const uint8_t* __restrict__ bytes, const ImgSrc* __restrict__ tab,
+                                                                     int target, float* __restrict__ out_all) {
+    constexpr int PER = VEC4 ? 4 : 1;
+    const ImgSrc s = tab[blockIdx.y];
+    const int total = target * target;
+    const int i0 = (blockIdx.x * 256 + threadIdx.x) * PER;
+    if (i0 >= total) return;
+    const uint8_t* rgb = bytes + s.off;
+    float* out = out_all + (int64_t)blockIdx.y * 3 * total;
+    const int y = i0 / target, x0 = i0 - y * target;
+    int sy = (int)floorf(((float)y + 0.5f) * (float)s.h / (float)target);
+    sy = sy < s.h - 1 ? sy : s.h - 1;
+    float v[3][PER];
+#pragma unroll
+    for (int k = 0; k < PER; ++k) {
+        int sx = (int)floorf(((float)(x0 + k) + 0.5f) * (float)s.w / (float)target);
+        sx = sx < s.w - 1 ? sx : s.w - 1;
+        const uint8_t* px = rgb + ((int64_t)sy * s.w + sx) * 3;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) v[c][k] = (float)px[c] / 255.0f;
+    }
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        float* o = out + (int64_t)c * total + i0;
+        if constexpr (VEC4)
+            *reinterpret_cast<float4*>(o) = make_float4(v[c][0], v[c][1], v[c][2], v[c][3]);
+        else
+            o[0] = v[c][0];
+    }
+}
+
+// yolo_seg_postprocess_sized's device table: SizedImg[N], then the pixel kernel's work list int2[blocks] = {image, first pixel}
+struct SizedImg {
+    int64_t mask_off;  // of the image's first pixel in out_mask
+    int64_t ws_off;    // of the image's bit tables in the workspace, in 32-bit words
+    int32_t w, h;
+};
+
+constexpr int kDetWords = (kQueries + 31) / 32;  // a 300-bit set of detections
+constexpr int kPixPerBlock = 2048;               // pixels of one image a block of yolo_pixels_kernel takes
+
+// yolo_dets_kernel with the image's own size, read from the table
+__global__ __launch_bounds__(320) void yolo_dets_sized_kernel(const float* __restrict__ logits_all, const SizedImg* __restrict__ tab,
+                                                              float threshold, int num_classes, float* __restrict__ dets_all,
+                                                              int32_t* __restrict__ count_all) {
+    __shared__ int wave_cnt[5];
+    const float img_w = (float)tab[blockIdx.x].w, img_h = (float)tab[blockIdx.x].h;
+    const float* logits = logits_all + (int64_t)blockIdx.x * kQueries * kLogitLen;
+    float* dets = dets_all + (int64_t)blockIdx.x * kQueries * kLogitLen;
+    int32_t* count = count_all + blockIdx.x;
+    const int i = threadIdx.x, lane = i & 63, wave = i >> 6;
+    const float* q = logits + (int64_t)(i < kQueries ? i : 0) * kLogitLen;
+    const float score = q[4];
+    const float x1r = q[0], y1r = q[1], x2r = q[2], y2r = q[3];
+    const bool keep = i < kQueries && !(score < threshold) && !(x2r <= x1r || y2r <= y1r);
+    const unsigned long long m = __ballot(keep);
+    if (lane == 0) wave_cnt[wave] = __popcll(m);
+    __syncthreads();
+    int pos = __popcll(m & ((1ull << lane) - 1ull));
+    for (int w = 0; w < wave; ++w) pos += wave_cnt[w];
+    if (keep) {
+        const float sx = img_w / 640.0f, sy = img_h / 640.0f;
+        float* d = dets + (int64_t)pos * kLogitLen;
+        d[0] = fmaxf(x1r * sx, 0.0f);
+        d[1] = fmaxf(y1r * sy, 0.0f);
+        d[2] = fminf(x2r * sx, img_w);
+        d[3] = fminf(y2r * sy, img_h);
+        d[4] = score;
+        const float cf = q[5];
+        int cid = cf > 0.0f ? (cf >= 2147483520.0f ? 2147483647 : (int)cf) : 0;
+        cid = cid < num_classes - 1 ? cid : num_classes - 1;
+        d[5] = (float)cid;
+        for (int j = 0; j < kMaskDim; ++j) d[6 + j] = q[6 + j];
+    }
+    const int total = wave_cnt[0] + wave_cnt[1] + wave_cnt[2] + wave_cnt[3] + wave_cnt[4];
+    if (i == 0) *count = total;
+    for (int r = total + i; r < kQueries; r += blockDim.x)
+        for (int j = 0; j < kLogitLen; ++j) dets[(int64_t)r * kLogitLen + j] = 0.0f;
+}
+
+// the mask cell that pixel coordinate v (an integer, as a float) reads: yolo_mask_kernel's expression, non-decreasing in v
+__device__ inline int yolo_cell_of(float v, float scale, int side) {
+    const int m = (int)floorf((v + 0.5f) * scale);
+    return m < side - 1 ? m : side - 1;
+}
+
+// The three bit tables of an image, word-major so that neighbouring lanes touch neighbouring words:
+//     cell bits [kDetWords][S S] | column bits [kDetWords][w] | row bits [kDetWords][h]          (32-bit words; S = the mask's side)
+// bit (d & 31) of word d >> 5.  Grid (cell tiles + box tiles, kDetWords, image); a block whose word lies behind the image's kept
+// detections leaves at once (those words are never read).  A thread owns ONE table entry and all 32 bits of its word, so the word is
+// written once with a plain store: no atomics, no ballots.
+//   cell tiles: the thread keeps its cell's 32 feature values in registers and walks the word's detections (uniform over the wave: the
+//     coefficients are scalar loads); the sigmoid is evaluated only where the cell lies in the rectangle the box's pixels map to --
+//     pixels ceil(x1) .. min(floor(x2), w - 1) are exactly those with (float)ix >= x1 && (float)ix <= x2, and the cell of a pixel is
+//     non-decreasing in the pixel, so no pixel inside the box reads a cell outside [cell(first), cell(last)] -- and then exactly as
+//     yolo_mask_kernel evaluates it.
+//   box tiles: entry p < w is column p, else row p - w; the bit is yolo_mask_kernel's own comparison pair.
+__global__ __launch_bounds__(256) void yolo_bits_kernel(const float* __restrict__ dets_all, const int32_t* __restrict__ count_all,
+                                                        const float* __restrict__ feat_all, int64_t feat_stride, int side,
+                                                        const SizedImg* __restrict__ tab, uint32_t* __restrict__ ws) {
+    const int img = blockIdx.z, word = blockIdx.y;
+    const int n = count_all[img], d0 = word * 32;
+    if (d0 >= n) return;
+    const int d1 = n < d0 + 32 ? n : d0 + 32;
+    const SizedImg im = tab[img];
+    const float* dets = dets_all + (int64_t)img * kQueries * kLogitLen;
+    const int cells = side * side, cell_tiles = (cells + 255) / 256;
+    uint32_t* tables = ws + im.ws_off;
+    uint32_t bits = 0;
+    if ((int)blockIdx.x < cell_tiles) {
+        const int cell = blockIdx.x * 256 + threadIdx.x;
+        if (cell >= cells) return;
+        const int cy = cell / side, cx = cell - cy * side;
+        const float* feat = feat_all + (int64_t)img * feat_stride + cell;
+        float f[kMaskDim];
+#pragma unroll
+        for (int c = 0; c < kMaskDim; ++c) f[c] = feat[(int64_t)c * cells];
+        const float scale_x = (float)side / (float)im.w, scale_y = (float)side / (float)im.h;
+        for (int d = d0; d < d1; ++d) {
+            const float* det = dets + (int64_t)d * kLogitLen;
+            const float xlo = ceilf(det[0]), xhi = fminf(floorf(det[2]), (float)(im.w - 1));
+            const float ylo = ceilf(det[1]), yhi = fminf(floorf(det[3]), (float)(im.h - 1));
+            if (!(xlo <= xhi && ylo <= yhi)) continue;  // no pixel inside the box (det[0], det[1] >= 0: yolo_dets_sized_kernel's fmaxf)
+            if (cx < yolo_cell_of(xlo, scale_x, side) || cx > yolo_cell_of(xhi, scale_x, side) || cy < yolo_cell_of(ylo, scale_y, side) ||
+                cy > yolo_cell_of(yhi, scale_y, side))
+                continue;
+            float sum = 0.0f;
+#pragma unroll
+            for (int c = 0; c < kMaskDim; ++c) sum = sum + det[6 + c] * f[c];  // separate multiply and add
+            const float e = (float)exp((double)(-sum));
+            const float mv = 1.0f / (1.0f + e);
+            if (mv > 0.5f && mv * det[4] > 0.5f) bits |= 1u << (d - d0);
+        }
+        tables[(int64_t)word * cells + cell] = bits;
+    } else {
+        const int64_t p = (int64_t)(blockIdx.x - cell_tiles) * 256 + threadIdx.x;
+        if (p >= (int64_t)im.w + im.h) return;
+        const bool col = p < im.w;
+        const int at = (int)(col ? p : p - im.w);
+        const float v = (float)at;
+        for (int d = d0; d < d1; ++d) {
+            const float* det = dets + (int64_t)d * kLogitLen;
+            if (v >= det[col ? 0 : 1] && v <= det[col ? 2 : 3]) bits |= 1u << (d - d0);
+        }
+        uint32_t* t = tables + (int64_t)kDetWords * cells;
+        if (col)
+            t[(int64_t)word * im.w + at] = bits;
+        else
+            t[(int64_t)kDetWords * im.w + (int64_t)word * im.h + at] = bits;
+    }
+}
+
+// block b takes kPixPerBlock pixels of image work[b].x from pixel work[b].y on: 255 where some detection has its column bit, its row
+// bit and the bit of the pixel's cell set -- yolo_mask_kernel's in_bbox && mv > 0.5f && mv * score > 0.5f for that detection; only the
+// ceil(count / 32) words that hold kept detections are visited
+__global__ __launch_bounds__(256) void yolo_pixels_kernel(const int32_t* __restrict__ count_all, int side, const SizedImg* __restrict__ tab,
+                                                          const int2* __restrict__ work, const uint32_t* __restrict__ ws,
+                                                          uint8_t* __restrict__ mask_all) {
+    const int2 wk = work[blockIdx.x];
+    const SizedImg im = tab[wk.x];
+    const int words = (count_all[wk.x] + 31) >> 5;
+    const unsigned total = (unsigned)im.w * (unsigned)im.h;  // < 2^31 (checked on the host), so first pixel + 2047 fits 32 bits
+    const int cells = side * side;
+    const uint32_t* cellb = ws + im.ws_off;
+    const uint32_t* colb = cellb + (int64_t)kDetWords * cells;
+    const uint32_t* rowb = colb + (int64_t)kDetWords * im.w;
+    uint8_t* mask = mask_all + im.mask_off;
+    const float scale_x = (float)side / (float)im.w, scale_y = (float)side / (float)im.h;
+    for (int k = 0; k < kPixPerBlock / 256; ++k) {
+        const unsigned i = (unsigned)wk.y + k * 256 + threadIdx.x;
+        if (i >= total) break;
+        const int iy = (int)(i / (unsigned)im.w), ix = (int)(i - (unsigned)iy * (unsigned)im.w);
+        const int cell = yolo_cell_of((float)iy, scale_y, side) * side + yolo_cell_of((float)ix, scale_x, side);
+        uint32_t any = 0;
+        for (int wd = 0; wd < words; ++wd)
+            any |= colb[(int64_t)wd * im.w + ix] & rowb[(int64_t)wd * im.h + iy] & cellb[(int64_t)wd * cells + cell];
+        mask[i] = any ? 255 : 0;
+    }
+}
+
 }  // namespace
 
 extern "C" {
@@ -1104,6 +1299,154 @@ int lele_hip_yolo_seg_postprocess(LeleCtx* ctx, const LeleTensor* logits, const 
                        (const float*)out_dets->data, (const int32_t*)out_count->data, (const float*)df, mask_h, mask_w, img_width,
                        img_height, (uint8_t*)out_mask->data);
     LELE_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
+}  // extern "C"
+
+namespace {
+struct ImgTableArg {
+    const int64_t* offsets;
+    const int32_t *heights, *widths;
+    int64_t count;
+};
+void build_img_table(const void* arg, std::vector<char>& blob) {
+    const ImgTableArg& a = *(const ImgTableArg*)arg;
+    blob.resize((size_t)a.count * sizeof(ImgSrc));
+    ImgSrc* t = (ImgSrc*)blob.data();
+    for (int64_t i = 0; i < a.count; ++i) t[i] = ImgSrc{a.offsets[i], a.heights[i], a.widths[i]};
+}
+
+// the sized post-processing's table: SizedImg[count], then yolo_pixels_kernel's work list, kPixPerBlock pixels of one image a block
+struct SizedTableArg {
+    const int32_t *widths, *heights;
+    int64_t count, cells;
+};
+int64_t sized_blocks(int32_t w, int32_t h) { return ((int64_t)w * h + kPixPerBlock - 1) / kPixPerBlock; }
+int64_t sized_ws_words(int64_t cells, int32_t w, int32_t h) { return (int64_t)kDetWords * (cells + w + h); }
+void build_sized_table(const void* arg, std::vector<char>& blob) {
+    const SizedTableArg& a = *(const SizedTableArg*)arg;
+    int64_t blocks = 0;
+    for (int64_t n = 0; n < a.count; ++n) blocks += sized_blocks(a.widths[n], a.heights[n]);
+    blob.resize((size_t)a.count * sizeof(SizedImg) + (size_t)blocks * sizeof(int2));
+    SizedImg* t = (SizedImg*)blob.data();
+    int2* work = (int2*)(blob.data() + (size_t)a.count * sizeof(SizedImg));
+    int64_t mask_off = 0, ws_off = 0;
+    for (int64_t n = 0; n < a.count; ++n) {
+        const int32_t w = a.widths[n], h = a.heights[n];
+        t[n] = SizedImg{mask_off, ws_off, w, h};
+        for (int64_t b = 0; b < sized_blocks(w, h); ++b) *work++ = make_int2((int)n, (int)(b * kPixPerBlock));
+        mask_off += (int64_t)w * h;
+        ws_off += sized_ws_words(a.cells, w, h);
+    }
+}
+}  // namespace
+
+extern "C" {
+
+int lele_hip_image_preprocess_batch(LeleCtx* ctx, const LeleTensor* bytes, const int64_t* offsets, const int32_t* heights,
+                                    const int32_t* widths, int64_t count, int32_t target, LeleBuf* out, int64_t* out_shape,
+                                    int32_t* out_rank) {
+    LELE_REQUIRE(ctx && bytes && out, "image_preprocess_batch: NULL argument");
+    LELE_REQUIRE(bytes->dtype == LELE_U8 && bytes->rank == 1, "image_preprocess_batch: bytes must be u8 [total]");
+    LELE_REQUIRE(count >= 0 && count < 65536, "image_preprocess_batch: count = %lld outside [0, 65536)", (long long)count);
+    LELE_REQUIRE(count == 0 || (offsets && heights && widths), "image_preprocess_batch: NULL argument");  // (an empty std::vector's data())
+    LELE_REQUIRE(target >= 1 && target <= 16384, "image_preprocess_batch: target = %d outside [1, 16384]", (int)target);
+    const int64_t total = bytes->shape[0];
+    for (int64_t i = 0; i < count; ++i) {
+        LELE_REQUIRE(heights[i] >= 1 && widths[i] >= 1 && heights[i] < (1 << 24) && widths[i] < (1 << 24),
+                     "image_preprocess_batch: image %lld is %d x %d (sides in [1, 2^24) required)", (long long)i, (int)heights[i], (int)widths[i]);
+        const int64_t len = (int64_t)3 * heights[i] * widths[i];
+        LELE_REQUIRE(offsets[i] >= 0 && len <= total && offsets[i] <= total - len,
+                     "image_preprocess_batch: image %lld (%d x %d at offset %lld) does not lie inside the %lld bytes", (long long)i,
+                     (int)heights[i], (int)widths[i], (long long)offsets[i], (long long)total);
+    }
+    LELE_HIP_CHECK(hipSetDevice(ctx->device));
+    const void* tab = nullptr;
+    if (count > 0) {
+        std::vector<int64_t> key;  // the table's contents are its key
+        for (int64_t i = 0; i < count; ++i) key.insert(key.end(), {offsets[i], (int64_t)heights[i], (int64_t)widths[i]});
+        const ImgTableArg arg{offsets, heights, widths, count};
+        LELE_TRY(layout_table(ctx, "imgb", count, 0, key.data(), (int64_t)key.size() - 1, build_img_table, &arg, &tab));
+    }
+    LELE_TRY(ctx->arena_reset());
+    const void* db = nullptr;
+    if (count > 0) LELE_TRY(ctx->dev_ptr(bytes, &db));
+    const int64_t pixels = (int64_t)target * target;
+    LELE_TRY(out->reserve((size_t)(count * 3 * pixels) * 4));
+    if (count > 0) {
+        const bool vec4 = target % 4 == 0;
+        const unsigned tiles = (unsigned)((pixels / (vec4 ? 4 : 1) + 255) / 256);
+        hipLaunchKernelGGL(vec4 ? image_preprocess_batch_kernel<true> : image_preprocess_batch_kernel<false>, dim3(tiles, (unsigned)count), dim3(256),
+                           0, ctx->stream, (const uint8_t*)db, (const ImgSrc*)tab, (int)target, (float*)out->data);
+        LELE_HIP_CHECK(hipGetLastError());
+    }
+    return set_shape(out_shape, out_rank, {count, 3, (int64_t)target, (int64_t)target});
+}
+
+int lele_hip_yolo_seg_postprocess_sized(LeleCtx* ctx, const LeleTensor* logits, const LeleTensor* mask_features,
+                                        const int32_t* img_widths, const int32_t* img_heights, int64_t count, float threshold,
+                                        int32_t num_classes, LeleBuf* out_dets, LeleBuf* out_count, LeleBuf* out_mask,
+                                        int64_t* mask_offsets) {
+    LELE_REQUIRE(ctx && logits && mask_features && img_widths && img_heights && out_dets && out_count, "yolo_seg_postprocess_sized: NULL argument");
+    LELE_REQUIRE(out_dets != out_count && out_dets != out_mask && out_count != out_mask, "yolo_seg_postprocess_sized: the output buffers must be distinct");
+    const int64_t per = (int64_t)kQueries * kLogitLen;
+    LELE_REQUIRE(logits->dtype == LELE_F32 && numel(logits) > 0 && numel(logits) % per == 0,
+                 "yolo_seg_postprocess_sized: logits must hold N x 300 x 38 f32 values");
+    const int64_t images = numel(logits) / per;
+    LELE_REQUIRE(count == images, "yolo_seg_postprocess_sized: %lld sizes for N = %lld images", (long long)count, (long long)images);
+    LELE_REQUIRE(mask_features->dtype == LELE_F32 && num_classes > 0, "yolo_seg_postprocess_sized: f32 mask features and a positive class count required");
+    LELE_REQUIRE(numel(mask_features) % (images * kMaskDim) == 0 && images < 65536,
+                 "yolo_seg_postprocess_sized: mask features do not match %lld images", (long long)images);
+    const int64_t mask_hw = numel(mask_features) / (images * kMaskDim);  // image.rs:142-145, as lele_hip_yolo_seg_postprocess reads it
+    const int side = (int)sqrtf((float)mask_hw);
+    LELE_REQUIRE(side > 0 && side < 32768, "yolo_seg_postprocess_sized: empty mask features, or a mask side of 2^15 or more");
+    const int64_t cells = (int64_t)side * side;
+    int64_t pixels = 0, ws_words = 0, blocks = 0, longest = 0;
+    for (int64_t n = 0; n < images; ++n) {
+        const int32_t w = img_widths[n], h = img_heights[n];
+        LELE_REQUIRE(w >= 1 && h >= 1 && w < (1 << 24) && h < (1 << 24), "yolo_seg_postprocess_sized: image %lld is %d x %d (sides in [1, 2^24) required)",
+                     (long long)n, (int)w, (int)h);
+        pixels += (int64_t)w * h;
+        LELE_REQUIRE(pixels < (int64_t(1) << 31), "yolo_seg_postprocess_sized: the masks up to image %lld hold 2^31 pixels or more", (long long)n);
+        ws_words += sized_ws_words(cells, w, h);
+        blocks += sized_blocks(w, h);
+        longest = std::max<int64_t>(longest, (int64_t)w + h);
+    }
+    LELE_HIP_CHECK(hipSetDevice(ctx->device));
+    std::vector<int64_t> key;
+    for (int64_t n = 0; n < images; ++n) key.insert(key.end(), {(int64_t)img_widths[n], (int64_t)img_heights[n]});
+    const SizedTableArg arg{img_widths, img_heights, images, cells};
+    const void* tab = nullptr;
+    LELE_TRY(layout_table(ctx, "ysiz", cells, 0, key.data(), (int64_t)key.size() - 1, build_sized_table, &arg, &tab));
+    LELE_TRY(ctx->arena_reset());
+    const void *dl = nullptr, *df = nullptr;
+    LELE_TRY(ctx->dev_ptr(logits, &dl));
+    if (out_mask) LELE_TRY(ctx->dev_ptr(mask_features, &df));
+    void* ws = nullptr;
+    if (out_mask) {  // 40 * sum (S S + w + h) bytes: the arena while it holds them, else the scratch block (grown once, then kept)
+        const size_t ws_bytes = (size_t)ws_words * 4;
+        if (ctx->arena_used + ws_bytes + 256 <= ctx->arena_cap) LELE_TRY(ctx->arena_alloc(ws_bytes, &ws));
+        else LELE_TRY(ctx->get_scratch(ws_bytes, &ws));
+    }
+    LELE_TRY(out_dets->reserve((size_t)(images * per) * 4));
+    LELE_TRY(out_count->reserve((size_t)images * 4));
+    if (out_mask) LELE_TRY(out_mask->reserve((size_t)pixels));
+    const SizedImg* imgs = (const SizedImg*)tab;
+    hipLaunchKernelGGL(yolo_dets_sized_kernel, dim3((unsigned)images), dim3(320), 0, ctx->stream, (const float*)dl, imgs, threshold, num_classes,
+                       (float*)out_dets->data, (int32_t*)out_count->data);
+    if (out_mask) {
+        const unsigned tiles = (unsigned)((cells + 255) / 256 + (longest + 255) / 256);
+        hipLaunchKernelGGL(yolo_bits_kernel, dim3(tiles, kDetWords, (unsigned)images), dim3(256), 0, ctx->stream, (const float*)out_dets->data,
+                           (const int32_t*)out_count->data, (const float*)df, (int64_t)kMaskDim * mask_hw, side, imgs, (uint32_t*)ws);
+        hipLaunchKernelGGL(yolo_pixels_kernel, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, (const int32_t*)out_count->data, side, imgs,
+                           (const int2*)(imgs + images), (const uint32_t*)ws, (uint8_t*)out_mask->data);
+    }
+    LELE_HIP_CHECK(hipGetLastError());
+    if (mask_offsets) {
+        mask_offsets[0] = 0;
+        for (int64_t n = 0; n < images; ++n) mask_offsets[n + 1] = mask_offsets[n] + (int64_t)img_widths[n] * img_heights[n];
+    }
     return 0;
 }
 

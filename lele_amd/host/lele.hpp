@@ -841,6 +841,38 @@ inline SegOutputs yolo_seg_postprocess(const TensorView& logits, const TensorVie
     return {TensorView::from_device(dets, {n, 300, 38}, LELE_F32), TensorView::from_device(count, {n}, LELE_I32),
             TensorView::from_device(mask, {n, img_height, img_width}, LELE_U8)};
 }
+// A queue of images of different sizes in one launch (image.rs:62-111 per image): image i is HWC RGB at
+// bytes[offsets[i] .. offsets[i] + 3 heights[i] widths[i]) of one u8 buffer -> f32 [count, 3, target, target], image i bit for bit
+// image_preprocess of that image alone
+inline TensorView image_preprocess_batch(const TensorView& bytes, const std::vector<int64_t>& offsets, const std::vector<int32_t>& heights,
+                                         const std::vector<int32_t>& widths, int target, Buffer& out) {
+    if (offsets.size() != heights.size() || offsets.size() != widths.size())
+        throw Error("image_preprocess_batch: offsets, heights and widths differ in length");
+    Shape sh;
+    LeleTensor tb = bytes.c();
+    check(lele_hip_image_preprocess_batch(ctx(), &tb, offsets.data(), heights.data(), widths.data(), (int64_t)offsets.size(), target,
+                                          out.raw(), sh.dims, &sh.rank));
+    LELE_RET(out, LELE_F32);
+}
+struct SizedSegOutputs {
+    // f32 [N, 300, 38], i32 [N], u8 [sum h w] (empty without masks); image n's [h, w] mask at mask_offsets[n] .. mask_offsets[n + 1]
+    TensorView dets, count, mask;
+    std::vector<int64_t> mask_offsets;
+};
+// yolo_seg_postprocess (image.rs:127-265) with a size of its own for every image of the batch; every image's results are equal to
+// that call on the image alone.  mask == nullptr: detections only, no mask work.
+inline SizedSegOutputs yolo_seg_postprocess_sized(const TensorView& logits, const TensorView& mask_features,
+                                                  const std::vector<int32_t>& img_widths, const std::vector<int32_t>& img_heights,
+                                                  float threshold, int num_classes, Buffer& dets, Buffer& count, Buffer* mask) {
+    if (img_widths.size() != img_heights.size()) throw Error("yolo_seg_postprocess_sized: widths and heights differ in length");
+    LeleTensor tl = logits.c(), tm = mask_features.c();
+    std::vector<int64_t> off(img_widths.size() + 1, 0);
+    check(lele_hip_yolo_seg_postprocess_sized(ctx(), &tl, &tm, img_widths.data(), img_heights.data(), (int64_t)img_widths.size(), threshold,
+                                              num_classes, dets.raw(), count.raw(), mask ? mask->raw() : nullptr, off.data()));
+    const int64_t n = logits.size() / (300 * 38);
+    return {TensorView::from_device(dets, {n, 300, 38}, LELE_F32), TensorView::from_device(count, {n}, LELE_I32),
+            mask ? TensorView::from_device(*mask, {off.back()}, LELE_U8) : TensorView(), off};
+}
 // examples/silero/src/main.rs:151-228: speech segments (sample indices) from per-chunk probabilities; host-only
 struct VadConfig {  // main.rs:18-28
     float threshold = 0.3f, min_silence_ms = 200.0f, min_speech_ms = 400.0f, speech_pad_ms = 120.0f, merge_gap_ms = 200.0f;

@@ -859,6 +859,40 @@ def yolo_seg_postprocess(logits, mask_features, img_width, img_height, threshold
             TensorView(_lib.DevTensor(om, lead + [int(img_height), int(img_width)], np.uint8)))
 
 
+def image_preprocess_batch(bytes, offsets, heights, widths, target=640, out=None, ctx=None):
+    """image_preprocess of a queue of images of different sizes in one launch (apps.pack_images builds the arguments): image i is
+    HWC RGB at bytes[offsets[i] : offsets[i] + 3 * heights[i] * widths[i]] of one u8 buffer -> f32 [count, 3, target, target], image i
+    bit for bit image_preprocess of that image alone.  offsets / heights / widths are host lists (shape metadata)."""
+    off = np.ascontiguousarray(np.asarray(offsets, dtype=np.int64).reshape(-1))
+    hs, ws = _i32_list(heights), _i32_list(widths)
+    if not (len(off) == len(hs) == len(ws)):
+        raise _lib.LeleError("image_preprocess_batch: %d offsets, %d heights, %d widths" % (len(off), len(hs), len(ws)))
+    return _op(ctx, _lib.lib().lele_hip_image_preprocess_batch, [bytes],
+               [_lib.i64_ptr(off), _i32_ptr(hs), _i32_ptr(ws), C.c_int64(len(off)), C.c_int32(int(target))], out)
+
+
+def yolo_seg_postprocess_sized(logits, mask_features, sizes, threshold, num_classes=80, out_dets=None, out_count=None, out_mask=None,
+                               masks=True, ctx=None):
+    """yolo_seg_postprocess with a size of its own for every image: sizes = [(img_width, img_height)] * N ->
+    (dets f32 [N, 300, 38], count i32 [N], mask u8 [sum h * w], mask_offsets np.int64 [N + 1]); image n's three results are equal to
+    yolo_seg_postprocess of that image alone at its size, its [h, w] mask at mask[mask_offsets[n] : mask_offsets[n + 1]]
+    (apps.unpack_masks).  masks=False: detections only, no mask work; mask is None and out_mask is not touched."""
+    ctx = _ctx(ctx)
+    keep = []
+    sz = np.asarray(sizes, dtype=np.int64).reshape(-1, 2)
+    ws, hs = _i32_list(sz[:, 0]), _i32_list(sz[:, 1])
+    od, oc = out_dets or ctx.buf(), out_count or ctx.buf()
+    om = (out_mask or ctx.buf()) if masks else None
+    n = int(np.prod(unwrap(logits).shape, dtype=np.int64)) // (300 * 38)
+    moff = np.zeros(len(ws) + 1, np.int64)
+    _lib.check(_lib.lib().lele_hip_yolo_seg_postprocess_sized(
+        ctx._h, _lib.as_tensor(unwrap(logits), keep), _lib.as_tensor(unwrap(mask_features), keep), _i32_ptr(ws), _i32_ptr(hs),
+        C.c_int64(len(ws)), C.c_float(float(threshold)), C.c_int32(int(num_classes)), od._h, oc._h, om._h if masks else None,
+        _lib.i64_ptr(moff)))
+    return (TensorView(_lib.DevTensor(od, [n, 300, 38], np.float32)), TensorView(_lib.DevTensor(oc, [n], np.int32)),
+            TensorView(_lib.DevTensor(om, [int(moff[-1])], np.uint8)) if masks else None, moff)
+
+
 def _reshape_strides(shape, strides, new):
     """strides of `new` over the same memory, or None when the view cannot be reshaped without a copy"""
     old = [(d, st) for d, st in zip(shape, strides) if d != 1]
