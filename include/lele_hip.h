@@ -905,6 +905,19 @@ int lele_hip_ctc_align_segments(LeleCtx* ctx, const LeleTensor* at, const int32_
 int lele_hip_attention_segments(LeleCtx* ctx, const LeleTensor* qkv, int64_t q_offset, int64_t k_offset, int64_t v_offset, int64_t heads,
                                 int64_t dh, const int64_t* row_offsets, int64_t count, const LeleTensor* scale_or_null, LeleBuf* out,
                                 int64_t* out_shape, int32_t* out_rank);
+/* lele_hip_attention_segments with no limit on a segment's rows (utterances over 30 s in a packed batch): same arguments, same checks,
+ * same result shape.  A segment of at most 512 rows runs through that call's own work lists, kernels and launches and gets its result
+ * bit for bit, whatever else is in the layout.  Longer segments take ONE more launch a call, of the one-pass kernel behind
+ * attention_view's large grids (online softmax over 32-key tiles, split-bf16 products) in a single fixed form behind a block locator:
+ * 128 query rows of one (segment, head) a workgroup, the longest segments' workgroups first; a long segment's result depends on its own
+ * rows only -- not on the batch, the order or the position -- and is the node sequence's values to ~1e-6 relative, not its bits.  So
+ * under LELE_HIP_ATTENTION_EXACT=1, which promises those bits, a segment of more than 512 rows is an error that names it and the
+ * switch; shorter ones behave as in lele_hip_attention_segments.  No key split: one long utterance alone is heads * ceil(len / 128)
+ * workgroups.  Everything is checked before anything is launched or resized: a failing call leaves `out` as it was.
+ * Graph-capturable after one eager run of the same layout. */
+int lele_hip_attention_segments_long(LeleCtx* ctx, const LeleTensor* qkv, int64_t q_offset, int64_t k_offset, int64_t v_offset,
+                                     int64_t heads, int64_t dh, const int64_t* row_offsets, int64_t count, const LeleTensor* scale_or_null,
+                                     LeleBuf* out, int64_t* out_shape, int32_t* out_rank);
 /* lele_hip_depthwise_conv1d_tlc (conv1d.rs:837 between two transposes) per segment: x f32 [R, P], channels [x_offset, x_offset + C),
  * w [C, 1, K], pad_left + pad_right == K - 1 (rows are kept) -> out [R, C].  A segment ends where its rows end: taps outside it are
  * skipped, so segment i is bit for bit the dense entry point on it alone as [1, len, P], segments shorter than the stencil included. */

@@ -23,6 +23,7 @@
 // Each workgroup also leaves the {min, max} of what it stored next to the result, one pair per (utterance, head, row block):
 // the output projection's dynamic quantisation needs no range pass (LeleBuf::rowstat kind 2, see quant.hip).
 #include "common.h"
+#include <algorithm>
 #include <type_traits>
 #include "lane_ops.h"
 #include "norm_core.h"
@@ -623,22 +624,37 @@ constexpr int FA_ROWS = 128;                                                    
 #define FA_STAMP(n_)
 #endif
 
+// SEG (lele_hip_attention_segments_long): the workgroup finds its {first row, rows, query block of 128 rows, head} in a.work as the
+// 16- / 32-row kernels do, and everything below -- the key loop, the masks, the clamped re-reads, the last rows -- runs on that
+// segment's own length: nothing in the loop knows how many keys there are but nkt and a.tk.  One form for every long segment, so a
+// segment's bits are its own rows' alone.  The order of the blocks, XCDs included, is the work list's (build_attn_long_work): no remap here.
+template <bool SEG>
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) void attention_flash_kernel(AttnArgs a) {
     extern __shared__ __attribute__((aligned(16))) char fa_lds[];
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int hv = lane >> 5, l31 = lane & 31;
-    // workgroup b runs on XCD b % 8 (each with its own L2): the nqb workgroups of a head are 8 apart in b, so the second one's K / V
-    // come out of the L2 the first one filled (heads in groups of 8; a ragged last group keeps the plain order)
-    int qb = blockIdx.x % a.nqb, bh = blockIdx.x / a.nqb;
-    {
-        const int per = 8 * a.nqb, grp = blockIdx.x / per, heads = (int)(gridDim.x / a.nqb);
-        if ((grp + 1) * 8 <= heads) {
-            const int in = blockIdx.x - grp * per;
-            bh = grp * 8 + (in & 7);
-            qb = in >> 3;
+    int qb, bi, bo;
+    if constexpr (SEG) {
+        const int4 wk = a.work[blockIdx.x];
+        bo = wk.x, a.tq = a.tk = wk.y, qb = wk.z, bi = wk.w;
+#ifdef LELE_HIP_LAB
+        a.dbg = nullptr;  // the stamps index 3 + 4 t into 64 slots a wave: more than 15 key tiles would leave them
+#endif
+    } else {
+        // workgroup b runs on XCD b % 8 (each with its own L2): the nqb workgroups of a head are 8 apart in b, so the second one's K / V
+        // come out of the L2 the first one filled (heads in groups of 8; a ragged last group keeps the plain order)
+        int bh = blockIdx.x / a.nqb;
+        qb = blockIdx.x % a.nqb;
+        {
+            const int per = 8 * a.nqb, grp = blockIdx.x / per, heads = (int)(gridDim.x / a.nqb);
+            if ((grp + 1) * 8 <= heads) {
+                const int in = blockIdx.x - grp * per;
+                bh = grp * 8 + (in & 7);
+                qb = in >> 3;
+            }
         }
+        bi = bh % a.batch_inner, bo = bh / a.batch_inner;
     }
-    const int bi = bh % a.batch_inner, bo = bh / a.batch_inner;
     const int nkt = (a.tk + 31) / 32;
     // (a raw s_barrier: the compiler's own would wait vmcnt(0), i.e. for every load in flight.  What it must wait for is this wave's LDS
     // traffic -- a parked chunk's ds_writes are only ISSUED when the instruction after them runs, and the barrier hands the stage over)
@@ -994,7 +1010,7 @@ int lele_hip_attention_view(LeleCtx* ctx, const LeleTensor* q, const LeleMatView
         else LELE_ATTN(NT_, 1);                                                                                \
     } while (0)
     if (flash) {
-        auto kern = attention_flash_kernel;
+        auto kern = attention_flash_kernel<false>;
         LELE_HIP_CHECK(ensure_dyn_lds(reinterpret_cast<const void*>(kern), FA_LDS));
         hipLaunchKernelGGL(kern, grid, dim3(512), FA_LDS, ctx->stream, a);
         ctx->set_route("attn.flash");
@@ -1059,46 +1075,84 @@ void build_attn_work(const void* arg, std::vector<char>& blob) {
     blob.resize(w.size() * 4);
     if (!w.empty()) memcpy(blob.data(), w.data(), blob.size());
 }
-}  // namespace
+// The work list of a layout's LONG segments (more than 512 rows) for attention_flash_kernel<true>: {first row, rows, query block of
+// FA_ROWS rows, head} per block.  The (segment, head) pairs, longest segment first (a block's cost is its segment's length: what
+// starts last should be short), are dealt round-robin to eight queues, one per XCD, and the list takes one block of every queue in
+// turn: workgroup b runs on XCD b % 8, so while all eight queues last the blocks of a pair share one L2 for their K and V, as the dense
+// kernel's remap arranges it (8 x 1004 rows: 91.6 us against 95.6 in the plain order; one utterance, and 32 of mixed lengths: +-0.5 %).
+void build_attn_long_work(const void* arg, std::vector<char>& blob) {
+    const SegWorkArg& a = *(const SegWorkArg*)arg;
+    std::vector<int64_t> seg;
+    for (int64_t i = 0; i < a.count; ++i)
+        if (a.off[i + 1] - a.off[i] > 512) seg.push_back(i);
+    std::stable_sort(seg.begin(), seg.end(), [&](int64_t x, int64_t y) { return a.off[x + 1] - a.off[x] > a.off[y + 1] - a.off[y]; });
+    std::vector<int> w, q[8];
+    int pair = 0;
+    for (int64_t i : seg) {
+        const int64_t len = a.off[i + 1] - a.off[i];
+        for (int h = 0; h < a.heads; ++h, ++pair)
+            for (int qb = 0; qb < (int)((len + FA_ROWS - 1) / FA_ROWS); ++qb) {
+                const int e[4] = {(int)a.off[i], (int)len, qb, h};
+                q[pair & 7].insert(q[pair & 7].end(), e, e + 4);
+            }
+    }
+    for (size_t r = 0, more = 1; more; r += 4) {
+        more = 0;
+        for (int x = 0; x < 8; ++x)
+            if (r < q[x].size()) w.insert(w.end(), q[x].begin() + r, q[x].begin() + r + 4), more = 1;
+    }
+    blob.resize(w.size() * 4);
+    if (!w.empty()) memcpy(blob.data(), w.data(), blob.size());
+}
 
-/* softmax(Q K^T scale) V of every segment of a packed qkv [R, P] over that segment's rows only, heads merged in the result: the
- * 16-row and 32-row kernels of lele_hip_attention_view behind a block locator, one launch per (key-tile class, block height) present
- * in the layout: at most 9 (8 classes, and the height rule splits at most one of them for a given number of heads). */
-int lele_hip_attention_segments(LeleCtx* ctx, const LeleTensor* qkv, int64_t q_offset, int64_t k_offset, int64_t v_offset, int64_t heads,
-                                int64_t dh, const int64_t* row_offsets, int64_t count, const LeleTensor* scale, LeleBuf* out,
-                                int64_t* out_shape, int32_t* out_rank) {
-    LELE_REQUIRE(ctx && qkv && out, "attention_segments: NULL argument");
+// both packed entry points.  `lng`: segments of more than 512 rows are taken (one more launch, of the one-pass kernel) instead of refused
+int attention_segments_impl(LeleCtx* ctx, const LeleTensor* qkv, int64_t q_offset, int64_t k_offset, int64_t v_offset, int64_t heads, int64_t dh,
+                            const int64_t* row_offsets, int64_t count, const LeleTensor* scale, LeleBuf* out, int64_t* out_shape,
+                            int32_t* out_rank, bool lng, const char* who) {
+    LELE_REQUIRE(ctx && qkv && out, "%s: NULL argument", who);
     int64_t rows = 0, p = 0, tmax = 0;
-    LELE_TRY(seg_offsets(qkv, row_offsets, count, &rows, &p, &tmax, "attention_segments"));
-    LELE_REQUIRE(!scale || (scale->dtype == LELE_F32 && numel(scale) == 1), "attention_segments: the scale must be one f32 value");
-    LELE_REQUIRE(heads >= 1 && heads < (1 << 20) && dh == kDh, "attention_segments: unsupported geometry (head dimension %lld, %lld heads)", (long long)dh,
+    LELE_TRY(seg_offsets(qkv, row_offsets, count, &rows, &p, &tmax, who));
+    LELE_REQUIRE(!scale || (scale->dtype == LELE_F32 && numel(scale) == 1), "%s: the scale must be one f32 value", who);
+    LELE_REQUIRE(heads >= 1 && heads < (1 << 20) && dh == kDh, "%s: unsupported geometry (head dimension %lld, %lld heads)", who, (long long)dh,
                  (long long)heads);
     const int64_t d = heads * dh;
     LELE_REQUIRE(q_offset >= 0 && k_offset >= 0 && v_offset >= 0 && q_offset + d <= p && k_offset + d <= p && v_offset + d <= p,
-                 "attention_segments: Q / K / V columns [%lld, %lld, %lld) + %lld leave the row (%lld)", (long long)q_offset, (long long)k_offset,
+                 "%s: Q / K / V columns [%lld, %lld, %lld) + %lld leave the row (%lld)", who, (long long)q_offset, (long long)k_offset,
                  (long long)v_offset, (long long)d, (long long)p);
-    LELE_REQUIRE(q_offset % 4 == 0 && k_offset % 4 == 0 && p % 4 == 0, "attention_segments: unsupported geometry (Q / K rows are not 16-byte aligned)");
+    LELE_REQUIRE(q_offset % 4 == 0 && k_offset % 4 == 0 && p % 4 == 0, "%s: unsupported geometry (Q / K rows are not 16-byte aligned)", who);
+    const char* ex_env = getenv("LELE_HIP_ATTENTION_EXACT");
+    const bool exact = ex_env && *ex_env && atoi(ex_env) != 0;
     const int half_cus = ctx->num_cus / 2;
-    int64_t blocks[9][2] = {};
+    int64_t blocks[9][2] = {}, long_blocks = 0;
     for (int64_t i = 0; i < count; ++i) {
         const int64_t len = row_offsets[i + 1] - row_offsets[i];
-        LELE_REQUIRE(len <= 512, "attention_segments: segment %lld has %lld rows, at most 512 are supported", (long long)i, (long long)len);
+        LELE_REQUIRE(lng || len <= 512, "%s: segment %lld has %lld rows, at most 512 are supported", who, (long long)i, (long long)len);
+        // the switch promises the bits of the three-call sequence, which needs a whole score row: no one-pass kernel can give them
+        LELE_REQUIRE(len <= 512 || !exact, "%s: segment %lld has %lld rows, LELE_HIP_ATTENTION_EXACT=1 supports at most 512", who, (long long)i,
+                     (long long)len);
         if (!len) continue;
-        if (seg_rows16(len, (int)heads, half_cus)) blocks[(len + 63) / 64][0] += heads * ((len + 15) / 16);
+        if (len > 512) long_blocks += heads * ((len + FA_ROWS - 1) / FA_ROWS);
+        else if (seg_rows16(len, (int)heads, half_cus)) blocks[(len + 63) / 64][0] += heads * ((len + 15) / 16);
         else blocks[(len + 63) / 64][1] += heads * ((len + 31) / 32);
     }
-    LELE_REQUIRE(rows < (int64_t(1) << 31) && heads * ((rows + 15) / 16 + count) < (int64_t(1) << 31), "attention_segments: too many blocks");
+    LELE_REQUIRE(rows < (int64_t(1) << 31) && heads * ((rows + 15) / 16 + count) < (int64_t(1) << 31), "%s: too many blocks", who);
     LELE_HIP_CHECK(hipSetDevice(ctx->device));
-    const void* work = nullptr;
-    if (rows > 0) {
-        const SegWorkArg arg{row_offsets, count, (int)heads, half_cus};
+    const void *work = nullptr, *long_work = nullptr;
+    const SegWorkArg arg{row_offsets, count, (int)heads, half_cus};
+    // (the short lists are lele_hip_attention_segments' own, under its key: build_attn_work passes over what is longer than 512 rows)
+    if (rows > 0) LELE_TRY(layout_table(ctx, "attn", heads, half_cus, row_offsets, count, build_attn_work, &arg, &work));
+    if (long_blocks) {
+        // a second table in one call: a miss may drop every table no capture has used, the one fetched a moment ago among them.  It
+        // does so only with 64 of them around and leaves none, so of two misses in a row the second drops nothing: ask for the short
+        // lists again (a hit, or a rebuild that cannot touch the long list)
+        LELE_TRY(layout_table(ctx, "attL", heads, 0, row_offsets, count, build_attn_long_work, &arg, &long_work));
         LELE_TRY(layout_table(ctx, "attn", heads, half_cus, row_offsets, count, build_attn_work, &arg, &work));
     }
     LELE_TRY(ctx->arena_reset());
     const void *dq = nullptr, *dsc = nullptr;
     if (rows > 0) LELE_TRY(ctx->dev_ptr(qkv, &dq));
     if (scale) LELE_TRY(ctx->dev_ptr(scale, &dsc));
-    LELE_REQUIRE(rows == 0 || aligned16(dq), "attention_segments: unsupported geometry (Q / K rows are not 16-byte aligned)");
+    LELE_REQUIRE(rows == 0 || aligned16(dq), "%s: unsupported geometry (Q / K rows are not 16-byte aligned)", who);
     LELE_TRY(out->reserve((size_t)rows * d * 4));
     ctx->set_route(nullptr);
     if (rows == 0) return set_shape(out_shape, out_rank, {rows, d});
@@ -1113,9 +1167,14 @@ int lele_hip_attention_segments(LeleCtx* ctx, const LeleTensor* qkv, int64_t q_o
     a.batch_inner = (int)heads;
     a.nqb = 1;
     a.scale = (const float*)dsc;
-    const char* ex_env = getenv("LELE_HIP_ATTENTION_EXACT");
-    const bool exact = ex_env && *ex_env && atoi(ex_env) != 0;
     ctx->set_route(exact ? "attn.seg_exact" : "attn.seg");  // one name: a layout may take several launches
+    if (long_blocks) {  // the one launch more than lele_hip_attention_segments issues (launches of one stream do not overlap: any place will do)
+        a.work = (const int4*)long_work;
+        a.tq = a.tk = a.tpad = 0;  // (every workgroup takes its own from the work list)
+        auto kern = attention_flash_kernel<true>;
+        LELE_HIP_CHECK(ensure_dyn_lds(reinterpret_cast<const void*>(kern), FA_LDS));
+        hipLaunchKernelGGL(kern, dim3((unsigned)long_blocks), dim3(512), FA_LDS, ctx->stream, a);
+    }
     const int4* wp = (const int4*)work;
     for (int c = 1; c <= 8; ++c)
         for (int tall = 0; tall < 2; ++tall) {
@@ -1153,6 +1212,26 @@ int lele_hip_attention_segments(LeleCtx* ctx, const LeleTensor* qkv, int64_t q_o
         }
     LELE_HIP_CHECK(hipGetLastError());
     return set_shape(out_shape, out_rank, {rows, d});
+}
+}  // namespace
+
+/* softmax(Q K^T scale) V of every segment of a packed qkv [R, P] over that segment's rows only, heads merged in the result: the
+ * 16-row and 32-row kernels of lele_hip_attention_view behind a block locator, one launch per (key-tile class, block height) present
+ * in the layout: at most 9 (8 classes, and the height rule splits at most one of them for a given number of heads). */
+int lele_hip_attention_segments(LeleCtx* ctx, const LeleTensor* qkv, int64_t q_offset, int64_t k_offset, int64_t v_offset, int64_t heads,
+                                int64_t dh, const int64_t* row_offsets, int64_t count, const LeleTensor* scale, LeleBuf* out,
+                                int64_t* out_shape, int32_t* out_rank) {
+    return attention_segments_impl(ctx, qkv, q_offset, k_offset, v_offset, heads, dh, row_offsets, count, scale, out, out_shape, out_rank, false,
+                                   "attention_segments");
+}
+
+/* The same with no length wall: segments of at most 512 rows run exactly as above (the same lists, kernels and launches), longer ones
+ * on attention_flash_kernel<true> in one more launch, each from its own length. */
+int lele_hip_attention_segments_long(LeleCtx* ctx, const LeleTensor* qkv, int64_t q_offset, int64_t k_offset, int64_t v_offset, int64_t heads,
+                                     int64_t dh, const int64_t* row_offsets, int64_t count, const LeleTensor* scale, LeleBuf* out,
+                                     int64_t* out_shape, int32_t* out_rank) {
+    return attention_segments_impl(ctx, qkv, q_offset, k_offset, v_offset, heads, dh, row_offsets, count, scale, out, out_shape, out_rank, true,
+                                   "attention_segments_long");
 }
 
 }  // extern "C"

@@ -1190,6 +1190,16 @@ inline TensorView attention_segments(const TensorView& qkv, const std::vector<in
                                       out.raw(), sh.dims, &sh.rank));
     LELE_RET(out, LELE_F32);
 }
+// attention_segments without its 512-row limit: longer segments run the one-pass kernel, shorter ones exactly as above
+inline TensorView attention_segments_long(const TensorView& qkv, const std::vector<int64_t>& offsets, int64_t q_offset, int64_t k_offset,
+                                          int64_t v_offset, int64_t heads, int64_t dh, const TensorView* scale, Buffer& out) {
+    Shape sh;
+    LeleTensor t = qkv.c();
+    Opt os(scale);
+    check(lele_hip_attention_segments_long(ctx(), &t, q_offset, k_offset, v_offset, heads, dh, offsets.data(), (int64_t)offsets.size() - 1,
+                                           os.p, out.raw(), sh.dims, &sh.rank));
+    LELE_RET(out, LELE_F32);
+}
 inline TensorView depthwise_conv1d_tlc_segments(const TensorView& x, const std::vector<int64_t>& offsets, const TensorView& w,
                                                 const TensorView* bias, int64_t pad_left, int64_t pad_right, bool relu, int64_t x_offset,
                                                 bool add_input, Buffer& out) {

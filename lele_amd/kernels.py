@@ -1455,7 +1455,18 @@ def ctc_beam_search_segments(ids, logprob, offsets, blank=0, beam=4, nbest=1, sk
 def attention_segments(qkv, offsets, heads, dh, scale=None, q_offset=0, k_offset=None, v_offset=None, out=None, ctx=None):
     """softmax(Q K^T * scale) V per segment and head over that segment's rows only: qkv [R, P] holds Q | K | V at the column offsets
     (default: the packed projection, 0, heads * dh, 2 * heads * dh) -> [R, heads * dh], heads merged.  dh == 128, segments of at most
-    512 rows; anything else raises (there is no fallback)."""
+    512 rows; anything else raises (there is no fallback).  attention_segments_long takes longer segments too."""
+    return _attention_segments(_lib.lib().lele_hip_attention_segments, qkv, offsets, heads, dh, scale, q_offset, k_offset, v_offset, out, ctx)
+
+
+def attention_segments_long(qkv, offsets, heads, dh, scale=None, q_offset=0, k_offset=None, v_offset=None, out=None, ctx=None):
+    """attention_segments with no limit on a segment's rows (utterances over 30 s): a segment of at most 512 rows gets that call's result
+    bit for bit, longer ones run the one-pass kernel in one more launch, each a function of its own rows alone.  Under
+    LELE_HIP_ATTENTION_EXACT=1 a segment of more than 512 rows raises."""
+    return _attention_segments(_lib.lib().lele_hip_attention_segments_long, qkv, offsets, heads, dh, scale, q_offset, k_offset, v_offset, out, ctx)
+
+
+def _attention_segments(fn, qkv, offsets, heads, dh, scale, q_offset, k_offset, v_offset, out, ctx):
     ctx = _ctx(ctx)
     keep = []
     out = out or ctx.buf()
@@ -1464,7 +1475,7 @@ def attention_segments(qkv, offsets, heads, dh, scale=None, q_offset=0, k_offset
     d = int(heads) * int(dh)
     k_offset = q_offset + d if k_offset is None else k_offset
     v_offset = k_offset + d if v_offset is None else v_offset
-    _lib.check(_lib.lib().lele_hip_attention_segments(
+    _lib.check(fn(
         ctx._h, _t(qkv, keep), C.c_int64(int(q_offset)), C.c_int64(int(k_offset)), C.c_int64(int(v_offset)), C.c_int64(int(heads)),
         C.c_int64(int(dh)), _lib.i64_ptr(off), C.c_int64(len(off) - 1), _t(scale, keep), out._h, sh.shape, C.byref(sh.rank)))
     return TensorView(_lib.DevTensor(out, sh.get(), np.float32))

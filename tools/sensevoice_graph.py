@@ -206,7 +206,7 @@ class Encoder:
 
     def layer_segments(self, x, off, i, taps=None):
         """Encoder.layer on a packed batch [R, d_in]: the same node list with one C-ABI call per node; the split / transposes /
-        matmul / softmax / matmul are attention_segments and the transpose / conv / transpose / add is depthwise_conv1d_tlc_segments
+        matmul / softmax / matmul are attention_segments_long and the transpose / conv / transpose / add is depthwise_conv1d_tlc_segments
         (the substitutions the compiler makes for dense plans).  taps: as Encoder.layer, every node's input and output"""
         K, ctx, ws, L = self.K, self.ctx, self.ws, self.layers[i]
         xin = x
@@ -214,7 +214,7 @@ class Encoder:
         qkv = self.qls(xn, off, L.qkv, False, 2)                                # [R,1536]
         mem = K.depthwise_conv1d_tlc_segments(qkv, off, L.fsmn, None, FSMN_K // 2, FSMN_K // 2, x_offset=2 * D, add_input=True,
                                               out=ws[7], ctx=ctx)              # FSMN memory + v
-        av = K.attention_segments(qkv, off, HEADS, DH, self.scale, out=ws[5], ctx=ctx)        # [R,512], heads merged
+        av = K.attention_segments_long(qkv, off, HEADS, DH, self.scale, out=ws[5], ctx=ctx)   # [R,512], heads merged; no length limit
         att = self.qls(av, off, L.out, False, 8)
         if taps is not None:
             taps.update(x=xin.numpy(), xn=xn.numpy(), qkv=qkv.numpy(), mem=mem.numpy(), av=av.numpy(), att=att.numpy())
