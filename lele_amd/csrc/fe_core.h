@@ -224,6 +224,123 @@ FE_HD void phase_a_fast(const float* x, cf* a, const TW& tw_re, const TW& tw_im)
     }
 }
 
+// ---- phase A on real and conjugate values ----------------------------------------------------------
+// The same network again, with two more kinds of work taken out.  Every register is in one of three classes:
+//   real    -- the imaginary part is structurally zero (up to its sign): kept as ONE scalar, combined by real adds;
+//   normal  -- the pair holds (re, im);
+//   primed  -- the pair holds (re, -im), the conjugate of the value.
+// Conjugation commutes with every rounding: a butterfly on two primed operands with the conjugate twiddle (wr, -wi) gives the
+// conjugates of the normal butterfly's outputs bit for bit -- fma(wr, -oi, (-wi) * or) == -fma(wr, oi, wi * or), and so on down to
+// e' +- t'.  The network ends in re * re + im * im, which does not see the sign of im, so nothing is ever flipped back: phase B reads
+// conjugated twiddles in the lanes that hold primed values (tw_conj_image below) and the power is the same bits.
+// Where classes come from: a butterfly of stage s at k = 0 has w = (1, -0) and, in phase A, two REAL inputs, so it is a real add and
+// subtract (the "alike zeros" argument above covers the sign of the zero it no longer computes); at k = half / 2 it has two real inputs
+// e, o and gives (e + wr * o, wi * o) and (e - wr * o, -(wi * o)): with nti = (-wi) * o == -(wi * o) the first is stored primed as
+// (e + tr, nti), the second normal as (e - tr, nti) -- one product, no sign flip.  Every other butterfly keeps the class of its inputs.
+// CLASS INVARIANT: both operands of every complex butterfly share a class (a primed register is never paired with a normal one), and
+// the class a register has once it is complex is the class it ends with: primed(r).  Both are asserted below over every (s, b, k).
+// Registers 0 and 16 end real (bins 0 and 256 come from them).
+FE_HD constexpr bool primed(int r) { return r == 8 || ((0x2636 >> (r & 15)) & 1) != 0; }  // r % 16 in {1, 2, 4, 5, 9, 10, 13}, or r == 8
+enum : int { kClsReal = 0, kClsNormal = 1, kClsPrimed = 2 };
+// class of register r after stage s (1..5) of phase_a_conj, from the rules above alone
+FE_HD constexpr int conj_class(int s, int r) {
+    if (s <= 1) return kClsReal;
+    const int half = 1 << (s - 1), k = r & (half - 1);
+    if (k == 0) return kClsReal;
+    if (k == half / 2 && conj_class(s - 1, r) == kClsReal) return (r & half) ? kClsNormal : kClsPrimed;
+    return conj_class(s - 1, r);
+}
+FE_HD constexpr bool conj_classes_hold() {
+    for (int s = 2; s <= 5; ++s) {
+        const int half = 1 << (s - 1);
+        for (int b = 0; b < kRegs; b += 2 * half)
+            for (int k = 0; k < half; ++k) {
+                const int ce = conj_class(s - 1, b + k), co = conj_class(s - 1, b + half + k);
+                if (ce != co) return false;                                         // the operands of a butterfly share a class
+                if ((k == 0 || k == half / 2) != (ce == kClsReal)) return false;   // real inputs exactly at k = 0 and k = half / 2
+                if (ce != kClsReal && (ce == kClsPrimed) != primed(b + k)) return false;           // a complex register's class is final
+                if (ce != kClsReal && (co == kClsPrimed) != primed(b + half + k)) return false;
+            }
+    }
+    for (int r = 0; r < kRegs; ++r) {
+        if ((conj_class(5, r) == kClsReal) != (r == 0 || r == 16)) return false;
+        if ((conj_class(5, r) == kClsPrimed) != primed(r)) return false;
+    }
+    return true;
+}
+static_assert(conj_classes_hold(), "phase_a_conj never pairs a primed register with a normal one, and ends in primed(r)");
+
+// REQUIRES what phase_a_fast requires of the table -- tw_re[i]==1, tw_im[i]==+-0 for i = 0, 1, tw_off(4), tw_off(5) -- and the same of entry
+// tw_off(3): stage 3 at k = 0 is a bare add and subtract here, where phase_a_fast still multiplies by the entry.  (The nti fold at
+// k = half / 2 holds for any table.)  precompute_twiddles gives (1, -0) at every one of them; a host caller with another table checks.  Input: x[r] real.  Output: a[r] = (re, primed(r) ? -im : im); a[0], a[16] = (re, 0).
+template <typename TW>
+FE_HD void phase_a_conj(const float* x, cf* a, const TW& tw_re, const TW& tw_im) {
+    float s1[kRegs];
+    // stage 1, as in phase_a_fast
+#pragma unroll
+    for (int r = 0; r < kRegs; r += 2) {
+        if (rev5(r + 1) >= kQ) {
+            s1[r] = x[r];
+            s1[r + 1] = x[r];
+        } else {
+            s1[r] = fadd(x[r], x[r + 1]);
+            s1[r + 1] = fsub(x[r], x[r + 1]);
+        }
+    }
+    float re[kRegs];  // the registers that are real at this point of the network (the others' entries are unused)
+    // stage 2: k = 0 real; k = 1 = half / 2 on a real odd input
+    {
+        const float wr = tw_re[tw_off(2) + 1], nwi = -tw_im[tw_off(2) + 1];
+#pragma unroll
+        for (int b = 0; b < kRegs; b += 4) {
+            re[b] = fadd(s1[b], s1[b + 2]);
+            re[b + 2] = fsub(s1[b], s1[b + 2]);
+            const float tr = fmul(wr, s1[b + 3]);
+            const float nti = fmul(nwi, s1[b + 3]);
+            a[b + 1] = cmk(fadd(s1[b + 1], tr), nti);  // primed
+            a[b + 3] = cmk(fsub(s1[b + 1], tr), nti);  // normal
+        }
+    }
+#pragma unroll
+    for (int s = 3; s <= 5; ++s) {
+        const int half = 1 << (s - 1);
+#pragma unroll
+        for (int b = 0; b < kRegs; b += 2 * half) {
+#pragma unroll
+            for (int k = 0; k < half; ++k) {
+                const int i = b + k, j = b + half + k;
+                if (k == 0) {  // w = (1, -0) on two real values
+                    const float e = re[i], o = re[j];
+                    re[i] = fadd(e, o);
+                    re[j] = fsub(e, o);
+                } else if (k == half / 2) {  // two real values
+                    const float wr = tw_re[tw_off(s) + k], nwi = -tw_im[tw_off(s) + k];
+                    const float e = re[i], o = re[j];
+                    const float tr = fmul(wr, o);    // fma(wr, or, -(wi * 0))
+                    const float nti = fmul(nwi, o);  // -fma(wr, 0, wi * or)
+                    a[i] = cmk(fadd(e, tr), nti);  // primed
+                    a[j] = cmk(fsub(e, tr), nti);  // normal
+                } else {
+                    const float wr = tw_re[tw_off(s) + k], wi = tw_im[tw_off(s) + k];
+                    bfly_fma(make_tw(wr, primed(i) ? -wi : wi), a[i], a[j]);
+                }
+            }
+        }
+    }
+    a[0] = cmk(re[0], 0.0f);
+    a[16] = cmk(re[16], 0.0f);
+}
+
+// The interleaved (re, im) twiddle table that phase B reads behind phase_a_conj: after the exchange lane c of round rho holds only
+// values of class primed(16 * rho + c), and its twiddle index is tw_off(s) + 32 * k + 16 * rho + c with tw_off(s) + 1 a multiple of 32
+// (s >= 6), so entry i >= 31 is conjugated exactly where primed((i + 1) & 31).  Entries below 31 (phase A's) are copied.
+inline void tw_conj_image(const float* tw_re, const float* tw_im, int n, float* out /* 2 n */) {
+    for (int i = 0; i < n; ++i) {
+        out[2 * i] = tw_re[i];
+        out[2 * i + 1] = (i >= tw_off(6) && primed((i + 1) & 31)) ? -tw_im[i] : tw_im[i];
+    }
+}
+
 // ---- the entries phase_a_fast reads, as compile-time constants -------------------------------------
 // Stages 2..5 use wave-uniform entries tw_off(2)+1, tw_off(3)+0..3, tw_off(4)+1..7 and tw_off(5)+1..15: 27 of the first 31
 // table entries, the same in every pass of every launch.  Below are the f32 bit patterns of entries 0..30 as

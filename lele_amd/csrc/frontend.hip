@@ -43,6 +43,7 @@ struct FeDev {                 // device tables (all owned by LeleFrontend)
     int n_mels;
     int lfr_m, lfr_n;
     int tile_dma;              // aligned runs of the fused kernels are staged by direct-to-LDS loads (LELE_HIP_FE_TILE_DMA, default 1)
+    const float2* tw_conj;     // tw with the entries of primed lanes conjugated (fe::tw_conj_image): what phase B reads behind phase_a_conj
 };
 
 // Which 64-frame block of which utterance a workgroup takes.  compute / compute_batch: block x of utterance y of the grid (equal-length
@@ -205,7 +206,10 @@ constexpr int kStdMelOff[6] = {0, 3, 7, 13, 23, 40};
 // pass's sample pointer is carried instead of rebuilt from the frame index.  The
 // phase-B twiddle reads stay paired: read singly, their (-wi, wi) operand is no longer an operand modifier of the packed multiply
 // but two more instructions a twiddle, which costs more than the LDS cycles give (docs/experiments.md).
-constexpr int kFeConstTw = 1, kFeLdsMel = 2, kFeLeanLds = 4;
+// bit 3 (kFeConjA, with the other three only) -- phase A keeps structurally real values as scalars and half of the complex ones as
+// conjugates (fe::phase_a_conj: no sign flips, real butterflies where both inputs are real), and s_tw is filled from the table image
+// whose entries are conjugated for the lanes that then hold conjugates (tb.tw_conj); phase B's code and the power are unchanged.
+constexpr int kFeConstTw = 1, kFeLdsMel = 2, kFeLeanLds = 4, kFeConjA = 8;
 // One eight-byte LDS access that stays one ds_read_b64 / ds_write_b64: a volatile access is not merged with its neighbour.  The
 // compiler still counts it (lgkmcnt) and still folds the constant part of the address into the instruction's offset.
 typedef float fe_f2 __attribute__((ext_vector_type(2)));
@@ -237,7 +241,9 @@ __device__ __forceinline__ void fe_main_body(const float* __restrict__ pcm, int6
     constexpr bool kConstTw = (OPT & kFeConstTw) != 0;
     constexpr bool kLdsMel = (OPT & kFeLdsMel) != 0;
     constexpr bool kLean = (OPT & kFeLeanLds) != 0;
+    constexpr bool kConj = (OPT & kFeConjA) != 0;
     static_assert(!kLean || (kConstTw && kLdsMel), "the lean pass is a form of the constant-table kernel");
+    static_assert(!kConj || kLean, "the conjugate phase A is a form of the lean pass");
     static_assert(OPT == 0 || (STDMEL && FUSED && !LOWREG), "the constant / LDS table forms belong to the default bank's fused kernel");
     __shared__ __attribute__((aligned(16))) float s_melt[kLdsMel ? kMelLdsFloats : 4];
     // three workgroups a CU: 160 KiB / 3 = 54 613 bytes each (the table-driven mel loop's dynamic s_melw comes on top where OPT == 0)
@@ -289,7 +295,7 @@ __device__ __forceinline__ void fe_main_body(const float* __restrict__ pcm, int6
             auto* tw_lds = (__attribute__((address_space(3))) char*)s_tw;
 #pragma unroll
             for (int k = 0; k < 4; ++k)
-                fe_dma16(reinterpret_cast<const char*>(tb.tw) + 1024 * k + 16 * lane, tw_lds + 1024 * k);
+                fe_dma16(reinterpret_cast<const char*>(kConj ? tb.tw_conj : tb.tw) + 1024 * k + 16 * lane, tw_lds + 1024 * k);
         }
         if (kLdsMel && wave == 2) {  // s_melt: three 1 KiB loads of the host-built image, beside the twiddle table's
             auto* mel_lds = (__attribute__((address_space(3))) char*)s_melt;
@@ -475,7 +481,9 @@ __device__ __forceinline__ void fe_main_body(const float* __restrict__ pcm, int6
 
         // 5. FFT stages 1..5 (wave-uniform twiddles straight from the table)
         fe::cf a[fe::kRegs];
-        if constexpr (kConstTw)
+        if constexpr (kConj)
+            fe::phase_a_conj(xin, a, fe::TwConst{false}, fe::TwConst{true});
+        else if constexpr (kConstTw)
             fe::phase_a_fast(xin, a, fe::TwConst{false}, fe::TwConst{true});
         else
             fe::phase_a_fast(xin, a, fe_const_table(tb.tw_re, pass), fe_const_table(tb.tw_im, pass));
@@ -1003,6 +1011,7 @@ struct LeleFrontend {
     bool fused = true;  // frame sums computed inside fe_main_kernel (LELE_HIP_FE_FUSED=0 selects the two-kernel form)
     int opt = 0;        // kFeConstTw | kFeLdsMel: the form of the default bank's fused kernels (0: every table read as before)
     bool lean = false;  // kFeLeanLds on top of opt == kFeConstTw | kFeLdsMel (LELE_HIP_FE_LEAN_LDS=0 keeps the pass without it)
+    bool conj = false;  // kFeConjA on top of the lean pass (LELE_HIP_FE_CONJ_A=0 keeps the pass without it)
     // generic path tables (configs other than 400/160/512)
     const float* g_window = nullptr;
     const int* g_mstart = nullptr;
@@ -1217,6 +1226,11 @@ int lele_hip_frontend_create(LeleCtx* ctx, const LeleFeatureConfig* cfg, LeleFro
     rc |= upload(fe, twr, &d.tw_re);
     rc |= upload(fe, twi, &d.tw_im);
     rc |= upload(fe, tw, &d.tw);
+    {   // the same table with the entries of primed lanes conjugated (fe_core.h), padded to 512 like tw
+        std::vector<float2> twc(512, make_float2(0.f, 0.f));
+        fe::tw_conj_image(twr.data(), twi.data(), 511, reinterpret_cast<float*>(twc.data()));
+        rc |= upload(fe, twc, &d.tw_conj);
+    }
     rc |= upload(fe, win, &d.window);
     rc |= upload(fe, melw, &d.melw);
     {   // the default bank's weights as the kernel's LDS image: weight s = step_off[rd] + t of lane pm at [s / 4][pm][s % 4]
@@ -1258,6 +1272,10 @@ int lele_hip_frontend_create(LeleCtx* ctx, const LeleFeatureConfig* cfg, LeleFro
     // sample address rebuilt every pass
     const char* envn = getenv("LELE_HIP_FE_LEAN_LDS");
     fe->lean = fe->opt == (kFeConstTw | kFeLdsMel) && !(envn && *envn && atoi(envn) == 0);
+    // product switch, same bits either way: LELE_HIP_FE_CONJ_A=0 keeps phase A with its sign flips and packed butterflies on real values
+    // (fe::phase_a_fast).  The conjugate form reads the same compiled-in constants, so it is selected where they are (const_tw above).
+    const char* enva = getenv("LELE_HIP_FE_CONJ_A");
+    fe->conj = fe->lean && !(enva && *enva && atoi(enva) == 0);
     *out = fe;
     return 0;
 }
@@ -1267,6 +1285,8 @@ int lele_hip_frontend_create(LeleCtx* ctx, const LeleFeatureConfig* cfg, LeleFro
 int lele_hip_frontend_kernel_form(const LeleFrontend* fe) { return fe ? fe->opt : -1; }
 /* test hook: 1 where the default bank's fused kernels run the lean pass (kFeLeanLds), 0 where LELE_HIP_FE_LEAN_LDS=0 or another form keeps it out */
 int lele_hip_frontend_lean_lds(const LeleFrontend* fe) { return fe ? (int)fe->lean : -1; }
+/* test hook: 1 where the default bank's fused kernels run phase A on real and conjugate values (kFeConjA), 0 where LELE_HIP_FE_CONJ_A=0 or another form keeps it out */
+int lele_hip_frontend_conj_a(const LeleFrontend* fe) { return fe ? (int)fe->conj : -1; }
 
 int lele_hip_frontend_destroy(LeleFrontend* fe) {
     if (!fe) return 0;
@@ -1448,7 +1468,9 @@ static int fe_run(LeleFrontend* fe, const LeleTensor* pcm, int64_t batch, int64_
         const float* cmean = (const float*)dmean + c0 * nf;
         float* o = want_logmel ? nullptr : (float*)out->data + c0 * t_lfr * cols;
         float* lm = want_logmel ? (float*)out->data + c0 * nf * fe->cfg.n_mels : nullptr;
-        if (fe->lean) {  // (opt != 0: the default bank, fused, DPP -- frontend_create)
+        if (fe->conj) {  // (opt != 0: the default bank, fused, DPP -- frontend_create)
+            FE_LAUNCH(1, true, true, kFeConstTw | kFeLdsMel | kFeLeanLds | kFeConjA);
+        } else if (fe->lean) {
             FE_LAUNCH(1, true, true, kFeConstTw | kFeLdsMel | kFeLeanLds);
         } else if (fe->opt == (kFeConstTw | kFeLdsMel)) {
             FE_LAUNCH(1, true, true, kFeConstTw | kFeLdsMel);
@@ -1603,7 +1625,9 @@ int lele_hip_frontend_compute_segments(LeleFrontend* fe, const LeleTensor* pcm, 
 #define FE_SEG_LAUNCH(MODE, STD, ...)                                                                                            \
     hipLaunchKernelGGL((fe_seg_main_kernel<MODE, STD, ##__VA_ARGS__>), dim3((unsigned)blocks), dim3(256), mel_lds, ctx->stream, (const float*)dpcm, \
                        dsegs, dblk, fe->dev, o)
-    if (fe->lean) {
+    if (fe->conj) {
+        FE_SEG_LAUNCH(1, true, kFeConstTw | kFeLdsMel | kFeLeanLds | kFeConjA);
+    } else if (fe->lean) {
         FE_SEG_LAUNCH(1, true, kFeConstTw | kFeLdsMel | kFeLeanLds);
     } else if (fe->opt == (kFeConstTw | kFeLdsMel)) {
         FE_SEG_LAUNCH(1, true, kFeConstTw | kFeLdsMel);
@@ -1858,7 +1882,9 @@ int lele_hip_frontend_stream_push(LeleFrontendStream* st, const LeleTensor* pcm,
 #define FE_STREAM_LAUNCH(MODE, STD, ...)                                                                                           \
     hipLaunchKernelGGL((fe_stream_main_kernel<MODE, STD, ##__VA_ARGS__>), dim3((unsigned)blk.size()), dim3(256), mel_lds, ctx->stream,              \
                        (const float*)st->pcm_state, st->pcm_pitch, drecs, dblk, fe->dev, st->mel_state, st->mel_pitch)
-        if (fe->lean) {
+        if (fe->conj) {
+            FE_STREAM_LAUNCH(1, true, kFeConstTw | kFeLdsMel | kFeLeanLds | kFeConjA);
+        } else if (fe->lean) {
             FE_STREAM_LAUNCH(1, true, kFeConstTw | kFeLdsMel | kFeLeanLds);
         } else if (fe->opt == (kFeConstTw | kFeLdsMel)) {
             FE_STREAM_LAUNCH(1, true, kFeConstTw | kFeLdsMel);
