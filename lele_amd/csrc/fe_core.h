@@ -426,4 +426,26 @@ constexpr int kMelLdsWeights = 40;
 constexpr int kMelLdsChunks = kMelLdsWeights / 4;
 FE_HD constexpr int mel_lds_index(int s, int p) { return ((s >> 2) * kLanes + p) * 4 + (s & 3); }
 
+// ---- which fused kernel a front-end runs (host) ------------------------------------------------------
+// The template tuple <MODE, STDMEL, FUSED, OPT> of fe_main_kernel / fe_seg_main_kernel / fe_stream_main_kernel (frontend.hip describes
+// the parameters).  opt is a chain: each bit is a form of the kernel with every lower bit set.
+constexpr int kFeConstTw = 1, kFeLdsMel = 2, kFeLeanLds = 4, kFeConjA = 8;
+struct FeForm {
+    int mode;      // 1: the lane rotation is a DPP row_ror, 0: __shfl
+    bool std_mel;  // the mel bank has the default round structure
+    bool fused;    // the frame sums are computed inside the kernel
+    int opt;       // kFe* bits; non-zero only with mode == 1, std_mel and fused
+};
+// The one statement of the selection rule.  std_mel: the bank has the default round structure; const_match: the twiddle table holds the
+// compiled-in constants (tw_const_matches); const_tw, lds_tables, lean, conj: the product switches LELE_HIP_FE_CONST_TW / _LDS_TABLES /
+// _LEAN_LDS / _CONJ_A; dpp, fused: the lab values LELE_HIP_FE_DPP / _FUSED (1 and true outside the lab build).
+inline FeForm select_form(bool std_mel, bool const_match, bool const_tw, bool lds_tables, bool lean, bool conj, int dpp, bool fused) {
+    FeForm f{dpp == 1 ? 1 : 0, std_mel, fused, 0};
+    if (const_match && const_tw && std_mel && fused && dpp == 1) {
+        f.opt = kFeConstTw | (lds_tables ? kFeLdsMel : 0);
+        if (f.opt == (kFeConstTw | kFeLdsMel) && lean) f.opt |= kFeLeanLds | (conj ? kFeConjA : 0);
+    }
+    return f;
+}
+
 }  // namespace fe

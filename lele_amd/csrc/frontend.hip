@@ -192,11 +192,8 @@ constexpr int kStdMelOff[6] = {0, 3, 7, 13, 23, 40};
 // FUSED: the block first stages its run of PCM (64 frames = 10 480 samples, read from HBM once) into an LDS tile that
 // aliases the exchange region, wave 0 computes the 64 exact sequential frame sums from it (as fe_frame_sum_kernel
 // does), and the per-pass sample loads below then hit L2 -- no separate sum kernel, no second HBM read of the PCM.
-// PASSES: frames per workgroup = 16 * PASSES (a wave takes 4 frames a pass).  LOWREG: the 25 window coefficients of a lane are
-// re-read from the (L1-resident) table every pass instead of living in registers.  Four waves per SIMD (<= 128 registers, PASSES = 3 so
-// that four workgroups' LDS fits a CU) were measured twice in round 4: <3, true> with 48 spilled registers 7.41 ms per 2048 x 30 s, and
-// -- after the pass body lost its copies -- <3, false> at 128 registers without a spill in the loop 3.59 ms against 3.47 ms for
-// <4, false> at three waves (148 registers) in the same call: the product instantiates <4, false> only; docs/experiments.md.
+// One form: four passes a workgroup (64 frames, a wave takes 4 frames a pass) at three waves per SIMD; four waves with three passes were
+// measured twice and lost (docs/experiments.md).
 // OPT (the default bank's fused kernels only; 0 elsewhere): bit 0 (kFeConstTw) -- phase A's 27 wave-uniform twiddles are literals
 // (fe::TwConst) instead of scalar loads from the table; bit 1 (kFeLdsMel) -- the 640 mel weights are read from an LDS copy, ten
 // ds_read_b128 a pass, instead of 40 global loads a pass.  OPT = 0 is the table-reading form; the host selects (frontend_create).
@@ -209,7 +206,8 @@ constexpr int kStdMelOff[6] = {0, 3, 7, 13, 23, 40};
 // bit 3 (kFeConjA, with the other three only) -- phase A keeps structurally real values as scalars and half of the complex ones as
 // conjugates (fe::phase_a_conj: no sign flips, real butterflies where both inputs are real), and s_tw is filled from the table image
 // whose entries are conjugated for the lanes that then hold conjugates (tb.tw_conj); phase B's code and the power are unchanged.
-constexpr int kFeConstTw = 1, kFeLdsMel = 2, kFeLeanLds = 4, kFeConjA = 8;
+using fe::FeForm;
+using fe::kFeConstTw, fe::kFeLdsMel, fe::kFeLeanLds, fe::kFeConjA;
 // One eight-byte LDS access that stays one ds_read_b64 / ds_write_b64: a volatile access is not merged with its neighbour.  The
 // compiler still counts it (lgkmcnt) and still folds the constant part of the address into the instruction's offset.
 typedef float fe_f2 __attribute__((ext_vector_type(2)));
@@ -222,29 +220,29 @@ __device__ __forceinline__ void fe_lds_write8(float* p, fe::cf v) { *(fe_lds_f2v
 constexpr int kMelLdsFloats = 768;  // 640 weights at fe::mel_lds_index (fe_core.h), padded to three 1 KiB loads
 static_assert(fe::mel_lds_index(fe::kMelLdsWeights - 1, 15) < kMelLdsFloats && kStdMelOff[5] == fe::kMelLdsWeights, "the image holds the default bank");
 
-template <int MODE, bool STDMEL, bool FUSED, int PASSES, bool LOWREG, int OPT, class Blk>
+template <int MODE, bool STDMEL, bool FUSED, int OPT, class Blk>
 __device__ __forceinline__ void fe_main_body(const float* __restrict__ pcm, int64_t utt_stride,
                                              int64_t num_frames, int64_t t_lfr,
                                              const float* __restrict__ means, const FeDev& tb,
                                              float* __restrict__ out, float* __restrict__ logmel_out,
                                              int aligned16, float* s_melw, Blk bl) {
+    constexpr int PASSES = 4;
     constexpr int FR = 16 * PASSES;           // frames per workgroup
     constexpr int kRows = FR + 2;             // hop rows of the run (400 = 2.5 hops)
     constexpr int kXFloats = FUSED ? (kRows * kSumPitch > 4 * kWaveLdsFloats ? kRows * kSumPitch : 4 * kWaveLdsFloats)
                                    : 4 * kWaveLdsFloats;
-    __shared__ float2 s_tw[LOWREG ? 480 : 512];   // LOWREG: only the entries phase B reads (stages 6..9: 31 .. 510)
+    __shared__ float2 s_tw[512];
     __shared__ __attribute__((aligned(16))) float s_x[kXFloats];
     __shared__ float s_mean[64];
     __shared__ int s_mstart[16 * (STDMEL ? 5 : kMaxMelRounds)];
     __shared__ int s_moff[kMaxMelRounds + 1];
-    constexpr int kTwBase = LOWREG ? 31 : 0;
     constexpr bool kConstTw = (OPT & kFeConstTw) != 0;
     constexpr bool kLdsMel = (OPT & kFeLdsMel) != 0;
     constexpr bool kLean = (OPT & kFeLeanLds) != 0;
     constexpr bool kConj = (OPT & kFeConjA) != 0;
     static_assert(!kLean || (kConstTw && kLdsMel), "the lean pass is a form of the constant-table kernel");
     static_assert(!kConj || kLean, "the conjugate phase A is a form of the lean pass");
-    static_assert(OPT == 0 || (STDMEL && FUSED && !LOWREG), "the constant / LDS table forms belong to the default bank's fused kernel");
+    static_assert(OPT == 0 || (MODE == 1 && STDMEL && FUSED), "the constant / LDS table forms belong to the default bank's fused kernel");
     __shared__ __attribute__((aligned(16))) float s_melt[kLdsMel ? kMelLdsFloats : 4];
     // three workgroups a CU: 160 KiB / 3 = 54 613 bytes each (the table-driven mel loop's dynamic s_melw comes on top where OPT == 0)
     static_assert(sizeof(s_tw) + sizeof(s_x) + sizeof(s_mean) + sizeof(s_mstart) + sizeof(s_moff) + sizeof(s_melt) <= 54613, "LDS of three workgroups fits a CU");
@@ -254,7 +252,7 @@ __device__ __forceinline__ void fe_main_body(const float* __restrict__ pcm, int6
     constexpr int kVecPerRow = fe::kHop / 4;
     constexpr int kVecs = kRows * kVecPerRow;
     constexpr int kIters = (kVecs + 255) / 256;
-    constexpr bool kTwDma = FUSED && !LOWREG;  // the whole 4 KiB twiddle table by four direct-to-LDS loads
+    constexpr bool kTwDma = FUSED;  // the whole 4 KiB twiddle table by four direct-to-LDS loads
     // FUSED: the block's run [64*blockIdx.x*hop, +66 hops) goes into the LDS tile as [hop row][offset] -- the layout and bank argument of
     // fe_frame_sum_kernel -- as RAW samples (the x32768 is in the sum chain below).  The tile is a copy, so where the run is 16-byte
     // aligned it is made by direct-to-LDS loads: no staging registers, no ds_write, half a dozen address instructions a KiB.  A wave
@@ -268,7 +266,7 @@ __device__ __forceinline__ void fe_main_body(const float* __restrict__ pcm, int6
     // there on (wave-uniform, at least one frame; capped far above the run's 10 560 so that it fits an int), and a slot that would end
     // past it fetches the utterance's last four samples instead.  No lane reads outside its utterance; slots that are clamped only
     // ever feed frames >= num_frames, whose sums are discarded.
-    const bool tile_dma = FUSED && !LOWREG && aligned16 && tb.tile_dma;  // wave-uniform (LELE_HIP_FE_TILE_DMA=0: register staging everywhere)
+    const bool tile_dma = FUSED && aligned16 && tb.tile_dma;  // wave-uniform (LELE_HIP_FE_TILE_DMA=0: register staging everywhere)
     float4 st[FUSED ? kIters : 1];
     if constexpr (FUSED) {
         const float* run = pcm + (int64_t)bl.y() * utt_stride + (int64_t)bl.x() * FR * fe::kHop;
@@ -320,7 +318,7 @@ __device__ __forceinline__ void fe_main_body(const float* __restrict__ pcm, int6
         }
     }
     if (!kTwDma)
-        for (int i = threadIdx.x; i < 511 - kTwBase; i += 256) s_tw[i] = tb.tw[i + kTwBase];
+        for (int i = threadIdx.x; i < 511; i += 256) s_tw[i] = tb.tw[i];
     if (!STDMEL)
         for (int i = threadIdx.x; i < tb.mel_steps * 16; i += 256) s_melw[i] = tb.melw[i];
     if (threadIdx.x < tb.mel_rounds * 16) s_mstart[threadIdx.x] = tb.mel_start[threadIdx.x];
@@ -350,12 +348,10 @@ __device__ __forceinline__ void fe_main_body(const float* __restrict__ pcm, int6
     float* out_u = out ? out + (int64_t)bl.y() * t_lfr * d_out : nullptr;
     float* lm_u = logmel_out ? logmel_out + (int64_t)bl.y() * num_frames * tb.n_mels : nullptr;
 
-    // Hann window coefficients of this lane's samples n = p + 16 q (features/window.rs), kept in registers (LOWREG: re-read per pass)
+    // Hann window coefficients of this lane's samples n = p + 16 q (features/window.rs), kept in registers
     float win[fe::kQ];
-    if (!LOWREG) {
 #pragma unroll
-        for (int q = 0; q < fe::kQ; ++q) win[q] = tb.window[p + 16 * q];
-    }
+    for (int q = 0; q < fe::kQ; ++q) win[q] = tb.window[p + 16 * q];
 
     // raw PCM of the next pass is fetched while the current pass computes (software prefetch): the loads are
     // unconditional (clamped to frame 0 for the tail) so that all 25 are in flight together.
@@ -445,12 +441,6 @@ __device__ __forceinline__ void fe_main_body(const float* __restrict__ pcm, int6
         const int fi = f_first + pass * 4;
         const bool valid = fi < nfr;
         const float mean = FUSED ? s_mean[wave * (4 * PASSES) + pass * 4 + g] : mean_next;
-        if (LOWREG) {  // the compiler must not hoist these loads out of the pass loop (that is the register form again)
-            int off = 0;
-            asm volatile("" : "+v"(off));
-#pragma unroll
-            for (int q = 0; q < fe::kQ; ++q) win[q] = tb.window[p + 16 * q + off];
-        }
 
         // 1./2. scale and mean subtraction (pipeline.rs:90-137): x * 32768 is exact (a power of two), so the product followed by the
         // subtraction rounds once -- which is what ONE fused multiply-add does: the same bits in half the instructions
@@ -516,7 +506,7 @@ __device__ __forceinline__ void fe_main_body(const float* __restrict__ pcm, int6
             __builtin_amdgcn_wave_barrier();
             // stages 6..9 with per-lane twiddles from LDS
             float re256 = 0.0f;
-            fe::phase_b(bq, p, rho, [&](int i) { const float2 w = s_tw[i - kTwBase]; return fe::cmk(w.x, w.y); }, &re256);
+            fe::phase_b(bq, p, rho, [&](int i) { const float2 w = s_tw[i]; return fe::cmk(w.x, w.y); }, &re256);
             if (rho == 0) p256 = re256;  // position 256 (used by lane p == 0)
             // 6. power spectrum (pipeline.rs:165-169); bins 0 and 256 have im forced to 0 (kernels/fft.rs:256-261)
 #pragma unroll
@@ -638,8 +628,7 @@ __global__ __launch_bounds__(256) void fe_main_kernel(const float* __restrict__ 
                                                       const float* __restrict__ means, FeDev tb, float* __restrict__ out,
                                                       float* __restrict__ logmel_out, int aligned16) {
     extern __shared__ float s_melw[];  // [mel_steps][16] (the table-driven mel loop only)
-    fe_main_body<MODE, STDMEL, FUSED, 4, false, OPT>(pcm, utt_stride, num_frames, t_lfr, means, tb, out, logmel_out, aligned16, s_melw,
-                                                GridBlock{});
+    fe_main_body<MODE, STDMEL, FUSED, OPT>(pcm, utt_stride, num_frames, t_lfr, means, tb, out, logmel_out, aligned16, s_melw, GridBlock{});
 }
 
 // ------------------------------------------------------------------------------------------------------
@@ -657,8 +646,8 @@ __global__ __launch_bounds__(256) void fe_seg_main_kernel(const float* __restric
     const FeSeg s = segs[blk_seg[blockIdx.x]];
     const float* base = pcm + s.start;
     const int aligned16 = (((uintptr_t)base & 15) == 0) && (s.len % 4 == 0);  // per block: the segment's own alignment and length
-    fe_main_body<MODE, STDMEL, true, 4, false, OPT>(base, s.len, s.num_frames, s.t_lfr, nullptr, tb, out + s.row0 * (tb.n_mels * tb.lfr_m),
-                                               nullptr, aligned16, s_melw, SegBlock{(unsigned)(blockIdx.x - s.block0)});
+    fe_main_body<MODE, STDMEL, true, OPT>(base, s.len, s.num_frames, s.t_lfr, nullptr, tb, out + s.row0 * (tb.n_mels * tb.lfr_m), nullptr,
+                                          aligned16, s_melw, SegBlock{(unsigned)(blockIdx.x - s.block0)});
 }
 // ------------------------------------------------------------------------------------------------------
 // Generic path: any FeatureConfig the reference accepts (other sample rates / frame lengths / n_fft = 1024).
@@ -928,9 +917,9 @@ __global__ __launch_bounds__(256) void fe_stream_main_kernel(const float* __rest
     const float* base = pcm_state + (int64_t)s * pcm_pitch;  // 16-byte aligned: the region's base is, and the pitch is a multiple of 4
     const int64_t len = (int64_t)r.carry + r.chunk;
     const int aligned16 = len % 4 == 0;
-    fe_main_body<MODE, STDMEL, true, 4, false, OPT>(base, len, r.nf, 0, nullptr, tb, nullptr,
-                                               mel_state + (int64_t)s * mel_pitch + (int64_t)r.mel_carry * tb.n_mels, aligned16, s_melw,
-                                               StreamBlock{(unsigned)(blockIdx.x - r.block0)});
+    fe_main_body<MODE, STDMEL, true, OPT>(base, len, r.nf, 0, nullptr, tb, nullptr,
+                                          mel_state + (int64_t)s * mel_pitch + (int64_t)r.mel_carry * tb.n_mels, aligned16, s_melw,
+                                          StreamBlock{(unsigned)(blockIdx.x - r.block0)});
 }
 
 // 3. emit: LFR row i of a stream is blocks b = 0 .. m-1 = frames i*n + b - pad; frame g sits in row g - mel_base of the stream's
@@ -1006,12 +995,10 @@ struct LeleFrontend {
     LeleFeatureConfig cfg{};
     int64_t frame_len = 0, hop_len = 0, n_fft = 0;
     bool fast = false;
-    bool std_mel = false;  // mel bank has the default round structure (fully unrolled kernel variant)
-    int dpp_mode = 0;  // 0: __shfl, 1: DPP row_ror (selected after a self-test)
-    bool fused = true;  // frame sums computed inside fe_main_kernel (LELE_HIP_FE_FUSED=0 selects the two-kernel form)
-    int opt = 0;        // kFeConstTw | kFeLdsMel: the form of the default bank's fused kernels (0: every table read as before)
-    bool lean = false;  // kFeLeanLds on top of opt == kFeConstTw | kFeLdsMel (LELE_HIP_FE_LEAN_LDS=0 keeps the pass without it)
-    bool conj = false;  // kFeConjA on top of the lean pass (LELE_HIP_FE_CONJ_A=0 keeps the pass without it)
+    // the fused kernel this front-end runs (fe::select_form, once, in frontend_create).  mode: the DPP row_ror unless the lab's
+    // LELE_HIP_FE_DPP says __shfl; fused: the lab's LELE_HIP_FE_FUSED=0 selects the two-kernel form of compute()
+    FeForm form{1, false, true, 0};
+    int last_launch = -1;  // the tuple fe_dispatch launched last (test hook lele_hip_frontend_last_launch)
     // generic path tables (configs other than 400/160/512)
     const float* g_window = nullptr;
     const int* g_mstart = nullptr;
@@ -1105,6 +1092,49 @@ int upload(LeleFrontend* fe, const std::vector<T>& v, const T** out) {
     *out = (const T*)d;
     return 0;
 }
+
+// a product switch ("Run-time switches"): on unless set to something whose atoi is 0
+bool fe_switch(const char* name) {
+    const char* e = getenv(name);
+    return !(e && *e && atoi(e) == 0);
+}
+
+// The tag fe_dispatch hands to its callable: the template arguments <MODE, STDMEL, FUSED, OPT> of fe_main_kernel, fe_seg_main_kernel and
+// fe_stream_main_kernel as constants.
+template <int MODE, bool STDMEL, bool FUSED, int OPT>
+struct FeTag {
+    static constexpr int mode = MODE, opt = OPT;
+    static constexpr bool std_mel = STDMEL, fused = FUSED;
+    static constexpr int id = MODE | STDMEL << 1 | FUSED << 2 | OPT << 3;  // what lele_hip_frontend_last_launch reports
+};
+// Calls launch(tag) with the tag of form f and records the tuple it launches from the tag's own constants.  The fused kernels that exist
+// are listed here and nowhere else; mode == 0 and fused == false are lab values (lab_env), so their tuples are compiled into the lab
+// library alone.  A form outside the list is an error (select_form yields none with the lab values at their defaults).
+template <class F>
+int fe_dispatch(LeleFrontend* fe, FeForm f, F&& launch) {
+    const int id = f.mode | f.std_mel << 1 | f.fused << 2 | f.opt << 3;
+    auto is = [&](auto t) {
+        if (id != t.id) return false;
+        fe->last_launch = t.id;
+        launch(t);
+        return true;
+    };
+    const bool found = is(FeTag<1, false, true, 0>{}) || is(FeTag<1, true, true, 0>{}) || is(FeTag<1, true, true, kFeConstTw>{}) ||
+                       is(FeTag<1, true, true, kFeConstTw | kFeLdsMel>{}) || is(FeTag<1, true, true, kFeConstTw | kFeLdsMel | kFeLeanLds>{}) ||
+                       is(FeTag<1, true, true, kFeConstTw | kFeLdsMel | kFeLeanLds | kFeConjA>{})
+#ifdef LELE_HIP_LAB
+                       || is(FeTag<0, false, true, 0>{}) || is(FeTag<0, true, true, 0>{}) || is(FeTag<1, false, false, 0>{}) ||
+                       is(FeTag<1, true, false, 0>{}) || is(FeTag<0, false, false, 0>{}) || is(FeTag<0, true, false, 0>{})
+#endif
+        ;
+    LELE_REQUIRE(found, "frontend: no kernel for the form mode %d std_mel %d fused %d opt %d", f.mode, (int)f.std_mel, (int)f.fused, f.opt);
+    return 0;
+}
+// dynamic LDS of a fused kernel: the table-driven mel loop's weights (opt != 0: the kernel's own static tables instead)
+size_t fe_mel_lds(const LeleFrontend* fe) { return fe->form.opt ? 0 : (size_t)fe->dev.mel_steps * 16 * sizeof(float); }
+// lele_hip_last_route: how the fused kernel's blocks stage their PCM tile -- n_dma of the launch's n utterances / segments / streams meet
+// fe_main_body's own condition (`tile_dma` there: a 16-byte aligned run and LELE_HIP_FE_TILE_DMA on)
+const char* fe_tile_route(int64_t n_dma, int64_t n) { return n_dma == n ? "fe.tile_dma" : n_dma == 0 ? "fe.tile_regs" : "fe.tile_mixed"; }
 
 }  // namespace
 
@@ -1215,13 +1245,13 @@ int lele_hip_frontend_create(LeleCtx* ctx, const LeleFeatureConfig* cfg, LeleFro
     }
     step_off[d.mel_rounds] = off;
     d.mel_steps = off;
-    fe->std_mel = (d.mel_rounds == 5 && cfg->n_mels == 80);
-    for (int rd = 0; fe->std_mel && rd < 5; ++rd) {
-        if (step_off[rd] != kStdMelOff[rd] || step_off[rd + 1] != kStdMelOff[rd + 1]) fe->std_mel = false;
+    bool std_mel = (d.mel_rounds == 5 && cfg->n_mels == 80);  // the bank has the default round structure (fully unrolled kernel variant)
+    for (int rd = 0; std_mel && rd < 5; ++rd) {
+        if (step_off[rd] != kStdMelOff[rd] || step_off[rd + 1] != kStdMelOff[rd + 1]) std_mel = false;
         for (int pm = 0; pm < 16; ++pm)
-            if (start_pad[rd * 16 + pm] + kStdMelLen[rd] - 1 > 256) fe->std_mel = false;
+            if (start_pad[rd * 16 + pm] + kStdMelLen[rd] - 1 > 256) std_mel = false;
     }
-    if (lab_env("LELE_HIP_FE_GENERIC_MEL")) fe->std_mel = false;
+    if (lab_env("LELE_HIP_FE_GENERIC_MEL")) std_mel = false;
     int rc = 0;
     rc |= upload(fe, twr, &d.tw_re);
     rc |= upload(fe, twi, &d.tw_im);
@@ -1235,7 +1265,7 @@ int lele_hip_frontend_create(LeleCtx* ctx, const LeleFeatureConfig* cfg, LeleFro
     rc |= upload(fe, melw, &d.melw);
     {   // the default bank's weights as the kernel's LDS image: weight s = step_off[rd] + t of lane pm at [s / 4][pm][s % 4]
         std::vector<float> img(kMelLdsFloats, 0.0f);
-        for (int sidx = 0; fe->std_mel && sidx < fe::kMelLdsWeights; ++sidx)
+        for (int sidx = 0; std_mel && sidx < fe::kMelLdsWeights; ++sidx)
             for (int pm = 0; pm < 16; ++pm) img[fe::mel_lds_index(sidx, pm)] = melw[sidx * 16 + pm];
         rc |= upload(fe, img, &d.melw_lds);
     }
@@ -1245,48 +1275,41 @@ int lele_hip_frontend_create(LeleCtx* ctx, const LeleFeatureConfig* cfg, LeleFro
         lele_hip_frontend_destroy(fe);
         return rc;
     }
-    const char* env = lab_env("LELE_HIP_FE_DPP");
-    fe->dpp_mode = env ? atoi(env) : 1;  // 1: DPP row_ror (default), 0: __shfl (ds_bpermute)
-    const char* envf = lab_env("LELE_HIP_FE_FUSED");
-    fe->fused = envf ? atoi(envf) != 0 : true;
     // product switch: 0 = aligned runs take the register staging of unaligned ones -- same bits, the A/B handle and
     // the on-device cross-check of the direct-to-LDS tile
-    const char* envd = getenv("LELE_HIP_FE_TILE_DMA");
-    d.tile_dma = envd && *envd ? atoi(envd) != 0 : 1;
-    // product switches, same bits either way: LELE_HIP_FE_CONST_TW=0 keeps the kernels that read every twiddle from the table -- also
-    // what a table that differs from the compiled-in constants in any bit selects (another libm; "mismatch" is the tests' way to get
-    // there) -- and LELE_HIP_FE_LDS_TABLES=0 keeps the mel weights in global memory
+    d.tile_dma = fe_switch("LELE_HIP_FE_TILE_DMA");
+    // a table that differs from the compiled-in constants in any bit (another libm) keeps the kernels that read every twiddle from
+    // it.  LELE_HIP_FE_CONST_TW=mismatch is the tests' way to get there: the switch counts as on, and the check alone -- on a table
+    // with one entry moved by an ulp -- decides
     const char* envc = getenv("LELE_HIP_FE_CONST_TW");
-    const char* envl = getenv("LELE_HIP_FE_LDS_TABLES");
-    bool const_tw = fe::tw_const_matches(twr.data(), twi.data());
-    if (envc && !strcmp(envc, "mismatch")) {
+    const bool mismatch = envc && !strcmp(envc, "mismatch");
+    bool const_match = fe::tw_const_matches(twr.data(), twi.data());
+    if (mismatch) {
         std::vector<float> other = twr;
         other[fe::tw_off(5) + 3] = nextafterf(other[fe::tw_off(5) + 3], 2.0f);
-        const_tw = fe::tw_const_matches(other.data(), twi.data());
-    } else if (envc && *envc && atoi(envc) == 0) {
-        const_tw = false;
+        const_match = fe::tw_const_matches(other.data(), twi.data());
     }
-    if (const_tw && fe->std_mel && fe->fused && fe->dpp_mode == 1)
-        fe->opt = kFeConstTw | ((envl && *envl && atoi(envl) == 0) ? 0 : kFeLdsMel);
-    // product switch, same bits either way: LELE_HIP_FE_LEAN_LDS=0 keeps the pass loop with the exchange's paired LDS accesses and the
-    // sample address rebuilt every pass
-    const char* envn = getenv("LELE_HIP_FE_LEAN_LDS");
-    fe->lean = fe->opt == (kFeConstTw | kFeLdsMel) && !(envn && *envn && atoi(envn) == 0);
-    // product switch, same bits either way: LELE_HIP_FE_CONJ_A=0 keeps phase A with its sign flips and packed butterflies on real values
-    // (fe::phase_a_fast).  The conjugate form reads the same compiled-in constants, so it is selected where they are (const_tw above).
-    const char* enva = getenv("LELE_HIP_FE_CONJ_A");
-    fe->conj = fe->lean && !(enva && *enva && atoi(enva) == 0);
+    // The four product switches give the same bits either way.  LELE_HIP_FE_CONST_TW=0: every twiddle is read from the table;
+    // _LDS_TABLES=0: the mel weights stay in global memory; _LEAN_LDS=0: the pass loop keeps the exchange's paired LDS accesses and
+    // rebuilds the sample address every pass; _CONJ_A=0: phase A keeps its sign flips and packed butterflies on real values
+    // (fe::phase_a_fast).  The two lab values: 1 = DPP row_ror, 0 = __shfl (ds_bpermute); fused = 0: the two-kernel form.
+    const char* envp = lab_env("LELE_HIP_FE_DPP");
+    const char* envf = lab_env("LELE_HIP_FE_FUSED");
+    fe->form = fe::select_form(std_mel, const_match, mismatch || fe_switch("LELE_HIP_FE_CONST_TW"), fe_switch("LELE_HIP_FE_LDS_TABLES"),
+                               fe_switch("LELE_HIP_FE_LEAN_LDS"), fe_switch("LELE_HIP_FE_CONJ_A"), envp ? atoi(envp) : 1, envf ? atoi(envf) != 0 : true);
     *out = fe;
     return 0;
 }
 
-/* test hook (not part of include/lele_hip.h): the form frontend_create selected for the default bank's fused kernels -- bit 0: phase A's
- * twiddles are compiled-in constants, bit 1: the mel weights are read from LDS; 0: the table-reading kernels */
-int lele_hip_frontend_kernel_form(const LeleFrontend* fe) { return fe ? fe->opt : -1; }
-/* test hook: 1 where the default bank's fused kernels run the lean pass (kFeLeanLds), 0 where LELE_HIP_FE_LEAN_LDS=0 or another form keeps it out */
-int lele_hip_frontend_lean_lds(const LeleFrontend* fe) { return fe ? (int)fe->lean : -1; }
-/* test hook: 1 where the default bank's fused kernels run phase A on real and conjugate values (kFeConjA), 0 where LELE_HIP_FE_CONJ_A=0 or another form keeps it out */
-int lele_hip_frontend_conj_a(const LeleFrontend* fe) { return fe ? (int)fe->conj : -1; }
+/* test hooks (not part of include/lele_hip.h), views of the form frontend_create selected.  kernel_form -- bit 0: phase A's twiddles are
+ * compiled-in constants, bit 1: the mel weights are read from LDS; 0: the table-reading kernels.  lean_lds / conj_a -- 1 where the
+ * default bank's fused kernels run the lean pass (kFeLeanLds) / phase A on real and conjugate values (kFeConjA). */
+int lele_hip_frontend_kernel_form(const LeleFrontend* fe) { return fe ? fe->form.opt & (kFeConstTw | kFeLdsMel) : -1; }
+int lele_hip_frontend_lean_lds(const LeleFrontend* fe) { return fe ? (fe->form.opt & kFeLeanLds) != 0 : -1; }
+int lele_hip_frontend_conj_a(const LeleFrontend* fe) { return fe ? (fe->form.opt & kFeConjA) != 0 : -1; }
+/* test hook: the tuple the last fused launch of this front-end ran, mode | std_mel << 1 | fused << 2 | opt << 3 as fe_dispatch
+ * recorded it; -1 before any */
+int lele_hip_frontend_last_launch(const LeleFrontend* fe) { return fe ? fe->last_launch : -1; }
 
 int lele_hip_frontend_destroy(LeleFrontend* fe) {
     if (!fe) return 0;
@@ -1328,7 +1351,7 @@ static int fe_generic(LeleFrontend* fe, const float* dpcm, int64_t batch, int64_
     const int64_t bins = fe->n_fft / 2 + 1, nm = fe->cfg.n_mels;
     // the fused form (fe_generic_fused_kernel): frames per workgroup so that their LDS image stays under 64 KB; anything larger
     // (n_fft > 4096) keeps the four kernels
-    if (fe->fused && fe->n_fft <= 4096 && fe->frame_len <= fe->n_fft && batch <= 65535) {   // (lab: LELE_HIP_FE_FUSED=0 keeps the four kernels)
+    if (fe->form.fused && fe->n_fft <= 4096 && fe->frame_len <= fe->n_fft && batch <= 65535) {   // (lab: LELE_HIP_FE_FUSED=0 keeps the four kernels)
         const int n = (int)fe->n_fft;
         // (the kernel is bound by latency under its barriers, so by occupancy against work per workgroup: 4 frames of 1024 points with
         // the twiddles in LDS = 55 KB = two workgroups a CU ran 15 ms where the four kernels took 12)
@@ -1429,8 +1452,9 @@ static int fe_run(LeleFrontend* fe, const LeleTensor* pcm, int64_t batch, int64_
     const int aligned16 = ((uintptr_t)dpcm % 16 == 0) && (pcm_len % 4 == 0);
     // lele_hip_last_route: the kernel, then how it stages its PCM tile -- the condition fe_main_body evaluates (`tile_dma` there) on the
     // same two values; the two-kernel lab form has no tile
-    ctx->set_route(fe->std_mel ? "fe.main_std" : "fe.main_table",
-                   !fe->fused ? "fe.two_kernel" : (aligned16 && fe->dev.tile_dma) ? "fe.tile_dma" : "fe.tile_regs");
+    const FeForm form = fe->form;
+    ctx->set_route(form.std_mel ? "fe.main_std" : "fe.main_table",
+                   !form.fused ? "fe.two_kernel" : fe_tile_route(aligned16 && fe->dev.tile_dma, 1));
     constexpr int64_t kMaxGridY = 65535;  // utterances a launch: a longer batch runs in chunks (pcm_len % 4 == 0 where aligned16, so it holds for every chunk)
     hipEvent_t* ev = nullptr;
     if (fe->profiling) {
@@ -1445,45 +1469,22 @@ static int fe_run(LeleFrontend* fe, const LeleTensor* pcm, int64_t batch, int64_
         fe->events_used += 3;
         LELE_HIP_CHECK(hipEventRecord(ev[0], ctx->stream));
     }
-    for (int64_t c0 = 0; !fe->fused && c0 < batch; c0 += kMaxGridY) {
+    for (int64_t c0 = 0; !form.fused && c0 < batch; c0 += kMaxGridY) {
         const dim3 grid((unsigned)((nf + 63) / 64), (unsigned)std::min<int64_t>(kMaxGridY, batch - c0));
         hipLaunchKernelGGL(fe_frame_sum_kernel, grid, dim3(64), 0, ctx->stream, (const float*)dpcm + c0 * pcm_len, pcm_len, pcm_len, nf,
                            (float*)dmean + c0 * nf, aligned16);
     }
     if (ev) LELE_HIP_CHECK(hipEventRecord(ev[1], ctx->stream));
-    const size_t mel_lds = fe->opt ? 0 : (size_t)fe->dev.mel_steps * 16 * sizeof(float);  // (the table-driven mel loop's; opt != 0: its own static tables instead)
-#define FE_LAUNCH(MODE, STD, FUS, OPT)                                                                                               \
-    hipLaunchKernelGGL((fe_main_kernel<MODE, STD, FUS, OPT>), grid, dim3(256), mel_lds, ctx->stream, cpcm, pcm_len, nf, t_lfr, cmean, fe->dev, \
-                       o, lm, aligned16)
-#define FE_LAUNCH2(MODE, STD) \
-    do {                      \
-        if (fe->fused)        \
-            FE_LAUNCH(MODE, STD, true, 0); \
-        else                  \
-            FE_LAUNCH(MODE, STD, false, 0); \
-    } while (0)
-    for (int64_t c0 = 0; c0 < batch; c0 += kMaxGridY) {  // every chunk's utterances land where the one launch would put them
-        const dim3 grid((unsigned)((nf + 63) / 64), (unsigned)std::min<int64_t>(kMaxGridY, batch - c0));
-        const float* cpcm = (const float*)dpcm + c0 * pcm_len;
-        const float* cmean = (const float*)dmean + c0 * nf;
-        float* o = want_logmel ? nullptr : (float*)out->data + c0 * t_lfr * cols;
-        float* lm = want_logmel ? (float*)out->data + c0 * nf * fe->cfg.n_mels : nullptr;
-        if (fe->conj) {  // (opt != 0: the default bank, fused, DPP -- frontend_create)
-            FE_LAUNCH(1, true, true, kFeConstTw | kFeLdsMel | kFeLeanLds | kFeConjA);
-        } else if (fe->lean) {
-            FE_LAUNCH(1, true, true, kFeConstTw | kFeLdsMel | kFeLeanLds);
-        } else if (fe->opt == (kFeConstTw | kFeLdsMel)) {
-            FE_LAUNCH(1, true, true, kFeConstTw | kFeLdsMel);
-        } else if (fe->opt == kFeConstTw) {
-            FE_LAUNCH(1, true, true, kFeConstTw);
-        } else if (fe->dpp_mode == 1) {
-            if (fe->std_mel) FE_LAUNCH2(1, true); else FE_LAUNCH2(1, false);
-        } else {
-            if (fe->std_mel) FE_LAUNCH2(0, true); else FE_LAUNCH2(0, false);
+    LELE_TRY(fe_dispatch(fe, form, [&](auto t) {
+        using T = decltype(t);
+        for (int64_t c0 = 0; c0 < batch; c0 += kMaxGridY) {  // every chunk's utterances land where the one launch would put them
+            const dim3 grid((unsigned)((nf + 63) / 64), (unsigned)std::min<int64_t>(kMaxGridY, batch - c0));
+            float* o = want_logmel ? nullptr : (float*)out->data + c0 * t_lfr * cols;
+            float* lm = want_logmel ? (float*)out->data + c0 * nf * fe->cfg.n_mels : nullptr;
+            hipLaunchKernelGGL((fe_main_kernel<T::mode, T::std_mel, T::fused, T::opt>), grid, dim3(256), fe_mel_lds(fe), ctx->stream,
+                               (const float*)dpcm + c0 * pcm_len, pcm_len, nf, t_lfr, (const float*)dmean + c0 * nf, fe->dev, o, lm, aligned16);
         }
-    }
-#undef FE_LAUNCH2
-#undef FE_LAUNCH
+    }));
     LELE_HIP_CHECK(hipGetLastError());
     if (ev) LELE_HIP_CHECK(hipEventRecord(ev[2], ctx->stream));
     if (want_logmel) {
@@ -1614,31 +1615,20 @@ int lele_hip_frontend_compute_segments(LeleFrontend* fe, const LeleTensor* pcm, 
     for (int64_t i = 0; i < count; ++i) nseg += lengths[i] >= fe->frame_len;
     const FeSeg* dsegs = (const FeSeg*)table;
     const int* dblk = (const int*)(dsegs + nseg);
-    const size_t mel_lds = fe->opt ? 0 : (size_t)fe->dev.mel_steps * 16 * sizeof(float);  // (the table-driven mel loop's; opt != 0: its own static tables instead)
     // lele_hip_last_route: the kernel, then the tile staging of its blocks -- fe_seg_main_kernel's own per-segment condition, evaluated
     // here on the same values; one name for a launch that holds both kinds
     int64_t n_dma = 0;
     for (int64_t i = 0; i < count; ++i)
         if (lengths[i] >= fe->frame_len)
             n_dma += (((uintptr_t)((const float*)dpcm + starts[i]) & 15) == 0) && (lengths[i] % 4 == 0) && fe->dev.tile_dma;
-    ctx->set_route(fe->std_mel ? "fe.seg_std" : "fe.seg_table", n_dma == nseg ? "fe.tile_dma" : n_dma == 0 ? "fe.tile_regs" : "fe.tile_mixed");
-#define FE_SEG_LAUNCH(MODE, STD, ...)                                                                                            \
-    hipLaunchKernelGGL((fe_seg_main_kernel<MODE, STD, ##__VA_ARGS__>), dim3((unsigned)blocks), dim3(256), mel_lds, ctx->stream, (const float*)dpcm, \
-                       dsegs, dblk, fe->dev, o)
-    if (fe->conj) {
-        FE_SEG_LAUNCH(1, true, kFeConstTw | kFeLdsMel | kFeLeanLds | kFeConjA);
-    } else if (fe->lean) {
-        FE_SEG_LAUNCH(1, true, kFeConstTw | kFeLdsMel | kFeLeanLds);
-    } else if (fe->opt == (kFeConstTw | kFeLdsMel)) {
-        FE_SEG_LAUNCH(1, true, kFeConstTw | kFeLdsMel);
-    } else if (fe->opt == kFeConstTw) {
-        FE_SEG_LAUNCH(1, true, kFeConstTw);
-    } else if (fe->dpp_mode == 1) {
-        if (fe->std_mel) FE_SEG_LAUNCH(1, true); else FE_SEG_LAUNCH(1, false);
-    } else {
-        if (fe->std_mel) FE_SEG_LAUNCH(0, true); else FE_SEG_LAUNCH(0, false);
-    }
-#undef FE_SEG_LAUNCH
+    FeForm form = fe->form;
+    form.fused = true;  // (the two-kernel form is a lab switch of compute() alone)
+    ctx->set_route(form.std_mel ? "fe.seg_std" : "fe.seg_table", fe_tile_route(n_dma, nseg));
+    LELE_TRY(fe_dispatch(fe, form, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((fe_seg_main_kernel<T::mode, T::std_mel, T::opt>), dim3((unsigned)blocks), dim3(256), fe_mel_lds(fe), ctx->stream,
+                           (const float*)dpcm, dsegs, dblk, fe->dev, o);
+    }));
     LELE_HIP_CHECK(hipGetLastError());
     return set_shape(out_shape, out_rank, {rows, cols});
 }
@@ -1877,25 +1867,14 @@ int lele_hip_frontend_stream_push(LeleFrontendStream* st, const LeleTensor* pcm,
         }
     } else if (n_live) {
         // lele_hip_last_route: this is the segment kernel's body over the streams' regions, so it reports the segment names
-        ctx->set_route(fe->std_mel ? "fe.seg_std" : "fe.seg_table", n_dma == n_live ? "fe.tile_dma" : n_dma == 0 ? "fe.tile_regs" : "fe.tile_mixed");
-        const size_t mel_lds = fe->opt ? 0 : (size_t)fe->dev.mel_steps * 16 * sizeof(float);  // (the table-driven mel loop's; opt != 0: its own static tables instead)
-#define FE_STREAM_LAUNCH(MODE, STD, ...)                                                                                           \
-    hipLaunchKernelGGL((fe_stream_main_kernel<MODE, STD, ##__VA_ARGS__>), dim3((unsigned)blk.size()), dim3(256), mel_lds, ctx->stream,              \
-                       (const float*)st->pcm_state, st->pcm_pitch, drecs, dblk, fe->dev, st->mel_state, st->mel_pitch)
-        if (fe->conj) {
-            FE_STREAM_LAUNCH(1, true, kFeConstTw | kFeLdsMel | kFeLeanLds | kFeConjA);
-        } else if (fe->lean) {
-            FE_STREAM_LAUNCH(1, true, kFeConstTw | kFeLdsMel | kFeLeanLds);
-        } else if (fe->opt == (kFeConstTw | kFeLdsMel)) {
-            FE_STREAM_LAUNCH(1, true, kFeConstTw | kFeLdsMel);
-        } else if (fe->opt == kFeConstTw) {
-            FE_STREAM_LAUNCH(1, true, kFeConstTw);
-        } else if (fe->dpp_mode == 1) {
-            if (fe->std_mel) FE_STREAM_LAUNCH(1, true); else FE_STREAM_LAUNCH(1, false);
-        } else {
-            if (fe->std_mel) FE_STREAM_LAUNCH(0, true); else FE_STREAM_LAUNCH(0, false);
-        }
-#undef FE_STREAM_LAUNCH
+        FeForm form = fe->form;
+        form.fused = true;
+        ctx->set_route(form.std_mel ? "fe.seg_std" : "fe.seg_table", fe_tile_route(n_dma, n_live));
+        LELE_TRY(fe_dispatch(fe, form, [&](auto t) {
+            using T = decltype(t);
+            hipLaunchKernelGGL((fe_stream_main_kernel<T::mode, T::std_mel, T::opt>), dim3((unsigned)blk.size()), dim3(256), fe_mel_lds(fe),
+                               ctx->stream, (const float*)st->pcm_state, st->pcm_pitch, drecs, dblk, fe->dev, st->mel_state, st->mel_pitch);
+        }));
     }
     if (total_rows) {
         if (nm % 4 == 0)

@@ -1,5 +1,6 @@
 // tests/emu/fe_tables_emu.cpp -- host-side view of the compile-time tables of lele_amd/csrc/fe_core.h (test infrastructure):
 // the constant twiddles of phase_a_fast and the LDS layout of the default mel bank.  tests/test_frontend_tables.py drives it.
+// Also the host's choice of the fused kernel's form (fe::select_form), which tests/test_frontend_form.py enumerates.
 #include <math.h>
 #include <string.h>
 #include "../../lele_amd/csrc/fe_core.h"
@@ -45,4 +46,10 @@ void fe_phase_a_fast_both(const float* x, const float* tw_re, const float* tw_im
 int fe_mel_lds_weights() { return fe::kMelLdsWeights; }
 int fe_mel_lds_chunks() { return fe::kMelLdsChunks; }
 int fe_mel_lds_index(int s, int p) { return fe::mel_lds_index(s, p); }
+
+// fe::select_form (tests/test_frontend_form.py): out = {mode, std_mel, fused, opt}
+void fe_select_form(int std_mel, int const_match, int const_tw, int lds_tables, int lean, int conj, int dpp, int fused, int* out) {
+    const fe::FeForm f = fe::select_form(std_mel != 0, const_match != 0, const_tw != 0, lds_tables != 0, lean != 0, conj != 0, dpp, fused != 0);
+    out[0] = f.mode, out[1] = f.std_mel, out[2] = f.fused, out[3] = f.opt;
+}
 }
