@@ -279,7 +279,9 @@ int lele_hip_cmvn_apply_with_stats(LeleCtx* ctx, const LeleTensor* x, const Lele
  * x [rows, n] real, n power of two -> re, im [rows, n/2+1] */
 int lele_hip_rfft(LeleCtx* ctx, const LeleTensor* x, LeleBuf* out_re, LeleBuf* out_im, int64_t* out_shape,
                   int32_t* out_rank);
-/* kernels::stft / stft_power_spectrum, src/kernels/math.rs:2304-2439; window may be NULL (periodic Hann) */
+/* kernels::stft / stft_power_spectrum, src/kernels/math.rs:2304-2439; window may be NULL (periodic Hann).  signal: ONE signal, [L]
+ * -> [frames, n_fft/2+1(, 2)] or [1, L] -> [1, frames, n_fft/2+1(, 2)].  Leading dimensions whose product exceeds 1 are an error
+ * ("Data length mismatch"): upstream transforms the flattened data once, shapes the result [batch, ..] and panics there (tensor.rs:66). */
 int lele_hip_stft(LeleCtx* ctx, const LeleTensor* signal, int64_t n_fft, int64_t hop_length, int64_t win_length,
                   const LeleTensor* window, LeleBuf* out, int64_t* out_shape, int32_t* out_rank);
 int lele_hip_stft_power_spectrum(LeleCtx* ctx, const LeleTensor* signal, int64_t n_fft, int64_t hop_length,
@@ -547,7 +549,9 @@ int lele_hip_fused_scale_bias(LeleCtx* ctx, const LeleTensor* data, const LeleTe
  * 8-bit: (b - 128) / 128; stereo: (l + r) / 2.  bytes: U8 [n].  out: f32 [frames] */
 int lele_hip_wav_to_f32(LeleCtx* ctx, const LeleTensor* bytes, int32_t bits_per_sample, int32_t num_channels, LeleBuf* out,
                         int64_t* out_shape, int32_t* out_rank);
-/* examples/sensevoice/src/tokenizer.rs:50-61: arg-max over the last axis; the LAST of equal maxima wins (Iterator::max_by).
+/* examples/sensevoice/src/tokenizer.rs:50-61: arg-max over the last axis; the LAST of equal maxima wins (Iterator::max_by;
+ * +0.0 == -0.0).  A NaN loses to every number (upstream panics on one): the id is the last maximum among the row's non-NaN entries,
+ * V - 1 for a row of nothing but NaN; rows without a NaN are unaffected.
  * x: f32 [.., V] -> i32 ids [..]; only the ids need to leave the device */
 int lele_hip_argmax_last(LeleCtx* ctx, const LeleTensor* x, LeleBuf* out, int64_t* out_shape, int32_t* out_rank);
 

@@ -43,7 +43,11 @@ __global__ void wav_to_f32_kernel(const uint8_t* __restrict__ bytes, int64_t fra
     }
 }
 
-// one workgroup per row; (value, index) pairs reduced with "greater value wins, equal values: greater index wins"
+// one workgroup per row; (value, index) pairs reduced with "greater value wins, equal values: greater index wins".
+// A NaN loses to every number (the reference panics on one, tokenizer.rs:56: partial_cmp().unwrap()): a thread never takes a NaN, so
+// the pairs that reach the reduction hold numbers only, and a thread that saw nothing but NaN enters it with index -1, which loses to
+// every pair.  The result is the LAST maximum among the row's non-NaN entries, V - 1 for a row without any; rows without a NaN are
+// decided by exactly the comparisons they always were.
 __global__ __launch_bounds__(256) void argmax_last_kernel(const float* __restrict__ x, int64_t rows, int64_t v,
                                                           int32_t* __restrict__ out) {
     const int64_t row = blockIdx.x;
@@ -52,7 +56,7 @@ __global__ __launch_bounds__(256) void argmax_last_kernel(const float* __restric
     int64_t bi = -1;
     for (int64_t j = threadIdx.x; j < v; j += 256) {
         const float val = p[j];
-        if (bi < 0 || val >= best) {  // later index replaces an equal value
+        if (val == val && (bi < 0 || val >= best)) {  // later index replaces an equal value; val != val: NaN, never taken
             best = val;
             bi = j;
         }
@@ -68,14 +72,15 @@ __global__ __launch_bounds__(256) void argmax_last_kernel(const float* __restric
             const int64_t oi = si[threadIdx.x + off];
             const float mv = sv[threadIdx.x];
             const int64_t mi = si[threadIdx.x];
-            if (oi >= 0 && (mi < 0 || ov > mv || (ov == mv && oi > mi))) {
+            if (oi >= 0 && (mi < 0 || ov > mv || (ov == mv && oi > mi))) {  // index -1 (empty or all-NaN slot) loses; no NaN in sv
                 sv[threadIdx.x] = ov;
                 si[threadIdx.x] = oi;
             }
         }
         __syncthreads();
     }
-    if (threadIdx.x == 0) out[row] = (int32_t)(si[0] < 0 ? 0 : si[0]);  // unwrap_or(0) for empty rows
+    // no number in the row: V - 1 (all NaN), or unwrap_or(0) for an empty row
+    if (threadIdx.x == 0) out[row] = (int32_t)(si[0] >= 0 ? si[0] : (v > 0 ? v - 1 : 0));
 }
 
 // one workgroup per batch row: ordered compaction of the ids whose skip flag is clear (ballot prefix inside a wave,

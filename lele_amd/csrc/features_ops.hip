@@ -266,8 +266,15 @@ int stft_common(LeleCtx* ctx, const LeleTensor* signal, int64_t n_fft, int64_t h
     LELE_REQUIRE(ctx && signal && out, "stft: NULL argument");
     LELE_REQUIRE(signal->dtype == LELE_F32, "stft: signal must be f32");
     LELE_REQUIRE(win_length <= n_fft && hop > 0 && win_length > 0, "stft: need 0 < win_length <= n_fft and hop > 0");
+    // The reference treats input.data as ONE signal (math.rs:2312) but shapes the result [batch, frames, ..] (math.rs:2362-2369): with
+    // batch > 1 that shape holds batch times the values it computed and TensorView::from_slice panics (tensor.rs:66).  Same here,
+    // before anything is reserved or launched.
+    int64_t batch = 1;
+    for (int i = 0; i + 1 < signal->rank; ++i) batch *= signal->shape[i];
+    LELE_REQUIRE(batch <= 1, "stft: Data length mismatch: a [%lld, L] signal is transformed as one signal of %lld samples, its result cannot "
+                 "have %lld batch entries (pass [L] or [1, L])", (long long)batch, (long long)numel(signal), (long long)batch);
     LELE_HIP_CHECK(hipSetDevice(ctx->device));
-    const int64_t len = numel(signal);  // the reference treats input.data as ONE signal (math.rs:2312)
+    const int64_t len = numel(signal);
     const int64_t nfreq = n_fft / 2 + 1;
     if (len == 0) {  // math.rs:2313-2316
         out->bytes = 0;
@@ -297,9 +304,7 @@ int stft_common(LeleCtx* ctx, const LeleTensor* signal, int64_t n_fft, int64_t h
     LELE_TRY(out->reserve((size_t)frames * nfreq * (power ? 1 : 2) * 4));
     LELE_TRY(launch_fft(ctx, (const float*)dsig, 1, len, 0, hop, n_fft, win_length, dwin, frames, power ? 1 : 0,
                         (float*)out->data, nullptr));
-    // shape rule of math.rs:2362-2369
-    int64_t batch = 1;
-    for (int i = 0; i + 1 < signal->rank; ++i) batch *= signal->shape[i];
+    // shape rule of math.rs:2362-2369 (batch == 1 here)
     if (signal->rank <= 1) {
         if (power) return set_shape(out_shape, out_rank, {frames, nfreq});
         return set_shape(out_shape, out_rank, {frames, nfreq, 2});

@@ -405,10 +405,13 @@ class RealFft:  # features/fft.rs:1-49
         self.n, self.ctx = length, ctx
 
     def process(self, x):
-        """x [rows, n] or [n] real -> (re, im) each [rows, n/2+1]"""
+        """x [rows, n] or [n] real -> (re, im) each [rows, n/2+1]; n must be the length this RealFft was made for (the assert_eq of fft.rs:24)"""
+        a = np.asarray(unwrap(x), np.float32) if not isinstance(unwrap(x), _lib.DevTensor) else unwrap(x)
+        last = a.shape[-1] if len(a.shape) else 1
+        if last != self.n:
+            raise _lib.LeleError("RealFft(%d).process: the input's last dimension is %d, not %d" % (self.n, last, self.n))
         ctx = _ctx(self.ctx)
         keep = []
-        a = np.asarray(unwrap(x), np.float32) if not isinstance(unwrap(x), _lib.DevTensor) else unwrap(x)
         if isinstance(a, np.ndarray) and a.ndim == 1:
             a = a.reshape(1, -1)
         o_re, o_im = ctx.buf(), ctx.buf()

@@ -820,7 +820,7 @@ def wav_to_f32(payload, bits_per_sample=16, num_channels=1, out=None, ctx=None):
 
 
 def argmax_last(input, out=None, ctx=None):
-    """examples/sensevoice/src/tokenizer.rs:50-61: greedy ids, last of equal maxima (Iterator::max_by) -> int32"""
+    """examples/sensevoice/src/tokenizer.rs:50-61: greedy ids, last of equal maxima (Iterator::max_by) -> int32; a NaN loses to every number (all NaN: V - 1)"""
     return _op(ctx, _lib.lib().lele_hip_argmax_last, [input], [], out, np.int32)
 
 

@@ -275,9 +275,19 @@ def wav_to_f32(payload, bits_per_sample=16, num_channels=1):
 
 
 def argmax_last(x):
-    """tokenizer.rs:50-61: Iterator::max_by keeps the last of equal maxima"""
+    """tokenizer.rs:50-61: Iterator::max_by keeps the last of equal maxima (+0.0 == -0.0).  A NaN loses to every number (the
+    reference panics on one: partial_cmp().unwrap()): the result is the last maximum among the non-NaN entries, V - 1 for a row
+    that holds nothing but NaN.  Rows without a NaN are untouched by that rule."""
     x = np.asarray(x, np.float32)
     v = x.shape[-1]
+    nan = np.isnan(x)
+    if nan.any():  # a NaN becomes -inf, which ties with a row's real -inf entries only where the row holds no greater number
+        y = np.where(nan, np.float32(-np.inf), x)
+        top = y.max(axis=-1, keepdims=True)
+        hit = (y == top) & ~nan                    # the maxima among the numbers
+        none = ~hit.any(axis=-1)
+        last = v - 1 - np.argmax(hit[..., ::-1], axis=-1)
+        return np.where(none, v - 1, last).astype(np.int32)
     return (v - 1 - np.argmax(x[..., ::-1], axis=-1)).astype(np.int32)
 
 

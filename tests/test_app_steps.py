@@ -4,6 +4,7 @@ import numpy as np
 import pytest
 
 from oracle import npref
+from parity import same_bits_f32
 
 
 def test_numpy_restatement_hand_cases():
@@ -14,6 +15,78 @@ def test_numpy_restatement_hand_cases():
     assert np.array_equal(npref.wav_to_f32(bytes([0, 128, 255]), 8, 1), np.array([-1.0, 0.0, 127 / 128], np.float32))
     # Iterator::max_by returns the last maximum
     assert npref.argmax_last(np.array([[1, 3, 3, 2], [5, 5, 5, 5], [0, -1, -2, -3]], np.float32)).tolist() == [2, 3, 0]
+    # a NaN loses to every number: the last maximum among the non-NaN entries; nothing but NaN: V - 1
+    nan, inf = np.nan, np.inf
+    rows = np.array([[nan, 1, 3, 3], [3, nan, 3, 1], [1, 3, 3, nan], [nan, nan, nan, nan], [nan, -inf, nan, nan], [-inf, nan, -inf, nan],
+                     [nan, 2, nan, 7], [7, nan, 2, nan], [0.0, nan, -0.0, nan], [1, 3, 3, 2]], np.float32)
+    assert npref.argmax_last(rows).tolist() == [3, 2, 2, 3, 1, 2, 3, 0, 2, 2]
+    assert npref.argmax_last(rows[6]).tolist() == 3 and npref.argmax_last(rows[None]).shape == (1, 10)
+
+
+def last_max_of_the_numbers(row):
+    """the rule of lele_hip_argmax_last spelled as the reference's loop (tokenizer.rs:50-61, max_by keeps the last maximum), NaN skipped"""
+    best = None
+    for j, v in enumerate(row):
+        if v == v and (best is None or v >= row[best]):
+            best = j
+    return len(row) - 1 if best is None else best
+
+
+ARGMAX_V = (1, 2, 255, 256, 257, 511, 513, 1000)
+
+
+def argmax_rows(v, later_zero):
+    """[5, v]: random | one repeated value | all -inf | +inf at two places | +0.0 and -0.0 as the two maxima (the later one: later_zero)"""
+    rng = np.random.default_rng(v)
+    x = rng.standard_normal((5, v)).astype(np.float32)
+    x[1] = -1.25
+    x[2] = -np.inf
+    a, b = sorted({v // 3, v - 1 - v // 4})[0], sorted({v // 3, v - 1 - v // 4})[-1]
+    x[3, a] = x[3, b] = np.inf
+    x[4] = -np.abs(x[4]) - 1.0
+    x[4, a], x[4, b] = -later_zero, later_zero
+    return x, [None, v - 1, v - 1, b, b]
+
+
+def argmax_nan_rows(v):
+    """rows of [v] (v > 256) with one NaN each -- at column 0, column 255, the maximum's own position, column v - 1, the true maximum
+    before and after it, and in the column a thread of the 256-wide block visits before the maximum -- between rows without a NaN"""
+    rng = np.random.default_rng(7 * v)
+    cases = [(0, v - 2), (0, 256), (255, 100), (255, v - 1), (v - 1, 3), (v - 1, v - 2), (3, 259 if v > 259 else 256), (255, 511 if v > 511 else 256)]
+    x = rng.uniform(-1.0, 1.0, (2 * len(cases) + 5, v)).astype(np.float32)
+    want = {}
+    for i, (pn, pm) in enumerate(cases):
+        x[2 * i + 1, pm] = 5.0
+        x[2 * i + 1, pn] = np.nan
+        want[2 * i + 1] = pm
+    r = 2 * len(cases) + 1
+    x[r, 200] = np.nan                  # the NaN sits where the maximum was: the last of the two runners-up wins
+    x[r, 17] = x[r, 256] = 4.0
+    want[r] = 256
+    x[r + 2] = np.nan                   # nothing but NaN
+    want[r + 2] = v - 1
+    x[r + 3, :v - 1] = np.nan           # one number, -inf, behind v - 1 NaN ...
+    x[r + 3, v - 1] = -np.inf
+    want[r + 3] = v - 1
+    x[r - 1, 1:] = np.nan               # ... and one number in front of them
+    want[r - 1] = 0
+    return x, want
+
+
+def test_argmax_nan_rule_of_the_numpy_restatement():
+    for v in (257, 513, 1000):
+        x, want = argmax_nan_rows(v)
+        ref = npref.argmax_last(x)
+        assert ref.tolist() == [last_max_of_the_numbers(row) for row in x], v
+        assert all(ref[r] == i for r, i in want.items()), v
+        clean = [r for r in range(len(x)) if not np.isnan(x[r]).any()]
+        assert len(clean) >= 8 and np.array_equal(ref[clean], x.shape[1] - 1 - np.argmax(x[clean][:, ::-1], axis=1))
+    for v in ARGMAX_V:
+        for z in (0.0, -0.0):
+            x, want = argmax_rows(v, np.float32(z))
+            ref = npref.argmax_last(x)
+            assert ref.tolist() == [last_max_of_the_numbers(row) for row in x], v
+            assert all(w is None or ref[r] == w for r, w in enumerate(want)), (v, ref, want)
 
 
 @pytest.mark.gpu
@@ -24,9 +97,9 @@ def test_device_wav_to_f32_bit_exact(ctx):
     payload = rng.integers(0, 256, 2 * 48001 + 1, dtype=np.uint8).tobytes()  # odd trailing byte is dropped (chunks_exact)
     for bits, ch in ((16, 1), (8, 1), (8, 2)):
         pl = payload if (bits, ch) != (8, 2) else payload[:-1]
-        assert np.array_equal(K.wav_to_f32(pl, bits, ch, ctx=ctx).numpy(), npref.wav_to_f32(pl, bits, ch))
+        assert same_bits_f32(K.wav_to_f32(pl, bits, ch, ctx=ctx).numpy(), npref.wav_to_f32(pl, bits, ch))
     even = payload[:4 * 24000]
-    assert np.array_equal(K.wav_to_f32(even, 16, 2, ctx=ctx).numpy(), npref.wav_to_f32(even, 16, 2))
+    assert same_bits_f32(K.wav_to_f32(even, 16, 2, ctx=ctx).numpy(), npref.wav_to_f32(even, 16, 2))
     with pytest.raises(lele_amd.LeleError, match="Unsupported bits per sample: 24"):
         K.wav_to_f32(payload, 24, 1, ctx=ctx)
 
@@ -43,6 +116,64 @@ def test_device_argmax_last_bit_exact(ctx):
     assert np.array_equal(got, npref.argmax_last(x))
     assert got[0, 5] == 20000 and got[1, 7] == 25054
     assert K.argmax_last(np.array([3.0, 1.0], np.float32), ctx=ctx).numpy().tolist() == 0
+
+
+@pytest.mark.gpu
+def test_device_wav_to_f32_every_sample_value(ctx):
+    """every 16-bit and 8-bit sample once, the stereo mean at the ends of the range and on every byte pair, an empty payload, an
+    int8-typed tensor, and 2 200 000 frames: a second trip through the grid-stride loop (8192 x 256 threads)"""
+    import lele_amd
+    from lele_amd import kernels as K
+    rng = np.random.default_rng(3)
+    all16 = np.arange(-32768, 32768).astype("<i2")
+    got = K.wav_to_f32(all16.tobytes(), 16, 1, ctx=ctx).numpy()
+    same_bits_f32(got, npref.wav_to_f32(all16.tobytes(), 16, 1), "all 16-bit values")
+    same_bits_f32(got, (np.arange(-32768, 32768) / 32768.0).astype(np.float32), "all 16-bit values: v / 32768 is exact")
+    all8 = np.arange(256, dtype=np.uint8)
+    got = K.wav_to_f32(all8.tobytes(), 8, 1, ctx=ctx).numpy()
+    same_bits_f32(got, npref.wav_to_f32(all8.tobytes(), 8, 1), "all 8-bit values")
+    same_bits_f32(got, ((np.arange(256) - 128) / 128.0).astype(np.float32), "all 8-bit values: (b - 128) / 128 is exact")
+    pairs = np.concatenate([np.array([[-32768, -32768], [32767, 32767], [32767, -32768], [1, 0], [-1, 0]]),
+                            rng.integers(-32768, 32768, (1000, 2))]).astype("<i2")
+    got = K.wav_to_f32(pairs.tobytes(), 16, 2, ctx=ctx).numpy()
+    same_bits_f32(got, npref.wav_to_f32(pairs.tobytes(), 16, 2), "16-bit stereo")
+    assert got[:5].tolist() == [-1.0, 32767 / 32768, -1 / 65536, 1 / 65536, -1 / 65536]
+    bytes2 = np.stack(np.meshgrid(all8, all8, indexing="ij"), axis=-1).reshape(-1, 2)
+    same_bits_f32(K.wav_to_f32(bytes2.tobytes(), 8, 2, ctx=ctx).numpy(), npref.wav_to_f32(bytes2.tobytes(), 8, 2), "every 8-bit stereo pair")
+    empty = K.wav_to_f32(b"", 16, 1, ctx=ctx)
+    assert empty.shape == (0,) and empty.numpy().size == 0
+    same_bits_f32(K.wav_to_f32(np.frombuffer(all16.tobytes(), np.int8), 16, 1, ctx=ctx).numpy(), npref.wav_to_f32(all16.tobytes(), 16, 1),
+                  "an int8-typed payload")
+    long = rng.integers(-32768, 32768, 2200000).astype("<i2").tobytes()
+    assert 2200000 > 8192 * 256
+    same_bits_f32(K.wav_to_f32(long, 16, 1, ctx=ctx).numpy(), npref.wav_to_f32(long, 16, 1), "2 200 000 frames")
+    with pytest.raises(lele_amd.LeleError, match="sample count 3 is not a multiple of 2 channels"):
+        K.wav_to_f32(all16[:3].tobytes(), 16, 2, ctx=ctx)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("v", ARGMAX_V)
+def test_device_argmax_last_around_the_block_width(ctx, v):
+    """V below, at and above the 256-wide block and its multiples; ties, -inf rows, +inf twice, +0.0 / -0.0 as equal maxima"""
+    from lele_amd import kernels as K
+    for z in (0.0, -0.0):
+        x, want = argmax_rows(v, np.float32(z))
+        got = K.argmax_last(x, ctx=ctx).numpy()
+        assert got.dtype == np.int32 and got.tolist() == npref.argmax_last(x).tolist(), (v, z)
+        assert all(w is None or got[r] == w for r, w in enumerate(want)), (v, z, got, want)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("v", [257, 513, 1000])
+def test_device_argmax_last_nan_loses_to_every_number(ctx, v):
+    """Upstream panics on a NaN (partial_cmp().unwrap()).  The device used to return an index that depended on its launch geometry: a
+    NaN among the first 256 columns made its thread ignore every later value of that strided column, and the tree reduction never
+    replaced a NaN.  Now: the last maximum among the non-NaN entries, V - 1 for a row of nothing else; other rows unaffected."""
+    from lele_amd import kernels as K
+    x, want = argmax_nan_rows(v)
+    got = K.argmax_last(x, ctx=ctx).numpy()
+    assert {r: int(got[r]) for r in want} == want
+    assert got.tolist() == npref.argmax_last(x).tolist()
 
 
 # ---- token filter, image pre-processing, segmentation post-processing, VAD segments (oracle/apps.cpp restates the reference)
@@ -153,6 +284,37 @@ def test_device_token_filter_bit_exact(ctx):
     ids = np.array([[5, 250, 30, 0, 31]], np.int32)
     gi, gc = K.token_filter(ids, skip, ctx=ctx)
     assert gi.numpy().tolist() == [[5, 30, 31, -1, -1]] and gc.numpy().tolist() == [3]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("t", [255, 256, 257, 512, 513])
+def test_device_token_filter_across_chunks(ctx, t):
+    """the running base across 256-id chunks: all kept, all skipped, alternating, kept only in the last position, and a mix with ids -1,
+    vocab and vocab + 1 (dropped); counts and the -1 fill behind the kept ids exactly"""
+    from lele_amd import apps, kernels as K
+    rng = np.random.default_rng(t)
+    vocab = 200
+    skip = apps.special_token_mask(_vocab(vocab))
+    kept_ids, skipped_ids = np.flatnonzero(skip == 0), np.flatnonzero(skip != 0)
+    ids = np.empty((6, t), np.int32)
+    ids[0] = rng.choice(kept_ids, t)
+    ids[1] = rng.choice(skipped_ids, t)
+    ids[2] = np.where(np.arange(t) % 2, rng.choice(kept_ids, t), rng.choice(skipped_ids, t))
+    ids[3] = rng.choice(skipped_ids, t)
+    ids[3, -1] = 31
+    ids[4] = rng.choice(np.concatenate([kept_ids, skipped_ids, [-1, vocab, vocab + 1]]), t)
+    ids[4, :3] = [-1, vocab, vocab + 1]
+    ids[5] = np.where(np.arange(t) < 256, rng.choice(skipped_ids, t), rng.choice(kept_ids, t))     # nothing kept in the first chunk
+    want = np.full((6, t), -1, np.int32)
+    counts = np.zeros(6, np.int32)
+    for r in range(6):
+        keep = (ids[r] >= 0) & (ids[r] < vocab) & (skip[np.clip(ids[r], 0, vocab - 1)] == 0)
+        counts[r] = keep.sum()
+        want[r, :counts[r]] = ids[r][keep]
+    assert counts[0] == t and counts[1] == 0 and counts[2] == t // 2 and counts[3] == 1 and 0 < counts[4] < t - 3
+    got, got_counts = K.token_filter(ids, skip, ctx=ctx)
+    assert got_counts.numpy().tolist() == counts.tolist()
+    assert np.array_equal(got.numpy(), want)
 
 
 @pytest.mark.gpu

@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 from conftest import synth_pcm
+from parity import same_bits_f32
 
 pytestmark = pytest.mark.gpu
 
@@ -198,7 +199,7 @@ def test_lfr_op_bit_exact(ctx, orc):
     rng = np.random.default_rng(0)
     for t, d, m, n in ((1, 80, 7, 6), (5, 80, 7, 6), (6, 80, 7, 6), (7, 8, 7, 6), (100, 80, 7, 6), (33, 5, 3, 2)):
         x = rng.standard_normal((t, d)).astype(np.float32)
-        assert np.array_equal(Lfr(m, n, ctx).compute(x).numpy(), orc.lfr(x, m, n))
+        assert same_bits_f32(Lfr(m, n, ctx).compute(x).numpy(), orc.lfr(x, m, n))
 
 
 def test_cmvn_bit_exact(ctx, orc):
@@ -206,12 +207,12 @@ def test_cmvn_bit_exact(ctx, orc):
     rng = np.random.default_rng(1)
     for t, d in ((1, 560), (3, 2), (93, 560), (500, 560)):
         x = (rng.standard_normal((t, d)) * 3 + 10).astype(np.float32)
-        assert np.array_equal(Cmvn(ctx=ctx).compute(x).numpy(), orc.cmvn(x))
+        assert same_bits_f32(Cmvn(ctx=ctx).compute(x).numpy(), orc.cmvn(x))
     x = rng.standard_normal((1, 17, 9)).astype(np.float32)
-    assert np.array_equal(Cmvn(ctx=ctx).compute(x).numpy(), orc.cmvn(x))
+    assert same_bits_f32(Cmvn(ctx=ctx).compute(x).numpy(), orc.cmvn(x))
     mean, std = rng.standard_normal(9).astype(np.float32), rng.uniform(0.5, 2, 9).astype(np.float32)
-    assert np.array_equal(Cmvn(ctx=ctx).apply_with_stats(x, mean, std).numpy(),
-                          orc.cmvn_apply_with_stats(x, mean, std))
+    assert same_bits_f32(Cmvn(ctx=ctx).apply_with_stats(x, mean, std).numpy(),
+                         orc.cmvn_apply_with_stats(x, mean, std))
 
 
 def test_rfft_bit_exact(ctx, orc):
@@ -222,7 +223,7 @@ def test_rfft_bit_exact(ctx, orc):
         re, im = RealFft(n, ctx).process(x)
         for r in range(3):
             ore, oim = orc.rfft(x[r], 2)
-            assert np.array_equal(re.numpy()[r], ore) and np.array_equal(im.numpy()[r], oim)
+            assert same_bits_f32(re.numpy()[r], ore) and same_bits_f32(im.numpy()[r], oim)
 
 
 def test_stft_ops_bit_exact(ctx, orc):
@@ -232,13 +233,13 @@ def test_stft_ops_bit_exact(ctx, orc):
         s = K.stft(sig.reshape(shape), 256, 128, 256, ctx=ctx)
         p = K.stft_power_spectrum(sig.reshape(shape), 256, 128, 256, ctx=ctx)
         assert s.shape == ((5, 129, 2) if len(shape) == 1 else (1, 5, 129, 2))
-        assert np.array_equal(s.numpy().reshape(5, 129, 2), orc.stft(sig, 256, 128, 256))
-        assert np.array_equal(p.numpy().reshape(5, 129), orc.stft_power(sig, 256, 128, 256))
+        assert same_bits_f32(s.numpy().reshape(5, 129, 2), orc.stft(sig, 256, 128, 256))
+        assert same_bits_f32(p.numpy().reshape(5, 129), orc.stft_power(sig, 256, 128, 256))
     w = np.hanning(200).astype(np.float32)
-    assert np.array_equal(K.stft(sig, 256, 64, 200, w, ctx=ctx).numpy(), orc.stft(sig, 256, 64, 200, w))
+    assert same_bits_f32(K.stft(sig, 256, 64, 200, w, ctx=ctx).numpy(), orc.stft(sig, 256, 64, 200, w))
     short = sig[:100]
-    assert np.array_equal(K.stft_power_spectrum(short, 256, 64, 256, ctx=ctx).numpy(),
-                          orc.stft_power(short, 256, 64, 256))
+    assert same_bits_f32(K.stft_power_spectrum(short, 256, 64, 256, ctx=ctx).numpy(),
+                         orc.stft_power(short, 256, 64, 256))
 
 
 def test_plain_bench_run_times_the_front_end_and_dumps_its_last_step(orc, tmp_path):
